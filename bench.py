@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: FiLMAViT-small training samples/sec, 4 fields, 16x192x192 clip, batch 8 per GPU (BASELINE.json configs[1]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs1|configs3|configs4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs1|configs3|configs4] [--dump-outputs DIR]
 
   --gpus N > 1 without a launcher: this script starts N rank processes itself (one per GPU, RCCL) BEFORE anything touches the GPU
   and relays rank 0's JSON line.  Launched externally (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...) it
@@ -11,6 +11,11 @@
            configs3  BASELINE configs[3]: the long-aspect 32x384x192 training step (batch 4 per GPU: 36,864 tokens)
            configs4  BASELINE configs[4]: 200-step autoregressive rollout at batch 1, forward captured in a HIP graph; --record PATH
                      writes the per-step record (relative L2, Eikonal residual, heater heat flux) there
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB):
+                     training: `loss`, and `params_sample` / `grads_sample`, the updated parameters and their gradients at a fixed, seeded
+                     sample of 4,194,304 positions of the flat parameter vector (model parameter order, alignment padding left out);
+                     rollout: `prediction`, the last fed-back step's (T, C, H, W) output.  The inputs are seeded: the same arguments
+                     give the same inputs on every run, so two builds can be compared file by file.
   --data device-store  every timed step draws its batch from HBM-resident trajectories (DeviceClipStore.gather = bf_clip_gather) instead of
                      re-using one resident batch; the default run reports that rate too, beside the headline, as `clip_supply`
 
@@ -26,13 +31,6 @@ import os
 import subprocess
 import sys
 import time
-
-# HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues round-robin; with the default of 4, the streams RCCL creates push this
-# library's weight-gradient side stream onto the main stream's queue and the two serialise (measured with a 1-rank RCCL group:
-# 479 samples/s at 4 queues, 577-584 at 2 / 3 / 6 / 8 / 16).  Must be set before the HIP runtime initialises.
-# (Rehearsals that put several ranks on ONE GPU -- BENCH_DEVICE -- keep the default of 4: two processes x 8 queues plus gloo's copy
-# streams oversubscribe the device's hardware queues and the ranks stall in their first collectives; measured.)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "4" if os.environ.get("BENCH_DEVICE") is not None else "8")
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
@@ -387,7 +385,7 @@ def run_rollout(args, w, dev, dtype, profile=True):
             df, tp = p[-1, 0].contiguous(), p[-1, 1].contiguous()
             _lib.check(_lib.lib().bf_heatflux_rows(_p(df), _p(tp), 1, w["H"] * w["W"], w["W"], -8.0, 16.0 / w["W"], 1.0, 0.0007, _p(flux), _stream()), "bf_heatflux_rows")
             rec.append({"step": s, "rel_l2": l2, "eikonal": eik, "heatflux": float(flux)})
-    return dt, prof, rec
+    return dt, prof, rec, preds[steps - 1]
 
 
 def other_config_legs(dev, cdt, dtype_name):
@@ -437,7 +435,7 @@ def other_config_legs(dev, cdt, dtype_name):
     def configs4():
         w = WORKLOADS["configs4"]
         a = types.SimpleNamespace(steps=50, warmup=3)
-        dt, _prof, rec = run_rollout(a, w, dev, cdt, profile=False)
+        dt, _prof, rec, _last = run_rollout(a, w, dev, cdt, profile=False)
         v = a.steps / dt
         return {"metric": w["metric"], "value": v, "unit": "steps/s", "ms_per_step": dt / a.steps * 1e3, "steps": a.steps, "warmup": a.warmup,
                 "rel_l2_last": rec[-1]["rel_l2"], "step_roofline": roof(w, v, "rollout"), "what": w["what"] + " (random-init weights: plumbing, not physics)"}
@@ -446,6 +444,38 @@ def other_config_legs(dev, cdt, dtype_name):
     guarded("configs4", configs4)
     guarded("eager_gpu_baseline_bf16", lambda: eager_gpu_baseline(WORKLOADS["configs1"], dev, True, nsteps=3, nwarm=1))
     return legs
+
+
+DUMP_SAMPLE = 1 << 22             # --dump-outputs: sampled positions of the flat parameter / gradient vectors (2 x 16 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def training_outputs(step, loss):
+    """What a caller of TrainStep holds after a step: the loss it returned, and the model's updated parameters and their gradients
+    (a fixed sample of DUMP_SAMPLE positions drawn with a seeded CPU generator, the same on every run)."""
+    import torch
+    fl = step.flat
+    live = torch.cat([torch.arange(o, o + p.numel()) for p, o in zip(fl.params, fl.offsets)])
+    if live.numel() > DUMP_SAMPLE:
+        live = live[torch.randperm(live.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values]
+    idx = live.to(fl.flat.device)
+    return {"loss": torch.as_tensor(loss).detach().double().cpu().numpy(),
+            "params_sample": fl.flat[idx].float().cpu().numpy(), "grads_sample": fl.grad[idx].float().cpu().numpy()}
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": path, "files": files, "bytes": total}
 
 
 def main():
@@ -460,9 +490,13 @@ def main():
                     help="device-store: every timed step draws its batch from a DeviceClipStore (HBM-resident trajectories, bf_clip_gather)")
     ap.add_argument("--record", default=None, help="configs4: write the per-step rollout record (relative L2, Eikonal, heat flux) to this file")
     ap.add_argument("--eager-gpu-baseline", action="store_true", help="also time the oracle eagerly on the GPU (fp32 and bf16 autocast)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the bounded configs3 / configs4 / eager-GPU legs the default one-GPU configs1 run adds as `other_configs`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     w = WORKLOADS[args.config]
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -512,10 +546,13 @@ def main():
 
     rollout_record = None
     clip_supply = None
+    dumped = None
     if w["kind"] == "rollout":                                   # replicas only: every rank runs its own rollout
         sync()
-        dt, prof, rollout_record = run_rollout(args, w, dev, cdt)
+        dt, prof, rollout_record, last_pred = run_rollout(args, w, dev, cdt)
         sync()
+        if args.dump_outputs:
+            dumped = {"prediction": last_pred.float().cpu().numpy()}
         final_loss = rollout_record[-1]["rel_l2"]
     else:
         model = get_model("filmavit", time_window=w["T"], drop_path=DROP_PATH, compute_dtype=cdt, **CFG).to(dev).train()
@@ -548,11 +585,15 @@ def main():
                 raise SystemExit("--data device-store is built for configs1 (the 16x192x192 training step)")
             timed(store_fn, min(3, args.steps))                 # first gathers (index tables, allocator)
             dt, loss = timed(store_fn, args.steps)
+            if args.dump_outputs:
+                dumped = training_outputs(step, loss)
             dt_syn, _ = timed(lambda s_: (x, cond, y), min(args.steps, 50))
             clip_supply = {"samples_per_s_device_store": w["batch"] * world * args.steps / dt,
                            "samples_per_s_synthetic_same_run": w["batch"] * world * min(args.steps, 50) / dt_syn}
         else:
             dt, loss = timed(lambda s_: (x, cond, y), args.steps)
+            if args.dump_outputs:
+                dumped = training_outputs(step, loss)
             if store_fn is not None:                             # the clip supply in a timed loop beside the resident-batch figure (bounded: 50 steps)
                 n2 = min(args.steps, 50)
                 timed(store_fn, 3)
@@ -606,6 +647,8 @@ def main():
                 out["rollout_record"]["file"] = args.record
             except OSError as e:
                 out["rollout_record"]["error"] = str(e)
+    if dumped is not None:
+        out["dump_outputs"] = write_outputs(args.dump_outputs, dumped)
     if clip_supply is not None:
         out["clip_supply"] = clip_supply
         if args.data == "device-store":

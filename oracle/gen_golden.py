@@ -4,7 +4,7 @@ ORACLE -- TEST INFRASTRUCTURE ONLY.  Generates tests/golden/*.npz by IMPORTING
 the real reference from /root/reference (CPU, fp64 and fp32) in the build
 container.  The reference never travels: only the data this script writes is
 committed.  Run:  PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py
-(`--only-small`: scheduler / physics / rollout fixtures only; `--fullsize [names]`: the full-width statistics
+(`--only-small`: scheduler / physics / rollout fixtures only; `--only-boundary`: reference_boundary.json only; `--fullsize [names]`: the full-width statistics
 fixtures fullsize_*.npz, a few minutes of CPU time, not part of the default run).
 
 ``timm`` (the reference's only missing dependency on this path: one symbol,
@@ -302,9 +302,53 @@ def gen_fullsize(gold, ref_models, LpLoss, only=None):
         print(f"fullsize {name}: loss {float(loss.detach()):.9f} ({time.time() - t0:.0f} s)", flush=True)
 
 
+BOUNDARY_CFGS = OrderedDict(
+    small=dict(input_fields=4, output_fields=4, time_window=16, patch_size=16, embed_dim=384, num_heads=6, processor_blocks=12,
+               drop_path=0.2, attn_scale=True, feat_scale=True),        # config/model_cfg/film_avit_small.yaml + modules.py:51-53
+    tiny=dict(input_fields=3, output_fields=2, time_window=3, patch_size=8, embed_dim=96, num_heads=4, processor_blocks=2, drop_path=0.0,
+              attn_scale=False, feat_scale=False),
+)
+
+
+def gen_reference_boundary(gold, ref_models):
+    """tests/golden/reference_boundary.json: what a reference checkpoint looks like to the native classes -- the reference registry's
+    model names and, per (model, config), the reference class's state_dict keys / shapes / dtypes and its first module names
+    (tests/test_reference_boundary.py)."""
+    import json
+    from bubbleformer.models import axial_vit as ref_axial
+    import bubbleformer.layers.attention as ref_attention      # binds timm.layers.DropPath at import
+    keep = ref_attention.DropPath
+
+    class DropPath(torch.nn.Module):       # parameterless: constructed for drop_path > 0, never run here
+        def __init__(self, drop_prob=0.0, scale_by_keep=True):
+            super().__init__()
+
+    ref_attention.DropPath = DropPath
+    try:
+        out = {"registry": sorted(ref_models._api.MODELS.keys()), "configs": BOUNDARY_CFGS, "models": {}}
+        for name, cls, extra in (("filmavit", ref_axial.FiLMConditionedAViT, dict(num_fluid_params=9)), ("avit", ref_axial.AViT, {})):
+            for cname, cfg in BOUNDARY_CFGS.items():
+                torch.manual_seed(0)
+                ref = cls(**cfg, **extra)
+                out["models"][f"{name}/{cname}"] = {
+                    "class": cls.__name__,
+                    "state_dict": [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in ref.state_dict().items()],
+                    "first_modules": [n for n, _ in ref.named_modules()][:4]}
+    finally:
+        ref_attention.DropPath = keep
+    with open(os.path.join(gold, "reference_boundary.json"), "w") as f:
+        json.dump(out, f, indent=0)
+        f.write("\n")
+
+
 def main():
     gold = os.path.join(REPO, "tests", "golden")
     os.makedirs(gold, exist_ok=True)
+    if "--only-boundary" in sys.argv:
+        ref_models, _, _ = _import_reference()
+        gen_reference_boundary(gold, ref_models)
+        print("wrote reference_boundary.json")
+        return
     if "--fullsize" in sys.argv:           # minutes of CPU time: its own switch
         ref_models, _, LpLoss = _import_reference()
         torch.set_num_threads(8)
@@ -321,6 +365,7 @@ def main():
     gen_physics(gold)
     ref_models, ref_layers, LpLoss = _import_reference()
     gen_rollout(gold, ref_models, LpLoss)
+    gen_reference_boundary(gold, ref_models)
     for name, spec in VARIANTS.items():
         np.savez(os.path.join(gold, f"model_{name}.npz"), **run_variant(name, spec, ref_models, LpLoss))
 

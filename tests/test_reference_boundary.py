@@ -1,58 +1,57 @@
-"""The drop-in boundary against the REAL reference: `bubbleformer_amd.install_into_reference()` puts the native
+"""The drop-in boundary against the reference: `bubbleformer_amd.install_into_reference()` puts the native
 classes into the reference's own registry, so `bubbleformer.models.get_model("filmavit", ...)` -- what `ForecastModule.__init__`
 (bubbleformer/modules.py:51-54) and scripts/inference.py:202 call -- returns the native class with the reference class's state_dict
-keys and shapes.  Needs the reference checkout (/root/reference: the build container only; skipped on the GPU box, where it does not
-exist).  Runs in a child process so that the reference's `bubbleformer` package never enters this test session's module table."""
-import os
-import subprocess
-import sys
-import textwrap
+keys, shapes and dtypes, and a reference checkpoint loads as it stands.
 
-import pytest
+The reference side is recorded data: tests/golden/reference_boundary.json (oracle/gen_golden.py --only-boundary) holds the reference
+registry's model names and, per model and configuration, the reference class's state_dict layout and first module names.  The registry
+that `install_into_reference()` writes into is `bubbleformer.models._api`, stood in for by a fresh copy of this package's own registry
+module (the same contract as the reference's: models/_api.py:5-40), holding the recorded names."""
+import importlib.util
+import json
+import os
+import sys
+import types
+
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(REPO, "tests", "golden", "reference_boundary.json")
 
-CHILD = textwrap.dedent("""
-    import sys, types
-    sys.dont_write_bytecode = True
-    import torch
-    timm = types.ModuleType("timm"); layers = types.ModuleType("timm.layers")
-    class DropPath(torch.nn.Module):            # timm is not installed here (SURVEY.md section 8c); never executed, only constructed
-        def __init__(self, drop_prob=0.0, scale_by_keep=True):
-            super().__init__(); self.drop_prob = drop_prob
-    layers.DropPath = DropPath; timm.layers = layers
-    sys.modules["timm"] = timm; sys.modules["timm.layers"] = layers
-    sys.path.insert(0, %r); sys.path.insert(0, %r)
-    import bubbleformer.models as ref_models
-    from bubbleformer.models import axial_vit as ref_axial
-    ref_cls = {"filmavit": ref_axial.FiLMConditionedAViT, "avit": ref_axial.AViT}
-    assert ref_models.get_model("filmavit", input_fields=4, output_fields=4, time_window=4, patch_size=4, embed_dim=64, num_heads=2,
-                                processor_blocks=1, drop_path=0.0, num_fluid_params=9).__class__ is ref_cls["filmavit"]
+
+def _stand_in_registry(monkeypatch, names):
+    spec = importlib.util.spec_from_file_location("bubbleformer.models._api", os.path.join(REPO, "bubbleformer_amd", "models", "_api.py"))
+    api = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(api)
+    for n in names:
+        api.MODELS[n] = lambda **cfg: None          # the reference's own entries; the native install replaces two of them
+    pkg, models = types.ModuleType("bubbleformer"), types.ModuleType("bubbleformer.models")
+    pkg.__path__, models.__path__ = [], []
+    pkg.models, models._api = models, api
+    models.get_model, models.list_models = api.get_model, api.list_models
+    for name, mod in (("bubbleformer", pkg), ("bubbleformer.models", models), ("bubbleformer.models._api", api)):
+        monkeypatch.setitem(sys.modules, name, mod)
+    return models
+
+
+def test_install_into_reference_registers_native_classes_with_reference_state_dict(monkeypatch):
+    with open(GOLDEN) as f:
+        ref = json.load(f)
+    ref_models = _stand_in_registry(monkeypatch, ref["registry"])
     import bubbleformer_amd
     from bubbleformer_amd.models import axial_vit as native
     bubbleformer_amd.install_into_reference()
-    small = dict(input_fields=4, output_fields=4, time_window=16, patch_size=16, embed_dim=384, num_heads=6, processor_blocks=12,
-                 drop_path=0.2, attn_scale=True, feat_scale=True)       # config/model_cfg/film_avit_small.yaml + modules.py:51-53
-    tiny = dict(input_fields=3, output_fields=2, time_window=3, patch_size=8, embed_dim=96, num_heads=4, processor_blocks=2, drop_path=0.0,
-                attn_scale=False, feat_scale=False)
     for name, extra in (("filmavit", dict(num_fluid_params=9)), ("avit", {})):
-        for cfg in (small, tiny):
-            m = ref_models.get_model(name.upper() if cfg is tiny else name, **cfg, **extra)       # the registry lower-cases (models/_api.py:35)
-            assert type(m) is getattr(native, ref_cls[name].__name__), type(m)
-            ref = ref_cls[name](**cfg, **extra)
-            a, b = m.state_dict(), ref.state_dict()
-            assert list(a.keys()) == list(b.keys()), (name, set(a) ^ set(b))
-            assert all(tuple(a[k].shape) == tuple(b[k].shape) and a[k].dtype == b[k].dtype for k in a)
-            m.load_state_dict(b)                                      # a reference checkpoint loads as it stands
-            assert [n for n, _ in m.named_modules()][:4] == [n for n, _ in ref.named_modules()][:4]
-    assert ref_models.list_models() == ["avit", "filmavit", "unet_classic", "unet_modern"]
-    print("BOUNDARY-OK")
-""")
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "bubbleformer")), reason="reference checkout not present (GPU box)")
-def test_install_into_reference_registers_native_classes_with_reference_state_dict():
-    res = subprocess.run([sys.executable, "-c", CHILD % (REF, REPO)], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert res.returncode == 0 and "BOUNDARY-OK" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        for cname, cfg in ref["configs"].items():
+            want = ref["models"][f"{name}/{cname}"]
+            m = ref_models.get_model(name.upper() if cname == "tiny" else name, **cfg, **extra)   # the registry lower-cases (models/_api.py:35)
+            assert type(m) is getattr(native, want["class"]), type(m)
+            a = m.state_dict()
+            assert list(a.keys()) == [k for k, _, _ in want["state_dict"]], (name, cname, set(a) ^ {k for k, _, _ in want["state_dict"]})
+            for k, shape, dtype in want["state_dict"]:
+                assert list(a[k].shape) == shape and a[k].dtype == getattr(torch, dtype), (name, cname, k)
+            b = {k: torch.full(shape, 0.5, dtype=getattr(torch, dtype)) for k, shape, dtype in want["state_dict"]}
+            m.load_state_dict(b)                                       # a reference checkpoint loads as it stands
+            assert all(torch.equal(v, b[k]) for k, v in m.state_dict().items())
+            assert [n for n, _ in m.named_modules()][:4] == want["first_modules"]
+    assert ref_models.list_models() == ref["registry"] == ["avit", "filmavit", "unet_classic", "unet_modern"]

@@ -2,7 +2,6 @@
 """Where the host spends its time while it enqueues a training step (the GPU runs ~13.5 ms per step; the host must stay ahead)."""
 import cProfile, os, pstats, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import bench as B
 from bubbleformer_amd.models import get_model
