@@ -16,6 +16,7 @@ def install_into_reference() -> None:
     """Register the native models in an importable reference checkout's registry so that the reference's own
     ``scripts/train.py`` / ``scripts/inference.py`` pick them up unchanged."""
     import bubbleformer.models._api as ref_api  # the user's reference checkout
-    from .models import axial_vit
+    from .models import axial_vit, unets
     ref_api.MODELS["filmavit"] = axial_vit.FiLMConditionedAViT
     ref_api.MODELS["avit"] = axial_vit.AViT
+    ref_api.MODELS["unet_modern"] = unets.ModernUnet

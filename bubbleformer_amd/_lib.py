@@ -69,6 +69,17 @@ class DebedParams(C.Structure):
     _fields_ = [("conv_w", fp * BF_MAX_STAGES), ("in_w", fp * BF_MAX_STAGES), ("in_b", fp * BF_MAX_STAGES)]
 
 
+class ConvSrc(C.Structure):
+    """bf_conv_src: one activation tensor of a ModernUnet conv / GroupNorm call (channels-last, or NCHW with nchw = 1)."""
+    _fields_ = [("p", vp), ("C", i32), ("nchw", i32), ("f32", i32)]
+
+
+class ConvGeo(C.Structure):
+    _fields_ = [(n, i32) for n in ("F", "Hi", "Wi", "Ho", "Wo", "kh", "kw", "stride", "pad")]
+
+
+BF_CONV_PRO_NONE, BF_CONV_PRO_AFFINE_GELU, BF_CONV_PRO_GELU = 0, 1, 2
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # bf_stage_done_fn
 P = C.POINTER
 # name -> (restype, argtypes); mirrors include/bubbleformer_hip.h one to one
@@ -164,6 +175,17 @@ SIGNATURES = {
     "bf_embed_bwd": (C.c_int, [P(Dims), P(EmbedParams), P(EmbedParams), vp, fp, vp, vp, vp]),
     "bf_debed_fwd": (C.c_int, [P(Dims), P(DebedParams), vp, fp, fp, fp, vp, vp, vp]),
     "bf_debed_bwd": (C.c_int, [P(Dims), P(DebedParams), P(DebedParams), vp, fp, fp, fp, fp, vp, vp, vp, vp]),
+    "bf_conv_fwd": (C.c_int, [C.c_int, P(ConvGeo), P(ConvSrc), P(ConvSrc), C.c_int, fp, fp, vp, C.c_int, fp, P(ConvSrc), P(ConvSrc),
+                              C.c_int, vp]),
+    "bf_conv_wgrad_ws_floats": (i64, [C.c_int, C.c_int, i64]),
+    "bf_conv_wgrad": (C.c_int, [C.c_int, P(ConvGeo), P(ConvSrc), P(ConvSrc), P(ConvSrc), C.c_int, fp, fp, fp, C.c_int, fp, i64, vp]),
+    "bf_conv_colsum": (C.c_int, [C.c_int, P(ConvSrc), C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, i64, vp]),
+    "bf_gn_ws_floats": (i64, [C.c_int, C.c_int, C.c_int]),
+    "bf_gn_fwd": (C.c_int, [C.c_int, P(ConvSrc), P(ConvSrc), C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, f32, fp, fp, fp, fp, fp, vp]),
+    "bf_gn_bwd": (C.c_int, [C.c_int, fp, P(ConvSrc), P(ConvSrc), C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, P(ConvSrc), P(ConvSrc),
+                            P(ConvSrc), fp, fp, C.c_int, fp, vp]),
+    "bf_unet_lploss_fwd": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, i64, fp, fp, fp, vp]),
+    "bf_unet_lploss_bwd": (C.c_int, [fp, fp, fp, fp, C.c_int, i64, fp, vp]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
-# same export list as the reference's bubbleformer/layers/__init__.py:1-5 (U-Net conv layers are out of scope)
+# same export list as the reference's bubbleformer/layers/__init__.py:1-5, plus the ModernUnet blocks (conv_layers.py:5-86)
 from .positional_encoding import ContinuousPositionBias1D, RelativePositionBias
 from .linear_layers import GeluMLP, SirenMLP, FiLMMLP
 from .patching import HMLPEmbed, HMLPDebed
 from .attention import AxialAttentionBlock, AttentionBlock
+from .conv_layers import ResidualBlock, MiddleBlock

@@ -1,2 +1,3 @@
 from .axial_vit import *
 from ._api import *
+from .unets import *

@@ -926,3 +926,361 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
     L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                              float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
     _weights_changed()
+
+
+# ------------------------------------------------------------------------------------------------ ModernUnet (conv.hip)
+# Activations between U-Net layers are channels-last (B, H, W, C) tensors in the compute dtype; the clip and the prediction stay in the
+# reference's (B, T, C, H, W) fp32 layout and are read / written in place by the first and last conv.  Weights are re-laid out per call
+# as the GEMM operand [kh*kw][C_src][C_dst] in the compute dtype; parameter gradients are fp32 in the reference layout.
+GN_GROUPS, GN_EPS = 8, 1e-5
+
+
+def _csrc(t: Optional[torch.Tensor], C: int = 0, nchw: bool = False) -> Optional[L.ConvSrc]:
+    if t is None:
+        return None
+    return L.ConvSrc(t.data_ptr(), int(C), int(nchw), int(t.dtype == torch.float32))
+
+
+def _ref(s):
+    return None if s is None else C.byref(s)
+
+
+def _ws(n: int, device, what: str) -> torch.Tensor:
+    if n < 0:
+        L.check(-1, what)
+    return torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
+
+
+def _conv(dt, geo, s0, s1, w, N, out, pro=L.BF_CONV_PRO_NONE, sc=None, sh=None, bias=None, resid=None, transposed=False):
+    L.check(L.lib().bf_conv_fwd(_dt(dt), C.byref(geo), C.byref(s0), _ref(s1), pro, _p(sc), _p(sh), _p(w), N, _p(bias), _ref(resid),
+                                C.byref(out), int(transposed), _stream()), "bf_conv_fwd")
+
+
+def _wgrad(dt, geo, rows, s0, s1, K, dw, pro=L.BF_CONV_PRO_NONE, sc=None, sh=None):
+    lib = L.lib()
+    M = geo.F * geo.Ho * geo.Wo
+    n = lib.bf_conv_wgrad_ws_floats(rows.C, K, M)
+    ws = _ws(n, dw.device, "bf_conv_wgrad_ws_floats")
+    L.check(lib.bf_conv_wgrad(_dt(dt), C.byref(geo), C.byref(rows), C.byref(s0), _ref(s1), pro, _p(sc), _p(sh), _p(dw), 0, _p(ws), ws.numel(),
+                              _stream()), "bf_conv_wgrad")
+
+
+def _colsum(dt, src, F, H, W, out):
+    ws = _ws(64 * src.C, out.device, "bf_conv_colsum")
+    L.check(L.lib().bf_conv_colsum(_dt(dt), C.byref(src), F, H, W, _p(out), 0, _p(ws), ws.numel(), _stream()), "bf_conv_colsum")
+
+
+def _geo(F, Hi, Wi, Ho, Wo, k, stride, pad) -> L.ConvGeo:
+    return L.ConvGeo(F, Hi, Wi, Ho, Wo, k, k, stride, pad)
+
+
+def _wfwd(w, dt):
+    """Conv2d weight [Cout][Cin][kh][kw] -> forward GEMM operand [kh*kw][Cin][Cout]."""
+    return w.detach().permute(2, 3, 1, 0).to(dt).contiguous()
+
+
+def _wswap(w, dt):
+    """[A][B][kh][kw] -> [kh*kw][A][B]: a Conv2d weight as its data-gradient operand, a ConvTranspose2d weight as its forward one."""
+    return w.detach().permute(2, 3, 0, 1).to(dt).contiguous()
+
+
+def _gn_fwd(dt, x0, C0, x1, C1, B, H, W, gamma, beta):
+    """-> (mean, rstd, sc, sh) of GroupNorm(8) over the channel concatenation of x0 and x1."""
+    dev = x0.device
+    Cin = C0 + C1
+    mean = torch.empty(B, GN_GROUPS, dtype=torch.float32, device=dev)
+    rstd = torch.empty_like(mean)
+    sc = torch.empty(B, Cin, dtype=torch.float32, device=dev)
+    sh = torch.empty_like(sc)
+    lib = L.lib()
+    ws = _ws(lib.bf_gn_ws_floats(B, Cin, GN_GROUPS), dev, "bf_gn_ws_floats")
+    L.check(lib.bf_gn_fwd(_dt(dt), C.byref(_csrc(x0, C0)), _ref(_csrc(x1, C1)), B, H, W, GN_GROUPS, _p(_f32c(gamma)), _p(_f32c(beta)), GN_EPS,
+                          _p(mean), _p(rstd), _p(sc), _p(sh), _p(ws), _stream()), "bf_gn_fwd")
+    return mean, rstd, sc, sh
+
+
+def _gn_bwd(dt, dA, x0, C0, x1, C1, B, H, W, gamma, stats, add, add_f32_ch, dgamma, dbeta):
+    """dA: fp32 [B*H*W][C0+C1] gradient w.r.t. gelu(gn(cat(x0, x1))) -> (dx0, dx1) in the compute dtype, + add."""
+    dx0 = torch.empty_like(x0)
+    dx1 = torch.empty_like(x1) if x1 is not None else None
+    lib = L.lib()
+    ws = None
+    if gamma is not None:
+        ws = _ws(lib.bf_gn_ws_floats(B, C0 + C1, GN_GROUPS), dA.device, "bf_gn_ws_floats")
+    mean, rstd, sc, sh = stats if stats is not None else (None,) * 4
+    L.check(lib.bf_gn_bwd(_dt(dt), _p(dA), C.byref(_csrc(x0, C0)), _ref(_csrc(x1, C1)), B, H, W, GN_GROUPS, _p(gamma), _p(mean), _p(rstd), _p(sc),
+                          _p(sh), _ref(_csrc(add, add_f32_ch)), C.byref(_csrc(dx0, C0)), _ref(_csrc(dx1, C1)), _p(dgamma), _p(dbeta), 0, _p(ws),
+                          _stream()), "bf_gn_bwd")
+    return dx0, dx1
+
+
+def _pro(norm: bool):
+    return L.BF_CONV_PRO_AFFINE_GELU if norm else L.BF_CONV_PRO_GELU
+
+
+class _ResBlockFn(torch.autograd.Function):
+    """ResidualBlock.forward (bubbleformer/layers/conv_layers.py:41-51) on cat(x, s):
+    GN stats -> conv1 (GN affine + GELU prologue) -> GN stats -> conv2 (prologue) + bias + shortcut(x).
+    Backward in reverse; the gradient of the skip input s is returned on its own (autograd adds it to the skip tensor's other uses)."""
+
+    @staticmethod
+    def forward(ctx, x, s, n1w, n1b, w1, b1, n2w, n2b, w2, b2, scw, scb):
+        _require_gpu(x)
+        dt = x.dtype
+        B, H, W, C0 = x.shape
+        C1 = 0 if s is None else s.shape[3]
+        Cout = w1.shape[0]
+        norm = n1w is not None
+        g3 = _geo(B, H, W, H, W, 3, 1, 1)
+        st1 = _gn_fwd(dt, x, C0, s, C1, B, H, W, n1w, n1b) if norm else None
+        h = torch.empty(B, H, W, Cout, dtype=dt, device=x.device)
+        _conv(dt, g3, _csrc(x, C0), _csrc(s, C1), _wfwd(w1, dt), Cout, _csrc(h, Cout), _pro(norm), *(st1[2:] if norm else (None, None)),
+              bias=_f32c(b1))
+        st2 = _gn_fwd(dt, h, Cout, None, 0, B, H, W, n2w, n2b) if norm else None
+        if scw is not None:
+            r = torch.empty(B, H, W, Cout, dtype=dt, device=x.device)
+            _conv(dt, _geo(B, H, W, H, W, 1, 1, 0), _csrc(x, C0), _csrc(s, C1), _wfwd(scw, dt), Cout, _csrc(r, Cout), bias=_f32c(scb))
+        else:
+            if C1 or C0 != Cout:
+                raise L.BubbleformerHipError("identity shortcut needs in_channels == out_channels")
+            r = x
+        out = torch.empty(B, H, W, Cout, dtype=dt, device=x.device)
+        _conv(dt, g3, _csrc(h, Cout), None, _wfwd(w2, dt), Cout, _csrc(out, Cout), _pro(norm), *(st2[2:] if norm else (None, None)),
+              bias=_f32c(b2), resid=_csrc(r, Cout))
+        ctx.norm, ctx.has_s, ctx.has_sc = norm, s is not None, scw is not None
+        st1 = st1 if norm else ()
+        st2 = st2 if norm else ()
+        ctx.save_for_backward(x, s if s is not None else x, h, w1, w2, scw if scw is not None else w1, n1w if norm else w1,
+                              n2w if norm else w1, *st1, *st2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, s, h, w1, w2, scw, n1w, n2w, *st = ctx.saved_tensors
+        norm = ctx.norm
+        s = s if ctx.has_s else None
+        dt = x.dtype
+        dout = dout.to(dt).contiguous()
+        B, H, W, C0 = x.shape
+        C1 = 0 if s is None else s.shape[3]
+        Cin, Cout = C0 + C1, w1.shape[0]
+        dev = x.device
+        st1, st2 = (st[:4], st[4:]) if norm else (None, None)
+        f32 = dict(dtype=torch.float32, device=dev)
+        g3 = _geo(B, H, W, H, W, 3, 1, 1)
+        g1 = _geo(B, H, W, H, W, 1, 1, 0)
+        # conv2
+        dw2 = torch.empty(Cout, 9 * Cout, **f32)
+        db2 = torch.empty(Cout, **f32)
+        _wgrad(dt, g3, _csrc(dout, Cout), _csrc(h, Cout), None, 9 * Cout, dw2, _pro(norm), *(st2[2:] if norm else (None, None)))
+        _colsum(dt, _csrc(dout, Cout), B, H, W, db2)
+        dA2 = torch.empty(B * H * W, Cout, **f32)
+        _conv(dt, g3, _csrc(dout, Cout), None, _wswap(w2, dt), Cout, _csrc(dA2, Cout), transposed=True)
+        dn2w = torch.empty(Cout, **f32) if norm else None
+        dn2b = torch.empty(Cout, **f32) if norm else None
+        dh, _ = _gn_bwd(dt, dA2, h, Cout, None, 0, B, H, W, n2w if norm else None, st2, None, 0, dn2w, dn2b)
+        # shortcut
+        dscw = dscb = None
+        if ctx.has_sc:
+            dscw = torch.empty(Cout, Cin, **f32)
+            dscb = torch.empty(Cout, **f32)
+            _wgrad(dt, g1, _csrc(dout, Cout), _csrc(x, C0), _csrc(s, C1), Cin, dscw)
+            _colsum(dt, _csrc(dout, Cout), B, H, W, dscb)
+            dxs = torch.empty(B * H * W, Cin, **f32)
+            _conv(dt, g1, _csrc(dout, Cout), None, _wswap(scw, dt), Cin, _csrc(dxs, Cin), transposed=True)
+            dscw = dscw.view(Cout, Cin, 1, 1)
+        else:
+            dxs = dout
+        # conv1
+        dw1 = torch.empty(Cout, 9 * Cin, **f32)
+        db1 = torch.empty(Cout, **f32)
+        _wgrad(dt, g3, _csrc(dh, Cout), _csrc(x, C0), _csrc(s, C1), 9 * Cin, dw1, _pro(norm), *(st1[2:] if norm else (None, None)))
+        _colsum(dt, _csrc(dh, Cout), B, H, W, db1)
+        dA1 = torch.empty(B * H * W, Cin, **f32)
+        _conv(dt, g3, _csrc(dh, Cout), None, _wswap(w1, dt), Cin, _csrc(dA1, Cin), transposed=True)
+        dn1w = torch.empty(Cin, **f32) if norm else None
+        dn1b = torch.empty(Cin, **f32) if norm else None
+        dx, ds = _gn_bwd(dt, dA1, x, C0, s, C1, B, H, W, n1w if norm else None, st1, dxs, Cin, dn1w, dn1b)
+        dw1 = dw1.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+        dw2 = dw2.view(Cout, 3, 3, Cout).permute(0, 3, 1, 2).contiguous()
+        return dx, ds, dn1w, dn1b, dw1, db1, dn2w, dn2b, dw2, db2, dscw, dscb
+
+
+def res_block(x, s, n1w, n1b, w1, b1, n2w, n2b, w2, b2, scw, scb):
+    """ResidualBlock on cat(x, s) (s may be None); x, s: (B, H, W, C) channels-last in the compute dtype."""
+    return _ResBlockFn.apply(x, s, n1w, n1b, w1, b1, n2w, n2b, w2, b2, scw, scb)
+
+
+class _DownFn(torch.autograd.Function):
+    """Downsample: Conv2d(C, C, 3, stride 2, pad 1) (unets.py:37-62).  Data gradient: the 1- / 2-tap phases of the transposed gather."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _require_gpu(x)
+        dt = x.dtype
+        B, H, W, Cc = x.shape
+        Ho, Wo = (H + 1) // 2, (W + 1) // 2
+        out = torch.empty(B, Ho, Wo, Cc, dtype=dt, device=x.device)
+        _conv(dt, _geo(B, H, W, Ho, Wo, 3, 2, 1), _csrc(x, Cc), None, _wfwd(w, dt), Cc, _csrc(out, Cc), bias=_f32c(b))
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dt = x.dtype
+        dout = dout.to(dt).contiguous()
+        B, H, W, Cc = x.shape
+        Ho, Wo = dout.shape[1:3]
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dw = torch.empty(Cc, 9 * Cc, **f32)
+        db = torch.empty(Cc, **f32)
+        _wgrad(dt, _geo(B, H, W, Ho, Wo, 3, 2, 1), _csrc(dout, Cc), _csrc(x, Cc), None, 9 * Cc, dw)
+        _colsum(dt, _csrc(dout, Cc), B, Ho, Wo, db)
+        dx = torch.empty_like(x)
+        _conv(dt, _geo(B, Ho, Wo, H, W, 3, 2, 1), _csrc(dout, Cc), None, _wswap(w, dt), Cc, _csrc(dx, Cc), transposed=True)
+        return dx, dw.view(Cc, 3, 3, Cc).permute(0, 3, 1, 2).contiguous(), db
+
+
+class _UpFn(torch.autograd.Function):
+    """Upsample: ConvTranspose2d(C, C, 4, stride 2, pad 1) (unets.py:10-34) as four 2x2-tap parity phases; its data gradient is the
+    forward gather with stride 2, its weight gradient the forward-gather weight GEMM with the roles of input and output swapped."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _require_gpu(x)
+        dt = x.dtype
+        B, H, W, Cc = x.shape
+        out = torch.empty(B, 2 * H, 2 * W, Cc, dtype=dt, device=x.device)
+        _conv(dt, _geo(B, H, W, 2 * H, 2 * W, 4, 2, 1), _csrc(x, Cc), None, _wswap(w, dt), Cc, _csrc(out, Cc), bias=_f32c(b), transposed=True)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dt = x.dtype
+        dout = dout.to(dt).contiguous()
+        B, H, W, Cc = x.shape
+        f32 = dict(dtype=torch.float32, device=x.device)
+        g = _geo(B, 2 * H, 2 * W, H, W, 4, 2, 1)
+        dw = torch.empty(Cc, 16 * Cc, **f32)        # [Cin][(ky, kx, Cout)]
+        db = torch.empty(Cc, **f32)
+        _wgrad(dt, g, _csrc(x, Cc), _csrc(dout, Cc), None, 16 * Cc, dw)
+        _colsum(dt, _csrc(dout, Cc), B, 2 * H, 2 * W, db)
+        dx = torch.empty_like(x)
+        _conv(dt, g, _csrc(dout, Cc), None, _wfwd(w, dt), Cc, _csrc(dx, Cc))
+        return dx, dw.view(Cc, 4, 4, Cc).permute(0, 3, 1, 2).contiguous(), db
+
+
+class _ProjFn(torch.autograd.Function):
+    """image_proj: Conv2d(T*C, hidden, 1) reading the (B, T, C, H, W) fp32 clip in place (channel = t*C + c)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, dt):
+        _require_gpu(x)
+        x = x.contiguous().float()
+        B, T, Cf, H, W = x.shape
+        Cin, N = T * Cf, w.shape[0]
+        out = torch.empty(B, H, W, N, dtype=dt, device=x.device)
+        _conv(dt, _geo(B, H, W, H, W, 1, 1, 0), _csrc(x, Cin, nchw=True), None, _wfwd(w, dt), N, _csrc(out, N), bias=_f32c(b))
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        B, T, Cf, H, W = x.shape
+        Cin, N = T * Cf, w.shape[0]
+        dt = dout.dtype
+        dout = dout.contiguous()
+        f32 = dict(dtype=torch.float32, device=x.device)
+        g = _geo(B, H, W, H, W, 1, 1, 0)
+        dw = torch.empty(N, Cin, **f32)
+        db = torch.empty(N, **f32)
+        _wgrad(dt, g, _csrc(dout, N), _csrc(x, Cin, nchw=True), None, Cin, dw)
+        _colsum(dt, _csrc(dout, N), B, H, W, db)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _conv(dt, g, _csrc(dout, N), None, _wswap(w, dt), Cin, _csrc(dx, Cin, nchw=True), transposed=True)
+        return dx, dw.view(N, Cin, 1, 1), db, None
+
+
+class _FinalFn(torch.autograd.Function):
+    """final(gelu(norm(x))) (unets.py:205) writing the (B, T, C_out, H, W) fp32 prediction in place; with ``target`` also the
+    relative-L2 loss (LpLoss d=2, p=2, mean B, mean T, sum C; modules.py:50), reduced in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, target, T, nw, nb, w, b):
+        _require_gpu(x)
+        dt = x.dtype
+        B, H, W, Cc = x.shape
+        N = w.shape[0]
+        norm = nw is not None
+        st = _gn_fwd(dt, x, Cc, None, 0, B, H, W, nw, nb) if norm else None
+        pred = torch.empty(B, T, N // T, H, W, dtype=torch.float32, device=x.device)
+        _conv(dt, _geo(B, H, W, H, W, 1, 1, 0), _csrc(x, Cc), None, _wfwd(w, dt), N, _csrc(pred, N, nchw=True), _pro(norm),
+              *(st[2:] if norm else (None, None)), bias=_f32c(b))
+        loss = torch.zeros((), dtype=torch.float32, device=x.device)
+        coef = None
+        if target is not None:
+            target = target.contiguous().float()
+            if target.shape != pred.shape:
+                raise L.BubbleformerHipError(f"target shape {tuple(target.shape)} != prediction shape {tuple(pred.shape)}")
+            coef = torch.empty(B * N, dtype=torch.float32, device=x.device)
+            ws = torch.empty(4 * B * N, dtype=torch.float32, device=x.device)
+            L.check(L.lib().bf_unet_lploss_fwd(_p(pred), _p(target), B, T, N // T, H * W, _p(loss), _p(coef), _p(ws), _stream()),
+                    "bf_unet_lploss_fwd")
+        ctx.norm, ctx.fused = norm, target is not None
+        ctx.save_for_backward(x, w, nw if norm else w, pred, target if target is not None else pred, coef if coef is not None else pred,
+                              *(st if norm else ()))
+        ctx.set_materialize_grads(False)
+        return pred, loss
+
+    @staticmethod
+    def backward(ctx, dpred, dloss):
+        x, w, nw, pred, target, coef, *st = ctx.saved_tensors
+        norm = ctx.norm
+        if ctx.fused and dpred is not None:
+            raise L.BubbleformerHipError("a gradient w.r.t. the prediction is not supported beside the fused loss")
+        if (dloss if ctx.fused else dpred) is None:
+            return (None,) * 7
+        dt = x.dtype
+        B, H, W, Cc = x.shape
+        N = w.shape[0]
+        f32 = dict(dtype=torch.float32, device=x.device)
+        if ctx.fused:
+            dpred = torch.empty_like(pred)
+            L.check(L.lib().bf_unet_lploss_bwd(_p(pred), _p(target), _p(coef), _p(dloss.contiguous().float().reshape(1)), B * N, H * W, _p(dpred),
+                                               _stream()), "bf_unet_lploss_bwd")
+        else:
+            dpred = dpred.contiguous().float()
+        g = _geo(B, H, W, H, W, 1, 1, 0)
+        dw = torch.empty(N, Cc, **f32)
+        db = torch.empty(N, **f32)
+        _wgrad(dt, g, _csrc(dpred, N, nchw=True), _csrc(x, Cc), None, Cc, dw, _pro(norm), *(st[2:] if norm else (None, None)))
+        _colsum(dt, _csrc(dpred, N, nchw=True), B, H, W, db)
+        dA = torch.empty(B * H * W, Cc, **f32)
+        _conv(dt, g, _csrc(dpred, N, nchw=True), None, _wswap(w, dt), Cc, _csrc(dA, Cc), transposed=True)
+        dnw = torch.empty(Cc, **f32) if norm else None
+        dnb = torch.empty(Cc, **f32) if norm else None
+        dx, _ = _gn_bwd(dt, dA, x, Cc, None, 0, B, H, W, nw if norm else None, st if norm else None, None, 0, dnw, dnb)
+        return dx, None, None, dnw, dnb, dw.view(N, Cc, 1, 1), db
+
+
+def unet_proj(x, w, b, compute_dtype):
+    return _ProjFn.apply(x, w, b, compute_dtype)
+
+
+def unet_down(x, w, b):
+    return _DownFn.apply(x, w, b)
+
+
+def unet_up(x, w, b):
+    return _UpFn.apply(x, w, b)
+
+
+def unet_final(x, T, nw, nb, w, b, target=None):
+    """-> (pred (B, T, C, H, W) fp32, loss); only ``loss`` carries gradient when ``target`` is given."""
+    return _FinalFn.apply(x, target, T, nw, nb, w, b)

@@ -473,6 +473,53 @@ int bf_debed_bwd(const bf_dims* d, const bf_debed_params* p, const bf_debed_para
                  const float* pred, const float* target, const float* loss_scale, void* dx, void* saved, void* scratch,
                  bf_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------------- ModernUnet (conv.hip)
+ * Replaces, for models/unets.py:67-209 (ModernUnet) and layers/conv_layers.py:5-86 (ResidualBlock, MiddleBlock):
+ *   bf_conv_fwd ......... nn.Conv2d 1x1 / 3x3 s1 / 3x3 s2 (unets.py:93,37-62; conv_layers.py:28-29,34) and nn.ConvTranspose2d k4 s2 p1
+ *                         (unets.py:10-34, transposed = 1); with transposed = 1 also the data gradient of every conv
+ *   bf_conv_wgrad ....... their weight gradients (autograd); bf_conv_colsum their bias gradients
+ *   bf_gn_fwd / bf_gn_bwd nn.GroupNorm(8, C) + nn.GELU in front of every conv (conv_layers.py:38-39, unets.py:140,205)
+ *   bf_unet_lploss_* .... LpLoss(d=2, p=2, reduce_dims=[0,1,2], reductions=[mean, mean, sum]) (modules.py:50, utils/losses.py:67-94)
+ * A bf_conv_src is one activation tensor: element (frame, y, x, c) at ((frame*H + y)*W + x)*C + c (channels-last), or, with nchw = 1,
+ * at ((frame*C + c)*H + y)*W + x (the reference's (B, T*C, H, W) clip / prediction).  f32 = 1: fp32 storage, else the call's dtype.
+ * Two sources are concatenated along channels (torch.cat((x, s), 1)) without being materialised. */
+enum { BF_CONV_PRO_NONE = 0, BF_CONV_PRO_AFFINE_GELU = 1 /* gelu(x*sc[f][c] + sh[f][c]) */, BF_CONV_PRO_GELU = 2 /* gelu(x) */ };
+typedef struct bf_conv_src {
+    const void* p;
+    int32_t C, nchw, f32;
+} bf_conv_src;
+/* F frames; input Hi x Wi, output Ho x Wo; kernel kh x kw, stride, pad (the forward conv's, also when transposed) */
+typedef struct bf_conv_geo {
+    int32_t F, Hi, Wi, Ho, Wo, kh, kw, stride, pad;
+} bf_conv_geo;
+/* out[f][oy][ox][n] = bias[n] + resid + sum_(tap, c) w[tap][c][n] * pro(src(f, iy, ix, c)); w: [kh*kw][C0+C1][N] in the dtype.
+ * transposed = 0: iy = oy*stride - pad + ky.  transposed = 1: iy = (oy + pad - ky) / stride where exact (no prologue).
+ * The prologue is applied to in-bounds taps only; padding taps are zeros.  sc / sh: [F][C0+C1]. */
+int bf_conv_fwd(int dtype, const bf_conv_geo* geo, const bf_conv_src* s0, const bf_conv_src* s1, int pro, const float* sc, const float* sh,
+                const void* w, int N, const float* bias, const bf_conv_src* resid, const bf_conv_src* out, int transposed, bf_stream_t stream);
+/* dw[r][(ky*kw + kx)*Cs + c] (+)= sum over output pixels m of rows(m, r) * pro(src(m, tap, c)) (forward-mode gather), in fixed-order slabs */
+int64_t bf_conv_wgrad_ws_floats(int R, int K, int64_t M);
+int bf_conv_wgrad(int dtype, const bf_conv_geo* geo, const bf_conv_src* rows, const bf_conv_src* s0, const bf_conv_src* s1, int pro,
+                  const float* sc, const float* sh, float* dw, int accumulate, float* ws, int64_t ws_floats, bf_stream_t stream);
+/* out[c] (+)= sum over pixels of src; ws: 64 * C floats */
+int bf_conv_colsum(int dtype, const bf_conv_src* src, int F, int H, int W, float* out, int accumulate, float* ws, int64_t ws_floats,
+                   bf_stream_t stream);
+/* GroupNorm(G) statistics over the concatenation of s0 and s1 (fp64 partial sums, fixed order): mean / rstd [F][G], sc / sh [F][C] */
+int64_t bf_gn_ws_floats(int F, int C, int G);
+int bf_gn_fwd(int dtype, const bf_conv_src* s0, const bf_conv_src* s1, int F, int H, int W, int G, const float* gamma, const float* beta,
+              float eps, float* mean, float* rstd, float* sc, float* sh, float* ws, bf_stream_t stream);
+/* dA: [F*H*W][C] fp32 gradient w.r.t. gelu(gn(x)).  dx0 / dx1 (stored, the sources' layouts) = d/dx (+ add[F*H*W][C]); dgamma / dbeta
+ * (+)= (accumulate).  gamma = NULL: no norm (the prologue was gelu(x)). */
+int bf_gn_bwd(int dtype, const float* dA, const bf_conv_src* s0, const bf_conv_src* s1, int F, int H, int W, int G, const float* gamma,
+              const float* mean, const float* rstd, const float* sc, const float* sh, const bf_conv_src* add, const bf_conv_src* dx0,
+              const bf_conv_src* dx1, float* dgamma, float* dbeta, int accumulate, float* ws, bf_stream_t stream);
+/* pred, target: (B, T, C, HW) fp32; loss[0]; coef: [B*T*C]; ws: 4 * B*T*C floats */
+int bf_unet_lploss_fwd(const float* pred, const float* target, int B, int T, int C, int64_t HW, float* loss, float* coef, float* ws,
+                       bf_stream_t stream);
+/* dpred = dloss[0] * coef[plane] * (pred - target) */
+int bf_unet_lploss_bwd(const float* pred, const float* target, const float* coef, const float* dloss, int planes, int64_t HW, float* dpred,
+                       bf_stream_t stream);
+
 /* Optional per-launch HIP-event timing on the launch stream (bench.py's roofline leg); off by default. */
 void bf_prof_enable(int on);
 int bf_prof_report(char* buf, int n);   /* JSON {kernel: {calls, ms, flops, bytes}}; bytes written or -1 */

@@ -1,0 +1,267 @@
+"""GPU: the ModernUnet kernels (csrc/conv.hip) and model against fp64 -- conv forward / data gradient / weight gradient for 1x1, 3x3 s1,
+3x3 s2 and the transposed 4x4 s2, with and without the GroupNorm + GELU prologue, one and two (concatenated) sources, edge shapes; the
+model against the reference goldens and, at full width, against the fp64 restatement; bit reproducibility; training through TrainStep."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import unet_restatement as U
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _rel(a, b):
+    a, b = a.detach().double().flatten(), b.detach().double().flatten()
+    return float((a - b).norm() / b.norm().clamp_min(1e-300))
+
+
+def _check(got, want, tol, what, chdim):
+    """rel-L2 over the whole tensor and over every block of 16 channels along `chdim`."""
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    if _structurally_zero(want):
+        assert float(got.abs().max()) <= tol, (what, float(got.abs().max()))
+        return
+    assert _rel(got, want) <= tol, (what, _rel(got, want))
+    C = want.shape[chdim]
+    for c0 in range(0, C, 16):
+        g, w = got.narrow(chdim, c0, min(16, C - c0)), want.narrow(chdim, c0, min(16, C - c0))
+        if w.abs().max() > 0:
+            assert _rel(g, w) <= tol, (what, "channels %d.." % c0, _rel(g, w))
+
+
+def _structurally_zero(want) -> bool:
+    """A conv bias whose output goes straight into a GroupNorm with one channel per group (8 channels) has an exactly zero gradient: the
+    norm removes a per-channel constant.  Its fp64 value is rounding noise, so it is held to an absolute bound instead."""
+    return float(want.detach().abs().max()) < 1e-9
+
+
+def _randn(*shape, scale=1.0, seed=0):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).to(DEV)
+
+
+TOL = {torch.float32: 1e-5, torch.bfloat16: 1e-2}
+
+
+def _q(t, dt):
+    """The fp64 reference sees what the native path stores: inputs and weights rounded to the compute dtype."""
+    return t.to(dt).double() if t is not None else None
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,H,W,C0,C1,Cout,norm", [
+    (1, 3, 5, 8, 0, 8, True),          # identity shortcut, 3x5 frame
+    (3, 6, 6, 24, 16, 24, True),       # two sources, group 4 (channels 20..24) straddles them; 3 frames
+    (2, 6, 6, 40, 0, 24, False),       # prologue GELU only, 1x1 shortcut
+    (1, 3, 3, 2048, 512, 512, True),   # 2560 channels, groups of 320 straddling 2048 + 512
+])
+def test_residual_block_vs_fp64(dt, B, H, W, C0, C1, Cout, norm):
+    """conv 3x3 s1 and 1x1 forward / data gradient / weight gradient with the prologue on and off, through ops.res_block."""
+    from bubbleformer_amd import ops
+    Cin = C0 + C1
+    p = dict(w1=_randn(Cout, Cin, 3, 3, scale=(9 * Cin) ** -0.5, seed=1), b1=_randn(Cout, scale=0.1, seed=2),
+             w2=_randn(Cout, Cout, 3, 3, scale=(9 * Cout) ** -0.5, seed=3), b2=_randn(Cout, scale=0.1, seed=4))
+    if norm:
+        p.update(n1w=1 + _randn(Cin, scale=0.1, seed=5), n1b=_randn(Cin, scale=0.1, seed=6), n2w=1 + _randn(Cout, scale=0.1, seed=7),
+                 n2b=_randn(Cout, scale=0.1, seed=8))
+    if Cin != Cout:
+        p.update(scw=_randn(Cout, Cin, 1, 1, scale=Cin ** -0.5, seed=9), scb=_randn(Cout, scale=0.1, seed=10))
+    x = _q(_randn(B, C0, H, W, seed=11) * 2 + 0.5, dt)
+    s = _q(_randn(B, C1, H, W, seed=12), dt) if C1 else None
+    dout = _q(_randn(B, Cout, H, W, seed=13), dt)
+    p = {k: (_q(v, dt) if k[0] in "ws" else v) for k, v in p.items()}
+    # fp64 reference
+    ref = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+    xr = x.clone().requires_grad_(True)
+    sr = s.clone().requires_grad_(True) if s is not None else None
+    xin = torch.cat((xr, sr), 1) if s is not None else xr
+    a1 = F.gelu(F.group_norm(xin, 8, ref["n1w"], ref["n1b"], 1e-5) if norm else xin)
+    h = F.conv2d(a1, ref["w1"], ref["b1"], padding=1)
+    a2 = F.gelu(F.group_norm(h, 8, ref["n2w"], ref["n2b"], 1e-5) if norm else h)
+    out_r = F.conv2d(a2, ref["w2"], ref["b2"], padding=1) + (F.conv2d(xin, ref["scw"], ref["scb"]) if "scw" in ref else xin)
+    out_r.backward(dout)
+    # native
+    nat = {k: v.float().clone().requires_grad_(True) for k, v in p.items()}
+    cl = lambda t: t.permute(0, 2, 3, 1).to(dt).contiguous()
+    xn = cl(x).requires_grad_(True)
+    sn = cl(s).requires_grad_(True) if s is not None else None
+    out = ops.res_block(xn, sn, nat.get("n1w"), nat.get("n1b"), nat["w1"], nat["b1"], nat.get("n2w"), nat.get("n2b"), nat["w2"], nat["b2"],
+                        nat.get("scw"), nat.get("scb"))
+    out.backward(cl(dout))
+    torch.cuda.synchronize()
+    tol = TOL[dt]
+    _check(out.permute(0, 3, 1, 2), out_r, tol, "out", 1)
+    _check(xn.grad.permute(0, 3, 1, 2), xr.grad, tol, "dx", 1)
+    if s is not None:
+        _check(sn.grad.permute(0, 3, 1, 2), sr.grad, tol, "ds", 1)
+    for k in p:
+        _check(nat[k].grad, ref[k].grad, tol, "d" + k, 0)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,H,W,Cc", [(1, 3, 5, 8), (3, 6, 6, 24), (2, 6, 6, 40)])
+def test_down_and_up_sampling_vs_fp64(dt, B, H, W, Cc):
+    """3x3 stride-2 conv (data gradient: 1- / 2-tap phases) and ConvTranspose2d k4 s2 p1 (four 2x2-tap phases)."""
+    from bubbleformer_amd import ops
+    tol = TOL[dt]
+    cl = lambda t: t.permute(0, 2, 3, 1).to(dt).contiguous()
+    for kind in ("down", "up"):
+        k = 3 if kind == "down" else 4
+        w = _q(_randn(Cc, Cc, k, k, scale=(k * k * Cc) ** -0.5, seed=21), dt)
+        b = _randn(Cc, scale=0.1, seed=22)
+        x = _q(_randn(B, Cc, H, W, seed=23), dt)
+        wr, br, xr = (t.clone().requires_grad_(True) for t in (w, b, x))
+        if kind == "down":
+            yr = F.conv2d(xr, wr, br, stride=2, padding=1)
+        else:
+            yr = F.conv_transpose2d(xr, wr, br, stride=2, padding=1)
+        dy = _q(_randn(*yr.shape, seed=24), dt)
+        yr.backward(dy)
+        wn, bn = w.float().clone().requires_grad_(True), b.float().clone().requires_grad_(True)
+        xn = cl(x).requires_grad_(True)
+        y = (ops.unet_down if kind == "down" else ops.unet_up)(xn, wn, bn)
+        y.backward(cl(dy))
+        torch.cuda.synchronize()
+        _check(y.permute(0, 3, 1, 2), yr, tol, kind + " out", 1)
+        _check(xn.grad.permute(0, 3, 1, 2), xr.grad, tol, kind + " dx", 1)
+        _check(wn.grad, wr.grad, tol, kind + " dw", 0)
+        _check(bn.grad, br.grad, tol, kind + " db", 0)
+
+
+def test_group_norm_two_sources_vs_fp64():
+    """GroupNorm statistics over a straddling concatenation, and its backward (GELU' folded in, dx split into both sources)."""
+    from bubbleformer_amd import ops
+    B, H, W, C0, C1 = 2, 5, 7, 24, 16
+    x, s = _randn(B, C0, H, W, seed=31) * 3 + 1, _randn(B, C1, H, W, seed=32)
+    gw, gb = 1 + _randn(C0 + C1, scale=0.1, seed=33), _randn(C0 + C1, scale=0.1, seed=34)
+    dA = _randn(B, C0 + C1, H, W, seed=35)
+    xr, sr, gwr, gbr = (t.clone().requires_grad_(True) for t in (x, s, gw, gb))
+    yr = F.gelu(F.group_norm(torch.cat((xr, sr), 1), 8, gwr, gbr, 1e-5))
+    yr.backward(dA)
+    cl = lambda t: t.permute(0, 2, 3, 1).float().contiguous()
+    xn, sn = cl(x), cl(s)
+    mean, rstd, sc, sh = ops._gn_fwd(torch.float32, xn, C0, sn, C1, B, H, W, gw.float(), gb.float())
+    y = F.gelu(torch.cat((xn, sn), 3) * sc[:, None, None, :] + sh[:, None, None, :])     # the prologue the convs apply
+    _check(y.permute(0, 3, 1, 2), yr, 1e-5, "gn fwd", 1)
+    dgw, dgb = torch.empty_like(gw.float()), torch.empty_like(gb.float())
+    dx, ds = ops._gn_bwd(torch.float32, cl(dA).reshape(-1, C0 + C1), xn, C0, sn, C1, B, H, W, gw.float().contiguous(), (mean, rstd, sc, sh),
+                         None, 0, dgw, dgb)
+    torch.cuda.synchronize()
+    _check(dx.permute(0, 3, 1, 2), xr.grad, 1e-5, "gn dx", 1)
+    _check(ds.permute(0, 3, 1, 2), sr.grad, 1e-5, "gn ds", 1)
+    _check(dgw, gwr.grad, 1e-5, "dgamma", 0)
+    _check(dgb, gbr.grad, 1e-5, "dbeta", 0)
+
+
+def _native(name_or_cfg, sd, dt=torch.float32):
+    from bubbleformer_amd.models import get_model
+    m = get_model("unet_modern", compute_dtype=dt, **name_or_cfg)
+    m.load_state_dict({k: v.float() for k, v in sd.items()})
+    return m.to(DEV)
+
+
+@pytest.mark.parametrize("name", ["h16_m122", "h16_m122_nonorm", "h8_m12", "h8_m0"])
+def test_model_fp32_vs_reference_goldens(name):
+    spec, z, sd = U.load_golden(name)
+    m = _native(spec["cfg"], sd)
+    x = torch.from_numpy(z["x"]).float().to(DEV).requires_grad_(True)
+    y = torch.from_numpy(z["y"]).float().to(DEV)
+    pred = m(x)
+    assert _rel(pred.cpu(), torch.from_numpy(z["pred"])) <= 1e-4
+    loss, pred2 = m.forward_loss(x, y)
+    loss.backward()
+    torch.cuda.synchronize()
+    assert torch.equal(pred, pred2)
+    assert abs(float(loss.detach()) - float(z["loss"])) <= 1e-4 * abs(float(z["loss"]))
+    assert _rel(x.grad.cpu(), torch.from_numpy(z["dx"])) <= 1e-4
+    grads = {k: p.grad for k, p in m.named_parameters()}
+    # every gradient against the goldens (whole, or through their sketch) ...
+    errs = U.golden_grad_errors(grads, z, zero_tol=1.0)
+    assert max(errs.values()) <= 1e-4, max(errs.items(), key=lambda kv: kv[1])
+    # ... and every gradient, whole, against the fp64 restatement of the same weights (pinned to the goldens by test_unet_modern.py)
+    _, _, dx_r, g_r = U.run(torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV), {k: v.to(DEV) for k, v in sd.items()},
+                            spec["cfg"])
+    assert _rel(x.grad, dx_r) <= 1e-4
+    for k, g in grads.items():
+        if _structurally_zero(g_r[k]):
+            assert float(g.abs().max()) <= 1e-4, k
+        else:
+            assert _rel(g, g_r[k]) <= 1e-4, k
+
+
+SHIPPED = dict(time_window=16, input_fields=4, output_fields=4, hidden_channels=32, ch_mults=[1, 2, 2, 4, 4], norm=True)
+
+
+def _shipped_weights():
+    from tools.gen_unet_golden import weights
+    from bubbleformer_amd.models.unets import ModernUnet
+    return weights(ModernUnet(**SHIPPED), 7)
+
+
+def test_full_width_parity_vs_fp64_restatement():
+    """Shipped config at T = 16, 4 fields, 96 x 96, batch 1 (down to 6 x 6 at 2048 channels).  fp32 mode against the fp64 restatement of
+    the same state_dict; bf16 mode against the fp64 restatement of the state_dict and clip rounded to bf16 (what its MFMAs consume)."""
+    sd = _shipped_weights()
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(1, 16, 4, 96, 96, generator=g, dtype=torch.float64)
+    y = torch.randn(1, 16, 4, 96, 96, generator=g, dtype=torch.float64)
+    for dt in (torch.float32, torch.bfloat16):
+        rnd = (lambda t: t) if dt == torch.float32 else (lambda t: t.bfloat16().double())
+        pred_r, loss_r, dx_r, g_r = U.run(rnd(x).to(DEV), y.to(DEV), {k: rnd(v).to(DEV) for k, v in sd.items()}, SHIPPED)
+        tol = 1e-4 if dt == torch.float32 else 2e-2
+        gtol = tol if dt == torch.float32 else 3e-2     # bf16: measured worst 2.7e-2 per tensor, at the 6 x 6 x 2048 levels
+        m = _native(SHIPPED, sd, dt)
+        xn = x.float().to(DEV).requires_grad_(True)
+        loss, pred = m.forward_loss(xn, y.float().to(DEV))
+        loss.backward()
+        torch.cuda.synchronize()
+        assert abs(float(loss.detach()) - float(loss_r)) <= tol * float(loss_r), dt
+        if dt == torch.float32:
+            assert _rel(pred, pred_r) <= tol
+            assert _rel(xn.grad, dx_r) <= tol
+        errs = {k: (float(p.grad.abs().max()) if _structurally_zero(g_r[k]) else _rel(p.grad, g_r[k])) for k, p in m.named_parameters()}
+        worst = sorted(errs.items(), key=lambda kv: -kv[1])[:8]
+        assert not [k for k, v in errs.items() if v > gtol], (dt, worst)
+        del m, pred_r, dx_r, g_r
+
+
+def test_bf16_training_pass_is_bit_reproducible():
+    sd = _shipped_weights()
+    m = _native(SHIPPED, sd, torch.bfloat16)
+    g = torch.Generator().manual_seed(9)
+    x = torch.randn(2, 16, 4, 192, 192, generator=g).to(DEV)
+    y = torch.randn(2, 16, 4, 192, 192, generator=g).to(DEV)
+    runs = []
+    for _ in range(2):
+        m.zero_grad(set_to_none=True)
+        loss, _ = m.forward_loss(x, y)
+        loss.backward()
+        torch.cuda.synchronize()
+        runs.append((loss.detach().clone(), {k: p.grad.clone() for k, p in m.named_parameters()}))
+    assert torch.equal(runs[0][0], runs[1][0])
+    for k in runs[0][1]:
+        assert torch.equal(runs[0][1][k], runs[1][1][k]), k
+
+
+@pytest.mark.parametrize("optimizer", ["adamw", "lion"])
+def test_train_step(optimizer):
+    from bubbleformer_amd.trainer import TrainStep
+    spec, z, sd = U.load_golden("h8_m12")
+    m = _native(spec["cfg"], sd)
+    x = torch.from_numpy(z["x"]).to(DEV)
+    y = torch.from_numpy(z["y"]).to(DEV)
+    step = TrainStep(m, lr=1e-3, optimizer=optimizer)
+    losses = [float(step(x.float(), None, y.float())) for _ in range(3)]
+    assert all(torch.isfinite(torch.tensor(losses)))
+    if optimizer == "lion":
+        assert losses[-1] < losses[0]
+        return
+    ref = {k: v.to(DEV).clone().requires_grad_(True) for k, v in sd.items()}
+    opt = torch.optim.AdamW(list(ref.values()), lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    for i in range(3):
+        opt.zero_grad()
+        loss = U.lp_loss(U.forward(x, ref, spec["cfg"]["time_window"], spec["cfg"]["ch_mults"], spec["cfg"]["norm"]), y)
+        loss.backward()
+        opt.step()
+        assert abs(losses[i] - float(loss)) <= 1e-4 * float(loss), (i, losses[i], float(loss))
