@@ -20,3 +20,4 @@ def install_into_reference() -> None:
     ref_api.MODELS["filmavit"] = axial_vit.FiLMConditionedAViT
     ref_api.MODELS["avit"] = axial_vit.AViT
     ref_api.MODELS["unet_modern"] = unets.ModernUnet
+    ref_api.MODELS["unet_classic"] = unets.ClassicUnet

@@ -186,6 +186,12 @@ SIGNATURES = {
                             P(ConvSrc), fp, fp, C.c_int, fp, vp]),
     "bf_unet_lploss_fwd": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, i64, fp, fp, fp, vp]),
     "bf_unet_lploss_bwd": (C.c_int, [fp, fp, fp, fp, C.c_int, i64, fp, vp]),
+    "bf_bn_ws_floats": (i64, [i64, C.c_int]),
+    "bf_bn_fwd": (C.c_int, [C.c_int, vp, C.c_int, i64, C.c_int, fp, fp, f32, f32, fp, fp, vp, fp, fp, fp, fp, fp, vp]),
+    "bf_bn_eval": (C.c_int, [C.c_int, C.c_int, fp, fp, f32, fp, fp, fp, fp, vp]),
+    "bf_bn_act": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, vp, vp, vp, vp]),
+    "bf_bn_bwd": (C.c_int, [C.c_int, fp, i64, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, fp, fp, C.c_int,
+                            fp, vp]),
 }
 
 _lib = None

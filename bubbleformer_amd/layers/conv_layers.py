@@ -1,4 +1,5 @@
-"""ResidualBlock and MiddleBlock -- mirror of bubbleformer/layers/conv_layers.py:5-86 (the ModernUnet blocks).
+"""ResidualBlock and MiddleBlock -- mirror of bubbleformer/layers/conv_layers.py:5-86 (the ModernUnet blocks) -- and ClassicUnetBlock
+(conv_layers.py:96-141, the ClassicUnet block).
 
 Constructor signatures, sub-module names and ``state_dict`` keys are the reference's; the sub-modules only hold the parameters.
 ``forward`` takes the reference's (B, C, H, W) tensor; inside the U-Net the blocks exchange channels-last (B, H, W, C) tensors in the
@@ -10,7 +11,7 @@ import torch.nn as nn
 
 from .. import ops
 
-__all__ = ["ResidualBlock", "MiddleBlock"]
+__all__ = ["ResidualBlock", "MiddleBlock", "ClassicUnetBlock"]
 
 
 def _check_gelu(activation) -> None:
@@ -66,3 +67,46 @@ class MiddleBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward_cl(_cl(x)).permute(0, 3, 1, 2)
+
+
+def bn_args(norm: nn.BatchNorm2d):
+    """(running_mean, running_var, num_batches_tracked, eps, momentum, training) of a BatchNorm2d, as ops' classic functions take them."""
+    if not (norm.affine and norm.track_running_stats):
+        raise NotImplementedError("the native BatchNorm2d needs affine=True and track_running_stats=True, as the reference builds it")
+    if norm.momentum is None:
+        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented; the reference uses 0.1")
+    return (norm.running_mean, norm.running_var, norm.num_batches_tracked, float(norm.eps), float(norm.momentum), norm.training)
+
+
+class ClassicUnetBlock(nn.Module):
+    """conv1 (3x3, no bias) -> norm1 (BatchNorm2d) -> act1 (GELU) -> conv2 -> norm2 -> act2.  The norms are real nn.BatchNorm2d modules:
+    train() / eval() select batch or running statistics, and training forwards update the running buffers on the device.
+
+    Inside the U-Net the block is split in two (ops.classic_conv / ops.classic_act or ops.classic_final): ``forward_conv`` returns the raw
+    conv2 output and the consumer applies norm2 + act2 -- materialised with the encoders' 2x2 max pool, or as the final conv's prologue."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels=in_channels, out_channels=out_channels, kernel_size=3, padding=1, bias=False)
+        self.norm1 = nn.BatchNorm2d(num_features=out_channels)
+        self.act1 = nn.GELU()
+        self.conv2 = nn.Conv2d(in_channels=out_channels, out_channels=out_channels, kernel_size=3, padding=1, bias=False)
+        self.norm2 = nn.BatchNorm2d(num_features=out_channels)
+        self.act2 = nn.GELU()
+
+    def forward_conv(self, x, skip=None, skip_port=None, compute_dtype=None, nchw=False):
+        """x (B, H, W, C) channels-last (or, with nchw, the (B, T, C, H, W) fp32 clip), skip: the decoder's skip activation, concatenated
+        after x.  -> raw conv2 output (B, H, W, out_channels)."""
+        _check_gelu(self.act1)
+        dt = compute_dtype if compute_dtype is not None else x.dtype
+        return ops.classic_conv(x, skip, skip_port, self.conv1.weight, self.norm1.weight, self.norm1.bias, self.conv2.weight,
+                                bn_args(self.norm1), dt, nchw)
+
+    def act(self, c, pool=False):
+        """norm2 + act2 of forward_conv's output -> (a, port) or (a, port, maxpool2x2(a))."""
+        _check_gelu(self.act2)
+        return ops.classic_act(c, self.norm2.weight, self.norm2.bias, bn_args(self.norm2), pool)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (B, in_ch, H, W) -> (B, out_ch, H, W) (a permuted view of channels-last memory)."""
+        return self.act(self.forward_conv(_cl(x)))[0].permute(0, 3, 1, 2)

@@ -1284,3 +1284,327 @@ def unet_up(x, w, b):
 def unet_final(x, T, nw, nb, w, b, target=None):
     """-> (pred (B, T, C, H, W) fp32, loss); only ``loss`` carries gradient when ``target`` is given."""
     return _FinalFn.apply(x, target, T, nw, nb, w, b)
+
+
+# ------------------------------------------------------------------------------------------------ ClassicUnet (conv.hip + bn.hip)
+# A ClassicUnetBlock is conv1 -> BN1 -> GELU -> conv2 -> BN2 -> GELU with bias-free 3x3 convs.  BN1 + GELU is conv2's operand prologue
+# (never materialised); BN2 + GELU belongs to the block's consumer: bf_bn_act materialises it (and the 2x2 max pool of an encoder), the
+# final 1x1 conv takes it as its prologue.  An activation `a` that feeds another layer's input travels with a gradient PORT: a zero-
+# storage fp32 tensor of a's shape whose gradient is the fp32 data gradient the consumer computed for `a` (the skip half of a decoder's
+# conv1, an upconv's data gradient).  bf_bn_bwd reads it as it stands, beside the pooled gradient, so the gradient of an encoder output is
+# never rounded to the compute dtype and never summed by a PyTorch op.  `bn` below is a BatchNorm2d's (running_mean, running_var,
+# num_batches_tracked, eps, momentum, training): training mode normalises with the batch statistics and updates the buffers on the device.
+
+
+def _check_operands(dev, **named) -> None:
+    """Every tensor a launch reads or writes must live on the launching input's GPU: a host (or other-device) address handed to a kernel
+    faults.  Checked before the first launch of each classic function, since its convs have no bias to stop them earlier."""
+    for name, t in named.items():
+        if t is not None and t.device != dev:
+            raise L.BubbleformerHipError(f"{name} is on {t.device} but the input is on {dev}: move the model to the input's device")
+
+
+def _check_act(dt, **named) -> None:
+    """Activations the kernels address as dense channels-last (or NCHW) memory: contiguous, in the compute dtype or fp32."""
+    for name, t in named.items():
+        if t is not None and (not t.is_contiguous() or t.dtype not in (dt, torch.float32)):
+            raise L.BubbleformerHipError(f"{name} must be a contiguous {dt} or float32 tensor; got {t.dtype}, strides {t.stride()}")
+
+
+def _check_bn(dev, C: int, gamma, beta, bn) -> None:
+    """A BatchNorm2d's affine parameters and buffers, as bf_bn_fwd / bf_bn_eval read them: C fp32 values each on `dev`, an int64 counter."""
+    rm, rv, nbt = bn[:3]
+    _check_operands(dev, weight=gamma, bias=beta, running_mean=rm, running_var=rv, num_batches_tracked=nbt)
+    for name, t in (("weight", gamma), ("bias", beta), ("running_mean", rm), ("running_var", rv)):
+        if t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous():
+            raise L.BubbleformerHipError(f"BatchNorm2d {name} must be {C} contiguous fp32 values; got {tuple(t.shape)} {t.dtype}")
+    if nbt.dtype != torch.int64 or nbt.numel() != 1:
+        raise L.BubbleformerHipError(f"BatchNorm2d num_batches_tracked must be one int64; got {tuple(nbt.shape)} {nbt.dtype}")
+
+
+def _port(like: torch.Tensor) -> torch.Tensor:
+    return torch.empty_strided(like.shape, (0,) * like.dim(), dtype=torch.float32, device=like.device)
+
+
+def _bn_stats(dt, c, gamma, beta, bn):
+    """-> (mean, rstd, sc, sh) of BatchNorm2d over the channels-last conv output c (B, H, W, C); mean / rstd are None in eval mode."""
+    rm, rv, nbt, eps, momentum, training = bn
+    B, H, W, Cc = c.shape
+    dev = c.device
+    sc = torch.empty(B, Cc, dtype=torch.float32, device=dev)
+    sh = torch.empty_like(sc)
+    lib = L.lib()
+    if not training:
+        L.check(lib.bf_bn_eval(B, Cc, _p(_f32c(gamma)), _p(_f32c(beta)), float(eps), _p(rm), _p(rv), _p(sc), _p(sh), _stream()), "bf_bn_eval")
+        return None, None, sc, sh
+    mean = torch.empty(Cc, dtype=torch.float32, device=dev)
+    rstd = torch.empty_like(mean)
+    ws = _ws(lib.bf_bn_ws_floats(B * H * W, Cc), dev, "bf_bn_ws_floats")
+    L.check(lib.bf_bn_fwd(_dt(dt), _p(c), B, H * W, Cc, _p(_f32c(gamma)), _p(_f32c(beta)), float(eps), float(momentum), _p(rm), _p(rv), _p(nbt),
+                          _p(mean), _p(rstd), _p(sc), _p(sh), _p(ws), _stream()), "bf_bn_fwd")
+    return mean, rstd, sc, sh
+
+
+def _rows_view(g: torch.Tensor):
+    """(tensor, row stride) of an fp32 (B, H, W, C) gradient whose pixels are rows of a wider buffer (a channel slice), or contiguous."""
+    B, H, W, Cc = g.shape
+    s = g.stride()
+    if g.dtype == torch.float32 and s[3] == 1 and s[2] >= Cc and s[1] == W * s[2] and s[0] == H * s[1]:
+        return g, s[2]
+    return g.float().contiguous(), Cc
+
+
+def _bn_bwd(dt, dA, dP, idx, c, gamma, st):
+    """dA: fp32 (B, H, W, C) gradient w.r.t. gelu(bn(c)) or None; dP: gradient of its 2x2 max pool or None -> (dc, dgamma, dbeta)."""
+    mean, rstd, sc, sh = st
+    B, H, W, Cc = c.shape
+    dev = c.device
+    lib = L.lib()
+    ldA = 0
+    if dA is not None:
+        dA, ldA = _rows_view(dA)
+    if dP is not None:
+        dP = dP.to(dt).contiguous()
+    dc = torch.empty_like(c)
+    dg = torch.empty(Cc, dtype=torch.float32, device=dev)
+    db = torch.empty_like(dg)
+    ws = _ws(lib.bf_bn_ws_floats(B * H * W, Cc), dev, "bf_bn_ws_floats")
+    L.check(lib.bf_bn_bwd(_dt(dt), _p(dA), ldA, 0, _p(dP), _p(idx), _p(c), B, H, W, Cc, _p(_f32c(gamma)), _p(mean), _p(rstd), _p(sc), _p(sh),
+                          _p(dc), _p(dg), _p(db), 0, _p(ws), _stream()), "bf_bn_bwd")
+    return dc, dg, db
+
+
+def _eval_bn_backward():
+    return L.BubbleformerHipError("backward through an eval-mode BatchNorm2d is not implemented: train in model.train() mode")
+
+
+class _ClassicConvFn(torch.autograd.Function):
+    """conv1 (3x3, no bias) on cat(x0, x1) -> BN1 statistics -> conv2 (3x3, no bias) with BN1 + GELU as its prologue -> c2, the raw
+    conv2 output (BN2 + GELU are applied by the consumer).  x0: the (B, T, C, H, W) fp32 clip (nchw) or a channels-last activation;
+    x1: the skip activation of a decoder.  Its gradient leaves in fp32 through `port1` when one is given (the U-Net's encoder outputs, read
+    in place by bf_bn_bwd), otherwise as x1's own gradient in x1's dtype."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, port1, w1, g1, b1, w2, bn1, nchw, dt):
+        _require_gpu(x0)
+        if nchw:
+            B, T, Cf, H, W = x0.shape
+            C0 = T * Cf
+        else:
+            B, H, W, C0 = x0.shape
+        C1 = 0 if x1 is None else x1.shape[3]
+        Cout = w1.shape[0]
+        if w1.shape[1] != C0 + C1:
+            raise L.BubbleformerHipError(f"conv1 expects {w1.shape[1]} input channels, got {C0 + C1}")
+        _check_operands(x0.device, skip=x1, conv1_weight=w1, conv2_weight=w2)
+        _check_act(torch.float32 if nchw else dt, x=x0, skip=x1)
+        _check_bn(x0.device, Cout, g1, b1, bn1)
+        g3 = _geo(B, H, W, H, W, 3, 1, 1)
+        c1 = torch.empty(B, H, W, Cout, dtype=dt, device=x0.device)
+        _conv(dt, g3, _csrc(x0, C0, nchw), _csrc(x1, C1), _wfwd(w1, dt), Cout, _csrc(c1, Cout))
+        st1 = _bn_stats(dt, c1, g1, b1, bn1)
+        c2 = torch.empty_like(c1)
+        _conv(dt, g3, _csrc(c1, Cout), None, _wfwd(w2, dt), Cout, _csrc(c2, Cout), L.BF_CONV_PRO_AFFINE_GELU, st1[2], st1[3])
+        ctx.nchw, ctx.has_x1, ctx.has_port, ctx.training, ctx.C0, ctx.dt = nchw, x1 is not None, port1 is not None, bn1[5], C0, dt
+        ctx.save_for_backward(x0, x1 if x1 is not None else c1, w1, g1, w2, c1, *(st1 if bn1[5] else st1[2:]))
+        return c2
+
+    @staticmethod
+    def backward(ctx, dc2):
+        if not ctx.training:
+            raise _eval_bn_backward()
+        x0, x1, w1, g1, w2, c1, *st1 = ctx.saved_tensors
+        x1 = x1 if ctx.has_x1 else None
+        dt, C0, nchw = ctx.dt, ctx.C0, ctx.nchw
+        B, H, W, Cout = c1.shape
+        C1 = 0 if x1 is None else x1.shape[3]
+        Cin = C0 + C1
+        f32 = dict(dtype=torch.float32, device=c1.device)
+        g3 = _geo(B, H, W, H, W, 3, 1, 1)
+        dc2 = dc2.to(dt).contiguous()
+        # conv2 (prologue BN1 + GELU) and BN1
+        dw2 = torch.empty(Cout, 9 * Cout, **f32)
+        _wgrad(dt, g3, _csrc(dc2, Cout), _csrc(c1, Cout), None, 9 * Cout, dw2, L.BF_CONV_PRO_AFFINE_GELU, st1[2], st1[3])
+        dA2 = torch.empty(B, H, W, Cout, **f32)
+        _conv(dt, g3, _csrc(dc2, Cout), None, _wswap(w2, dt), Cout, _csrc(dA2, Cout), transposed=True)
+        dc1, dg1, db1 = _bn_bwd(dt, dA2, None, None, c1, g1, st1)
+        del dA2
+        # conv1 over cat(x0, x1)
+        dw1 = torch.empty(Cout, 9 * Cin, **f32)
+        _wgrad(dt, g3, _csrc(dc1, Cout), _csrc(x0, C0, nchw), _csrc(x1, C1), 9 * Cin, dw1)
+        dx0 = dx1 = dport = None
+        if ctx.needs_input_grad[0]:
+            dx0 = torch.empty_like(x0)
+            _conv(dt, g3, _csrc(dc1, Cout), None, _wswap(w1[:, :C0], dt), C0, _csrc(dx0, C0, nchw), transposed=True)
+        if x1 is not None and (ctx.needs_input_grad[2] if ctx.has_port else ctx.needs_input_grad[1]):
+            d1 = torch.empty(B, H, W, C1, **f32) if ctx.has_port else torch.empty_like(x1)
+            _conv(dt, g3, _csrc(dc1, Cout), None, _wswap(w1[:, C0:], dt), C1, _csrc(d1, C1), transposed=True)
+            dx1, dport = (None, d1) if ctx.has_port else (d1, None)
+        dw1 = dw1.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+        dw2 = dw2.view(Cout, 3, 3, Cout).permute(0, 3, 1, 2).contiguous()
+        return dx0, dx1, dport, dw1, dg1, db1, dw2, None, None, None
+
+
+class _BnActFn(torch.autograd.Function):
+    """BN2 + GELU of a block, materialised: a = gelu(bn(c)) and, with pool, p = MaxPool2d(2, 2)(a) -> (a, port[, p]).
+    Backward: bf_bn_bwd with the port's fp32 gradient (skip / upconv) and the pooled gradient together."""
+
+    @staticmethod
+    def forward(ctx, c, g, b, bn, pool):
+        _require_gpu(c)
+        dt = c.dtype
+        B, H, W, Cc = c.shape
+        _check_bn(c.device, Cc, g, b, bn)
+        _check_act(dt, c=c)
+        st = _bn_stats(dt, c, g, b, bn)
+        a = torch.empty_like(c)
+        p = idx = None
+        if pool:
+            p = torch.empty(B, H // 2, W // 2, Cc, dtype=dt, device=c.device)
+            idx = torch.empty(B, H // 2, W // 2, Cc, dtype=torch.uint8, device=c.device)
+        L.check(L.lib().bf_bn_act(_dt(dt), _p(c), B, H, W, Cc, _p(st[2]), _p(st[3]), _p(a), _p(p), _p(idx), _stream()), "bf_bn_act")
+        port = _port(a)
+        ctx.training, ctx.pool = bn[5], pool
+        ctx.save_for_backward(c, g, *(st if bn[5] else st[2:]), *((idx,) if pool else ()))
+        ctx.set_materialize_grads(False)
+        return (a, port, p) if pool else (a, port)
+
+    @staticmethod
+    def backward(ctx, da, dport, dp=None):
+        if not ctx.training:
+            raise _eval_bn_backward()
+        c, g, *st = ctx.saved_tensors
+        idx = st.pop() if ctx.pool else None
+        dA = dport
+        if da is not None:           # `a` used directly (ClassicUnetBlock.forward outside the U-Net): its gradient is in the compute dtype
+            dA = da.float() if dA is None else dA + da.float()
+        if dA is None and dp is None:
+            return None, None, None, None, None
+        dc, dg, db = _bn_bwd(c.dtype, dA, dp, idx, c, g, st)
+        return dc, dg, db, None, None
+
+
+class _UpConv2Fn(torch.autograd.Function):
+    """ConvTranspose2d(Cin, Cout, 2, stride 2) (unets.py:252-284): the transposed gather with four parity phases of one tap each.  Its data
+    gradient is the forward gather with stride 2, its weight gradient the forward-gather weight GEMM with input and output swapped.  With a
+    port, x's gradient leaves in fp32 through the port; without, in x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, port, w, b):
+        _require_gpu(x)
+        dt = x.dtype
+        B, H, W, Cin = x.shape
+        Cout = w.shape[1]
+        if w.shape[0] != Cin or tuple(w.shape[2:]) != (2, 2):
+            raise L.BubbleformerHipError(f"upconv weight {tuple(w.shape)} does not fit {Cin} input channels, kernel 2")
+        _check_operands(x.device, upconv_weight=w, upconv_bias=b)
+        _check_act(dt, x=x)
+        out = torch.empty(B, 2 * H, 2 * W, Cout, dtype=dt, device=x.device)
+        _conv(dt, _geo(B, H, W, 2 * H, 2 * W, 2, 2, 0), _csrc(x, Cin), None, _wswap(w, dt), Cout, _csrc(out, Cout), bias=_f32c(b),
+              transposed=True)
+        ctx.has_port = port is not None
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dt = x.dtype
+        dout = dout.to(dt).contiguous()
+        B, H, W, Cin = x.shape
+        Cout = w.shape[1]
+        f32 = dict(dtype=torch.float32, device=x.device)
+        g = _geo(B, 2 * H, 2 * W, H, W, 2, 2, 0)
+        dw = torch.empty(Cin, 4 * Cout, **f32)        # [Cin][(ky, kx, Cout)]
+        db = torch.empty(Cout, **f32)
+        _wgrad(dt, g, _csrc(x, Cin), _csrc(dout, Cout), None, 4 * Cout, dw)
+        _colsum(dt, _csrc(dout, Cout), B, 2 * H, 2 * W, db)
+        dx = dport = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            d = torch.empty(B, H, W, Cin, **f32) if ctx.has_port else torch.empty_like(x)
+            _conv(dt, g, _csrc(dout, Cout), None, _wfwd(w, dt), Cin, _csrc(d, Cin))
+            dx, dport = (None, d) if ctx.has_port else (d, None)
+        return dx, dport, dw.view(Cin, 2, 2, Cout).permute(0, 3, 1, 2).contiguous(), db
+
+
+class _ClassicFinalFn(torch.autograd.Function):
+    """conv(gelu(bn2(c))) of the last decoder (unets.py:290-319): BN2 statistics, then the 1x1 conv with BN2 + GELU as its prologue writing
+    the (B, T, C_out, H, W) fp32 prediction in place; with ``target`` also the fused relative-L2 loss, as _FinalFn."""
+
+    @staticmethod
+    def forward(ctx, c, target, T, g, b, bn, w, bias):
+        _require_gpu(c)
+        dt = c.dtype
+        B, H, W, Cc = c.shape
+        N = w.shape[0]
+        _check_operands(c.device, conv_weight=w, conv_bias=bias, target=target)
+        _check_bn(c.device, Cc, g, b, bn)
+        _check_act(dt, c=c)
+        st = _bn_stats(dt, c, g, b, bn)
+        pred = torch.empty(B, T, N // T, H, W, dtype=torch.float32, device=c.device)
+        _conv(dt, _geo(B, H, W, H, W, 1, 1, 0), _csrc(c, Cc), None, _wfwd(w, dt), N, _csrc(pred, N, nchw=True), L.BF_CONV_PRO_AFFINE_GELU,
+              st[2], st[3], bias=_f32c(bias))
+        loss = torch.zeros((), dtype=torch.float32, device=c.device)
+        coef = None
+        if target is not None:
+            target = target.contiguous().float()
+            if target.shape != pred.shape:
+                raise L.BubbleformerHipError(f"target shape {tuple(target.shape)} != prediction shape {tuple(pred.shape)}")
+            coef = torch.empty(B * N, dtype=torch.float32, device=c.device)
+            ws = torch.empty(4 * B * N, dtype=torch.float32, device=c.device)
+            L.check(L.lib().bf_unet_lploss_fwd(_p(pred), _p(target), B, T, N // T, H * W, _p(loss), _p(coef), _p(ws), _stream()),
+                    "bf_unet_lploss_fwd")
+        ctx.fused, ctx.training = target is not None, bn[5]
+        ctx.save_for_backward(c, g, w, pred, target if target is not None else pred, coef if coef is not None else pred,
+                              *(st if bn[5] else st[2:]))
+        ctx.set_materialize_grads(False)
+        return pred, loss
+
+    @staticmethod
+    def backward(ctx, dpred, dloss):
+        c, g, w, pred, target, coef, *st = ctx.saved_tensors
+        if ctx.fused and dpred is not None:
+            raise L.BubbleformerHipError("a gradient w.r.t. the prediction is not supported beside the fused loss")
+        if (dloss if ctx.fused else dpred) is None:
+            return (None,) * 8
+        if not ctx.training:
+            raise _eval_bn_backward()
+        dt = c.dtype
+        B, H, W, Cc = c.shape
+        N = w.shape[0]
+        f32 = dict(dtype=torch.float32, device=c.device)
+        if ctx.fused:
+            dpred = torch.empty_like(pred)
+            L.check(L.lib().bf_unet_lploss_bwd(_p(pred), _p(target), _p(coef), _p(dloss.contiguous().float().reshape(1)), B * N, H * W, _p(dpred),
+                                               _stream()), "bf_unet_lploss_bwd")
+        else:
+            dpred = dpred.contiguous().float()
+        geo = _geo(B, H, W, H, W, 1, 1, 0)
+        dw = torch.empty(N, Cc, **f32)
+        db = torch.empty(N, **f32)
+        _wgrad(dt, geo, _csrc(dpred, N, nchw=True), _csrc(c, Cc), None, Cc, dw, L.BF_CONV_PRO_AFFINE_GELU, st[2], st[3])
+        _colsum(dt, _csrc(dpred, N, nchw=True), B, H, W, db)
+        dA = torch.empty(B, H, W, Cc, **f32)
+        _conv(dt, geo, _csrc(dpred, N, nchw=True), None, _wswap(w, dt), Cc, _csrc(dA, Cc), transposed=True)
+        dc, dg, dbn = _bn_bwd(dt, dA, None, None, c, g, st)
+        return dc, None, None, dg, dbn, None, dw.view(N, Cc, 1, 1), db
+
+
+def classic_conv(x0, x1, port1, w1, g1, b1, w2, bn1, compute_dtype, nchw=False):
+    """conv1 -> BN1 + GELU -> conv2 of a ClassicUnetBlock -> the raw conv2 output (B, H, W, C) in the compute dtype."""
+    return _ClassicConvFn.apply(x0, x1, port1, w1, g1, b1, w2, bn1, bool(nchw), compute_dtype)
+
+
+def classic_act(c, g, b, bn, pool=False):
+    """gelu(bn(c)) -> (a, port) or, with pool, (a, port, maxpool2x2(a))."""
+    return _BnActFn.apply(c, g, b, bn, bool(pool))
+
+
+def unet_upconv2(x, w, b, port=None):
+    """ConvTranspose2d(Cin, Cout, kernel 2, stride 2) on a channels-last x -> (B, 2H, 2W, Cout)."""
+    return _UpConv2Fn.apply(x, port, w, b)
+
+
+def classic_final(c, T, g, b, bn, w, bias, target=None):
+    """-> (pred (B, T, C, H, W) fp32, loss) of conv(gelu(bn(c))); only ``loss`` carries gradient when ``target`` is given."""
+    return _ClassicFinalFn.apply(c, target, T, g, b, bn, w, bias)

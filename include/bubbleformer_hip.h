@@ -520,6 +520,34 @@ int bf_unet_lploss_fwd(const float* pred, const float* target, int B, int T, int
 int bf_unet_lploss_bwd(const float* pred, const float* target, const float* coef, const float* dloss, int planes, int64_t HW, float* dpred,
                        bf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------- ClassicUnet (bn.hip)
+ * Replaces, for models/unets.py:186-320 (ClassicUnet) and layers/conv_layers.py:96-141 (ClassicUnetBlock), together with conv.hip's
+ * bf_conv_fwd / bf_conv_wgrad / bf_conv_colsum (the bias-free 3x3 convs, ConvTranspose2d k2 s2 as the transposed gather, the final 1x1):
+ *   bf_bn_fwd / bf_bn_eval nn.BatchNorm2d (conv_layers.py:116,125) in training / eval mode, as the next conv's prologue coefficients
+ *   bf_bn_act ............. nn.BatchNorm2d + nn.GELU (conv_layers.py:117,126) materialised, optionally with nn.MaxPool2d(2, 2) (unets.py:209-236)
+ *   bf_bn_bwd ............. their backward (autograd)
+ * x is channels-last [B*H*W][C] in the dtype; statistics fp32, summed in fp64 in a fixed order (bit-reproducible). */
+/* ws floats for bf_bn_fwd / bf_bn_bwd over M = B*H*W pixels */
+int64_t bf_bn_ws_floats(int64_t M, int C);
+/* batch statistics over all B*HW pixels: mean / rstd [C]; sc = gamma*rstd, sh = beta - mean*sc broadcast to [B][C] (the conv prologue's
+ * layout); running_mean / running_var (may be NULL together) <- (1 - momentum)*r + momentum*stat, the variance unbiased by M/(M-1);
+ * num_batches_tracked[0] += 1 (may be NULL).  M > 1. */
+int bf_bn_fwd(int dtype, const void* x, int B, int64_t HW, int C, const float* gamma, const float* beta, float eps, float momentum,
+              float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, float* sc, float* sh, float* ws,
+              bf_stream_t stream);
+/* eval: sc = gamma / sqrt(running_var + eps), sh = beta - running_mean*sc, broadcast to [B][C] */
+int bf_bn_eval(int B, int C, const float* gamma, const float* beta, float eps, const float* running_mean, const float* running_var, float* sc,
+               float* sh, bf_stream_t stream);
+/* a = gelu(x*sc[f][c] + sh[f][c]) in the dtype; p != NULL: also p [B][H/2][W/2][C] = 2x2 stride-2 max of the stored a, idx = its
+ * row-major window position (0..3; ties to the first, NaN wins) */
+int bf_bn_act(int dtype, const void* x, int B, int H, int W, int C, const float* sc, const float* sh, void* a, void* p, uint8_t* idx,
+              bf_stream_t stream);
+/* g = (dA[m*ldA + offA + c] + dP routed to idx) * gelu'(x*sc + sh), dA fp32 (NULL: none), dP [B][H/2][W/2][C] in the dtype (NULL: none);
+ * dx = gamma*rstd*(g - sum(g)/M - xhat*sum(g*xhat)/M) in the dtype; dbeta = sum g, dgamma = sum g*xhat ((+)= with accumulate) */
+int bf_bn_bwd(int dtype, const float* dA, int64_t ldA, int offA, const void* dP, const uint8_t* idx, const void* x, int B, int H, int W, int C,
+              const float* gamma, const float* mean, const float* rstd, const float* sc, const float* sh, void* dx, float* dgamma, float* dbeta,
+              int accumulate, float* ws, bf_stream_t stream);
+
 /* Optional per-launch HIP-event timing on the launch stream (bench.py's roofline leg); off by default. */
 void bf_prof_enable(int on);
 int bf_prof_report(char* buf, int n);   /* JSON {kernel: {calls, ms, flops, bytes}}; bytes written or -1 */

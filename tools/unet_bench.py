@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Times the ModernUnet baseline (unet_modern, shipped config: hidden 32, ch_mults [1, 2, 2, 4, 4]) on one GPU at 16 x 192 x 192 x 4:
-a bf16 AdamW training step through trainer.TrainStep, an eval forward, and, for context only, the same step on stock PyTorch (eager,
-bf16 autocast, the plain restatement of tests/unet_restatement.py).  Prints one JSON line.
-Usage: python tools/unet_bench.py [--batch 8] [--steps 10] [--warmup 3] [--no-eager]"""
+"""Times a U-Net baseline on one GPU at 16 x 192 x 192 x 4: unet_modern (ModernUnet, shipped config: hidden 32, ch_mults
+[1, 2, 2, 4, 4]) or unet_classic (ClassicUnet, hidden 32).  A bf16 AdamW training step through trainer.TrainStep, an eval forward, and,
+for context only, the same step on stock PyTorch (eager, bf16 autocast, the plain restatement of tests/unet_restatement.py or
+tests/unet_classic_restatement.py).  Prints one JSON line.
+Usage: python tools/unet_bench.py [--model unet_modern|unet_classic] [--batch 8] [--steps 10] [--warmup 3] [--no-eager]"""
 import argparse
 import json
 import os
@@ -15,8 +16,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bubbleformer_amd.models import get_model  # noqa: E402
 from bubbleformer_amd.trainer import TrainStep  # noqa: E402
 
-CFG = dict(time_window=16, input_fields=4, output_fields=4, hidden_channels=32, ch_mults=[1, 2, 2, 4, 4], norm=True)
-GFLOP_FWD = 209.1          # conv MACs x 2 per sample at 192 x 192 (forward); a training step is counted as 3x
+# model -> (config, conv MACs x 2 per sample at 192 x 192 in the forward); a training step is counted as 3x the forward
+MODELS = {
+    "unet_modern": (dict(time_window=16, input_fields=4, output_fields=4, hidden_channels=32, ch_mults=[1, 2, 2, 4, 4], norm=True), 209.1),
+    "unet_classic": (dict(time_window=16, input_fields=4, output_fields=4, hidden_channels=32), 15.02),
+}
 
 
 def _time(fn, steps, warmup):
@@ -32,38 +36,45 @@ def _time(fn, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="unet_modern", choices=sorted(MODELS))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-eager", action="store_true")
     a = ap.parse_args()
+    CFG, GFLOP_FWD = MODELS[a.model]
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(a.batch, 16, 4, 192, 192, device=dev, generator=g)
     y = torch.randn(a.batch, 16, 4, 192, 192, device=dev, generator=g)
-    model = get_model("unet_modern", compute_dtype=torch.bfloat16, **CFG).to(dev)
+    model = get_model(a.model, compute_dtype=torch.bfloat16, **CFG).to(dev)
     step = TrainStep(model, lr=1e-4, optimizer="adamw")
     train_ms = _time(lambda: step(x, None, y), a.steps, a.warmup)
     model.eval()
     with torch.no_grad():
         eval_ms = _time(lambda: model(x), a.steps, a.warmup)
-    out = {"model": "unet_modern", "batch": a.batch, "geometry": "16x192x192x4", "dtype": "bf16", "optimizer": "adamw",
+    out = {"model": a.model, "batch": a.batch, "geometry": "16x192x192x4", "dtype": "bf16", "optimizer": "adamw",
            "train_ms_per_step": round(train_ms, 3), "train_samples_per_s": round(a.batch * 1e3 / train_ms, 3),
            "train_tflops": round(3 * GFLOP_FWD * a.batch / train_ms, 3), "eval_ms": round(eval_ms, 3),
            "eval_tflops": round(GFLOP_FWD * a.batch / eval_ms, 3)}
     del step, model
     torch.cuda.empty_cache()
     if not a.no_eager:
+        from tests import unet_classic_restatement as UC
         from tests import unet_restatement as U
-        ref = get_model("unet_modern", **CFG).to(dev)
+        ref = get_model(a.model, **CFG).to(dev)
         params = list(ref.parameters())
         names = [k for k, _ in ref.named_parameters()]
         opt = torch.optim.AdamW(params, lr=1e-4)
+        buf = {k: v for k, v in ref.named_buffers()}
 
         def eager():
             opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", dtype=torch.bfloat16):
-                pred = U.forward(x, dict(zip(names, params)), 16, CFG["ch_mults"], True)
+                if a.model == "unet_classic":
+                    pred = UC.forward(x, dict(zip(names, params)), buf, 16)
+                else:
+                    pred = U.forward(x, dict(zip(names, params)), 16, CFG["ch_mults"], True)
             loss = U.lp_loss(pred.float(), y)
             loss.backward()
             opt.step()
