@@ -199,19 +199,26 @@ def _shipped_weights():
     return weights(ModernUnet(**SHIPPED), 7)
 
 
+# about twice the largest native bf16 gradient error (2.6e-3, up.14.norm2.weight) among the tensors whose doubled storage-only error is
+# below it, measured at full width on the MI355X
+BF16_GRAD_FLOOR = 5e-3
+
+
 def test_full_width_parity_vs_fp64_restatement():
     """Shipped config at T = 16, 4 fields, 96 x 96, batch 1 (down to 6 x 6 at 2048 channels).  fp32 mode against the fp64 restatement of
-    the same state_dict; bf16 mode against the fp64 restatement of the state_dict and clip rounded to bf16 (what its MFMAs consume)."""
+    the same state_dict; bf16 mode against the fp64 restatement of the state_dict and clip rounded to bf16 (what its MFMAs consume; the
+    native model loads the same rounded state_dict).  bf16 gradients are held per tensor to twice what bf16 activation storage alone
+    does to the otherwise exact computation (the restatement with store=bf16), at least BF16_GRAD_FLOOR and at most 3e-2."""
     sd = _shipped_weights()
     g = torch.Generator().manual_seed(8)
     x = torch.randn(1, 16, 4, 96, 96, generator=g, dtype=torch.float64)
     y = torch.randn(1, 16, 4, 96, 96, generator=g, dtype=torch.float64)
     for dt in (torch.float32, torch.bfloat16):
         rnd = (lambda t: t) if dt == torch.float32 else (lambda t: t.bfloat16().double())
-        pred_r, loss_r, dx_r, g_r = U.run(rnd(x).to(DEV), y.to(DEV), {k: rnd(v).to(DEV) for k, v in sd.items()}, SHIPPED)
+        sdr = {k: rnd(v) for k, v in sd.items()}
+        pred_r, loss_r, dx_r, g_r = U.run(rnd(x).to(DEV), y.to(DEV), {k: v.to(DEV) for k, v in sdr.items()}, SHIPPED)
         tol = 1e-4 if dt == torch.float32 else 2e-2
-        gtol = tol if dt == torch.float32 else 3e-2     # bf16: measured worst 2.7e-2 per tensor, at the 6 x 6 x 2048 levels
-        m = _native(SHIPPED, sd, dt)
+        m = _native(SHIPPED, sdr, dt)
         xn = x.float().to(DEV).requires_grad_(True)
         loss, pred = m.forward_loss(xn, y.float().to(DEV))
         loss.backward()
@@ -220,9 +227,25 @@ def test_full_width_parity_vs_fp64_restatement():
         if dt == torch.float32:
             assert _rel(pred, pred_r) <= tol
             assert _rel(xn.grad, dx_r) <= tol
-        errs = {k: (float(p.grad.abs().max()) if _structurally_zero(g_r[k]) else _rel(p.grad, g_r[k])) for k, p in m.named_parameters()}
-        worst = sorted(errs.items(), key=lambda kv: -kv[1])[:8]
-        assert not [k for k, v in errs.items() if v > gtol], (dt, worst)
+        err = lambda q, k: float(q.abs().max()) if _structurally_zero(g_r[k]) else _rel(q, g_r[k])
+        errs = {k: err(p.grad, k) for k, p in m.named_parameters()}
+        if dt == torch.float32:
+            gtol = {k: tol for k in errs}
+        else:
+            _, _, _, g_s = U.run(rnd(x).to(DEV), y.to(DEV), {k: v.to(DEV) for k, v in sdr.items()}, SHIPPED, store=torch.bfloat16)
+            st = {k: err(g_s[k], k) for k in errs}
+            gtol = {k: min(3e-2, max(BF16_GRAD_FLOOR, 2 * st[k])) for k in errs}
+            ratio = sorted(((errs[k] / max(st[k], 1e-30), k) for k in errs), reverse=True)
+            print("bf16 gradients: native worst %s; storage alone worst %s; native / storage-alone worst %s, median %.3g; %d of %d tensors "
+                  "above 2e-2 (storage alone %d)" % (
+                      sorted(((v, k) for k, v in errs.items()), reverse=True)[:4], sorted(((v, k) for k, v in st.items()), reverse=True)[:4],
+                      ratio[:4], ratio[len(ratio) // 2][0], sum(v > 2e-2 for v in errs.values()), len(errs),
+                      sum(v > 2e-2 for v in st.values())))
+            print("bf16 gradients held by the floor (2 x storage alone < %g): worst native %s" % (
+                BF16_GRAD_FLOOR, sorted(((errs[k], st[k], k) for k in errs if 2 * st[k] < BF16_GRAD_FLOOR), reverse=True)[:4]))
+            del g_s
+        over = {k: (v, gtol[k]) for k, v in errs.items() if v > gtol[k]}
+        assert not over, (dt, over)
         del m, pred_r, dx_r, g_r
 
 

@@ -10,18 +10,52 @@ import torch.nn.functional as F
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _gn_act(x, sd, name, norm=True):
+class _Stored(torch.autograd.Function):
+    """A tensor stored in a narrower dtype and read back: rounds the value, and its gradient, to `dt` (bf16 activation storage)."""
+
+    @staticmethod
+    def forward(ctx, x, dt):
+        ctx.dt = dt
+        return x.to(dt).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(ctx.dt).to(g.dtype), None
+
+
+class _Operand(torch.autograd.Function):
+    """An MFMA operand rounded to `dt` on its way in: the value is rounded, the gradient passes in full precision."""
+
+    @staticmethod
+    def forward(ctx, x, dt):
+        return x.to(dt).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def _stored(x, store):
+    return x if store is None else _Stored.apply(x, store)
+
+
+def _operand(x, store):
+    return x if store is None else _Operand.apply(x, store)
+
+
+def _gn_act(x, sd, name, norm=True, store=None):
     if norm:
         x = F.group_norm(x, 8, sd[name + ".weight"], sd[name + ".bias"], eps=1e-5)
-    return F.gelu(x)
+    return _operand(F.gelu(x), store)
 
 
-def _res(x, sd, p):
-    h = F.conv2d(_gn_act(x, sd, p + ".norm1"), sd[p + ".conv1.weight"], sd[p + ".conv1.bias"], padding=1)
-    h = F.conv2d(_gn_act(h, sd, p + ".norm2"), sd[p + ".conv2.weight"], sd[p + ".conv2.bias"], padding=1)
+def _res(x, sd, p, store=None):
+    x = _stored(x, store)
+    h = _stored(F.conv2d(_gn_act(x, sd, p + ".norm1", store=store), sd[p + ".conv1.weight"], sd[p + ".conv1.bias"], padding=1), store)
+    h = F.conv2d(_gn_act(h, sd, p + ".norm2", store=store), sd[p + ".conv2.weight"], sd[p + ".conv2.bias"], padding=1)
     if p + ".shortcut.weight" in sd:
-        x = F.conv2d(x, sd[p + ".shortcut.weight"], sd[p + ".shortcut.bias"])
-    return h + x
+        x = _stored(F.conv2d(x, sd[p + ".shortcut.weight"], sd[p + ".shortcut.bias"]), store)
+    return _stored(h + x, store)
 
 
 def layer_plan(ch_mults):
@@ -35,24 +69,39 @@ def layer_plan(ch_mults):
     return down, up
 
 
-def forward(x, sd, time_window, ch_mults, norm=True):
-    """x: (B, T, C, H, W) -> (B, T, C_out, H, W)."""
+def forward(x, sd, time_window, ch_mults, norm=True, store=None):
+    """x: (B, T, C, H, W) -> (B, T, C_out, H, W).
+
+    store = torch.bfloat16 restates what bf16 storage alone does to an otherwise exact computation, at the points where the native path
+    (ops.py) rounds:
+      - value and gradient (_Stored): the image_proj output (_ProjFn: `out` in the compute dtype, `dout` arrives in it); in a residual
+        block (_ResBlockFn) its input, whose gradient dx / ds leaves bf_gn_bwd in the compute dtype with the shortcut's gradient added,
+        `h` (and its gradient dh), the 1x1 shortcut output and the block output (`dout.to(dt)`); the input and output of Downsample
+        (_DownFn) and Upsample (_UpFn); the input of the final layer (_FinalFn: dx in the compute dtype).  Every input is rounded again
+        where it is read, so a tensor with several consumers (the skips) has each consumer's gradient rounded before autograd sums them,
+        and the sum rounded, as autograd does with bf16 gradients.
+      - value only (_Operand): gelu(groupnorm(.)), the operand the prologue hands to the MFMAs of conv1 / conv2 / final; its gradient
+        dA is fp32.
+    Everything else -- the fp32 prediction, the conv accumulators, the fp32 data gradients -- stays in the input dtype."""
     B, T, C, H, W = x.shape
-    h = F.conv2d(x.reshape(B, T * C, H, W), sd["image_proj.weight"], sd["image_proj.bias"])
+    h = _stored(F.conv2d(x.reshape(B, T * C, H, W), sd["image_proj.weight"], sd["image_proj.bias"]), store)
     skips = [h]
     down, up = layer_plan(ch_mults)
     for i, kind in enumerate(down):
         p = f"down.{i}"
-        h = _res(h, sd, p) if kind == "res" else F.conv2d(h, sd[p + ".conv.weight"], sd[p + ".conv.bias"], stride=2, padding=1)
+        if kind == "res":
+            h = _res(h, sd, p, store)
+        else:
+            h = _stored(F.conv2d(_stored(h, store), sd[p + ".conv.weight"], sd[p + ".conv.bias"], stride=2, padding=1), store)
         skips.append(h)
-    h = _res(_res(h, sd, "middle.res1"), sd, "middle.res2")
+    h = _res(_res(h, sd, "middle.res1", store), sd, "middle.res2", store)
     for i, kind in enumerate(up):
         p = f"up.{i}"
         if kind == "up":
-            h = F.conv_transpose2d(h, sd[p + ".conv.weight"], sd[p + ".conv.bias"], stride=2, padding=1)
+            h = _stored(F.conv_transpose2d(_stored(h, store), sd[p + ".conv.weight"], sd[p + ".conv.bias"], stride=2, padding=1), store)
         else:
-            h = _res(torch.cat((h, skips.pop()), 1), sd, p)
-    h = F.conv2d(_gn_act(h, sd, "norm", norm), sd["final.weight"], sd["final.bias"])
+            h = _res(torch.cat((h, skips.pop()), 1), sd, p, store)
+    h = F.conv2d(_gn_act(_stored(h, store), sd, "norm", norm, store), sd["final.weight"], sd["final.bias"])
     return h.reshape(B, time_window, -1, H, W)
 
 
@@ -96,11 +145,11 @@ def golden_grad_errors(grads, z, zero_tol=None):
     return errs
 
 
-def run(x, y, sd, cfg):
-    """fp64 (or the state_dict's dtype) forward + loss + backward -> (pred, loss, dx, {name: grad})."""
+def run(x, y, sd, cfg, store=None):
+    """fp64 (or the state_dict's dtype) forward + loss + backward -> (pred, loss, dx, {name: grad}); `store` as in forward()."""
     sd = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
     x = x.detach().clone().requires_grad_(True)
-    pred = forward(x, sd, cfg["time_window"], cfg["ch_mults"], cfg["norm"])
+    pred = forward(x, sd, cfg["time_window"], cfg["ch_mults"], cfg["norm"], store)
     loss = lp_loss(pred, y)
     loss.backward()
     return pred.detach(), loss.detach(), x.grad, {k: v.grad for k, v in sd.items() if v.grad is not None}
