@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: FiLMAViT-small training samples/sec, 4 fields, 16x192x192 clip, batch 8 per GPU (BASELINE.json configs[1]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs1|configs3|configs4] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs1|configs3|configs4] [--dump-outputs DIR] [--full]
 
   --gpus N > 1 without a launcher: this script starts N rank processes itself (one per GPU, RCCL) BEFORE anything touches the GPU
   and relays rank 0's JSON line.  Launched externally (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...) it
@@ -9,20 +9,23 @@
 
   --config configs1  (default) the headline: training step at 16x192x192, batch 8 per GPU
            configs3  BASELINE configs[3]: the long-aspect 32x384x192 training step (batch 4 per GPU: 36,864 tokens)
-           configs4  BASELINE configs[4]: 200-step autoregressive rollout at batch 1, forward captured in a HIP graph; --record PATH
-                     writes the per-step record (relative L2, Eikonal residual, heater heat flux) there
+           configs4  BASELINE configs[4]: 200-step autoregressive rollout at batch 1, forward captured in a HIP graph; --full or
+                     --record PATH computes the per-step record (relative L2, Eikonal residual, heater heat flux), --record writes it to PATH
   --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB):
                      training: `loss`, and `params_sample` / `grads_sample`, the updated parameters and their gradients at a fixed, seeded
                      sample of 4,194,304 positions of the flat parameter vector (model parameter order, alignment padding left out);
                      rollout: `prediction`, the last fed-back step's (T, C, H, W) output.  The inputs are seeded: the same arguments
                      give the same inputs on every run, so two builds can be compared file by file.
   --data device-store  every timed step draws its batch from HBM-resident trajectories (DeviceClipStore.gather = bf_clip_gather) instead of
-                     re-using one resident batch; the default run reports that rate too, beside the headline, as `clip_supply`
+                     re-using one resident batch; a --full run reports that rate too, beside the headline, as `clip_supply`
+  --full             after the headline, also measure and check what it does not need (below); without it the run sets up, warms
+                     up, times the K steps, writes --dump-outputs and prints its line, with `roofline` null
 
 One process per GPU; training step = forward + fused relative-L2 loss + backward + (N>1: RCCL bucketed gradient all-reduce
-overlapped with backward) + fused AdamW.  Rank 0 prints ONE JSON line.  After the timed region the same step is run twice more with
-per-launch HIP-event timing enabled inside the library to produce the `roofline` object for the dominant kernel, and (N=1 only) the
-oracle is timed on the host cores for `cpu_baseline`.
+overlapped with backward) + fused AdamW.  Rank 0 prints ONE JSON line.  With --full, after the timed region the same step is run twice
+more with per-launch HIP-event timing enabled inside the library to produce the `roofline` object for the dominant kernel; configs1
+also times the clip supply (`clip_supply`) and, on one GPU in bf16, bounded legs of the other configurations (`other_configs`); and
+(N=1 only) the oracle is timed on the host cores for `cpu_baseline`.  --no-cpu-baseline / --no-other-configs trim a --full run.
 """
 import argparse
 import ctypes
@@ -339,7 +342,7 @@ def sample_trajectory(w, dev):
     return traj.repeat(1, 1, ry, rx)[..., :w["H"], :w["W"]].contiguous().to(dev)
 
 
-def run_rollout(args, w, dev, dtype, profile=True):
+def run_rollout(args, w, dev, dtype, profile=True, record=True):
     import torch
     from bubbleformer_amd import _lib
     from bubbleformer_amd.models import get_model
@@ -372,6 +375,8 @@ def run_rollout(args, w, dev, dtype, profile=True):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         prof = prof_steps(lambda: model(x0, cond)) if profile else {}
+        if not record:
+            return dt, prof, None, preds[steps - 1]
         # the record: per fed-back step, relative L2 against the sample-derived target (utils/losses.py:17-94 as inference.py:230 uses it),
         # Eikonal residual of the predicted signed-distance field (utils/losses.py:5-15), heater heat flux of the last frame of the step
         # (utils/heatflux.py:17-38 geometry scaled to this grid: 16-wide domain, dx = 16 / W, FC-72 constants)
@@ -389,7 +394,7 @@ def run_rollout(args, w, dev, dtype, profile=True):
 
 
 def other_config_legs(dev, cdt, dtype_name):
-    """Bounded legs of the default one-GPU run (a few seconds together), so that the driver's own record carries the other BASELINE
+    """Bounded legs of the one-GPU --full run (a few seconds together), so that its record carries the other BASELINE
     configurations and the un-accelerated GPU comparator beside the headline: configs3 (5 timed training steps at 32x384x192, batch 4),
     configs4 (50 HIP-graph replays of the batch-1 rollout step) and the oracle restatement run eagerly on this GPU (bf16 autocast, 3 steps)."""
     import types
@@ -485,15 +490,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--config", default="configs1", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, clip supply, other configurations and CPU baseline (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle timed on the host cores (`cpu_baseline`)")
     ap.add_argument("--data", default="synthetic", choices=["synthetic", "device-store"],
                     help="device-store: every timed step draws its batch from a DeviceClipStore (HBM-resident trajectories, bf_clip_gather)")
-    ap.add_argument("--record", default=None, help="configs4: write the per-step rollout record (relative L2, Eikonal, heat flux) to this file")
+    ap.add_argument("--record", default=None, help="configs4: compute the per-step rollout record (relative L2, Eikonal, heat flux) and write it to this file")
     ap.add_argument("--eager-gpu-baseline", action="store_true", help="also time the oracle eagerly on the GPU (fp32 and bf16 autocast)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the bounded configs3 / configs4 / eager-GPU legs the default one-GPU configs1 run adds as `other_configs`")
+                    help="skip the bounded configs3 / configs4 / eager-GPU legs a one-GPU configs1 --full run adds as `other_configs`")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -549,11 +556,11 @@ def main():
     dumped = None
     if w["kind"] == "rollout":                                   # replicas only: every rank runs its own rollout
         sync()
-        dt, prof, rollout_record, last_pred = run_rollout(args, w, dev, cdt)
+        dt, prof, rollout_record, last_pred = run_rollout(args, w, dev, cdt, profile=args.full, record=args.full or bool(args.record))
         sync()
         if args.dump_outputs:
             dumped = {"prediction": last_pred.float().cpu().numpy()}
-        final_loss = rollout_record[-1]["rel_l2"]
+        final_loss = rollout_record[-1]["rel_l2"] if rollout_record is not None else None
     else:
         model = get_model("filmavit", time_window=w["T"], drop_path=DROP_PATH, compute_dtype=cdt, **CFG).to(dev).train()
         step = TrainStep(model, lr=2.5e-4, weight_decay=1e-2)            # config/optim_cfg/adamw.yaml
@@ -578,7 +585,7 @@ def main():
             return time.perf_counter() - t0, ls
 
         store_fn = None
-        if args.config == "configs1" and (args.data == "device-store" or world == 1):
+        if args.config == "configs1" and (args.data == "device-store" or (args.full and world == 1)):
             store_fn = clip_store_batches(w, dev, rank, world)
         if args.data == "device-store":
             if store_fn is None:
@@ -587,9 +594,10 @@ def main():
             dt, loss = timed(store_fn, args.steps)
             if args.dump_outputs:
                 dumped = training_outputs(step, loss)
-            dt_syn, _ = timed(lambda s_: (x, cond, y), min(args.steps, 50))
-            clip_supply = {"samples_per_s_device_store": w["batch"] * world * args.steps / dt,
-                           "samples_per_s_synthetic_same_run": w["batch"] * world * min(args.steps, 50) / dt_syn}
+            if args.full:                                        # the resident-batch figure beside it (bounded: 50 steps)
+                dt_syn, _ = timed(lambda s_: (x, cond, y), min(args.steps, 50))
+                clip_supply = {"samples_per_s_device_store": w["batch"] * world * args.steps / dt,
+                               "samples_per_s_synthetic_same_run": w["batch"] * world * min(args.steps, 50) / dt_syn}
         else:
             dt, loss = timed(lambda s_: (x, cond, y), args.steps)
             if args.dump_outputs:
@@ -605,8 +613,8 @@ def main():
             clip_supply["what"] = ("each step: DeviceClipStore.gather(8 shuffled sample indices) -> (input, target, fluid parameters) -> TrainStep; "
                                    "trajectories: tests/golden/samples/sample_{1,2}.hdf5 tiled 3 x 3 to 192 x 192, 38 sliding windows")
         final_loss = float(loss)
-        # ---- roofline leg: per-launch HIP-event timing (on the launch stream) over two more steps
-        prof = prof_steps(lambda: step(x, cond, y))
+        # ---- roofline leg (--full): per-launch HIP-event timing (on the launch stream) over two more steps
+        prof = prof_steps(lambda: step(x, cond, y)) if args.full else {}
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -651,9 +659,9 @@ def main():
         out["dump_outputs"] = write_outputs(args.dump_outputs, dumped)
     if clip_supply is not None:
         out["clip_supply"] = clip_supply
-        if args.data == "device-store":
-            out["data"] = "device-store: batches gathered per step from HBM-resident trajectories (the reference's sample files tiled to 192 x 192, std-normalised; DeviceClipStore.gather = bf_clip_gather)"
-    if world == 1 and args.config == "configs1" and args.dtype == "bf16" and not args.no_other_configs and not force_dist:
+    if args.data == "device-store":
+        out["data"] = "device-store: batches gathered per step from HBM-resident trajectories (the reference's sample files tiled to 192 x 192, std-normalised; DeviceClipStore.gather = bf_clip_gather)"
+    if args.full and world == 1 and args.config == "configs1" and args.dtype == "bf16" and not args.no_other_configs and not force_dist:
         log("bounded legs: configs3, configs4, eager GPU comparator")
         del step, model, x, cond, y
         from bubbleformer_amd import ops as _ops
@@ -662,7 +670,7 @@ def main():
         torch.cuda.empty_cache()
         out["other_configs"] = other_config_legs(dev, cdt, args.dtype)
         step = model = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         log("timing the CPU baseline (oracle) on", host_threads(), "threads")
         out["cpu_baseline"] = cpu_baseline(w, host_threads())
     if world == 1 and args.eager_gpu_baseline and w["kind"] == "train":
