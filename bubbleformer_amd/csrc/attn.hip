@@ -1,4 +1,4 @@
-// Small-sequence attention for the factored space-time blocks (L <= 32 along T, W or H).
+// Small-sequence attention for the factored space-time blocks (L <= 32 along T, W or H; longer axes, up to 128, go to attn_long.hip).
 //
 // One wavefront owns one (sequence, head) problem: q/k/v rows are pulled into LDS as fp32
 // (16-byte global chunks, each token row contributes 3*d contiguous elements of the
@@ -20,7 +20,8 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-constexpr int LMAX = 32;
+constexpr int LMAX = 32;           // this file's kernels and attn_mfma.hip; 33..128 run in attn_long.hip
+constexpr int LONG_LMAX = 128;
 constexpr int DMAX = 128;
 
 // one-sided T5 bucket for |offset| (num_buckets 32 -> 16 per side, max_exact 8, max_distance 32);
@@ -351,7 +352,7 @@ int check_geo(const char* who, int dtype, int heads, int d, int L) {
     const int ch = dtype == BF_DTYPE_BF16 ? 8 : 4;
     if (heads < 1 || heads > 16) return bf_fail_msg("attention: heads must be in 1..16", who, 0);
     if (d < ch || d > DMAX || d % ch) return bf_fail_msg("attention: head dim must be a multiple of the 16-byte chunk and <= 128", who, 0);
-    if (L < 1 || L > LMAX) return bf_fail_msg("attention: sequence length must be in 1..32", who, 0);
+    if (L < 1 || L > LONG_LMAX) return bf_fail_msg("attention: sequence length must be in 1..128", who, 0);
     return 0;
 }
 
@@ -362,6 +363,14 @@ int bf_attn_fwd_mfma(const void* qkv, void* out, long nseq, int L, long inner, l
                      int d, const float* qw, const float* qb, const float* kw, const float* kb, const float* emb, const float* hscale,
                      float out_scale, int accumulate, hipStream_t st);
 int bf_attn_bwd_mfma(const void* qkv, const void* dout, void* dqkv, long nseq, int L, long inner, long outer_stride, long inner_stride,
+                     long tok_stride, int heads, int d, const float* qw, const float* qb, const float* kw, const float* kb, const float* emb,
+                     const float* hscale, float* dqw, float* dqb, float* dkw, float* dkb, float* demb, float* dhscale, float out_scale,
+                     int accumulate, float* ws, long ws_floats, int* rows_out, hipStream_t st);
+// attn_long.hip: 33 <= L <= 128
+int bf_attn_fwd_long(int dtype, const void* qkv, void* out, long nseq, int L, long inner, long outer_stride, long inner_stride, long tok_stride,
+                     int heads, int d, const float* qw, const float* qb, const float* kw, const float* kb, const float* emb, const float* hscale,
+                     float out_scale, int accumulate, hipStream_t st);
+int bf_attn_bwd_long(int dtype, const void* qkv, const void* dout, void* dqkv, long nseq, int L, long inner, long outer_stride, long inner_stride,
                      long tok_stride, int heads, int d, const float* qw, const float* qb, const float* kw, const float* kb, const float* emb,
                      const float* hscale, float* dqw, float* dqb, float* dkw, float* dkb, float* demb, float* dhscale, float out_scale,
                      int accumulate, float* ws, long ws_floats, int* rows_out, hipStream_t st);
@@ -380,6 +389,11 @@ extern "C" int bf_attn_fwd(int dtype, const void* qkv, void* out, int64_t nseq, 
                            int accumulate, bf_stream_t stream) {
     BF_REQUIRE(qkv && out && qw && qb && kw && kb && nseq > 0 && inner > 0, "bf_attn_fwd: bad arguments");
     if (int rc = check_geo("bf_attn_fwd", dtype, heads, d, L)) return rc;
+    if (L > LMAX) {       // long axes: one kernel for both dtypes (bf_debug_force_generic_attn does not apply)
+        BfProfScope prof((hipStream_t)stream, "attn_fwd", 4.0 * nseq * heads * L * L * d, (double)nseq * heads * L * d * bf_esize(dtype) * (accumulate ? 5.0 : 4.0));
+        return bf_attn_fwd_long(dtype, qkv, out, nseq, L, inner, outer_stride, inner_stride, tok_stride, heads, d, qw, qb, kw, kb, emb, hscale,
+                                out_scale, accumulate, (hipStream_t)stream);
+    }
     if (use_mfma(dtype, d)) {
         BfProfScope prof((hipStream_t)stream, "attn_fwd", 4.0 * nseq * heads * L * L * d, (double)nseq * heads * L * d * 2.0 * (accumulate ? 5.0 : 4.0));
         return bf_attn_fwd_mfma(qkv, out, nseq, L, inner, outer_stride, inner_stride, tok_stride, heads, d, qw, qb, kw, kb, emb, hscale, out_scale,
@@ -445,6 +459,11 @@ static int attn_bwd_impl(int dtype, const void* qkv, const void* dout, void* dqk
     if (int rc = check_geo("bf_attn_bwd", dtype, heads, d, L)) return rc;
     BF_REQUIRE(accumulate == 0 || accumulate == 1 || ((accumulate == 2 || accumulate == 5) && use_mfma(dtype, d)),
                "bf_attn_bwd: accumulate must be 0 / 1 (or 2 / 5, the raw-gradient pair of passes, on the bf16 MFMA path)");
+    if (L > LMAX) {
+        BfProfScope prof((hipStream_t)stream, "attn_bwd", 10.0 * nseq * heads * L * L * d, (double)nseq * heads * L * d * bf_esize(dtype) * (accumulate ? 10.0 : 7.0));
+        return bf_attn_bwd_long(dtype, qkv, dout, dqkv, nseq, L, inner, outer_stride, inner_stride, tok_stride, heads, d, qw, qb, kw, kb, emb, hscale,
+                                dqw, dqb, dkw, dkb, demb, dhscale, out_scale, accumulate, ws, (long)ws_floats, rows_out, (hipStream_t)stream);
+    }
     if (use_mfma(dtype, d)) {
         BfProfScope prof((hipStream_t)stream, "attn_bwd", 10.0 * nseq * heads * L * L * d, (double)nseq * heads * L * d * 2.0 * (accumulate ? 10.0 : 7.0));
         return bf_attn_bwd_mfma(qkv, dout, dqkv, nseq, L, inner, outer_stride, inner_stride, tok_stride, heads, d, qw, qb, kw, kb, emb, hscale, dqw,

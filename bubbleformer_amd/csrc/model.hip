@@ -49,7 +49,7 @@ int get_dims(const bf_dims* s, D* o) {
     o->es = bf_esize(o->dtype);
     const int ch = o->dtype == BF_DTYPE_BF16 ? 8 : 4;
     if (o->E % ch || o->d % ch) return bf_fail_msg("dims: E and head dim must be multiples of the 16-byte chunk", __FILE__, __LINE__);
-    if (o->T > 32 || o->h > 32 || o->w > 32) return bf_fail_msg("dims: attention axes are limited to 32 tokens", __FILE__, __LINE__);
+    if (o->T > 128 || o->h > 128 || o->w > 128) return bf_fail_msg("dims: attention axes are limited to 128 tokens", __FILE__, __LINE__);
     o->nst = 0;
     if (o->patch > 0) {
         int p = o->patch;

@@ -189,7 +189,8 @@ int bf_colsum(int dtype, const void* x, int64_t nrows, int C, const float* scale
 /* Strided small-sequence attention on the head-interleaved QKV tensor [N][3E] (channel = head*3d + {q,k,v}*d + e):
  * token(l) of sequence s = (s / inner) * outer_stride + (s % inner) * inner_stride + l * tok_stride.
  * q/k LayerNorm(d) + q k^T d^-1/2 + T5 bias (emb [32][heads] or NULL) + softmax + high-frequency rescale
- * (hscale [heads] or NULL) + P V.  out [N][E] = (accumulate ? out : 0) + out_scale * result. */
+ * (hscale [heads] or NULL) + P V.  out [N][E] = (accumulate ? out : 0) + out_scale * result.  1 <= L <= 128: L <= 32 runs the one-wave
+ * kernels, 33..128 the long-axis kernels (one workgroup per sequence and head, fp32 arithmetic in both dtypes); L > 128 returns an error. */
 int bf_attn_fwd(int dtype, const void* qkv, void* out, int64_t nseq, int L, int64_t inner, int64_t outer_stride,
                 int64_t inner_stride, int64_t tok_stride, int heads, int d, const float* qw, const float* qb, const float* kw,
                 const float* kb, const float* emb, const float* hscale, float out_scale, int accumulate, bf_stream_t stream);
@@ -218,7 +219,9 @@ int bf_attn_bwd(int dtype, const void* qkv, const void* dout, void* dqkv, int64_
                 float* ws, int64_t ws_floats, /* optional workspace for the block-partial parameter gradients (NULL: atomics) */
                 bf_stream_t stream);
 
-/* test hook: route bf16 attention through the generic fp32-VALU kernel instead of the MFMA kernel */
+/* test hook: route bf16 attention through the generic fp32-VALU kernel instead of the MFMA kernel (L <= 32; the long-axis kernels,
+ * L > 32, compute in fp32 VALU already and are the only path there: the hook does not change them, but with it on the raw-gradient
+ * modes are refused at every L, as bf_attn_raw_modes answers) */
 /* Weight-gradient GEMMs run on a library-owned side stream that every stage joins before it returns.  bf_side_defer(1) lets a
  * temporal / spatial backward return with its LAST weight-gradient GEMM still in flight: the next stage call on the stream joins it
  * (before it reuses what that GEMM reads), as does bf_side_join().  A caller that opts in must call bf_side_join(stream) before it
