@@ -155,6 +155,7 @@ SIGNATURES = {
     "bf_film_net_fwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]),
     "bf_film_net_bwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]),
     "bf_adamw": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
+    "bf_adam": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
     "bf_lion": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, vp]),
     "bf_eikonal_sum": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, vp, vp]),
     "bf_eikonal_l1_frames": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, vp]),

@@ -4,7 +4,7 @@
 //   nchw2pm (+ loss backward)  : d(pred) -> patch-major rows for the debed backward GEMMs
 //   wprep / wgrad_unprep       : fp32 state_dict weights -> GEMM operand layout/dtype and back (gradients)
 //   film_net fwd/bwd           : LayerNorm(P) + Linear(P, 2E) on B rows
-//   adamw                      : fused flat-buffer AdamW
+//   adamw / adam               : fused flat-buffer AdamW and Adam
 // All are bandwidth-bound; each thread moves 8..16 contiguous bytes where the layout allows.
 #include "bf_common.h"
 #include "param_reduce.h"
@@ -645,6 +645,41 @@ __global__ void __launch_bounds__(NT) adamw_kernel(float* __restrict__ p, const 
     }
 }
 
+// ---------------------------------------------------------------------------- Adam (torch.optim.Adam semantics, single-tensor path)
+// Weight decay is an L2 term on the gradient (g += wd*p), so it passes through both moments; AdamW above decays the parameter instead.
+// Zero padding stays zero: p = g = m = v = 0 gives m / (sqrt(v) / sqrt_bc2 + eps) = 0.
+__global__ void __launch_bounds__(NT) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                                 float bc1, float sqrt_bc2, float gscale) {
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+#define BF_ADAML2(X)                                                       \
+        { float gr = gg.X * gscale;                                         \
+          if (wd != 0.f) gr += wd * pp.X;                                   \
+          mm.X = b1 * mm.X + (1.f - b1) * gr;                               \
+          vv.X = b2 * vv.X + (1.f - b2) * gr * gr;                          \
+          pp.X -= (lr / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
+        BF_ADAML2(x) BF_ADAML2(y) BF_ADAML2(z) BF_ADAML2(w)
+#undef BF_ADAML2
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const long i = n4 * 4 + threadIdx.x;
+        float pp = p[i];
+        float gr = g[i] * gscale;
+        if (wd != 0.f) gr += wd * pp;
+        const float mm = b1 * m[i] + (1.f - b1) * gr;
+        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
+        pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
+        p[i] = pp; m[i] = mm; v[i] = vv;
+    }
+}
+
 int grid_for(long total) { return (int)std::max<long>(1, std::min<long>((total + NT - 1) / NT, 256L * 16)); }
 }  // namespace
 
@@ -1154,6 +1189,17 @@ extern "C" int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n,
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2, gscale);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
+                       float eps, float wd, float gscale, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adam: bad arguments");
+    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adam: buffers must be 16-byte aligned");
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2, gscale);
     BF_CHECK_LAUNCH();
     return 0;
 }

@@ -50,7 +50,9 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
-    (config/scheduler_cfg/cosine_warmup.yaml).  ``warmup_iters=None`` runs at a constant learning rate.  Returns the history."""
+    (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
+    (config/optim_cfg/adamw.yaml: lr 2.5e-4 wd 1e-2; adam.yaml: lr 2.5e-4 wd 1e-5).  ``resume_from`` takes a file written here or by
+    the reference's Lightning run (utils/checkpoint.py: load_checkpoint).  ``warmup_iters=None`` runs at a constant learning rate.  Returns the history."""
     dev = next(model.parameters()).device
     store = train_set.device_store(dev)
     vstore = val_set.device_store(dev) if val_set is not None else None
@@ -71,7 +73,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         for bi, idx in enumerate(batches(epoch_indices(len(train_set), epoch, seed, True, rank, world), batch_size, limit_train_batches)):
             got = store.gather(idx)
             x, y, c = (got[0], got[1], got[2]) if conditioned else (got[0], got[1], None)
-            cur_lr = sched.get_last_lr()[0] if sched is not None else lr
+            cur_lr = sched.get_last_lr()[0] if sched is not None else step.lr      # step.lr: a reference checkpoint brings its own
             loss = step(x, c, y)
             losses.append(loss)
             hist["lr"].append(cur_lr)

@@ -287,7 +287,7 @@ def refresh_eval_weights(owner: int) -> None:
 
 def clear_eval_weights() -> None:
     """Drop the prepared inference weights (they are re-made on the next eval forward).  Needed only after parameters were rewritten
-    through raw pointers by code outside this package; torch in-place ops and ops.adamw_ / ops.lion_ are noticed by themselves."""
+    through raw pointers by code outside this package; torch in-place ops and ops.adamw_ / ops.adam_ / ops.lion_ are noticed by themselves."""
     _EVAL_ARENAS.clear()
 
 
@@ -925,6 +925,16 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
     _require_gpu(p)
     L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                              float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
+    _weights_changed()
+
+
+def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
+          eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> None:
+    """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
+    weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay."""
+    _require_gpu(p)
+    L.check(L.lib().bf_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                            float(weight_decay), float(grad_scale), _stream()), "bf_adam")
     _weights_changed()
 
 

@@ -7,7 +7,7 @@
                       mean all-reduce of gradient buckets over ``torch.distributed`` (backend "nccl" = RCCL over xGMI),
                       issued per bucket as soon as backward has produced every gradient in it (debed first, then
                       blocks N-1 .. 0, then embed), overlapped with the rest of backward.  One process per GPU.
-* ``TrainStep``    -- forward (+ fused relative-L2 loss) -> backward -> bucket wait -> fused AdamW.
+* ``TrainStep``    -- forward (+ fused relative-L2 loss) -> backward -> bucket wait -> fused AdamW / Adam / Lion.
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
@@ -155,14 +155,16 @@ def stage_buckets(model: nn.Module, blocks_per_bucket: Optional[int] = None) -> 
 
 
 class TrainStep:
-    """optimizer: "adamw" (config/optim_cfg/adamw.yaml; modules.py:135-136) or "lion" (config/optim_cfg/lion.yaml, the reference
-    default; modules.py:139-140).  scheduler: optional object with get_last_lr() / step() (utils.lr_schedulers.CosineWarmupLR),
-    stepped once per optimizer step like the reference's ``interval="step"`` (modules.py:166-171)."""
+    """optimizer: "adamw" (config/optim_cfg/adamw.yaml; modules.py:135-136), "adam" (config/optim_cfg/adam.yaml, torch.optim.Adam
+    with its L2 weight decay; modules.py:137-138) or "lion" (config/optim_cfg/lion.yaml, the reference default; modules.py:139-140).
+    The constructor's weight_decay default is AdamW's; pass adam.yaml's 1e-5 / lion.yaml's 0.1 explicitly.  scheduler: optional
+    object with get_last_lr() / step() (utils.lr_schedulers.CosineWarmupLR), stepped once per optimizer step like the reference's
+    ``interval="step"`` (modules.py:166-171)."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None):
         from . import ops
-        if optimizer not in ("adamw", "lion"):
+        if optimizer not in ("adamw", "adam", "lion"):
             raise ValueError(f"Optimizer {optimizer} not supported")
         self.ops = ops
         self.model = model
@@ -171,9 +173,9 @@ class TrainStep:
         self.slots = {p.data_ptr(): p.grad for p in self.flat.params}
         self.optimizer = optimizer
         self.m = torch.zeros_like(self.flat.flat)
-        self.v = torch.zeros_like(self.flat.flat) if optimizer == "adamw" else None
+        self.v = torch.zeros_like(self.flat.flat) if optimizer in ("adamw", "adam") else None
         if betas is None:
-            betas = (0.9, 0.999) if optimizer == "adamw" else (0.9, 0.99)
+            betas = (0.9, 0.999) if optimizer in ("adamw", "adam") else (0.9, 0.99)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.scheduler = scheduler
         self.step_no = 0
@@ -209,6 +211,8 @@ class TrainStep:
         lr = self.scheduler.get_last_lr()[0] if self.scheduler is not None else self.lr
         if self.optimizer == "adamw":
             self.ops.adamw_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale)
+        elif self.optimizer == "adam":
+            self.ops.adam_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale)
         else:
             self.ops.lion_(self.flat.flat, self.flat.grad, self.m, lr, self.betas, self.wd, gscale)
         if self.scheduler is not None:

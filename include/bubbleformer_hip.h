@@ -28,6 +28,7 @@
  *   bf_debed_last_* .......... HMLPDebed last stage + LpLoss: layers/patching.py:92-100, utils/losses.py:67-94
  *   bf_film_* ................ FiLMMLP.forward: layers/linear_layers.py:63-77
  *   bf_adamw ................. torch.optim.AdamW as configured at bubbleformer/modules.py:135-136
+ *   bf_adam .................. torch.optim.Adam as configured at bubbleformer/modules.py:137-138 (config/optim_cfg/adam.yaml)
  *   bf_clip_gather ........... BubbleForecast.__getitem__ + DataLoader collate for a batch of clips: bubbleformer/data/dataset.py:120-182
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
@@ -322,6 +323,10 @@ int bf_film_net_bwd(const float* dgb, const float* chat, const float* lnw, const
                     float* dbias, float* dlnw, float* dlnb, int B, int P, int E2, bf_stream_t stream);
 int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
              float wd, float gscale, bf_stream_t stream);
+/* Adam (torch.optim.Adam, amsgrad = maximize = False), same buffers and checks as bf_adamw; weight decay is an L2 term on the gradient:
+ * g = gscale*grad; g += wd*p (wd != 0); m = beta1*m + (1-beta1)*g; v = beta2*v + (1-beta2)*g^2; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps) */
+int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+            float wd, float gscale, bf_stream_t stream);
 /* Batch of normalised clips from device-resident trajectories src [fields][frames][H][W] (fp32):
  * out[b][t][c][yo][xo] = (src[field[c]][first[b] + t0 + t][ys][xs] - diff[c]) / div[c], (ys, xs) = nearest-neighbour source pixel of
  * (yo, xo) when Ho x Wo < H x W (F.interpolate(mode="nearest") index rule), identity otherwise.  out is (B, T, C, Ho, Wo) fp32. */
