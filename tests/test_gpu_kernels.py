@@ -636,6 +636,13 @@ def test_attention_mfma_matches_generic_and_fp32(L, d, heads, axis):
             assert float((a - b).norm()) < 1e-2 * float(g_f[0].norm()), (name, float((a - b).norm()), float(g_f[0].norm()))
         else:
             assert float((a - b).norm()) / float(b.norm()) < (1e-1 if name == "dhscale" else 5e-2), (name, float((a - b).norm()) / float(b.norm()))
+    # and per element against the fp64 restatement, within the bound derived from the kernels' rounding points (tests/attn_bounds.py)
+    from tests import attn_bounds as AB
+    for (o, dq, gr), mode in (((o_m, dq_m, g_m), AB.MFMA), ((o_g, dq_g, g_g), AB.GENERIC_BF16)):
+        got = {"out": AB.from_tokens(o, geo, heads, 1, d), **{n: AB.from_tokens(dq, geo, heads, 3, d, i) for i, n in enumerate(("dq", "dk", "dv"))},
+               **dict(zip(AB.NAMES, gr))}
+        for k, (ref, bnd) in AB.plain(qkv, dout, geo, heads, d, prm, True, True, 0.5, mode).items():
+            AB.check(got[k], ref, bnd, k)
 
 
 @pytest.mark.parametrize("h,w,d,heads", [(12, 12, 64, 6), (6, 10, 64, 2), (16, 12, 32, 3), (24, 12, 64, 2)])
@@ -680,6 +687,13 @@ def test_axial_attention_backward_raw_pair_of_passes(h, w, d, heads):
             assert float((a - b).norm()) < 1e-2 * float(gref[0].norm()), name
         else:
             assert float((a - b).norm()) / float(b.norm()) < 5e-3, (name, float((a - b).norm()) / float(b.norm()))
+    # the raw pair per element against the fp64 gradient of both passes through the shared LayerNorm (tests/attn_bounds.py)
+    from tests import attn_bounds as AB
+    want = AB.axial_pair(qkv, dout, Fr, h, w, heads, d, prm + [prm[5]], AB.MFMA)
+    got = {n: parts(raw)[:, :, i] for i, n in enumerate(("dq", "dk", "dv"))}
+    got.update(dict(zip(AB.NAMES[:5], graw)))
+    for k in got:
+        AB.check(got[k], *want[k], k, ("token", "head", "channel") if want[k][0].dim() == 3 else ("bucket", "head"))
     # the raw modes exist on the bf16 MFMA path only
     lib.bf_debug_force_generic_attn(1)
     try:

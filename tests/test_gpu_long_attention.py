@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.attn_bounds import geometry, reference, t5_bucket, token_index  # noqa: F401  (the fp64 restatement, shared with the short axes)
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -16,59 +18,6 @@ NAMES = ("dqw", "dqb", "dkw", "dkb", "demb", "dhscale")
 def _rel(a, b):
     a, b = a.double().flatten(), b.double().flatten()
     return float((a - b).norm() / b.norm().clamp_min(1e-300))
-
-
-def t5_bucket(n):
-    """T5 bucket of offset n = query - key from the reference's own table (tests/golden/relpos_tables.npz, L = 40): every |n| >= 27
-    shares the last bucket of its side, so the 40-token table covers any length."""
-    tab = np.load(os.path.join(GOLDEN, "relpos_tables.npz"))["bucket_40"]
-    n = max(-39, min(39, n))
-    i = max(n, 0)
-    return int(tab[i][i - n])
-
-
-def geometry(kind, L, n_outer=3, inner=5):
-    """(nseq, L, inner, outer_stride, inner_stride, tok_stride) and the token count: contiguous sequences, the temporal block's
-    [B][T][S] layout, and the axial block's W and H passes over [F][h][w] frames."""
-    if kind == "contig":
-        return (4, L, 1, L, 0, 1), 4 * L
-    if kind == "temporal":      # tokens [B][T = L][S = inner]
-        return (n_outer * inner, L, inner, L * inner, 1, inner), n_outer * L * inner
-    if kind == "W":             # frames [F = n_outer][h = inner][w = L]
-        return (n_outer * inner, L, 1, L, 0, 1), n_outer * inner * L
-    if kind == "H":             # frames [F][h = L][w = inner]
-        return (n_outer * inner, L, inner, L * inner, 1, inner), n_outer * L * inner
-    raise ValueError(kind)
-
-
-def token_index(geo):
-    nseq, L, inner, ostr, istr, tstr = geo
-    s = torch.arange(nseq).view(-1, 1)
-    return (s // inner) * ostr + (s % inner) * istr + torch.arange(L).view(1, -1) * tstr
-
-
-def reference(qkv, dout, geo, heads, d, prm, out_scale, with_emb, with_hs):
-    """fp64 forward and gradients of bf_attn_fwd's contract on the same input values."""
-    idx = token_index(geo).to(qkv.device)
-    nseq, L = idx.shape
-    x = qkv.double().detach().requires_grad_(True)
-    qw, qb, kw, kb, emb, hs = (t.double().detach().requires_grad_(True) for t in prm)
-    t = x[idx].view(nseq, L, heads, 3, d).permute(0, 2, 1, 3, 4)           # [s][h][l][3][d]
-    ln = lambda z, w, b: torch.nn.functional.layer_norm(z, (d,), eps=1e-5) * w + b
-    q, k, v = ln(t[..., 0, :], qw, qb), ln(t[..., 1, :], kw, kb), t[..., 2, :]
-    sc = q @ k.transpose(-1, -2) / d ** 0.5
-    if with_emb:
-        bk = torch.tensor([[t5_bucket(i - j) for j in range(L)] for i in range(L)], device=qkv.device)
-        sc = sc + emb[bk].permute(2, 0, 1).unsqueeze(0)
-    p = torch.softmax(sc, -1)
-    if with_hs:
-        inv = float(np.float32(1.0) / np.float32(L))
-        p = inv + (p - inv) * hs.view(1, heads, 1, 1)
-    o = (p @ v).permute(0, 2, 1, 3).reshape(nseq * L, heads * d)
-    out = torch.zeros(qkv.shape[0], heads * d, dtype=torch.float64, device=qkv.device).index_add(0, idx.flatten(), o * out_scale)
-    out.backward(dout.double())
-    grads = [qw.grad, qb.grad, kw.grad, kb.grad, emb.grad if with_emb else torch.zeros_like(emb), hs.grad if with_hs else torch.zeros_like(hs)]
-    return out.detach(), x.grad, grads
 
 
 def params(d, heads, g):
