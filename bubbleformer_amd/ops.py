@@ -910,6 +910,40 @@ def clip_gather_batch(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch.
     return inp, out, fl
 
 
+def rollout_score_workspace(pred: torch.Tensor) -> torch.Tensor:
+    """The fp64 workspace ``rollout_score`` needs for predictions of this shape (allocate once, outside a graph capture)."""
+    B, T, Cn, Ho, Wo = pred.shape
+    return torch.empty(L.lib().bf_rollout_score_ws_doubles(B, T, Cn, Ho, Wo), dtype=torch.float64, device=pred.device)
+
+
+def rollout_score(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
+                  rel_l2: torch.Tensor, criterion: torch.Tensor, ws: torch.Tensor, eik_pred: Optional[torch.Tensor] = None,
+                  eik_tgt: Optional[torch.Tensor] = None, next_in: Optional[torch.Tensor] = None, archive: Optional[torch.Tensor] = None,
+                  dx: float = 1.0 / 32) -> None:
+    """All scores of one rollout step (bf_rollout_score; include/bubbleformer_hip.h has the contract): pred (B, T, C, Ho, Wo) fp32 against the
+    frames ``first[b] + (s + 1) * T + t`` of the store, s = the int32 ``step`` tensor ON THE DEVICE, which the call increments.  Writes row
+    s * T + t of rel_l2 (B, steps*T, C), criterion (B, steps), eik_pred / eik_tgt (B, steps*T) (sdf_channel >= 0), and the optional copies
+    next_in (like pred) and archive (B, steps*T, C, Ho, Wo).  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(pred)
+    ids, diff, div = table
+    nf, total, H, W = frames.shape
+    B, T, Cn, Ho, Wo = pred.shape
+    if pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise L.BubbleformerHipError("rollout_score: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
+    want = {"rel_l2": (rel_l2, (B, steps * T, Cn), torch.float32), "criterion": (criterion, (B, steps), torch.float32),
+            "eik_pred": (eik_pred, (B, steps * T), torch.float32), "eik_tgt": (eik_tgt, (B, steps * T), torch.float32),
+            "next_in": (next_in, (B, T, Cn, Ho, Wo), torch.float32), "archive": (archive, (B, steps * T, Cn, Ho, Wo), torch.float32),
+            "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32), "ws": (ws, (ws.numel(),), torch.float64)}
+    for name, (t, shape, dtype) in want.items():
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device):
+            raise L.BubbleformerHipError(f"rollout_score: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
+    if ids.numel() != Cn:
+        raise L.BubbleformerHipError(f"rollout_score: the field table has {ids.numel()} channels, the prediction {Cn}")
+    L.check(L.lib().bf_rollout_score(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(sdf_channel),
+                                     float(dx), _p(rel_l2), _p(criterion), _p(eik_pred), _p(eik_tgt), _p(next_in), _p(archive), _p(ws), ws.numel(),
+                                     B, T, Cn, H, W, Ho, Wo, int(steps), _stream()), "bf_rollout_score")
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
           grad_scale: float = 1.0) -> None:
     """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140)."""

@@ -2,9 +2,16 @@
 
 The reference moves every prediction to the host and back (`pred.squeeze(0).detach().cpu()` ... `inp.cuda()`); here the eval
 forward is captured once in a HIP graph and replayed per step with the previous prediction copied into the graph's static input,
-so a step is one graph launch and the trajectory never leaves HBM."""
-from typing import Callable, List, Optional, Tuple
+so a step is one graph launch and the trajectory never leaves HBM.
 
+``evaluate_rollouts`` is the reference's evaluation protocol on top of that (scripts/inference.py:230-266, utils/plot_utils.py:30-34, the
+rollout notebook's ``get_eikonal_loss``): many trajectories per forward, the targets read where they lie in a ``DeviceClipStore``, every
+score of a step from one pass over the prediction (``bf_rollout_score``), forward and scoring captured together as one graph."""
+import dataclasses
+import inspect
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
 import torch
 
 
@@ -13,6 +20,12 @@ def relative_l2_per_step(pred: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
     num = (pred - tgt).flatten(-2).norm(dim=-1)
     den = tgt.flatten(-2).norm(dim=-1)
     return (num / den).mean(0, keepdim=True).mean(1, keepdim=True).squeeze()
+
+
+def relative_l2_per_frame(pred: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+    """The error-versus-time curves of utils/plot_utils.py:30-33 on (T, C, H, W) clips: (T, C) relative L2 over (H, W), for callers
+    without a device store (``evaluate_rollouts`` computes the same on the device, in fp64, against the store's own frames)."""
+    return torch.norm(pred - tgt, p=2, dim=(2, 3)) / torch.norm(tgt, p=2, dim=(2, 3))
 
 
 class GraphedForward:
@@ -65,3 +78,134 @@ def autoregressive_rollout(model, first_input: torch.Tensor, steps: int, *extra:
                 errs.append(relative_l2_per_step(pred, target_fn(s)))
             x = pred.unsqueeze(0)
     return torch.cat(preds, dim=0), errs
+
+
+class RolloutPlan(NamedTuple):
+    first: List[int]                # absolute first input frame of step 0 on the store's frame axis, per trajectory
+    files: List[int]                # file of every trajectory
+    timesteps: torch.Tensor         # (B, steps*T) int64: frame number inside its file of every predicted frame (scripts/inference.py:251)
+
+
+def plan_rollouts(dataset, starts: Sequence[int], steps: int, model_time_window: Optional[int] = None) -> RolloutPlan:
+    """The host side of ``evaluate_rollouts``, without a GPU: trajectory b starts with the input clip of ``dataset[starts[b]]`` and is scored
+    at step s against the target clip of ``dataset[starts[b] + s * T]`` (`for itr in range(0, n, T)` of scripts/inference.py:239-252), so
+    every one of those samples must exist in the file of ``starts[b]``."""
+    T = int(dataset.time_window)
+    if list(dataset.input_fields) != list(dataset.output_fields):
+        raise ValueError(f"a rollout feeds predictions back as inputs: input fields {list(dataset.input_fields)} and output fields "
+                         f"{list(dataset.output_fields)} must be the same")
+    if int(steps) < 1:
+        raise ValueError("steps must be at least 1")
+    if model_time_window is not None and int(model_time_window) != T:
+        raise ValueError(f"the model was built for time_window = {model_time_window}, the dataset has {T}")
+    if len(starts) < 1:
+        raise ValueError("at least one trajectory")
+    ends = np.cumsum(dataset._per_traj())               # one past the last sample of every file
+    frame0 = np.concatenate([[0], np.cumsum(dataset.traj_lens)])
+    first, files, times = [], [], []
+    for b, idx in enumerate(starts):
+        idx = int(idx)
+        if idx < 0 or idx >= len(dataset):
+            raise IndexError(f"trajectory {b}: sample {idx} is outside the dataset (0 .. {len(dataset) - 1})")
+        fi, start = dataset.locate(idx)
+        fit = (int(ends[fi]) - 1 - idx) // T + 1        # steps whose target sample is still in this file
+        if steps > fit:
+            raise IndexError(f"trajectory {b} (sample {idx}, file {fi}): step {fit} is the last that fits, {steps} were asked for")
+        first.append(int(frame0[fi]) + start)
+        files.append(fi)
+        times.append(torch.arange(start + T, start + T + steps * T, dtype=torch.int64))
+    return RolloutPlan(first, files, torch.stack(times))
+
+
+@dataclasses.dataclass
+class RolloutReport:
+    """What ``evaluate_rollouts`` returns; every tensor is on the device.  Row s * T + t of the frame axis is frame t of step s."""
+    rel_l2: torch.Tensor                            # (B, steps*T, C)  relative L2 per predicted frame and field (plot_utils.py:30-33)
+    criterion: torch.Tensor                         # (B, steps)       their mean per step (the LpLoss scripts/inference.py:252 prints)
+    eikonal_pred: Optional[torch.Tensor]            # (B, steps*T)     the notebook's Eikonal score of the predicted interface, or None
+    eikonal_target: Optional[torch.Tensor]          # (B, steps*T)     the same of the simulated one
+    timesteps: torch.Tensor                         # (B, steps*T)     int64 frame numbers inside the trajectory's file
+    fields: List[str]                               # output field names in channel order
+    predictions: Optional[torch.Tensor] = None      # (B, steps*T, C, Ho, Wo) if kept
+
+    def save(self, path) -> None:
+        """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
+        out = {"timesteps": self.timesteps, "rel_l2": self.rel_l2, "criterion": self.criterion, "fields": list(self.fields)}
+        if self.predictions is not None:
+            out["preds"] = self.predictions
+        if self.eikonal_pred is not None:
+            out["eikonal_pred"], out["eikonal_target"] = self.eikonal_pred, self.eikonal_target
+        torch.save(out, path)
+
+
+def _to_device(values, dtype, device) -> torch.Tensor:
+    host = torch.as_tensor(values, dtype=dtype)
+    return host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host.to(device)
+
+
+def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
+                      keep_predictions: bool = False) -> RolloutReport:
+    """Roll ``model`` out over ``B = len(starts)`` test trajectories at once and score every predicted frame against the simulation.
+
+    data: a ``BubbleForecast`` (its device store is made on the model's device) or a ``DeviceClipStore``; starts: dataset sample indices.
+    A step is the eval forward on the batch of B clips followed by ONE scoring call (``ops.rollout_score``) that reads the prediction once,
+    takes its targets from the store, writes that step's rows of the report, the next step's input and, if kept, the archive, and advances
+    a step counter that lives on the device.  With ``use_graph`` both are captured as one linear HIP graph and replayed ``steps`` times with
+    no other host work between replays; without, the same two calls run eagerly and give the same bits.  A model whose ``forward`` takes
+    ``fluid_params`` gets the store's fluid row of each trajectory's file.  Never synchronises."""
+    from .. import ops
+    from ..data.dataset import DeviceClipStore
+    device = next(model.parameters()).device
+    store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
+    ds = store.ds
+    plan = plan_rollouts(ds, starts, steps, getattr(model, "time_window", None))
+    if store.frames.device != device:
+        raise ValueError(f"the store is on {store.frames.device}, the model on {device}")
+    B, T, f = len(plan.first), int(ds.time_window), int(ds.downsample_factor)
+    Ho, Wo = (store.H // f, store.W // f) if f > 1 else (store.H, store.W)
+    fields = list(ds.output_fields)
+    sdf = fields.index(sdf_field) if sdf_field in fields else -1
+    extra = ()
+    if "fluid_params" in inspect.signature(model.forward).parameters:
+        if store.fluid is None:
+            raise ValueError("the model is conditioned on fluid parameters; build the dataset with return_fluid_params=True")
+        extra = (store.fluid[_to_device(plan.files, torch.int64, device)],)
+    first = _to_device(plan.first, torch.int64, device)
+    x = ops.clip_gather(store.frames, first, 0, T, store.in_tab, Ho, Wo)          # the input clips of data[starts[b]], as gather() builds them
+    C = len(fields)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    rel_l2, criterion = new(B, steps * T, C), new(B, steps)
+    eik_p, eik_t = (new(B, steps * T), new(B, steps * T)) if sdf >= 0 else (None, None)
+    archive = new(B, steps * T, C, Ho, Wo) if keep_predictions else None
+    counter = torch.zeros(1, dtype=torch.int32, device=device)
+    ws = ops.rollout_score_workspace(x)
+
+    def score(pred, step, next_in, arch):
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            pred = pred.float().contiguous()
+        if pred.shape != x.shape:
+            raise ValueError(f"the model returned {tuple(pred.shape)} for an input of {tuple(x.shape)}: it cannot be fed back")
+        ops.rollout_score(pred, store.frames, first, step, store.out_tab, sdf, steps, rel_l2, criterion, ws, eik_p, eik_t, next_in, arch)
+
+    model.eval()
+    with torch.no_grad():
+        if use_graph:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):           # warm-up as GraphedForward's, plus one scoring call on a throw-away counter (no copies)
+                for _ in range(2):
+                    out = model(x, *extra)
+                score(out, torch.zeros(1, dtype=torch.int32, device=device), None, None)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                score(model(x, *extra), counter, x, archive)
+            owner = model.__dict__.get("_bf_eval_owner")
+            for _ in range(steps):
+                if owner is not None:
+                    ops.refresh_eval_weights(owner)         # a no-op while the parameters do not change
+                graph.replay()
+        else:
+            for _ in range(steps):
+                score(model(x, *extra), counter, x, archive)
+    return RolloutReport(rel_l2, criterion, eik_p, eik_t, plan.timesteps.to(device, non_blocking=True), fields, archive)

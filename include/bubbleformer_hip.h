@@ -31,6 +31,7 @@
  *   bf_adam .................. torch.optim.Adam as configured at bubbleformer/modules.py:137-138 (config/optim_cfg/adam.yaml)
  *   bf_clip_gather ........... BubbleForecast.__getitem__ + DataLoader collate for a batch of clips: bubbleformer/data/dataset.py:120-182
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
+ *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  */
 #ifndef BUBBLEFORMER_HIP_H
@@ -356,6 +357,26 @@ int bf_eikonal_sum(const float* phi, int64_t frames, int H, int W, float dx, dou
 int bf_eikonal_l1_frames(const float* phi, int64_t frames, int H, int W, float dx, float* out, bf_stream_t stream);
 int bf_heatflux_rows(const float* dfun, const float* temp, int64_t frames, int64_t frame_stride, int W, float x_min, float dx,
                      float heater_temp, float lc, float* flux, bf_stream_t stream);
+/* All scores of ONE autoregressive rollout step from one pass over the prediction (scripts/inference.py:230-266, utils/plot_utils.py:30-33, the
+ * rollout notebook's get_eikonal_loss); allocation-free, capturable, no atomics (two calls on the same inputs give the same bits).
+ * pred (B, T, C, Ho, Wo) fp32; frames [nfields][total_frames][H][W] fp32 with field_stride floats per field (DeviceClipStore.frames); first [B]
+ * int64 (device) = absolute first INPUT frame of step 0 per trajectory; step = one int32 in DEVICE memory, s = *step; field / diff / div [C] = the
+ * store's output-field table.  Target of (b, t, c): y = (frames[field[c]][first[b] + (s + 1) * T + t][ys][xs] - diff[c]) / div[c], the expression
+ * and nearest-neighbour map of bf_clip_gather (the same device functions), frame index clamped into the store.  Written at row s * T + t:
+ *   rel_l2 [B][steps*T][C]  = sqrt(sum (pred - y)^2 / sum y^2) over (Ho, Wo): differences, squares, sums, quotient and root in fp64, rounded once
+ *                             (a target frame of zeros gives inf or NaN, as the reference's quotient of norms does);
+ *   criterion [B][steps]    = mean over t, then over c, of those fp64 quotients (LpLoss(d=2, p=2, reduce_dims=[0, 1], reductions=["mean", "mean"]));
+ *   eik_pred, eik_tgt [B][steps*T] (sdf_channel >= 0 only; Ho, Wo >= 3) = bf_eikonal_l1_frames' score at spacing dx of the signed-distance field in
+ *                             physical units: prediction pred * div + diff (fp32 multiply, then add, unfused), target the stored frame (downsampled);
+ *   next_in (B, T, C, Ho, Wo), archive (B, steps*T, C, Ho, Wo) rows s*T .. s*T + T - 1 (each optional) = copies of pred.
+ * The last launch sets *step = s + 1.  The host cannot see s: with s outside [0, steps) the call writes nothing and leaves *step as it is.
+ * ws: bf_rollout_score_ws_doubles(B, T, C, Ho, Wo) doubles (fp64 partials per workgroup, added in a fixed order).  pred, frames and the copies
+ * 16-byte aligned; B * T * C <= 65535. */
+int64_t bf_rollout_score_ws_doubles(int B, int T, int C, int Ho, int Wo);
+int bf_rollout_score(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                     int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
+                     float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
+                     int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
 /* Lion: p *= 1 - lr*wd; p -= lr*sign(beta1*m + (1-beta1)*g); m = beta2*m + (1-beta2)*g   (g is multiplied by gscale first) */
 int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
             bf_stream_t stream);
