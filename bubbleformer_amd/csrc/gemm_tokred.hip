@@ -334,9 +334,10 @@ __global__ void __launch_bounds__(256) tokred_narrow_kernel(const bf16* __restri
     // The tile loop waits by COUNT for its own LDS-DMA pieces, so nothing else may sit in the vector-memory queue while it runs: the
     // frame's scale / shift (ordinary loads to registers) are fetched BETWEEN loops -- a wave's tile range is cut at frame boundaries, and
     // each segment starts with an empty queue (drain, load, drain) and restarts the two-slot pipeline.  (The earlier form, loads inside the
-    // loop, produced a second channel block 1-2 % off and different from run to run: traced at the ISA level to the packed fp32 form hipcc
-    // chose for that block's scale / shift -- v_pk_fma_f32 .. op_sel:[0,1,1], wrong with two workgroups on a CU; EXPERIMENTS.md round 4 --
-    // which tools/register_audit.py now refuses, as it refuses compiler loads inside a counted loop.)
+    // loop, produced a second channel block 1-2 % off and different from run to run.  The loads were NOT the cause: the fault followed the
+    // packed fp32 form hipcc chose for that block's scale / shift -- v_pk_fma_f32 .. op_sel:[0,1,1], with two workgroups on a CU -- and why
+    // that form goes wrong there is OPEN (EXPERIMENTS.md round 4: no micro-benchmark reproduces it).  tools/register_audit.py refuses the
+    // form, as it refuses compiler loads inside a counted loop.)
     float scv[CT], shv[CT];
     for (long s_beg = t_beg; s_beg < t_end;) {
         long s_end = t_end;
@@ -550,20 +551,21 @@ extern "C" int64_t bf_gemm_tokred_ws_floats(int Nout, int Kin, int64_t M) {
 // ---- deferred slab sums (library-internal, model.hip): bf_gemm_tokred_deferred leaves its slab sum PENDING -- the next deferred call on the
 // same stream carries it in extra workgroups of its own launch (FoldRed), bf_gemm_tokred_flush runs what is left as a launch of its own.
 // The caller alternates nothing: the two halves of `ws` are used in turn, so a pending sum's slabs are never the next launch's target.
+// One record per device, looked up once per call.  It remembers the stream that produced the slabs: a pending sum is only ever folded into,
+// or launched on, that stream, and a caller on another stream waits for it through the record's own event.
 namespace {
-struct PendingRed { bool on = false; FoldRed r{}; int NI = 0; };
+struct PendingRed { bool on = false; FoldRed r{}; int NI = 0; hipStream_t st = nullptr; bool half = false; hipEvent_t handoff = nullptr; };      // half: which half of `ws` the next deferred launch writes
 PendingRed g_pending[64];
-bool g_half[64];
 PendingRed& pending_slot() { int dev = 0; (void)hipGetDevice(&dev); return g_pending[(dev >= 0 && dev < 64) ? dev : 0]; }
-bool& half_slot() { int dev = 0; (void)hipGetDevice(&dev); return g_half[(dev >= 0 && dev < 64) ? dev : 0]; }
 constexpr int FOLD_WGS = 40;      // extra workgroups that carry a pending sum (they hold a CU's LDS like the others: 128 + 40 of 256)
 }  // namespace
 static int tokred_impl(int dtype, int Nout, int Kin, int64_t M, const void* dy, int64_t ldy, const void* x, int64_t ldx, float* out,
                        int accumulate, float* colsum, float* ws, int64_t ws_floats, bool defer, bf_stream_t stream);
-int bf_gemm_tokred_flush(hipStream_t st) {
-    PendingRed& p = pending_slot();
+// the pending sum runs on the stream that produced its slabs; `caller` (when it is another one) is made to wait for it
+static int flush_pending(PendingRed& p, hipStream_t caller) {
     if (!p.on) return 0;
     p.on = false;
+    hipStream_t st = p.st;
     const FoldRed& r = p.r;
     const long n = (long)r.Nout * r.Kin;
     const unsigned rblocks = (unsigned)bf_cdiv(std::max<long>(n / 4, r.Nout), 256);
@@ -576,8 +578,13 @@ int bf_gemm_tokred_flush(hipStream_t st) {
         else hipLaunchKernelGGL((tokred_pp_reduce_kernel<3, MAX_SLICES>), dim3(rblocks), dim3(256), 0, st, r.slab, r.cslab, r.nslice, r.ntiles, r.tiles_k, r.Nout, r.Kin, r.out, r.colsum, r.accumulate);
     }
     BF_CHECK_LAUNCH();
-    return 0;
+    if (caller == st) return 0;
+    hipError_t e = p.handoff ? hipSuccess : hipEventCreateWithFlags(&p.handoff, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(p.handoff, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(caller, p.handoff, 0);
+    return e == hipSuccess ? 0 : bf_fail(e, __FILE__, __LINE__);
 }
+int bf_gemm_tokred_flush(hipStream_t st) { return flush_pending(pending_slot(), st); }
 namespace { bool g_fold_off = false; }
 // test hook: run every slab sum as a launch of its own right behind its GEMM (the deferred entry point then behaves like bf_gemm_tokred)
 extern "C" void bf_debug_tokred_fold(int on) { g_fold_off = on == 0; }
@@ -635,11 +642,11 @@ static int tokred_impl(int dtype, int Nout, int Kin, int64_t M, const void* dy, 
         const int64_t half_floats = (ws_floats / 2) & ~(int64_t)3;
         const bool fold = defer && fold_on && !g_fold_off && (int64_t)ns * (n + Nout) <= half_floats;
         PendingRed& pend = pending_slot();
-        if (!fold && pend.on) { const int frc = bf_gemm_tokred_flush(st); if (frc) return frc; }      // (also: the immediate form may be about to overwrite its slabs)
-        if (fold && pend.on && pend.NI != (big ? 6 : 3)) { const int frc = bf_gemm_tokred_flush(st); if (frc) return frc; }
-        bool& hf = half_slot();
+        // what cannot ride in this launch goes out first: the immediate form may be about to overwrite its slabs, the fold workgroups are
+        // built for one tile shape, and a sum whose slabs another stream produced is not ordered before this launch
+        if (pend.on && (!fold || pend.NI != (big ? 6 : 3) || pend.st != st)) { const int frc = flush_pending(pend, st); if (frc) return frc; }
         float* region = ws;
-        if (fold) { region = ws + (hf ? half_floats : 0); hf = !hf; }
+        if (fold) { region = ws + (pend.half ? half_floats : 0); pend.half = !pend.half; }
         float* slab = region;
         float* cslab = colsum ? region + (size_t)ns * n : nullptr;
         const unsigned rblocks = (unsigned)bf_cdiv(std::max<long>(n / 4, Nout), 256);
@@ -664,7 +671,7 @@ static int tokred_impl(int dtype, int Nout, int Kin, int64_t M, const void* dy, 
                 BF_CHECK_LAUNCH();                                                                                                        \
             }                                                                                                                             \
             if (fold) {                                                                                                                   \
-                pend.on = true; pend.NI = NIV;                                                                                            \
+                pend.on = true; pend.NI = NIV; pend.st = st;                                                                              \
                 pend.r = FoldRed{slab, cslab, ns, ntiles, tiles_k, Nout, Kin, out, colsum, accumulate, 0};                                \
                 break;                                                                                                                    \
             }                                                                                                                             \
@@ -677,7 +684,7 @@ static int tokred_impl(int dtype, int Nout, int Kin, int64_t M, const void* dy, 
 #undef BF_PP_GO
         return 0;
     }
-    { const int frc = bf_gemm_tokred_flush(st); if (frc) return frc; }      // (a pending sum's slabs live in the workspace this form is about to use)
+    { const int frc = flush_pending(pending_slot(), st); if (frc) return frc; }      // (a pending sum's slabs live in the workspace this form is about to use)
     const long steps = M / BK;
     int nslice = slices_env > 0 ? slices_env : 8;
     nslice = (int)std::max<long>(1, std::min<long>({(long)nslice, (long)MAX_SLICES, steps}));

@@ -113,36 +113,136 @@ struct SideStream { hipStream_t st = nullptr; hipEvent_t fork = nullptr, join = 
 // last user of its set), so nothing the side stream still reads is overwritten and the side stream may lag by a whole stage.
 // Every other stage entry point joins everything at its start, as does bf_side_join().  Off by default: plain stream-ordered
 // semantics (every stage joins before it returns).
+// A process-wide MODE, not per-device state: bf_side_defer is documented as one and the Python binding's set_side_defer relies on it.
 bool g_side_defer = false;
-SideStream* side_stream() {
-    static SideStream tab[64];
-    static const bool enabled = bf_knob("BF_SIDE_STREAM", 1) != 0;
-    if (!enabled) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    SideStream& s = tab[dev];
-    if (!s.st && !s.failed) {
-        // lowest priority: the caller's stream is the one a consumer waits on (round 2: +0.3-0.5 % against normal priority; round 3: no
-        // difference between lowest, normal and highest)
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = least urgent (numerically greatest)
-        // the two streams are on one device: the events need no system-scope fence (an L2 write-back + invalidate at every fork / join)
-        const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
-        if (hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, lo) != hipSuccess || hipEventCreateWithFlags(&s.fork, ef) != hipSuccess ||
-            hipEventCreateWithFlags(&s.join, ef) != hipSuccess || hipEventCreateWithFlags(&s.tail[0], ef) != hipSuccess ||
-            hipEventCreateWithFlags(&s.tail[1], ef) != hipSuccess) { s.failed = true; s.st = nullptr; }
+
+// ------------------------------------------------------------------------------------------------ what links one call to the next
+// Hints for the call made next.  A setter (bf_stage_prepared, bf_stage_chain_next / _head, bf_stage_chain_tail, bf_stage_next_scale) arms
+// them; the next trunk stage entry point takes ALL of them out of the record at its top, whatever it then does with them (a call that
+// fails early leaves nothing armed for an unrelated later one).  The native trunk driver builds them locally instead: it knows the sequence.
+//  * prepared: the stage forward finds its weights prepared in `saved` (bf_prep_stages) and skips its own launch
+//  * head: a stage that ends in `out = resid + InstanceNorm(z)` (the spatial stage's MLP branch) or in the out-projection (temporal) leaves the
+//    next stage's opening InstanceNorm(out) behind in the same launch (norm.hip InChain, bf_gemm_fwd_frames): that stage's parameters and record
+//  * tail: the mirror image in the backward.  The temporal stage's last kernel (QKV data gradient + norm1 backward) produces the output
+//    gradient of the spatial stage in front of it, whose backward opens with its MLP-branch InstanceNorm: that stage's parameters, saved
+//    record and whether its MLP branch carried stochastic depth
+//  * scale: a temporal stage multiplies its incoming gradient by its per-sample stochastic-depth factors before anything else reads it.  That
+//    gradient is produced by the last kernel of the spatial stage in front of it: told the factors, the kernel writes the scaled copy as well
+//    (one elementwise launch and one read of the gradient less per block)
+struct NextHead { bool armed = false; const float *w = nullptr, *b = nullptr; float *mean = nullptr, *rstd = nullptr, *sc = nullptr, *sh = nullptr; void* xn = nullptr; const void* saved = nullptr; };
+struct NextTail { bool armed = false; const bf_spatial_params* p = nullptr; const void* saved = nullptr; bool drop = false; };
+struct NextScale { const float* f = nullptr; int fdiv = 1; };
+struct StageHints { bool prepared = false; NextHead head; NextTail tail; NextScale scale; };
+
+// All InstanceNorm / attention parameter-gradient reductions of one stage backward go out in ONE launch (stage_param_reduce_kernel).  Room for
+// a spatial (3 + 2) and a temporal (2 + 1) stage: see TrunkLinks::reduce
+struct ReduceJobs {
+    static constexpr int IN_CAP = 6, ATTN_CAP = 4;
+    int n_in = 0, n_attn = 0; InReduceJob in[IN_CAP]; AttnReduceJob at[ATTN_CAP];
+    bool fits(const ReduceJobs& o) const { return n_in + o.n_in <= IN_CAP && n_attn + o.n_attn <= ATTN_CAP; }
+    int push(const InReduceJob& j) { BF_REQUIRE(n_in < IN_CAP, "ReduceJobs: more InstanceNorm reductions than one launch holds"); in[n_in++] = j; return 0; }
+    int push(const AttnReduceJob& j) { BF_REQUIRE(n_attn < ATTN_CAP, "ReduceJobs: more attention reductions than one launch holds"); at[n_attn++] = j; return 0; }
+};
+
+// Host-side state that links one library call to the next: ONE record per device, looked up once by each exported entry point and handed
+// down by reference.  The record is per device, not per stream: every item remembers the stream it was made on.  A carry-over item found
+// by a call on another stream counts as absent (the consumer recomputes: the unchained path is always right); an obligation is launched
+// on the stream that produced its partial sums and the new stream waits for it (`handoff`).  Two trunk passes running CONCURRENTLY on two
+// streams of one device remain unsupported: they would interleave their hints and alternation bits.
+struct TrunkLinks {
+    // ---- 1. hints (see StageHints)
+    StageHints hints;
+    StageHints take_hints() { const StageHints h = hints; hints = StageHints{}; return h; }
+    // ---- 2. carry-over: what one stage call leaves for a later one
+    struct HeadDone { const void* saved = nullptr; hipStream_t st = nullptr; } head_done;      // the stage whose norm1 statistics and xn the stage in front left behind (hints.head)
+    // the spatial stage whose MLP-branch norm backward the temporal stage behind it applied (hints.tail): dz and the partial sums `ws` are in
+    // place -- usable only if that stage's dout IS `dx`, the gradient tensor the chained tail was computed from
+    struct TailDone { const void* saved = nullptr; const void* dx = nullptr; float* ws = nullptr; hipStream_t st = nullptr; } tail_done;
+    struct DbrReady { const void* dx = nullptr; const float* f = nullptr; void* buf = nullptr; hipStream_t st = nullptr; } dbr_ready;      // the pre-scaled copy `buf` of gradient `dx` (hints.scale)
+    // alternation bits.  scratch_parity: the scratch set of a trunk backward stage (deferred mode alternates, so that the side stream may still
+    // read the previous stage's set).  tail_ws_flip: where the chained tail leaves the norm's partial sums -- the spatial stage's reduction of
+    // them waits for the temporal stage behind it (reduce), whose own chained tail, for the NEXT spatial stage and the same scratch set, must
+    // not overwrite them.  dbr_flip: the two pre-scaled gradient buffers -- the temporal stage's side-stream work may still read its copy
+    // while the next spatial stage writes the next one
+    int scratch_parity = 0; bool tail_ws_flip = false, dbr_flip = false;
+    bool take_head_done(const void* saved, hipStream_t st) { const bool hit = head_done.saved == saved && head_done.st == st; head_done = HeadDone{}; return hit; }
+    // ---- 3. obligations: GPU work not yet launched that somebody must launch (the deferred slab sum is gemm_tokred.hip's own)
+    // Deferred mode (bf_side_defer): the spatial stage's reductions wait for the temporal stage's backward that follows it and ride in ITS launch
+    // (one launch per block pair instead of two: 12 launches less on the caller's queue per step).  The two stages use different scratch sets, so
+    // the spatial stage's partial sums are intact until the next spatial stage, which flushes a leftover first -- as does every full join.
+    struct { ReduceJobs jobs; bool on = false; hipStream_t st = nullptr; } reduce;
+    hipEvent_t handoff = nullptr;       // orders an obligation launched on its producing stream before a caller on another one
+    // ---- the library's own stream of this device, and saved records whose stage-0 embed map was NOT stored by the forward (host-side memory of
+    // a per-call decision; the record itself is device memory)
+    SideStream side;
+    std::vector<const void*> embed_lean;
+
+    SideStream* side_stream() {
+        static const bool enabled = bf_knob("BF_SIDE_STREAM", 1) != 0;
+        if (!enabled) return nullptr;
+        SideStream& s = side;
+        if (!s.st && !s.failed) {
+            // lowest priority: the caller's stream is the one a consumer waits on (round 2: +0.3-0.5 % against normal priority; round 3: no
+            // difference between lowest, normal and highest)
+            int lo = 0, hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = least urgent (numerically greatest)
+            // the two streams are on one device: the events need no system-scope fence (an L2 write-back + invalidate at every fork / join)
+            const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
+            if (hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, lo) != hipSuccess || hipEventCreateWithFlags(&s.fork, ef) != hipSuccess ||
+                hipEventCreateWithFlags(&s.join, ef) != hipSuccess || hipEventCreateWithFlags(&s.tail[0], ef) != hipSuccess ||
+                hipEventCreateWithFlags(&s.tail[1], ef) != hipSuccess) { s.failed = true; s.st = nullptr; }
+        }
+        return s.st ? &s : nullptr;
     }
-    return s.st ? &s : nullptr;
+    // `to` waits for what has been enqueued on `from` so far
+    int hand_over(hipStream_t from, hipStream_t to) {
+        if (from == to) return 0;
+        if (!handoff) HIP_TRY(hipEventCreateWithFlags(&handoff, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(handoff, from));
+        HIP_TRY(hipStreamWaitEvent(to, handoff, 0));
+        return 0;
+    }
+    // A forward pass starts at the embed and a backward pass at the debed: what an aborted pass left armed (a hint whose consumer never ran, a
+    // "done for" record whose address a later allocation may reuse) must not survive into the next one.
+    void clear(bool forward_side) {
+        if (forward_side) { hints.prepared = false; hints.head = NextHead{}; head_done = HeadDone{}; }
+        hints.tail = NextTail{}; hints.scale = NextScale{}; tail_done = TailDone{}; dbr_ready = DbrReady{};
+    }
+    bool embed_lean_get(const void* saved) const { return std::find(embed_lean.begin(), embed_lean.end(), saved) != embed_lean.end(); }
+    void embed_lean_set(const void* saved, bool lean) {
+        const auto it = std::find(embed_lean.begin(), embed_lean.end(), saved);
+        if (it == embed_lean.end()) { if (lean) embed_lean.push_back(saved); }
+        else if (!lean) { *it = embed_lean.back(); embed_lean.pop_back(); }
+    }
+};
+BfPerDevice<TrunkLinks> g_links;
+
+int launch_reduce_jobs(ReduceJobs& J, hipStream_t st);
+// a spatial stage's parameter reductions waiting for the temporal stage behind it: launched on the stream that made their partial sums
+int flush_pending_reduce(TrunkLinks& L, hipStream_t st) {
+    if (!L.reduce.on) return 0;
+    L.reduce.on = false;
+    TRY(launch_reduce_jobs(L.reduce.jobs, L.reduce.st));
+    return L.hand_over(L.reduce.st, st);
+}
+// J's launch carries the pending jobs where they were made on the same stream and fit; otherwise they go out first, as a launch of their own
+int launch_with_pending(TrunkLinks& L, ReduceJobs& J, hipStream_t st) {
+    if (L.reduce.on && L.reduce.st == st && J.fits(L.reduce.jobs)) {
+        L.reduce.on = false;
+        const ReduceJobs& P = L.reduce.jobs;
+        for (int i = 0; i < P.n_in; ++i) TRY(J.push(P.in[i]));
+        for (int i = 0; i < P.n_attn; ++i) TRY(J.push(P.at[i]));
+    }
+    TRY(flush_pending_reduce(L, st));
+    return launch_reduce_jobs(J, st);
 }
 // the previous stage's deferred tail (if any) is ordered before what `main` is given next
-int flush_pending_reduce(hipStream_t st);                    // (a spatial stage's parameter reductions waiting for the temporal stage behind it)
-int side_join_pending(hipStream_t main, int set = -1) {      // set: 0 / 1 = the work that reads that scratch set, -1 = everything
-    if (set < 0) { const int rc = flush_pending_reduce(main); if (rc) return rc; }
-    SideStream* s = side_stream();
+int side_join_pending(TrunkLinks& L, hipStream_t main, int set = -1) {      // set: 0 / 1 = the work that reads that scratch set, -1 = everything
+    if (set < 0) TRY(flush_pending_reduce(L, main));
+    SideStream* s = L.side_stream();
     if (set < 0 && bf_gemm_tokred_pending()) {               // the last weight-gradient GEMM's slab sum is still pending (bf_gemm_tokred_deferred): run it now
         hipStream_t ws_st = s ? s->st : main;
-        const int rc = bf_gemm_tokred_flush(ws_st);
-        if (rc) return rc;
+        TRY(bf_gemm_tokred_flush(ws_st));
         if (s) { HIP_TRY(hipEventRecord(s->join, s->st)); HIP_TRY(hipStreamWaitEvent(main, s->join, 0)); }
     }
     if (!s) return 0;
@@ -158,7 +258,7 @@ struct Fork {
     std::vector<std::function<int(hipStream_t)>> jobs;          // deferred mode: the stage's side work, launched by flush()
     std::vector<std::function<int(hipStream_t)>> late;          // ... and what must follow the stage's LAST weight-gradient launch (see run_late)
     hipStream_t last_side = nullptr;
-    explicit Fork(hipStream_t m, bool may_defer = false, int scratch_set = 0) : main(m), s(side_stream()), set(scratch_set) {
+    explicit Fork(TrunkLinks& L, hipStream_t m, bool may_defer = false, int scratch_set = 0) : main(m), s(L.side_stream()), set(scratch_set) {
         deferred = may_defer && g_side_defer && s != nullptr;
     }
     // stream for work that depends only on what has been issued on `main` so far
@@ -184,34 +284,29 @@ struct Fork {
     int drain_late() {
         if (late.empty()) return 0;
         hipStream_t ss = last_side ? last_side : main;
-        for (auto& j : late) { const int rc = j(ss); if (rc) return rc; }
+        for (auto& j : late) TRY(j(ss));
         late.clear();
         return 0;
     }
     // deferred mode: one fork for everything collected so far
     int flush() {
         if (!deferred || jobs.empty()) return 0;
-        int rc;
         hipStream_t ss;
-        if ((rc = begin(&ss))) return rc;
-        for (auto& j : jobs) if ((rc = j(ss))) return rc;
+        TRY(begin(&ss));
+        for (auto& j : jobs) TRY(j(ss));
         jobs.clear();
         return 0;
     }
     // everything forked so far is ordered before what `main` is given next (deferred mode: before the next stage's fork point)
     int join() {
         if (deferred) {
-            int rc = flush();
-            if (rc) return rc;
-            if ((rc = drain_late())) return rc;
+            TRY(flush());
+            TRY(drain_late());
             if (used) { HIP_TRY(hipEventRecord(s->tail[set], s->st)); s->pending[set] = true; used = false; }
             return 0;
         }
-        {   // plain stream-ordered semantics: nothing of the stage may stay pending
-            int rc = drain_late();
-            if (rc) return rc;
-            if (bf_gemm_tokred_pending() && (rc = bf_gemm_tokred_flush(last_side ? last_side : main))) return rc;
-        }
+        TRY(drain_late());      // plain stream-ordered semantics: nothing of the stage may stay pending
+        if (bf_gemm_tokred_pending()) TRY(bf_gemm_tokred_flush(last_side ? last_side : main));
         if (!s || !used) return 0;
         HIP_TRY(hipEventRecord(s->join, s->st));
         HIP_TRY(hipStreamWaitEvent(main, s->join, 0));
@@ -439,8 +534,6 @@ __global__ void __launch_bounds__(256) stage_prep_multi_kernel(PrepBatch b) {
         *reinterpret_cast<bf16x4*>(j.dst[w] + 4 * i) = o;
     }
 }
-// set by bf_stage_prepared(1): the next trunk stage forward finds its weights prepared in `saved` (bf_prep_stages) and skips its own launch
-bool g_stage_prepared = false;
 // weights[i] (fp32, count n[i], multiples of 4) -> compute-dtype operands: one cast launch in bf16 mode, aliases in f32 mode;
 // `prep` (optional): the out-projection fold of the stage, computed in the same launch
 int wviews(const D& d, int cnt, const float* const* src, void* const* dst, const long* n, const void** out, hipStream_t st, const PrepArgs* prep = nullptr) {
@@ -564,7 +657,6 @@ struct Scratch {
 // ------------------------------------------------------------------------------------------------ stage-end parameter reductions
 // All InstanceNorm / attention parameter-gradient reductions of one stage backward in ONE launch (grid z = job): nothing on the
 // critical path reads them, and eight dependent ~5 us launches per block are worth ~3 % of the step.
-struct ReduceJobs { int n_in = 0, n_attn = 0; InReduceJob in[6]; AttnReduceJob at[4]; };      // room for a spatial + a temporal stage (see g_pending_reduce.get())
 __global__ void __launch_bounds__(64 * BF_RED_FL) stage_param_reduce_kernel(ReduceJobs J) {
     __shared__ float red[5][BF_RED_FL][64];
     const int z = blockIdx.z;
@@ -589,26 +681,6 @@ int launch_reduce_jobs(ReduceJobs& J, hipStream_t st) {
     BF_CHECK_LAUNCH();
     return 0;
 }
-// Deferred mode (bf_side_defer): the spatial stage's reductions wait for the temporal stage's backward that follows it and ride in ITS launch
-// (one launch per block pair instead of two: 12 launches less on the caller's queue per step).  The two stages use different scratch sets, so
-// the spatial stage's partial sums are intact until the next spatial stage, which flushes a leftover first -- as does every full join.
-BfPerDevice<ReduceJobs> g_pending_reduce;
-BfPerDevice<bool> g_pending_reduce_on;
-int flush_pending_reduce(hipStream_t st) {
-    if (!g_pending_reduce_on.get()) return 0;
-    g_pending_reduce_on.get() = false;
-    return launch_reduce_jobs(g_pending_reduce.get(), st);
-}
-int launch_with_pending(ReduceJobs& J, hipStream_t st) {
-    if (g_pending_reduce_on.get()) {
-        g_pending_reduce_on.get() = false;
-        const ReduceJobs& P = g_pending_reduce.get();
-        for (int i = 0; i < P.n_in && J.n_in < 6; ++i) J.in[J.n_in++] = P.in[i];
-        for (int i = 0; i < P.n_attn && J.n_attn < 4; ++i) J.at[J.n_attn++] = P.at[i];
-    }
-    return launch_reduce_jobs(J, st);
-}
-
 
 // QKV projection + attention shared pieces -------------------------------------------------------
 // The InstanceNorm'd operand is materialised by the statistics kernel itself (bf_in_stats_apply: the frame is in registers there),
@@ -630,12 +702,11 @@ int outproj_gemm(const D& d, const void* on, const void* w_c, const float* alpha
     e.rowscale = drop; e.rows_per_group = (int)rows_per_group;
     return bf_gemm(d.dtype, (int)d.N, d.E, d.E, &A, &Bo, &e, 1, st);
 }
-// scratch set of a trunk backward stage: deferred mode alternates, so that the side stream may still read the previous stage's set
-BfPerDevice<int> g_scratch_parity;
-void* bwd_scratch(const D& d, void* scratch) {
-    if (!g_side_defer || !side_stream()) return scratch;
-    g_scratch_parity.get() ^= 1;
-    return (char*)scratch + (size_t)g_scratch_parity.get() * Scratch(d, nullptr).bytes;
+// scratch set of a trunk backward stage (TrunkLinks::scratch_parity)
+void* bwd_scratch(TrunkLinks& L, const D& d, void* scratch) {
+    if (!g_side_defer || !L.side_stream()) return scratch;
+    L.scratch_parity ^= 1;
+    return (char*)scratch + (size_t)L.scratch_parity * Scratch(d, nullptr).bytes;
 }
 // A data gradient dy @ W whose consumer is the backward of the InstanceNorm that fed the projection: when a frame is one
 // 144-row GEMM tile the two run as ONE kernel (gemm_frame.hip); otherwise GEMM into `tmp`, then the InstanceNorm backward.
@@ -760,89 +831,41 @@ extern "C" int64_t bf_scratch_bytes(const bf_dims* s) { D d; if (get_dims(s, &d)
 
 // Deferred weight-gradient tails (see SideStream): opt-in for callers that join explicitly before they consume parameter gradients
 extern "C" void bf_side_defer(int on) { g_side_defer = on != 0; }
-extern "C" int bf_side_join(bf_stream_t s) { return side_join_pending((hipStream_t)s); }
+extern "C" int bf_side_join(bf_stream_t s) { return side_join_pending(g_links.get(), (hipStream_t)s); }
 
-// ================================================================================================= temporal block
-// Chained stage heads: a stage that ends in `out = resid + InstanceNorm(z)` (the spatial stage's MLP branch) can leave the next stage's
-// opening InstanceNorm(out) behind in the same launch (norm.hip, InChain).  bf_stage_chain_head arms it with the next temporal stage's
-// parameters and saved record; the stage that consumed it remembers the record, and that stage's forward skips its own norm1.
-namespace {
-struct NextHead { bool armed = false; const float *w = nullptr, *b = nullptr; float *mean = nullptr, *rstd = nullptr, *sc = nullptr, *sh = nullptr; void* xn = nullptr; const void* saved = nullptr; };
-BfPerDevice<NextHead> g_next_head;
-BfPerDevice<const void*> g_head_done_for;
-}  // namespace
-// ... and the mirror image in the backward: the temporal stage's last kernel (QKV data gradient + norm1 backward) produces the output
-// gradient of the spatial stage in front of it, whose backward opens with its MLP-branch InstanceNorm.  bf_stage_chain_tail arms that
-// norm's backward (the spatial stage's parameters, saved record and whether its MLP branch carried stochastic depth) for the temporal
-// backward called next; the spatial backward on the same record then finds dz and the partial sums in place.
-namespace {
-struct NextTail { bool armed = false; const bf_spatial_params* p = nullptr; const void* saved = nullptr; bool drop = false; };
-BfPerDevice<NextTail> g_next_tail;
-BfPerDevice<const void*> g_tail_done_for;
-// where the chained tail left the norm's partial sums.  Two regions, alternating: the spatial stage's reduction of them waits for the temporal
-// stage behind it (g_pending_reduce.get()), whose own chained tail -- for the NEXT spatial stage, same scratch set -- must not overwrite them
-BfPerDevice<float*> g_tail_ws;
-BfPerDevice<bool> g_tail_ws_flip;
-BfPerDevice<const void*> g_tail_dx;     // the gradient tensor the chained tail was computed from: the spatial backward must be handed exactly that one
-}  // namespace
+// ================================================================================================= hint setters (see StageHints)
+// The per-stage callers arm a hint right before the stage call it is meant for; each setter only writes the record's slot.
+extern "C" void bf_stage_prepared(int on) { g_links.get().hints.prepared = on != 0; }
 extern "C" int bf_stage_chain_tail(const bf_spatial_params* prev_p, const void* prev_saved, int has_drop_mlp) {
-    g_next_tail.get().armed = prev_p && prev_saved;
-    g_next_tail.get().p = prev_p; g_next_tail.get().saved = prev_saved; g_next_tail.get().drop = has_drop_mlp != 0;
+    g_links.get().hints.tail = NextTail{prev_p && prev_saved, prev_p, prev_saved, has_drop_mlp != 0};
     return 0;
 }
-// Stochastic depth in the backward: a temporal stage multiplies its incoming gradient by its per-sample factors before anything else reads it.
-// That gradient is produced by the last kernel of the spatial stage in front of it (QKV data gradient + norm1 backward): told the factors
-// (bf_stage_next_scale, armed by the caller just before that spatial stage's backward), the kernel writes the scaled copy as well and the
-// temporal backward finds it in place (one elementwise launch and one read of the gradient less per block).  Two buffers, alternating: the
-// temporal stage's side-stream work may still read its copy while the next spatial stage writes the next one.
-namespace {
-struct NextScale { const float* f = nullptr; int fdiv = 1; };
-BfPerDevice<NextScale> g_next_scale;
-struct DbrReady { const void* dx = nullptr; const float* f = nullptr; void* buf = nullptr; };
-BfPerDevice<DbrReady> g_dbr_ready;
-BfPerDevice<bool> g_dbr_flip;
-}  // namespace
-// A forward pass starts at the embed and a backward pass at the debed: what an aborted pass left armed (a hint whose consumer never ran, a
-// "done for" record whose address a later allocation may reuse) must not survive into the next one.
-static void links_clear(bool forward_side) {
-    if (forward_side) { g_next_head.get().armed = false; g_head_done_for.get() = nullptr; }
-    g_next_tail.get().armed = false; g_tail_done_for.get() = nullptr; g_tail_dx.get() = nullptr;
-    g_next_scale.get() = NextScale{}; g_dbr_ready.get() = DbrReady{};
-}
-extern "C" int bf_stage_next_scale(const float* factors, int fdiv) {
-    g_next_scale.get().f = factors; g_next_scale.get().fdiv = fdiv > 0 ? fdiv : 1;
-    return 0;
+extern "C" int bf_stage_next_scale(const float* factors, int fdiv) { g_links.get().hints.scale = NextScale{factors, fdiv > 0 ? fdiv : 1}; return 0; }
+static NextHead next_head(const D& d, int kind, const void* params, void* saved) {      // kind: 0 temporal, 1 spatial (both name norm1 and its saved outputs alike)
+    auto of = [&](auto* np, const auto& sv) { return NextHead{true, np->norm1_w, np->norm1_b, sv.mean1, sv.rstd1, sv.sc1, sv.sh1, sv.xn, saved}; };
+    return kind == 0 ? of((const bf_temporal_params*)params, TemporalSaved(d, saved)) : of((const bf_spatial_params*)params, SpatialSaved(d, saved));
 }
 extern "C" int bf_stage_chain_next(const bf_dims* dims, int next_kind, const void* next_params, void* next_saved) {
-    g_next_head.get().armed = false;
+    NextHead& h = g_links.get().hints.head;
+    h = NextHead{};
     if (!dims || !next_params || !next_saved) return 0;     // disarm
     BF_REQUIRE(next_kind == 0 || next_kind == 1, "bf_stage_chain_next: kind must be 0 (temporal) or 1 (spatial)");
     D d; TRY(get_dims(dims, &d));
-    if (next_kind == 0) {
-        const bf_temporal_params* np = (const bf_temporal_params*)next_params;
-        TemporalSaved sv(d, next_saved);
-        g_next_head.get().w = np->norm1_w; g_next_head.get().b = np->norm1_b;
-        g_next_head.get().mean = sv.mean1; g_next_head.get().rstd = sv.rstd1; g_next_head.get().sc = sv.sc1; g_next_head.get().sh = sv.sh1; g_next_head.get().xn = sv.xn;
-    } else {
-        const bf_spatial_params* np = (const bf_spatial_params*)next_params;
-        SpatialSaved sv(d, next_saved);
-        g_next_head.get().w = np->norm1_w; g_next_head.get().b = np->norm1_b;
-        g_next_head.get().mean = sv.mean1; g_next_head.get().rstd = sv.rstd1; g_next_head.get().sc = sv.sc1; g_next_head.get().sh = sv.sh1; g_next_head.get().xn = sv.xn;
-    }
-    g_next_head.get().saved = next_saved;
-    g_next_head.get().armed = true;
+    h = next_head(d, next_kind, next_params, next_saved);
     return 0;
 }
 extern "C" int bf_stage_chain_head(const bf_dims* dims, const bf_temporal_params* next_p, void* next_saved) {
     return bf_stage_chain_next(dims, 0, next_p, next_saved);
 }
 
-extern "C" int bf_temporal_fwd(const bf_dims* dims, const bf_temporal_params* p, const void* x, void* out, void* saved, void* scratch,
-                               const float* drop, bf_stream_t s) {
+// ================================================================================================= temporal block
+static int temporal_fwd(TrunkLinks& L, const StageHints& H, const bf_dims* dims, const bf_temporal_params* p, const void* x, void* out, void* saved,
+                        void* scratch, const float* drop, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && x && out && saved && scratch, "bf_temporal_fwd: null pointer");
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    const bool head_done = L.take_head_done(saved, st);      // the stage in front left norm1's statistics and xn behind (hints.head)
+    TRY(side_join_pending(L, st));
     TemporalSaved sv(d, saved);
     Scratch sc(d, scratch);
     const void *win_c, *wout_c;
@@ -854,14 +877,12 @@ extern "C" int bf_temporal_fwd(const bf_dims* dims, const bf_temporal_params* p,
         const bool b16 = d.dtype == BF_DTYPE_BF16;
         const PrepArgs prep{p->output_head_w, p->output_head_b, p->norm2_b, p->gamma, nullptr, nullptr, sv.alpha, sv.beta, sv.mc, d.E, sv.wout_s, d.dtype,
                             nullptr, nullptr, nullptr, 0, b16 ? p->output_head_w : nullptr, b16 ? sv.wout_t : nullptr, d.E, d.E};
-        const bool ready = g_stage_prepared && d.dtype == BF_DTYPE_BF16;
-        g_stage_prepared = false;
+        const bool ready = H.prepared && d.dtype == BF_DTYPE_BF16;
         if (ready) { out[0] = sv.win_c; out[1] = sv.wout_c; }
         else TRY(wviews(d, 2, src, dst, n, out, st, &prep));
         win_c = out[0]; wout_c = out[1];
     }
-    if (g_head_done_for.get() == saved) g_head_done_for.get() = nullptr;      // the stage in front left norm1's statistics and xn behind (bf_stage_chain_head)
-    else
+    if (!head_done)
         TRY(bf_in_stats_apply(d.dtype, x, (int)d.F, (int)d.S, d.E, p->norm1_w, p->norm1_b, nullptr, 1, nullptr, sv.mean1, sv.rstd1, sv.sc1, sv.sh1, sc.in_ws,
                               nullptr, sv.xn, st));
     TRY(qkv_gemm(d, sv.xn, win_c, p->input_head_b, sv.qkv, st));
@@ -870,30 +891,28 @@ extern "C" int bf_temporal_fwd(const bf_dims* dims, const bf_temporal_params* p,
                     p->knorm_w, p->knorm_b, p->rel_pos_emb, d.attn_scale ? p->attn_scale_factor : nullptr, 1.f, 0, st));
     TRY(bf_in_stats_apply(d.dtype, sv.o, (int)d.F, (int)d.S, d.E, p->norm2_w, p->norm2_b, nullptr, 1, nullptr, sv.mean2, sv.rstd2, sv.sc2, sv.sh2, sc.in_ws,
                           nullptr, sv.on, st));
-    if (g_next_head.get().armed) {      // the stage behind opens with InstanceNorm(out): it rides in the out-projection's launch (bf_stage_chain_next)
-        const NextHead h = g_next_head.get();
-        g_next_head.get().armed = false;
-        g_head_done_for.get() = nullptr;
+    if (H.head.armed) {      // the stage behind opens with InstanceNorm(out): it rides in the out-projection's launch
+        const NextHead& h = H.head;
         const bf_frame_norm n2{h.w, h.b, nullptr, 1, h.mean, h.rstd, h.sc, h.sh, nullptr, h.xn};
         const int rc = bf_gemm_fwd_frames(d.dtype, (int)d.N, d.E, d.E, sv.on, d.E, sv.wout_t, d.E, nullptr, sv.alpha, sv.beta, drop, d.T, x, out, (int)d.S,
                                           nullptr, &n2, s);
         if (rc < 0) return rc;
-        if (rc == 0) { g_head_done_for.get() = h.saved; return 0; }
+        if (rc == 0) { L.head_done = {h.saved, st}; return 0; }
     }
     TRY(outproj_gemm(d, sv.on, wout_c, sv.alpha, sv.beta, x, out, drop, (long)d.T * d.S, st));   // mask per batch element
     return 0;
 }
 
-extern "C" int bf_temporal_bwd(const bf_dims* dims, const bf_temporal_params* p, const bf_temporal_params* g, const void* x, const void* dout,
-                               void* dx, void* saved, void* scratch, const float* drop, bf_stream_t s) {
+static int temporal_bwd(TrunkLinks& L, const StageHints& H, const bf_dims* dims, const bf_temporal_params* p, const bf_temporal_params* g, const void* x,
+                        const void* dout, void* dx, void* saved, void* scratch, const float* drop, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && g && x && dout && dx && saved && scratch, "bf_temporal_bwd: null pointer");
     hipStream_t st = (hipStream_t)s;
     TemporalSaved sv(d, saved);
-    Scratch sc(d, bwd_scratch(d, scratch));
+    Scratch sc(d, bwd_scratch(L, d, scratch));
     const void* win_c = d.dtype == BF_DTYPE_F32 ? (const void*)p->input_head_w : sv.win_c;
-    Fork fk(st, true, g_scratch_parity.get());      // weight-gradient GEMMs go to the side stream; nothing they read (dbr, t3, s1) is rewritten before the join
-    if (fk.deferred) TRY(side_join_pending(st, fk.set));      // the stage before the previous one used this scratch set
+    Fork fk(L, st, true, L.scratch_parity);      // weight-gradient GEMMs go to the side stream; nothing they read (dbr, t3, s1) is rewritten before the join
+    if (fk.deferred) TRY(side_join_pending(L, st, fk.set));      // the stage before the previous one used this scratch set
     void* don = sc.t1;      // [N][E]
     void* dO = sc.t1b;      // [N][E]
     void* dqkv = sc.t3;     // [N][3E]
@@ -901,69 +920,75 @@ extern "C" int bf_temporal_bwd(const bf_dims* dims, const bf_temporal_params* p,
     // stream instead was measured twice and lost: EXPERIMENTS.md)
     const void* dbr = dout;
     if (drop) {
-        if (g_dbr_ready.get().dx == dout && g_dbr_ready.get().f == drop && g_dbr_ready.get().buf) dbr = g_dbr_ready.get().buf;      // the stage in front left the scaled copy behind
+        const TrunkLinks::DbrReady& r = L.dbr_ready;
+        if (r.dx == dout && r.f == drop && r.buf && r.st == st) dbr = r.buf;      // the stage in front left the scaled copy behind
         else {
             TRY(bf_frame_scale(d.dtype, dout, drop, d.T, sc.t4, d.N, (int)d.S, d.E, st));
             dbr = sc.t4;
         }
     }
-    g_dbr_ready.get() = DbrReady{};
+    L.dbr_ready = TrunkLinks::DbrReady{};
     const InFuse fu2{sv.o, nullptr, dO, sv.mean2, sv.rstd2, p->norm2_w, p->norm2_b, sc.in_ws2};      // don @ ... then norm2's backward -> dO
     TRY(outproj_bwd(d, sc, dbr, sv.on, sv.wout_s, p->output_head_w, p->output_head_b, p->norm2_b, p->gamma, nullptr, nullptr,
                     sv.alpha, sv.mc, g->output_head_w, g->output_head_b, nullptr, g->gamma, nullptr, nullptr, don, st, fk, &fu2));
     ReduceJobs jobs;        // parameter-gradient reductions, all launched together at the end
-    jobs.in[jobs.n_in++] = InReduceJob{sc.in_ws2, (int)d.F, d.E, p->norm2_w, p->norm2_b, nullptr, 1, g->norm2_w, g->norm2_b, nullptr, nullptr, nullptr, nullptr};
+    TRY(jobs.push(InReduceJob{sc.in_ws2, (int)d.F, d.E, p->norm2_w, p->norm2_b, nullptr, 1, g->norm2_w, g->norm2_b, nullptr, nullptr, nullptr, nullptr}));
     {
         int rows = 0;
         TRY(bf_attn_bwd_partials(d.dtype, sv.qkv, dO, dqkv, (long)d.B * d.S, d.T, d.S, (long)d.T * d.S, 1, d.S, d.heads, d.d, p->qnorm_w, p->qnorm_b,
                                  p->knorm_w, p->knorm_b, p->rel_pos_emb, d.attn_scale ? p->attn_scale_factor : nullptr, g->qnorm_w, g->qnorm_b,
                                  g->knorm_w, g->knorm_b, g->rel_pos_emb, d.attn_scale ? g->attn_scale_factor : nullptr, 1.f, 0, sc.attn_ws,
                                  Scratch::ATTN_WS_FLOATS, &rows, st));
-        jobs.at[jobs.n_attn++] = AttnReduceJob{sc.attn_ws, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
-                                               d.attn_scale ? g->attn_scale_factor : nullptr};
+        TRY(jobs.push(AttnReduceJob{sc.attn_ws, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
+                                    d.attn_scale ? g->attn_scale_factor : nullptr}));
     }
     void* dxn = sc.t1;      // don is dead
     InFuse fu1{x, dout, dx, sv.mean1, sv.rstd1, p->norm1_w, p->norm1_b, sc.in_ws};             // dqkv @ W_in, then norm1's backward + residual
-    // Chained tail (bf_stage_chain_tail): dx is the output gradient of the spatial stage in front, whose backward opens with its MLP-branch
+    // Chained tail (hints.tail): dx is the output gradient of the spatial stage in front, whose backward opens with its MLP-branch
     // InstanceNorm -- applied here, into THAT stage's scratch set (the other one: its earlier user's side work is joined first, as the
     // spatial stage itself would at its start).
     TailNorm tn;
     bool tail_done = false;
-    if (g_next_tail.get().armed) {
-        const NextTail h = g_next_tail.get();
-        g_next_tail.get().armed = false;
-        static const bool chain_on = bf_knob("BF_BWD_CHAIN", 1) != 0;
-        if (chain_on && fk.deferred && d.dtype == BF_DTYPE_BF16 && d.S == 144 && d.F % 2 == 0) {
-            const int oset = g_scratch_parity.get() ^ 1;
-            TRY(side_join_pending(st, oset));
-            Scratch so(d, (char*)scratch + (size_t)oset * Scratch(d, nullptr).bytes);
-            SpatialSaved ps(d, const_cast<void*>(h.saved));
-            tn = TailNorm{ps.z, so.t1, ps.mean3, ps.rstd3, h.p->mlp_norm_w, h.drop ? ps.gtab : h.p->gamma_mlp, h.drop ? 1 : (int)d.F, g_tail_ws_flip.get() ? so.in_ws5 : so.in_ws4, &tail_done};
-            g_tail_ws.get() = tn.ws;
-            g_tail_ws_flip.get() = !g_tail_ws_flip.get();
-            fu1.tail = &tn;
-        }
-        g_tail_done_for.get() = nullptr;
-        TRY(linear_bwd(d, sc, dqkv, 3 * d.E, sv.xn, d.E, BF_PRO_NONE, nullptr, nullptr, win_c, g->input_head_w, g->input_head_b, dxn, nullptr, st, fk, &fu1, true));
-        if (tail_done) { g_tail_done_for.get() = h.saved; g_tail_dx.get() = dx; }
-    } else
+    static const bool chain_on = bf_knob("BF_BWD_CHAIN", 1) != 0;
+    if (H.tail.armed && chain_on && fk.deferred && d.dtype == BF_DTYPE_BF16 && d.S == 144 && d.F % 2 == 0) {
+        const NextTail& h = H.tail;
+        const int oset = L.scratch_parity ^ 1;
+        TRY(side_join_pending(L, st, oset));
+        Scratch so(d, (char*)scratch + (size_t)oset * Scratch(d, nullptr).bytes);
+        SpatialSaved ps(d, const_cast<void*>(h.saved));
+        tn = TailNorm{ps.z, so.t1, ps.mean3, ps.rstd3, h.p->mlp_norm_w, h.drop ? ps.gtab : h.p->gamma_mlp, h.drop ? 1 : (int)d.F, L.tail_ws_flip ? so.in_ws5 : so.in_ws4, &tail_done};
+        L.tail_ws_flip = !L.tail_ws_flip;
+        fu1.tail = &tn;
+    }
+    if (H.tail.armed) L.tail_done = TrunkLinks::TailDone{};
     TRY(linear_bwd(d, sc, dqkv, 3 * d.E, sv.xn, d.E, BF_PRO_NONE, nullptr, nullptr, win_c, g->input_head_w, g->input_head_b, dxn, nullptr, st, fk, &fu1, true));
-    jobs.in[jobs.n_in++] = InReduceJob{sc.in_ws, (int)d.F, d.E, p->norm1_w, p->norm1_b, nullptr, 1, g->norm1_w, g->norm1_b, nullptr, nullptr, nullptr, nullptr};
-    TRY(launch_with_pending(jobs, st));      // ... with the reductions the spatial stage behind (in the forward) left pending
+    if (tail_done) L.tail_done = {H.tail.saved, dx, tn.ws, st};
+    TRY(jobs.push(InReduceJob{sc.in_ws, (int)d.F, d.E, p->norm1_w, p->norm1_b, nullptr, 1, g->norm1_w, g->norm1_b, nullptr, nullptr, nullptr, nullptr}));
+    TRY(launch_with_pending(L, jobs, st));      // ... with the reductions the spatial stage behind (in the forward) left pending
     return fk.join();
+}
+extern "C" int bf_temporal_fwd(const bf_dims* dims, const bf_temporal_params* p, const void* x, void* out, void* saved, void* scratch,
+                               const float* drop, bf_stream_t s) {
+    TrunkLinks& L = g_links.get();
+    return temporal_fwd(L, L.take_hints(), dims, p, x, out, saved, scratch, drop, s);
+}
+extern "C" int bf_temporal_bwd(const bf_dims* dims, const bf_temporal_params* p, const bf_temporal_params* g, const void* x, const void* dout,
+                               void* dx, void* saved, void* scratch, const float* drop, bf_stream_t s) {
+    TrunkLinks& L = g_links.get();
+    return temporal_bwd(L, L.take_hints(), dims, p, g, x, dout, dx, saved, scratch, drop, s);
 }
 
 // Parameter preparation of many trunk stages at once (what each stage forward otherwise launches for itself): bf16 weight copies, the
 // out-projection fold and the MLP branch's stochastic-depth table, written into each stage's `saved` record.  kinds[i]: 0 temporal
 // (params[i] = bf_temporal_params*), 1 spatial (bf_spatial_params*); drop_mlp[i]: the spatial stage's MLP-branch factors or NULL.
 // A stage forward consumes it when bf_stage_prepared(1) was called just before.  bf16 only (returns 1 in fp32 mode: nothing to cast).
-extern "C" int bf_prep_stages(const bf_dims* dims, int n, const int32_t* kinds, const void* const* params, void* const* saved,
-                              const float* const* drop_mlp, bf_stream_t s) {
+static int prep_stages(TrunkLinks& L, const bf_dims* dims, int n, const int32_t* kinds, const void* const* params, void* const* saved,
+                       const float* const* drop_mlp, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(n >= 1 && kinds && params && saved, "bf_prep_stages: bad arguments");
     if (d.dtype != BF_DTYPE_BF16) return 1;
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    TRY(side_join_pending(L, st));
     for (int i0 = 0; i0 < n; i0 += PREP_BATCH) {
         PrepBatch b;
         memset(&b, 0, sizeof(b));
@@ -1001,17 +1026,20 @@ extern "C" int bf_prep_stages(const bf_dims* dims, int n, const int32_t* kinds, 
     }
     return 0;
 }
-extern "C" void bf_stage_prepared(int on) { g_stage_prepared = on != 0; }
+extern "C" int bf_prep_stages(const bf_dims* dims, int n, const int32_t* kinds, const void* const* params, void* const* saved,
+                              const float* const* drop_mlp, bf_stream_t s) {
+    return prep_stages(g_links.get(), dims, n, kinds, params, saved, drop_mlp, s);
+}
 
 // ================================================================================================= axial (spatial) block
-extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, const void* x, void* out, void* saved, void* scratch,
-                              const float* drop_att, const float* drop_mlp, bf_stream_t s) {
+static int spatial_fwd(TrunkLinks& L, const StageHints& H, const bf_dims* dims, const bf_spatial_params* p, const void* x, void* out, void* saved,
+                       void* scratch, const float* drop_att, const float* drop_mlp, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && x && out && saved && scratch, "bf_spatial_fwd: null pointer");
-    const bool head_done = g_head_done_for.get() == saved;      // the temporal stage in front left norm1's statistics and xn behind (bf_stage_chain_next)
-    g_head_done_for.get() = nullptr;         // (a chained head is consumed by the stage called right after the stage that made it)
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    // the temporal stage in front left norm1's statistics and xn behind (a chained head is consumed by the stage called right after the stage that made it)
+    const bool head_done = L.take_head_done(saved, st);
+    TRY(side_join_pending(L, st));
     SpatialSaved sv(d, saved);
     Scratch sc(d, scratch);
     const void *win_c, *wout_c, *w1_c, *w2_c;
@@ -1025,8 +1053,7 @@ extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, c
                             d.feat_scale ? p->high_freq_scalar : nullptr, sv.alpha, sv.beta, sv.mc, d.E, sv.wout_s, d.dtype,
                             tab ? drop_mlp : nullptr, tab ? p->gamma_mlp : nullptr, tab ? sv.gtab : nullptr, (int)d.F,
                             d.dtype == BF_DTYPE_BF16 ? p->fc2_w : nullptr, d.dtype == BF_DTYPE_BF16 ? sv.w2t_c : nullptr, d.E, 4 * d.E};
-        const bool ready = g_stage_prepared && d.dtype == BF_DTYPE_BF16;
-        g_stage_prepared = false;
+        const bool ready = H.prepared && d.dtype == BF_DTYPE_BF16;
         if (ready) { out[0] = sv.win_c; out[1] = sv.wout_c; out[2] = sv.w1_c; out[3] = sv.w2_c; }
         else TRY(wviews(d, 4, src, dst, n, out, st, &prep));
         win_c = out[0]; wout_c = out[1]; w1_c = out[2]; w2_c = out[3];
@@ -1070,14 +1097,13 @@ extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, c
     }
     if (d.dtype == BF_DTYPE_BF16) {      // z = hid @ W2^T + b2, the MLP-branch norm + residual and (armed) the next stage's opening norm in ONE launch
         const bf_frame_norm n1{p->mlp_norm_w, p->mlp_norm_b, g3, g3div, sv.mean3, sv.rstd3, sv.sc3, sv.sh3, sv.x1, out};
-        const NextHead h = g_next_head.get();
+        const NextHead& h = H.head;
         const bf_frame_norm n2{h.w, h.b, nullptr, 1, h.mean, h.rstd, h.sc, h.sh, nullptr, h.xn};
         const int rc = bf_gemm_fwd_frames(d.dtype, (int)d.N, d.E, 4 * d.E, sv.hid, 4L * d.E, sv.w2t_c, d.E, p->fc2_b, nullptr, nullptr, nullptr, 1, nullptr, sv.z,
                                           (int)d.S, &n1, h.armed ? &n2 : nullptr, s);
         if (rc < 0) return rc;
         if (rc == 0) {
-            g_next_head.get().armed = false;
-            g_head_done_for.get() = h.armed ? h.saved : nullptr;
+            if (h.armed) L.head_done = {h.saved, st};
             return 0;
         }
     }
@@ -1088,13 +1114,12 @@ extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, c
         e.bias = p->fc2_b;
         TRY(bf_gemm(d.dtype, (int)d.N, d.E, 4 * d.E, &A, &Bo, &e, 1, st));
     }
-    if (g_next_head.get().armed) {
-        const NextHead h = g_next_head.get();
-        g_next_head.get().armed = false;
+    if (H.head.armed) {
+        const NextHead& h = H.head;
         bool chained = false;
         TRY(bf_in_stats_apply_chain(d.dtype, sv.z, (int)d.F, (int)d.S, d.E, p->mlp_norm_w, p->mlp_norm_b, g3, g3div, nullptr, sv.mean3, sv.rstd3, sv.sc3, sv.sh3,
                                     sc.in_ws, sv.x1, out, h.w, h.b, h.mean, h.rstd, h.sc, h.sh, h.xn, &chained, st));
-        g_head_done_for.get() = chained ? h.saved : nullptr;
+        if (chained) L.head_done = {h.saved, st};
         return 0;
     }
     TRY(bf_in_stats_apply(d.dtype, sv.z, (int)d.F, (int)d.S, d.E, p->mlp_norm_w, p->mlp_norm_b, g3, g3div, nullptr, sv.mean3, sv.rstd3,
@@ -1102,40 +1127,37 @@ extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, c
     return 0;
 }
 
-extern "C" int bf_spatial_bwd(const bf_dims* dims, const bf_spatial_params* p, const bf_spatial_params* g, const void* x, const void* dout,
-                              void* dx, void* saved, void* scratch, const float* drop_att, const float* drop_mlp, bf_stream_t s) {
+static int spatial_bwd(TrunkLinks& L, const StageHints& H, const bf_dims* dims, const bf_spatial_params* p, const bf_spatial_params* g, const void* x,
+                       const void* dout, void* dx, void* saved, void* scratch, const float* drop_att, const float* drop_mlp, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && g && x && dout && dx && saved && scratch, "bf_spatial_bwd: null pointer");
     hipStream_t st = (hipStream_t)s;
     SpatialSaved sv(d, saved);
-    Scratch sc(d, bwd_scratch(d, scratch));
+    Scratch sc(d, bwd_scratch(L, d, scratch));
     const bool f32 = d.dtype == BF_DTYPE_F32;
     const void* win_c = f32 ? (const void*)p->input_head_w : sv.win_c;
     const void* w1_c = f32 ? (const void*)p->fc1_w : sv.w1_c;
     const void* w2_c = f32 ? (const void*)p->fc2_w : sv.w2_c;
     // weight-gradient GEMMs go to the side stream and are joined at the end; every buffer they read (dz = t1, dpre = t4,
     // dx1 = t1b, dbr = e5, dqkv = t3, s1) is written once per call, so the critical path below never recycles one under them.
-    TRY(flush_pending_reduce(st));      // (a spatial stage that no temporal stage followed: its partial sums live in the set this stage is about to use)
-    Fork fk(st, true, g_scratch_parity.get());
-    if (fk.deferred) TRY(side_join_pending(st, fk.set));      // the stage before the previous one used this scratch set
+    TRY(flush_pending_reduce(L, st));      // (a spatial stage that no temporal stage followed: its partial sums live in the set this stage is about to use)
+    Fork fk(L, st, true, L.scratch_parity);
+    if (fk.deferred) TRY(side_join_pending(L, st, fk.set));      // the stage before the previous one used this scratch set
     // out = x1 + gamma_mlp * IN(z)
     void* dz = sc.t1;
     ReduceJobs jobs;        // parameter-gradient reductions, all launched together at the end
-    // the temporal stage behind left dz and the partial sums in place (bf_stage_chain_tail) -- usable only if this call's dout IS the dx that stage
+    // the temporal stage behind left dz and the partial sums in place (hints.tail) -- usable only if this call's dout IS the dx that stage
     // wrote (another consumer of the stage's output, or a gradient hook, makes autograd hand over a different, summed tensor: recompute then)
-    const bool tail_done = g_tail_done_for.get() == saved && g_tail_dx.get() == dout;
-    g_tail_done_for.get() = nullptr; g_tail_dx.get() = nullptr;
-    if (drop_mlp) {   // gtab[f][c] = drop_mlp[f] * gamma_mlp[c] was the scale: d gamma_mlp = sum_f drop_mlp[f] * (w s2 + b s1), folded in the reduction
+    const TrunkLinks::TailDone td = L.tail_done;
+    L.tail_done = TrunkLinks::TailDone{};
+    const bool tail_done = td.saved == saved && td.dx == dout && td.st == st;
+    {   // with stochastic depth gtab[f][c] = drop_mlp[f] * gamma_mlp[c] was the scale: d gamma_mlp = sum_f drop_mlp[f] * (w s2 + b s1), folded in the reduction
+        const float* gsc = drop_mlp ? sv.gtab : p->gamma_mlp;
+        const int gdiv = drop_mlp ? 1 : (int)d.F;
         if (!tail_done)
-            TRY(bf_in_bwd_partials(d.dtype, dout, sv.z, nullptr, dz, (int)d.F, (int)d.S, d.E, sv.mean3, sv.rstd3, p->mlp_norm_w, p->mlp_norm_b, sv.gtab, 1, 0, sc.in_ws3, st));
-        jobs.in[jobs.n_in++] = InReduceJob{tail_done ? g_tail_ws.get() : sc.in_ws3, (int)d.F, d.E, p->mlp_norm_w, p->mlp_norm_b, sv.gtab, 1, g->mlp_norm_w, g->mlp_norm_b, nullptr, nullptr,
-                                           drop_mlp, g->gamma_mlp};
-    } else {
-        if (!tail_done)
-            TRY(bf_in_bwd_partials(d.dtype, dout, sv.z, nullptr, dz, (int)d.F, (int)d.S, d.E, sv.mean3, sv.rstd3, p->mlp_norm_w, p->mlp_norm_b, p->gamma_mlp,
-                                   (int)d.F, 0, sc.in_ws3, st));
-        jobs.in[jobs.n_in++] = InReduceJob{tail_done ? g_tail_ws.get() : sc.in_ws3, (int)d.F, d.E, p->mlp_norm_w, p->mlp_norm_b, p->gamma_mlp, (int)d.F, g->mlp_norm_w, g->mlp_norm_b,
-                                           g->gamma_mlp, nullptr, nullptr, nullptr};
+            TRY(bf_in_bwd_partials(d.dtype, dout, sv.z, nullptr, dz, (int)d.F, (int)d.S, d.E, sv.mean3, sv.rstd3, p->mlp_norm_w, p->mlp_norm_b, gsc, gdiv, 0, sc.in_ws3, st));
+        TRY(jobs.push(InReduceJob{tail_done ? td.ws : sc.in_ws3, (int)d.F, d.E, p->mlp_norm_w, p->mlp_norm_b, gsc, gdiv, g->mlp_norm_w, g->mlp_norm_b,
+                                  drop_mlp ? nullptr : g->gamma_mlp, nullptr, drop_mlp, drop_mlp ? g->gamma_mlp : nullptr}));
     }
     // fc2: z = gelu(pre) @ W2^T + b2 ; dpre = (dz @ W2) * gelu'(pre)
     void* dpre = sc.t4;
@@ -1170,7 +1192,7 @@ extern "C" int bf_spatial_bwd(const bf_dims* dims, const bf_spatial_params* p, c
                     d.feat_scale ? p->low_freq_scalar : nullptr, d.feat_scale ? p->high_freq_scalar : nullptr, sv.alpha, sv.mc,
                     g->output_head_w, g->output_head_b, g->norm2_b, g->gamma_att, d.feat_scale ? g->low_freq_scalar : nullptr,
                     d.feat_scale ? g->high_freq_scalar : nullptr, don, st, fk, &fu2));
-    jobs.in[jobs.n_in++] = InReduceJob{sc.in_ws2, (int)d.F, d.E, p->norm2_w, p->norm2_b, nullptr, 1, g->norm2_w, g->norm2_b, nullptr, nullptr, nullptr, nullptr};
+    TRY(jobs.push(InReduceJob{sc.in_ws2, (int)d.F, d.E, p->norm2_w, p->norm2_b, nullptr, 1, g->norm2_w, g->norm2_b, nullptr, nullptr, nullptr, nullptr}));
     void* dqkv = sc.t3;
     {
         int rows = 0;
@@ -1181,39 +1203,48 @@ extern "C" int bf_spatial_bwd(const bf_dims* dims, const bf_spatial_params* p, c
         TRY(bf_attn_bwd_partials(d.dtype, sv.qkv, dO, dqkv, d.F * d.h, d.w, 1, d.w, 0, 1, d.heads, d.d, p->qnorm_w, p->qnorm_b, p->knorm_w, p->knorm_b,
                                  p->rel_pos_emb, d.attn_scale ? p->attn_scale_factor_x : nullptr, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b,
                                  g->rel_pos_emb, d.attn_scale ? g->attn_scale_factor_x : nullptr, 0.5f, rawm ? 2 : 0, sc.attn_ws, Scratch::ATTN_WS_FLOATS, &rows, st));
-        jobs.at[jobs.n_attn++] = AttnReduceJob{sc.attn_ws, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
-                                               d.attn_scale ? g->attn_scale_factor_x : nullptr};
+        TRY(jobs.push(AttnReduceJob{sc.attn_ws, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
+                                    d.attn_scale ? g->attn_scale_factor_x : nullptr}));
         TRY(bf_attn_bwd_partials(d.dtype, sv.qkv, dO, dqkv, d.F * d.w, d.h, d.w, d.S, 1, d.w, d.heads, d.d, p->qnorm_w, p->qnorm_b, p->knorm_w, p->knorm_b,
                                  p->rel_pos_emb, d.attn_scale ? p->attn_scale_factor_y : nullptr, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b,
                                  g->rel_pos_emb, d.attn_scale ? g->attn_scale_factor_y : nullptr, 0.5f, rawm ? 5 : 1, sc.attn_ws2, Scratch::ATTN_WS_FLOATS, &rows, st));
-        jobs.at[jobs.n_attn++] = AttnReduceJob{sc.attn_ws2, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
-                                               d.attn_scale ? g->attn_scale_factor_y : nullptr};
+        TRY(jobs.push(AttnReduceJob{sc.attn_ws2, rows, d.d, d.heads, g->qnorm_w, g->qnorm_b, g->knorm_w, g->knorm_b, g->rel_pos_emb,
+                                    d.attn_scale ? g->attn_scale_factor_y : nullptr}));
     }
     void* dxn = sc.e6;      // don is dead (it was only read on this stream)
     InFuse fu1{x, dx1, dx, sv.mean1, sv.rstd1, p->norm1_w, p->norm1_b, sc.in_ws};              // dqkv @ W_in, then norm1's backward + residual
     bool scaled_done = false;
-    const NextScale ns = g_next_scale.get();
-    g_next_scale.get() = NextScale{};
-    g_dbr_ready.get() = DbrReady{};
+    const NextScale& ns = H.scale;
+    L.dbr_ready = TrunkLinks::DbrReady{};
     static const bool scaled_on = bf_knob("BF_BWD_SCALED_COPY", 1) != 0;
     if (ns.f && scaled_on && fk.deferred && d.dtype == BF_DTYPE_BF16) {
-        fu1.scaled_out = (char*)scratch + 2 * Scratch(d, nullptr).bytes + (g_dbr_flip.get() ? dbr_bytes(d) : 0);
+        fu1.scaled_out = (char*)scratch + 2 * Scratch(d, nullptr).bytes + (L.dbr_flip ? dbr_bytes(d) : 0);
         fu1.scaled_f = ns.f; fu1.scaled_fdiv = ns.fdiv; fu1.scaled_done = &scaled_done;
     }
     TRY(linear_bwd(d, sc, dqkv, 3 * d.E, sv.xn, d.E, BF_PRO_NONE, nullptr, nullptr, win_c, g->input_head_w, g->input_head_b, dxn, nullptr, st, fk, &fu1, true));
-    if (scaled_done) { g_dbr_ready.get() = DbrReady{dx, ns.f, fu1.scaled_out}; g_dbr_flip.get() = !g_dbr_flip.get(); }
-    jobs.in[jobs.n_in++] = InReduceJob{sc.in_ws, (int)d.F, d.E, p->norm1_w, p->norm1_b, nullptr, 1, g->norm1_w, g->norm1_b, nullptr, nullptr, nullptr, nullptr};
+    if (scaled_done) { L.dbr_ready = {dx, ns.f, fu1.scaled_out, st}; L.dbr_flip = !L.dbr_flip; }
+    TRY(jobs.push(InReduceJob{sc.in_ws, (int)d.F, d.E, p->norm1_w, p->norm1_b, nullptr, 1, g->norm1_w, g->norm1_b, nullptr, nullptr, nullptr, nullptr}));
     static const bool merge_on = bf_knob("BF_REDUCE_MERGE", 1) != 0;
-    if (fk.deferred && merge_on) { g_pending_reduce.get() = jobs; g_pending_reduce_on.get() = true; }      // rides in the next temporal stage's launch (or the next join)
+    if (fk.deferred && merge_on) { L.reduce.jobs = jobs; L.reduce.on = true; L.reduce.st = st; }      // rides in the next temporal stage's launch (or the next join)
     else TRY(launch_reduce_jobs(jobs, st));
     return fk.join();
+}
+extern "C" int bf_spatial_fwd(const bf_dims* dims, const bf_spatial_params* p, const void* x, void* out, void* saved, void* scratch,
+                              const float* drop_att, const float* drop_mlp, bf_stream_t s) {
+    TrunkLinks& L = g_links.get();
+    return spatial_fwd(L, L.take_hints(), dims, p, x, out, saved, scratch, drop_att, drop_mlp, s);
+}
+extern "C" int bf_spatial_bwd(const bf_dims* dims, const bf_spatial_params* p, const bf_spatial_params* g, const void* x, const void* dout,
+                              void* dx, void* saved, void* scratch, const float* drop_att, const float* drop_mlp, bf_stream_t s) {
+    TrunkLinks& L = g_links.get();
+    return spatial_bwd(L, L.take_hints(), dims, p, g, x, dout, dx, saved, scratch, drop_att, drop_mlp, s);
 }
 
 // ================================================================================================= the training trunk in one call per direction
 // The n trunk stages of a training step (SpaceTimeBlock x 12: temporal, spatial, temporal, ...; models/axial_vit.py:58-63, 234-235) enqueued
 // by ONE native call each way instead of one Python -> ctypes round trip per stage: the stage forwards / backwards above, called in a
-// loop with the chain hints between them (bf_stage_chain_next, bf_stage_chain_tail, bf_stage_next_scale) set here, where the whole sequence
-// is known.  Everything is caller-owned: saved[i] = stage i's record (bf_temporal_saved_bytes / bf_spatial_saved_bytes), acts[i] = stage
+// loop, each with the StageHints that this driver builds for it -- the whole sequence is known here, so nothing goes through the record's
+// hint slots.  Everything is caller-owned: saved[i] = stage i's record (bf_temporal_saved_bytes / bf_spatial_saved_bytes), acts[i] = stage
 // i's output [N][E] (the last one is the trunk's output), three [N][E] gradient buffers that rotate between consecutive backward stages
 // (a stage's side-stream work may read its incoming gradient until the stage after the next one starts).
 extern "C" int bf_trunk_train_fwd(const bf_dims* dims, int n, const int32_t* kinds, const void* const* params, void* const* saved,
@@ -1223,22 +1254,23 @@ extern "C" int bf_trunk_train_fwd(const bf_dims* dims, int n, const int32_t* kin
     BF_REQUIRE(n >= 1 && kinds && params && saved && x && acts && scratch, "bf_trunk_train_fwd: bad arguments");
     for (int i = 0; i < n; ++i)
         BF_REQUIRE(params[i] && saved[i] && acts[i] && (kinds[i] == 0 || kinds[i] == 1), "bf_trunk_train_fwd: bad stage entry");
+    TrunkLinks& L = g_links.get();
+    (void)L.take_hints();      // (armed for a per-stage call that never came: not this pass's)
     const bool b16 = d.dtype == BF_DTYPE_BF16;
     if (b16) {
-        const int rc = bf_prep_stages(dims, n, kinds, params, saved, drop_b, s);
+        const int rc = prep_stages(L, dims, n, kinds, params, saved, drop_b, s);
         if (rc < 0) return rc;
     }
     for (int i = 0; i < n; ++i) {
         const void* in = i ? acts[i - 1] : x;
+        StageHints H;
+        H.prepared = b16;
         // the next stage's opening InstanceNorm rides in this stage's last GEMM launch where the kinds alternate (bf16)
-        if (b16 && i + 1 < n && kinds[i + 1] != kinds[i]) TRY(bf_stage_chain_next(dims, kinds[i + 1], params[i + 1], saved[i + 1]));
-        else TRY(bf_stage_chain_next(nullptr, 0, nullptr, nullptr));
-        bf_stage_prepared(b16 ? 1 : 0);
-        const int rc = kinds[i] == 0
-            ? bf_temporal_fwd(dims, (const bf_temporal_params*)params[i], in, acts[i], saved[i], scratch, drop_a ? drop_a[i] : nullptr, s)
-            : bf_spatial_fwd(dims, (const bf_spatial_params*)params[i], in, acts[i], saved[i], scratch, drop_a ? drop_a[i] : nullptr,
-                             drop_b ? drop_b[i] : nullptr, s);
-        if (rc) { (void)bf_stage_chain_next(nullptr, 0, nullptr, nullptr); return rc; }
+        if (b16 && i + 1 < n && kinds[i + 1] != kinds[i]) H.head = next_head(d, kinds[i + 1], params[i + 1], saved[i + 1]);
+        TRY(kinds[i] == 0
+            ? temporal_fwd(L, H, dims, (const bf_temporal_params*)params[i], in, acts[i], saved[i], scratch, drop_a ? drop_a[i] : nullptr, s)
+            : spatial_fwd(L, H, dims, (const bf_spatial_params*)params[i], in, acts[i], saved[i], scratch, drop_a ? drop_a[i] : nullptr,
+                          drop_b ? drop_b[i] : nullptr, s));
     }
     return 0;
 }
@@ -1253,6 +1285,8 @@ extern "C" int bf_trunk_train_bwd(const bf_dims* dims, int n, const int32_t* kin
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(n >= 1 && kinds && params && grads && saved && x && acts && dout && gbuf3 && dx && scratch, "bf_trunk_train_bwd: bad arguments");
     BF_REQUIRE(gbuf3[0] && gbuf3[1] && gbuf3[2], "bf_trunk_train_bwd: three gradient buffers are needed");
+    TrunkLinks& L = g_links.get();
+    (void)L.take_hints();      // (armed for a per-stage call that never came: not this pass's)
     const void* cur = dout;
     int rot = 0;
     for (int i = n - 1; i >= 0; --i) {
@@ -1260,22 +1294,18 @@ extern "C" int bf_trunk_train_bwd(const bf_dims* dims, int n, const int32_t* kin
         const void* in = i ? acts[i - 1] : x;
         void* gout = i ? gbuf3[rot] : dx;
         rot = (rot + 1) % 3;
-        int rc;
+        StageHints H;
         if (kinds[i] == 0) {
             // the spatial stage in front (in the forward) opens its backward with its MLP-branch norm: applied by this stage's last kernel
-            if (i > 0 && kinds[i - 1] == 1)
-                TRY(bf_stage_chain_tail((const bf_spatial_params*)params[i - 1], saved[i - 1], drop_b && drop_b[i - 1] ? 1 : 0));
-            rc = bf_temporal_bwd(dims, (const bf_temporal_params*)params[i], (const bf_temporal_params*)grads[i], in, cur, gout, saved[i], scratch,
-                                 drop_a ? drop_a[i] : nullptr, s);
-            (void)bf_stage_chain_tail(nullptr, nullptr, 0);
+            if (i > 0 && kinds[i - 1] == 1) H.tail = NextTail{true, (const bf_spatial_params*)params[i - 1], saved[i - 1], drop_b && drop_b[i - 1]};
+            TRY(temporal_bwd(L, H, dims, (const bf_temporal_params*)params[i], (const bf_temporal_params*)grads[i], in, cur, gout, saved[i], scratch,
+                             drop_a ? drop_a[i] : nullptr, s));
         } else {
             // the temporal stage in front scales this stage's input gradient by its stochastic-depth factors: written here as a second copy
-            if (i > 0 && kinds[i - 1] == 0 && drop_a && drop_a[i - 1]) TRY(bf_stage_next_scale(drop_a[i - 1], d.T));
-            rc = bf_spatial_bwd(dims, (const bf_spatial_params*)params[i], (const bf_spatial_params*)grads[i], in, cur, gout, saved[i], scratch,
-                                drop_a ? drop_a[i] : nullptr, drop_b ? drop_b[i] : nullptr, s);
-            (void)bf_stage_next_scale(nullptr, 0);
+            if (i > 0 && kinds[i - 1] == 0 && drop_a && drop_a[i - 1]) H.scale = NextScale{drop_a[i - 1], d.T};
+            TRY(spatial_bwd(L, H, dims, (const bf_spatial_params*)params[i], (const bf_spatial_params*)grads[i], in, cur, gout, saved[i], scratch,
+                            drop_a ? drop_a[i] : nullptr, drop_b ? drop_b[i] : nullptr, s));
         }
-        if (rc) return rc;
         if (stage_done) stage_done(i, user);
         cur = gout;
     }
@@ -1360,7 +1390,8 @@ extern "C" int bf_trunk_eval_fwd(const bf_dims* dims, int n, const int32_t* kind
     BF_REQUIRE(n >= 1 && kinds && params && weights && x && out && scratch, "bf_trunk_eval_fwd: bad arguments");
     if (!trunk_eval_covers(d)) return 1;
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    TrunkLinks& L = g_links.get();
+    TRY(side_join_pending(L, st));
     Scratch sc(d, scratch);
     const int F = (int)d.F, E = d.E;
     void *qkv = sc.t3, *o = sc.t1, *on = sc.t1b, *x1 = sc.e5, *hid = sc.t4;
@@ -1490,27 +1521,15 @@ struct DebedSaved {
 extern "C" int64_t bf_embed_saved_bytes(const bf_dims* s) { D d; if (get_dims(s, &d) || d.nst < 1) return -1; return (int64_t)EmbedSaved(d, nullptr).bytes; }
 extern "C" int64_t bf_debed_saved_bytes(const bf_dims* s) { D d; if (get_dims(s, &d) || d.nst < 1) return -1; return (int64_t)DebedSaved(d, nullptr).bytes; }
 
-// saved records whose stage-0 map was NOT stored by the forward (host-side memory of a per-call decision; the record itself is device memory)
-namespace {
-BfPerDevice<std::vector<const void*>> g_embed_lean;
-void embed_lean_set(const void* saved, bool lean) {
-    for (size_t i = 0; i < g_embed_lean.get().size(); ++i)
-        if (g_embed_lean.get()[i] == saved) { if (!lean) { g_embed_lean.get()[i] = g_embed_lean.get().back(); g_embed_lean.get().pop_back(); } return; }
-    if (lean) g_embed_lean.get().push_back(saved);
-}
-bool embed_lean_get(const void* saved) {
-    for (const void* p : g_embed_lean.get()) if (p == saved) return true;
-    return false;
-}
-}  // namespace
 extern "C" int bf_embed_fwd(const bf_dims* dims, const bf_embed_params* p, const float* x, const float* fluid, void* out, void* saved,
                             void* scratch, bf_stream_t s) {
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && x && out && saved && scratch && d.nst >= 1 && d.cin >= 1, "bf_embed_fwd: bad arguments");
     BF_REQUIRE((d.nfluid > 0) == (fluid != nullptr), "bf_embed_fwd: fluid parameters must be given exactly when nfluid > 0");
     hipStream_t st = (hipStream_t)s;
-    links_clear(true);
-    TRY(side_join_pending(st));
+    TrunkLinks& L = g_links.get();
+    L.clear(true);
+    TRY(side_join_pending(L, st));
     EmbedSaved sv(d, saved);
     Scratch sc(d, scratch);
     const int n = d.nst, H = d.h * d.patch, W = d.w * d.patch;
@@ -1536,7 +1555,7 @@ extern "C" int bf_embed_fwd(const bf_dims* dims, const bf_embed_params* p, const
             static const bool part_on = bf_knob("BF_EMBED_STATS", 1) != 0;
             const bool part_ok = part_on && n > 1 && bf_in_ws_floats(d.dtype, (int)d.F, S0, sv.C[0]) >= (int64_t)2 * d.F * sv.C[0] * (1 + (S0 + 255) / 256);      // the sliced workspace holds 256-row slices
             // lean: the stage-0 map is W0 . patch -- when every consumer of this call's saved record can rebuild its rows (the streaming
-            // stage-1 kernels, the one-pass backward tail) it is not stored at all; g_embed_lean.get() remembers the decision for the backward
+            // stage-1 kernels, the one-pass backward tail) it is not stored at all; the record's embed_lean list remembers the decision for the backward
             static const bool lean_on = bf_knob("BF_EMBED_LEAN", 1) != 0;
             // ... and only when the BACKWARD kernels that rebuild the rows will take this frame count with the workspaces this call's scratch holds
             // (the one-pass tail's partials live in the token-reduction workspace, the rebuilt-rows weight gradient's slabs in t1b: a batch of
@@ -1550,7 +1569,7 @@ extern "C" int bf_embed_fwd(const bf_dims* dims, const bf_embed_params* p, const
                                           part_ok ? sc.in_ws + (size_t)2 * d.F * sv.C[0] : nullptr, st);
             if (rc < 0) return rc;
             if (rc == 1 && lean) return bf_fail_msg("bf_embed_fwd: the first-stage kernel declined a shape the lean path was chosen for", __FILE__, __LINE__);
-            embed_lean_set(saved, lean);
+            L.embed_lean_set(saved, lean);
             stats_done = rc == 0 && part_ok;
             if (rc == 1) {
                 TRY(bf_im2col_nchw(d.dtype, x, sv.patches, (int)d.F, d.cin, H, W, sv.Kp, st));
@@ -1562,7 +1581,7 @@ extern "C" int bf_embed_fwd(const bf_dims* dims, const bf_embed_params* p, const
         } else {
             const int cp = sv.C[i - 1];
             // the 96 -> 96 channel stages stream their map once through a weight-stationary kernel (gather_gemm.hip)
-            const bool reb = i == 1 && embed_lean_get(saved);
+            const bool reb = i == 1 && L.embed_lean_get(saved);
             const int grc = reb ? bf_gather_gemm_rebuilt(d.dtype, sv.patches, sv.wc[0], sv.wc[i], 0, sv.sc[0], sv.sh[0], sv.y[i], (int)d.F, sv.gh[i], sv.gw[i], cp, sv.C[i], st)
                                 : bf_gather_gemm(d.dtype, sv.y[i - 1], sv.wc[i], 0, sv.sc[i - 1], sv.sh[i - 1], sv.y[i], (int)d.F, sv.gh[i], sv.gw[i], cp, sv.C[i], st);
             if (grc < 0) return grc;
@@ -1583,7 +1602,7 @@ extern "C" int bf_embed_fwd(const bf_dims* dims, const bf_embed_params* p, const
                                                      sv.mean[0], sv.rstd[0], sv.sc[0], sv.sh[0], sc.in_ws, st);
             if (mrc < 0) return mrc;
             if (mrc == 0) continue;
-            if (embed_lean_get(saved)) return bf_fail_msg("bf_embed_fwd: slice statistics declined on the lean path", __FILE__, __LINE__);
+            if (L.embed_lean_get(saved)) return bf_fail_msg("bf_embed_fwd: slice statistics declined on the lean path", __FILE__, __LINE__);
         }
         if (last) {       // the tokens (InstanceNorm affine, FiLM folded in) leave the statistics kernel itself where a frame fits its registers
             TRY(bf_in_stats_apply(d.dtype, sv.y[i], (int)d.F, sv.gh[i] * sv.gw[i], sv.C[i], p->in_w[i], p->in_b[i], film ? sv.gb : nullptr, d.T,
@@ -1601,7 +1620,8 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && g && dout && saved && scratch && d.nst >= 1, "bf_embed_bwd: bad arguments");
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    TrunkLinks& L = g_links.get();
+    TRY(side_join_pending(L, st));
     EmbedSaved sv(d, saved);
     Scratch sc(d, scratch);
     const int n = d.nst, H = d.h * d.patch, W = d.w * d.patch;
@@ -1619,7 +1639,7 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
     // Weight gradients (memset, split-K GEMM into the prepared-layout scratch, un-prepare into the gradient) run on the side
     // stream while this stream continues with the data gradient and the InstanceNorm backward of the same stage.  The side work
     // of stage i is joined before stage i-1 forks: the two ping-pong gradient buffers and sc.wg are then never recycled under it.
-    Fork fk(st);
+    Fork fk(L, st);
     hipStream_t ss;
     for (int i = n - 1; i >= 1; --i) {
         const int cp = sv.C[i - 1], K4 = 4 * cp;
@@ -1628,17 +1648,17 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
         TRY(fk.begin(&ss));
         // dWprep[co][k] = sum_p dy[p][co] * act(patch)[p][k]: the 96-channel stages as one stream over the map with slabs summed in a fixed
         // order (gather_gemm.hip; its slabs live in t1b, which nothing else of this call touches), else split-K with fp32 atomics
-        const bool lean = embed_lean_get(saved);
+        const bool lean = L.embed_lean_get(saved);
         if (i == 1 && lean && dx_in) {      // the input wants a gradient after all: the generic chain below reads the map, so store it now (y0 = patches @ W0^T)
             bf_operand A0 = op_plain(sv.patches, sv.Kp, BF_LAY_KC);
             bf_operand B0 = op_plain(sv.wc[0], sv.Kp, BF_LAY_KC);
             bf_epilogue e0 = epi_store(sv.y[0], sv.C[0]);
             TRY(bf_gemm(d.dtype, (int)sv.P[0], sv.C[0], sv.Kp, &A0, &B0, &e0, 1, st));
-            embed_lean_set(saved, false);
+            L.embed_lean_set(saved, false);
             TRY(fk.join());                 // the side stream forked before the map existed
             TRY(fk.begin(&ss));
         }
-        const bool reb = i == 1 && embed_lean_get(saved);
+        const bool reb = i == 1 && L.embed_lean_get(saved);
         const int wrc = reb ? bf_gather_wgrad_rebuilt(d.dtype, sv.patches, sv.wc[0], dy, sv.sc[0], sv.sh[0], sc.wg, 1, (int)d.F, sv.gh[i], sv.gw[i], cp, sv.C[i],
                                                       (float*)sc.t1b, sc.t1b_floats, ss)
                             : bf_gather_wgrad(d.dtype, sv.y[i - 1], dy, sv.sc[i - 1], sv.sh[i - 1], nullptr, nullptr, sc.wg, 1, (int)d.F, sv.gh[i], sv.gw[i], cp,
@@ -1670,7 +1690,7 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
             if (tail_on && need > 0 && need + (int64_t)cp * sv.Kp <= sc.tokred_floats) {
                 float* dwprep = sc.tokred_ws + need;
                 static const bool tail_map = bf_knob("BF_EMBED_TAIL_MAP", 0) != 0;      // 1: read the stored stage-0 map instead of rebuilding its rows
-                const int trc = bf_embed_tail_bwd(d.dtype, dy, sv.wc[1], (tail_map && !embed_lean_get(saved)) ? sv.y[0] : nullptr, sv.patches, sv.wc[0], sv.sc[0], sv.sh[0], sv.mean[0], sv.rstd[0],
+                const int trc = bf_embed_tail_bwd(d.dtype, dy, sv.wc[1], (tail_map && !L.embed_lean_get(saved)) ? sv.y[0] : nullptr, sv.patches, sv.wc[0], sv.sc[0], sv.sh[0], sv.mean[0], sv.rstd[0],
                                                   p->in_w[0], dwprep, g->in_w[0], g->in_b[0], (int)d.F, sv.gh[1], sv.gw[1], sv.C[1], cp, sv.Kp,
                                                   sc.tokred_ws, need, s);
                 if (trc < 0) return trc;
@@ -1679,7 +1699,7 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
                     return fk.join();
                 }
             }
-            if (embed_lean_get(saved)) return bf_fail_msg("bf_embed_bwd: the one-pass tail declined on the lean path (no stored stage-0 map)", __FILE__, __LINE__);
+            if (L.embed_lean_get(saved)) return bf_fail_msg("bf_embed_bwd: the one-pass tail declined on the lean path (no stored stage-0 map)", __FILE__, __LINE__);
         }
         void* dact = buf(i - 1);
         {   // d(act patch)[p][k] = sum_co dy[p][co] * Wprep[co][k], scattered back to the input grid
@@ -1730,7 +1750,8 @@ extern "C" int bf_debed_fwd(const bf_dims* dims, const bf_debed_params* p, const
     BF_REQUIRE(p && x && pred && saved && scratch && d.nst >= 1 && d.cout >= 1, "bf_debed_fwd: bad arguments");
     BF_REQUIRE(!target || loss, "bf_debed_fwd: loss output missing");
     hipStream_t st = (hipStream_t)s;
-    TRY(side_join_pending(st));
+    TrunkLinks& L = g_links.get();
+    TRY(side_join_pending(L, st));
     DebedSaved sv(d, saved);
     Scratch sc(d, scratch);
     const int n = d.nst;
@@ -1799,14 +1820,15 @@ extern "C" int bf_debed_bwd(const bf_dims* dims, const bf_debed_params* p, const
     BF_REQUIRE(p && g && x && dx && saved && scratch && d.nst >= 1, "bf_debed_bwd: bad arguments");
     BF_REQUIRE(dpred || (pred && target), "bf_debed_bwd: need dpred or (pred, target) of the fused loss");
     hipStream_t st = (hipStream_t)s;
-    links_clear(false);
-    TRY(side_join_pending(st));
+    TrunkLinks& L = g_links.get();
+    L.clear(false);
+    TRY(side_join_pending(L, st));
     DebedSaved sv(d, saved);
     Scratch sc(d, scratch);
     const int n = d.nst;
     auto buf = [&](int stage) { return (stage & 1) ? sc.t3 : sc.t4; };   // gradient w.r.t. the INPUT of `stage`
     void* dy = nullptr;   // gradient w.r.t. the raw output of stage i-1 == (after IN/GELU backward) input of stage i
-    Fork fk(st);          // weight gradients on the side stream, joined before the next stage forks (see bf_embed_bwd)
+    Fork fk(L, st);          // weight gradients on the side stream, joined before the next stage forks (see bf_embed_bwd)
     hipStream_t ss;
     for (int i = n - 1; i >= 0; --i) {
         const bool last = i == n - 1;

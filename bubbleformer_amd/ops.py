@@ -194,12 +194,22 @@ def as_reference_layout(tok: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ processor blocks
-_PREPARED: dict = {}      # (kind, pointer of the stage's first parameter) -> (dims key, saved record with prepared weights)
+# What one per-stage forward call leaves for the next (the Python mirror of the library's per-device record).  Everything here holds tensors of
+# the pass in flight, so clear() -- called when a forward ends, see discard_prepared -- drops all of it:
+#   prepared        (kind, pointer of the stage's first parameter) -> (dims key, saved record with prepared weights, drop_mlp, params struct)
+#   next            key of the stage announced by chain_next
+#   last_spatial    (output pointer, (shape, dtype), params struct, saved, has drop_mlp, params) of the spatial stage just run
+#   last_temporal   (output pointer, stochastic-depth factors, T) of the temporal stage just run: the spatial stage behind it remembers them
+class _StageLinks:
+    def __init__(self):
+        self.clear()
+
+    def clear(self) -> None:
+        self.prepared = {}
+        self.next = self.last_spatial = self.last_temporal = None
 
 
-_CHAIN = {"next": None}
-_LAST_SPATIAL = {"v": None}
-_LAST_TEMPORAL = {"v": None}      # (output pointer, stochastic-depth factors, T) of the temporal stage just run: the spatial stage behind it remembers them
+_LINKS = _StageLinks()
 
 
 def chain_next(params, kind: str = "temporal") -> None:
@@ -207,8 +217,8 @@ def chain_next(params, kind: str = "temporal") -> None:
     stage called next: when both were prepared by `prepare_stages` for the same shape, that stage's opening InstanceNorm is computed by the
     last launch of the stage in front of it (bf_stage_chain_next: the temporal stage's out-projection, the spatial stage's fc2 + MLP-branch
     norm; bit-identical results, one launch and one read of the activation less)."""
-    on = _PREPARED and os.environ.get("BF_STAGE_CHAIN", "1") != "0"
-    _CHAIN["next"] = _stage_key(kind, [_f32c(p) for p in params]) if on else None
+    on = _LINKS.prepared and os.environ.get("BF_STAGE_CHAIN", "1") != "0"
+    _LINKS.next = _stage_key(kind, [_f32c(p) for p in params]) if on else None
 
 
 def _stage_key(kind: str, params) -> tuple:
@@ -219,7 +229,7 @@ def prepare_stages(tok: torch.Tensor, heads: int, attn_scale: bool, feat_scale: 
     """Parameter preparation of all trunk stages of one forward in one launch per 12 stages (bf_prep_stages) instead of one launch
     inside every stage.  stages: [(kind, params, drop_mlp or None)] in call order; each stage's `saved` record is allocated here and
     handed to the stage's forward, which must follow with the same tok shape / dtype.  bf16 on the GPU only; otherwise a no-op."""
-    _PREPARED.clear()
+    _LINKS.prepared = {}
     if not tok.is_cuda or tok.dtype != torch.bfloat16 or not stages or os.environ.get("BF_PREP_AHEAD", "1") == "0":
         return
     B, T, h, w, E = tok.shape
@@ -240,15 +250,16 @@ def prepare_stages(tok: torch.Tensor, heads: int, attn_scale: bool, feat_scale: 
         keep.append((st, params, drop_mlp))
         kinds[i] = 0 if kind == "temporal" else 1
         pp[i], sp[i], dp[i] = C.addressof(st), _p(saved), _p(drop_mlp)
-        _PREPARED[_stage_key(kind, params)] = (keys[kind], saved, drop_mlp, st)
+        _LINKS.prepared[_stage_key(kind, params)] = (keys[kind], saved, drop_mlp, st)
     rc = lib.bf_prep_stages(C.byref(d), n, kinds, pp, sp, dp, _stream())
     if rc != 0:
-        _PREPARED.clear()
+        _LINKS.prepared = {}
         L.check(min(rc, 0), "bf_prep_stages")
 
 
 def discard_prepared() -> None:
-    _PREPARED.clear()
+    """End of a forward: drop the prepared records no stage consumed and what the last per-stage calls remembered of each other."""
+    _LINKS.clear()
 
 
 # ------------------------------------------------------------------------------------------------ inference forward of the trunk
@@ -419,13 +430,13 @@ class _BlockFn(torch.autograd.Function):
         params = [_f32c(p) for p in params]
         drop_a = None if drop_a is None else drop_a.contiguous().float()
         drop_b = None if drop_b is None else drop_b.contiguous().float()
-        pre = _PREPARED.pop(_stage_key(kind, params), None) if _PREPARED else None
+        pre = _LINKS.prepared.pop(_stage_key(kind, params), None) if _LINKS.prepared else None
         if pre is not None and (pre[0] != _dims_key(d) or (pre[2] is None) != (drop_b is None) or
                                 (drop_b is not None and pre[2].data_ptr() != drop_b.data_ptr())):
             pre = None                                  # prepared for another shape or another stochastic-depth table: prepare here
-        nxt, _CHAIN["next"] = _CHAIN["next"], None
+        nxt, _LINKS.next = _LINKS.next, None
         if nxt is not None and nxt[0] != kind:          # the next stage's opening InstanceNorm rides in this stage's last launch
-            pn = _PREPARED.get(nxt)
+            pn = _LINKS.prepared.get(nxt)
             if pn is not None and pn[0][:7] == _dims_key(d)[:7]:      # same dtype and token geometry (the stages' own switches may differ)
                 dn = L.Dims(*pn[0])
                 L.check(lib.bf_stage_chain_next(C.byref(dn), 0 if nxt[0] == "temporal" else 1, C.addressof(pn[3]), _p(pn[1])), "bf_stage_chain_next")
@@ -446,17 +457,16 @@ class _BlockFn(torch.autograd.Function):
         L.check(rc, f"bf_{kind}_fwd")
         # Backward chain (bf_stage_chain_tail): a temporal stage fed by a spatial stage's output remembers that stage -- its backward's last
         # kernel produces that stage's output gradient and can open that stage's backward (the MLP-branch InstanceNorm) in the same launch
-        last, _LAST_SPATIAL["v"] = _LAST_SPATIAL["v"], None
-        lastt, _LAST_TEMPORAL["v"] = _LAST_TEMPORAL["v"], None
-        ctx.prev_spatial = None
-        ctx.next_scale = None
+        last, _LINKS.last_spatial = _LINKS.last_spatial, None
+        lastt, _LINKS.last_temporal = _LINKS.last_temporal, None
+        ctx.prev_spatial = ctx.next_scale = None
         if kind == "temporal" and drop_a is not None and x.dtype == torch.bfloat16:
-            _LAST_TEMPORAL["v"] = (out.data_ptr(), drop_a, T)
+            _LINKS.last_temporal = (out.data_ptr(), drop_a, T)
         if kind == "spatial" and lastt is not None and lastt[0] == x.data_ptr():
             ctx.next_scale = (lastt[1], lastt[2])      # the backward of the temporal stage in front scales this stage's dx by these factors (bf_stage_next_scale)
         if kind == "spatial":
             if x.dtype == torch.bfloat16 and os.environ.get("BF_STAGE_CHAIN", "1") != "0":
-                _LAST_SPATIAL["v"] = (out.data_ptr(), (tuple(x.shape), x.dtype), st, saved, drop_b is not None, params)
+                _LINKS.last_spatial = (out.data_ptr(), (tuple(x.shape), x.dtype), st, saved, drop_b is not None, params)
         elif last is not None and last[0] == x.data_ptr() and last[1] == (tuple(x.shape), x.dtype):
             ctx.prev_spatial = last[2:]
         ctx.drops = (drop_a, drop_b)
@@ -487,14 +497,12 @@ class _BlockFn(torch.autograd.Function):
             if ps is not None and direct:       # (the chained norm's partial sums are reduced by the spatial stage's own backward, which must follow)
                 L.check(lib.bf_stage_chain_tail(C.byref(ps[0]), _p(ps[1]), 1 if ps[2] else 0), "bf_stage_chain_tail")
             rc = bwd(C.byref(d), C.byref(st), C.byref(gs), _p(x), _p(dout), _p(dx), _p(saved), _p(scratch_for(d, x.device)), _p(drop_a), _stream())
-            lib.bf_stage_chain_tail(None, None, 0)
         else:
             ns = getattr(ctx, "next_scale", None)
             if ns is not None and direct:
                 lib.bf_stage_next_scale(_p(ns[0]), ns[1])
             rc = bwd(C.byref(d), C.byref(st), C.byref(gs), _p(x), _p(dout), _p(dx), _p(saved), _p(scratch_for(d, x.device)), _p(drop_a),
-                     _p(drop_b), _stream())
-            lib.bf_stage_next_scale(None, 0)
+                     _p(drop_b), _stream())      # (the stage call takes its hints out of the library's record at its top: nothing to disarm)
         L.check(rc, f"bf_{ctx.kind}_bwd")
         if _DEFER["on"]:
             _DEFER["keep"].append((saved, dout, x))
@@ -543,7 +551,7 @@ class _TrunkFn(torch.autograd.Function):
         L.check(lib.bf_trunk_train_fwd(C.byref(d), n, kinds_c, pp, sp, dap, dbp, _p(x), ap, _p(scratch_for(d, x.device)), _stream()), "bf_trunk_train_fwd")
         ctx.cfg, ctx.kinds, ctx.masks, ctx.offs = cfg, kinds, masks, offs
         ctx.drops = (da, db)
-        ctx.save_for_backward(x, arena, acts, *flat)
+        ctx.save_for_backward(x, arena, acts, *[p for ps in plist for p in ps if p is not None])      # what the native call was given (see _BlockFn)
         return out
 
     @staticmethod

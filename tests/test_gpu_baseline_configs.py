@@ -765,8 +765,9 @@ def test_training_step_is_bit_reproducible_run_to_run():
     trainer uses): the loss AND every one of the parameter gradients come out with the same bits.  Nothing in the step adds floats in
     arrival order any more: weight gradients are slab sums in slice order (gemm_tokred.hip, bf_gemm_slabs), the small parameter
     reductions have one writer per value (param_reduce.h), the loss is an integer sum.  (Round 4 found this the hard way: the check
-    exposed a kernel whose result was not merely re-ordered but WRONG by 1e-4 .. 1e-2 in one channel block -- tokred_narrow's prologue
-    loads inside a loop that waits for LDS-DMA by count.)"""
+    exposed a kernel whose result was not merely re-ordered but WRONG by 1e-4 .. 1e-2 in one channel block: tokred_narrow.  The fault
+    followed one packed fp32 instruction form (v_pk_fma_f32 with op_sel on the low lane, two workgroups on a CU), not the prologue
+    loads first suspected; its root cause is open -- EXPERIMENTS.md round 4 -- and the build's register audit refuses the form.)"""
     from bubbleformer_amd import ops
     from bubbleformer_amd.models import get_model
 
@@ -788,4 +789,44 @@ def test_training_step_is_bit_reproducible_run_to_run():
     l2, g2 = grads()
     assert l1 == l2
     differing = [k for k in g1 if not torch.equal(g1[k], g2[k])]
+    assert not differing, differing
+
+
+def test_pending_parameter_reduction_is_flushed_on_the_stream_that_made_it():
+    """The library's call-to-call record is per device, its scratch arenas per (device, stream).  One bf16 axial stage, forward and backward
+    on stream A in deferred mode with direct gradient slots: nothing joins at the end of the stage, so its InstanceNorm / attention
+    parameter reductions stay pending (no temporal stage follows to carry them).  `set_side_defer(False)` under stream B then has to launch
+    them: on A, behind the kernels that wrote their partial sums, with B waiting for that -- after a synchronise of B alone every
+    parameter gradient equals, bit for bit, the same calls made on one stream."""
+    from bubbleformer_amd import _lib as L, ops
+    dt, T = torch.bfloat16, 16
+    blk = _model(3, dt, T).train().blocks[0].spatial
+    params = list(blk.stage_params())
+    torch.manual_seed(4)
+    tok = torch.randn(2, T, 12, 12, 384, device="cuda").to(dt)
+    dout = torch.randn_like(tok)
+    da, dm = ops.drop_path_factors(2 * T, 0.2, tok.device), ops.drop_path_factors(2 * T, 0.2, tok.device)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def run(join_stream):
+        slots = {p.data_ptr(): torch.zeros_like(p) for p in params if p is not None}
+        torch.cuda.synchronize()
+        ops.set_direct_grad_slots(slots)
+        try:
+            with torch.cuda.stream(sa):
+                ops.set_side_defer(True)
+                ops.spatial_block(tok, 6, True, True, params, da, dm).backward(dout)
+            with torch.cuda.stream(join_stream):
+                ops.set_side_defer(False)
+                got = [None if p is None else slots[p.data_ptr()].clone() for p in params]
+            join_stream.synchronize()
+        finally:
+            ops.set_side_defer(False)
+            ops.set_direct_grad_slots(None)
+            torch.cuda.synchronize()
+        return got
+
+    one, two = run(sa), run(sb)
+    assert float(one[L.SPATIAL_FIELDS.index("norm1_w")].abs().max()) > 0      # (a gradient the pending reduction writes)
+    differing = [n for n, a, b in zip(L.SPATIAL_FIELDS, one, two) if a is not None and not torch.equal(a, b)]
     assert not differing, differing

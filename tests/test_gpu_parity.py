@@ -393,7 +393,7 @@ def test_batched_stage_preparation_is_bit_identical(monkeypatch):
         model.train(train)
         torch.manual_seed(5)
         loss, pred = model.forward_loss(x, c, y)
-        assert not ops._PREPARED
+        assert not ops._LINKS.prepared
         return float(loss), pred.clone()
 
     got = {}
