@@ -166,6 +166,10 @@ SIGNATURES = {
     "bf_rollout_score_ws_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_rollout_score": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_lp_rows_ws_doubles": (i64, [i64, i64]),
+    "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
+    "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),
+    "bf_eikonal_bwd": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, fp, vp]),
     "bf_temporal_saved_bytes": (i64, [P(Dims)]),
     "bf_spatial_saved_bytes": (i64, [P(Dims)]),
     "bf_embed_saved_bytes": (i64, [P(Dims)]),

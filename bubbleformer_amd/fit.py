@@ -47,19 +47,22 @@ def batches(order: List[int], batch_size: int, limit: Optional[int]) -> List[Lis
 def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max_epochs: int, optimizer: str = "lion", lr: float = 5e-5,
         weight_decay: float = 0.1, warmup_iters: Optional[int] = 1000, eta_min: float = 1e-6, limit_train_batches: Optional[int] = 1000,
         limit_val_batches: Optional[int] = 25, seed: int = 42, rank: int = 0, world: int = 1, checkpoint_path: Optional[str] = None,
-        resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None) -> Dict:
+        resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
+        criterion: Optional[Callable] = None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
     (config/optim_cfg/adamw.yaml: lr 2.5e-4 wd 1e-2; adam.yaml: lr 2.5e-4 wd 1e-5).  ``resume_from`` takes a file written here or by
-    the reference's Lightning run (utils/checkpoint.py: load_checkpoint).  ``warmup_iters=None`` runs at a constant learning rate.  Returns the history."""
+    the reference's Lightning run (utils/checkpoint.py: load_checkpoint).  ``warmup_iters=None`` runs at a constant learning rate.  ``criterion``: None = the
+    model's fused relative-L2 loss; or a callable (prediction, target) -> scalar tensor that training and validation both use (TrainStep).
+    Returns the history."""
     dev = next(model.parameters()).device
     store = train_set.device_store(dev)
     vstore = val_set.device_store(dev) if val_set is not None else None
     conditioned = getattr(train_set, "return_fluid_params", False)
     per_epoch = len(batches(epoch_indices(len(train_set), 0, seed, True, rank, world), batch_size, limit_train_batches))
     sched = CosineWarmupLR(lr, warmup_iters, max_epochs * per_epoch, eta_min) if warmup_iters is not None else None
-    step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched)
+    step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
     first_epoch = 0
@@ -83,7 +86,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         hist["train_loss"].extend(ep.tolist())
         hist["epoch_train_loss"].append(float(ep.mean()))
         if vstore is not None:
-            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world))
+            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion))
             if log is not None:
                 log({"epoch": epoch, "val_loss": hist["val_loss"][-1]})
         if checkpoint_path is not None and rank == 0:
@@ -92,7 +95,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
 
 
 @torch.no_grad()
-def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optional[int], rank: int = 0, world: int = 1) -> float:
+def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optional[int], rank: int = 0, world: int = 1, criterion=None) -> float:
     """Mean over the (limited) validation batches of the training criterion, as `validation_step` logs it on epoch end."""
     was_training = model.training
     model.eval()
@@ -100,7 +103,10 @@ def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optiona
     tot, n = 0.0, 0
     for idx in batches(epoch_indices(len(val_set), 0, 0, False, rank, world), batch_size, limit_val_batches):
         got = vstore.gather(idx)
-        loss, _ = model.forward_loss(got[0], got[2], got[1]) if conditioned else model.forward_loss(got[0], got[1])
+        if criterion is None:
+            loss, _ = model.forward_loss(got[0], got[2], got[1]) if conditioned else model.forward_loss(got[0], got[1])
+        else:
+            loss = criterion(model(got[0], got[2]) if conditioned else model(got[0]), got[1])
         tot += float(loss)
         n += 1
     model.train(was_training)

@@ -7,7 +7,8 @@
                       mean all-reduce of gradient buckets over ``torch.distributed`` (backend "nccl" = RCCL over xGMI),
                       issued per bucket as soon as backward has produced every gradient in it (debed first, then
                       blocks N-1 .. 0, then embed), overlapped with the rest of backward.  One process per GPU.
-* ``TrainStep``    -- forward (+ fused relative-L2 loss) -> backward -> bucket wait -> fused AdamW / Adam / Lion.
+* ``TrainStep``    -- forward (+ fused relative-L2 loss, or a caller's criterion on the prediction) -> backward -> bucket wait ->
+                      fused AdamW / Adam / Lion.
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
@@ -159,10 +160,12 @@ class TrainStep:
     with its L2 weight decay; modules.py:137-138) or "lion" (config/optim_cfg/lion.yaml, the reference default; modules.py:139-140).
     The constructor's weight_decay default is AdamW's; pass adam.yaml's 1e-5 / lion.yaml's 0.1 explicitly.  scheduler: optional
     object with get_last_lr() / step() (utils.lr_schedulers.CosineWarmupLR), stepped once per optimizer step like the reference's
-    ``interval="step"`` (modules.py:166-171)."""
+    ``interval="step"`` (modules.py:166-171).  criterion: None = the model's fused forward_loss (relative L2 as configured at
+    modules.py:50); or a callable (prediction, target) -> scalar tensor, e.g. utils.losses.LpLoss(...) plus a physics penalty: the step
+    then runs model(x[, fluid]), the criterion and loss.backward() through the same gradient slots and bucket reducer."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
-                 optimizer: str = "adamw", scheduler=None):
+                 optimizer: str = "adamw", scheduler=None, criterion=None):
         from . import ops
         if optimizer not in ("adamw", "adam", "lion"):
             raise ValueError(f"Optimizer {optimizer} not supported")
@@ -178,6 +181,7 @@ class TrainStep:
             betas = (0.9, 0.999) if optimizer in ("adamw", "adam") else (0.9, 0.99)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.scheduler = scheduler
+        self.criterion = criterion
         self.step_no = 0
         self.sync_from_rank0()
 
@@ -220,6 +224,9 @@ class TrainStep:
         return loss.detach()
 
     def _fwd_bwd(self, x, fluid, target):
-        loss, _ = self.model.forward_loss(x, fluid, target) if fluid is not None else self.model.forward_loss(x, target)
+        if self.criterion is None:
+            loss, _ = self.model.forward_loss(x, fluid, target) if fluid is not None else self.model.forward_loss(x, target)
+        else:
+            loss = self.criterion(self.model(x, fluid) if fluid is not None else self.model(x), target)
         loss.backward()
         return loss

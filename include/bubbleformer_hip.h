@@ -31,6 +31,7 @@
  *   bf_adam .................. torch.optim.Adam as configured at bubbleformer/modules.py:137-138 (config/optim_cfg/adam.yaml)
  *   bf_clip_gather ........... BubbleForecast.__getitem__ + DataLoader collate for a batch of clips: bubbleformer/data/dataset.py:120-182
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
+ *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  */
@@ -377,6 +378,23 @@ int bf_rollout_score(const float* pred, const float* frames, int64_t field_strid
                      int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
                      float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
                      int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+/* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
+ * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
+ * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
+ *   ratio[r] = (S_e / S_y)^(1/p), quotient and root in fp64, rounded once (S_y = 0 gives inf or NaN, as the reference's quotient of norms does).
+ *   ws: bf_lp_rows_ws_doubles(rows, n) doubles (0 for short rows; may then be NULL).
+ * bf_lp_rows_bwd: dpred[r][i] = g[r] * sign(e) |e|^(p-1) / (S_e^((p-1)/p) * S_y^(1/p)), e = pred - y, from the sums the forward left; g [rows] fp32 on
+ *   the device.  The row coefficient is fp64 and every element is rounded once.  A row with S_e = 0 gets zeros (torch's norm backward).
+ * p = 1, p = 2 and integer p <= 16 take no transcendental per element (fp64 products); any other p takes powf on the fp32 difference. */
+int64_t bf_lp_rows_ws_doubles(int64_t rows, int64_t n);
+int bf_lp_rows_fwd(const float* pred, const float* y, int64_t rows, int64_t n, double p, float* ratio, double* sums, double* ws, int64_t ws_doubles,
+                   bf_stream_t stream);
+int bf_lp_rows_bwd(const float* pred, const float* y, const float* g, const double* sums, int64_t rows, int64_t n, double p, float* dpred,
+                   bf_stream_t stream);
+/* dphi = d/dphi of g[0] * mean over frames x H x W of (|grad phi| - 1)^2 (the adjoint of bf_eikonal_sum's expression divided by the count); g = one fp32
+ * in DEVICE memory.  Gather form (no atomics), fp64 arithmetic, one rounding.  A cell with |grad phi| = 0 contributes 0 (autograd of the reference's
+ * expression gives 0 * inf = NaN there).  A 1-wide axis has a zero derivative. */
+int bf_eikonal_bwd(const float* phi, int64_t frames, int H, int W, float dx, const float* g, float* dphi, bf_stream_t stream);
 /* Lion: p *= 1 - lr*wd; p -= lr*sign(beta1*m + (1-beta1)*g); m = beta2*m + (1-beta2)*g   (g is multiplied by gscale first) */
 int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
             bf_stream_t stream);
