@@ -166,6 +166,10 @@ SIGNATURES = {
     "bf_rollout_score_ws_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_rollout_score": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_rollout_heatflux": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, fp, f32, f32, f32, f32, fp, fp, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_kde_kl_ws_doubles": (i64, [C.c_int, i64, i64, C.c_int]),
+    "bf_kde_kl": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, vp]),
     "bf_lp_rows_ws_doubles": (i64, [i64, i64]),
     "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
     "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),

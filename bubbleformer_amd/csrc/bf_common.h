@@ -163,6 +163,10 @@ __device__ __forceinline__ float dgelu_fast(float x) {
 template <typename T> __device__ __forceinline__ float gelu_t(float x) { if constexpr (sizeof(T) == 2) return gelu_fast(x); else return gelu_f(x); }
 template <typename T> __device__ __forceinline__ float dgelu_t(float x) { if constexpr (sizeof(T) == 2) return dgelu_fast(x); else return dgelu_f(x); }
 
+// ---------------------------------------------------------------- the clip store's downsampling map (patch.hip: gather and scoring; physics.hip)
+// Source index of F.interpolate(mode="nearest"): floor(dst * float(in / out)) clamped to in - 1 (identity at full resolution)
+__device__ __forceinline__ int nearest_src(int dst, float scale, int n, bool ident) { return ident ? dst : min((int)floorf((float)dst * scale), n - 1); }
+
 // ---------------------------------------------------------------- wave / block reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

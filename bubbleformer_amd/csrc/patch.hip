@@ -891,8 +891,7 @@ extern "C" int bf_film_net_bwd(const float* dgb, const float* chat, const float*
 // ---------------------------------------------------------------------------- per-pixel expressions with more than one user
 // The clip gather kernels and the notebook's Eikonal score share these with the rollout scoring kernel (rollout_score_kernel below):
 // one definition each, so that a target built on the fly has the bits a gathered clip has, and both Eikonal scores the same arithmetic.
-// Source index of F.interpolate(mode="nearest"): floor(dst * float(in / out)) clamped to in - 1 (identity at full resolution)
-__device__ __forceinline__ int nearest_src(int dst, float scale, int n, bool ident) { return ident ? dst : min((int)floorf((float)dst * scale), n - 1); }
+// (nearest_src, the gather's source-index map, lives in bf_common.h: physics.hip reads the store through it too)
 __device__ __forceinline__ float clip_norm(float v, float d, float q) { return (v - d) / q; }
 // | |grad phi| - 1 | at pixel (x, y) of an H x W frame read through at(row, column): central differences, replicate-padded borders
 template <class At>

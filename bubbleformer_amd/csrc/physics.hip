@@ -1,0 +1,231 @@
+// The reference's heat-flux evaluation inside a rollout: utils/heatflux.py per step of scripts/inference.py:239-252, and the comparison of
+// the two flux series that examples/data_visualization.ipynb (cell 4) makes: a Gaussian KDE of each, KL(sim || model) by Simpson's rule.
+//
+// rollout_heatflux_kernel: the expression of heatflux_kernel (patch.hip) on row 0 of the two fields of ONE rollout step, once on the
+// prediction (de-normalised as rollout_score_kernel de-normalises its Eikonal rows: fp32 multiply, then add, unfused) and once on the
+// stored simulation frame (through nearest_src, the gather's own map).  A wave per (trajectory, frame, side); 64 lanes stride over the row,
+// fp64 sum by the butterfly heatflux_kernel uses, one rounding.  The step number is READ from device memory, never written.
+//
+// KDE / KL, everything in fp64, three launches per call, no atomics (two calls give the same bits), O(n + m + points) memory:
+//   kde_stats_kernel  grid (2 sets, R rows): count is n; mean, then centred squares (np.cov(ddof=1)), min and max, each reduced in a fixed order;
+//   kde_partial_kernel grid (grid-point tiles of 256, slabs of both sets, R): a workgroup stages its slab of samples in LDS KDE_CHUNK at a time
+//                     (every lane reads the same address: a broadcast) and each thread adds exp(-((x_i - s_j) / h)^2 / 2) over the slab into
+//                     two accumulators (even / odd sample), leaving one fp64 partial per (slab, grid point) in the workspace.  The number of
+//                     slabs depends on n alone (at most KDE_MAX_SLABS), so a row has the same bits alone and in a batch;
+//   kde_finish_kernel grid (R): adds the slabs in slab order, divides by n h sqrt(2 pi), forms f = p log(p / q) (q == 0 -> eps; f = 0 where
+//                     p == 0, the limit -- numpy has NaN there) and applies scipy.integrate.simpson's rule for a uniform grid.
+#include "bf_common.h"
+#include <algorithm>
+#include <math.h>
+
+namespace {
+constexpr int NT = 256;
+constexpr int KDE_CHUNK = 1024;        // samples in LDS at a time: 8 KiB
+constexpr int KDE_SLAB_MIN = 256;      // a set is not cut into slabs shorter than this
+constexpr int KDE_MAX_SLABS = 64;      // bounds the workspace at 2 * 64 * points doubles per row, whatever n
+constexpr int KDE_STATS = 4;           // {mean, unbiased variance, min, max} per (row, set)
+
+struct HeatfluxArgs {
+    const float* pred; const float* src; long field_stride, total_frames; int nfields;
+    const long* first; const int* step; const int* field; const float* diff; const float* dv;
+    int dfun_c, temp_c; const float* heater_temp; float x_min, dx, coef;
+    float* flux_pred; float* flux_tgt;
+    int B, T, C, H, W, Ho, Wo, steps;
+};
+
+// pred * div + diff as torch forms it: an fp32 product, rounded, then an fp32 sum (contraction off: never one fused operation)
+__device__ __forceinline__ float denormalise(float v, float q, float d) {
+#pragma clang fp contract(off)
+    const float prod = v * q;
+    return prod + d;
+}
+
+__global__ void __launch_bounds__(64) rollout_heatflux_kernel(HeatfluxArgs a) {
+    const int s = *a.step;
+    if (s < 0 || s >= a.steps) return;                                     // behind the last row: nothing is written
+    const int bt = blockIdx.x, t = bt % a.T, b = bt / a.T, Wo = a.Wo;
+    const bool sim = blockIdx.y == 1;
+    const float ht = a.heater_temp[b];
+    const float* d;
+    const float* tp;
+    float dq = 1.f, dd = 0.f, tq = 1.f, td = 0.f, sx = 1.f;
+    bool ident = true;
+    if (sim) {
+        const int H = a.H, W = a.W;
+        ident = a.Ho == H && Wo == W;
+        sx = (float)W / (float)Wo;
+        const long frame = min(max(a.first[b] + (long)(s + 1) * a.T + t, 0L), a.total_frames - 1);      // as rollout_score_kernel clamps
+        const long off = frame * H * (long)W + (long)nearest_src(0, (float)H / (float)a.Ho, H, ident) * W;
+        d = a.src + (long)min(max(a.field[a.dfun_c], 0), a.nfields - 1) * a.field_stride + off;
+        tp = a.src + (long)min(max(a.field[a.temp_c], 0), a.nfields - 1) * a.field_stride + off;
+    } else {
+        const long px = (long)a.Ho * Wo;
+        d = a.pred + ((long)bt * a.C + a.dfun_c) * px;                     // row 0 of the frame: the heater row ([:, 0, :])
+        tp = a.pred + ((long)bt * a.C + a.temp_c) * px;
+        dq = a.dv[a.dfun_c]; dd = a.diff[a.dfun_c]; tq = a.dv[a.temp_c]; td = a.diff[a.temp_c];
+    }
+    double acc = 0.0;
+    for (int x = threadIdx.x; x < Wo; x += 64) {
+        const double xc = (double)a.x_min + ((double)x + 0.5) * (double)a.dx;
+        float dval, tval;
+        if (sim) { const int xs = nearest_src(x, sx, a.W, ident); dval = d[xs]; tval = tp[xs]; }
+        else { dval = denormalise(d[x], dq, dd); tval = denormalise(tp[x], tq, td); }
+        if (xc >= -5.0 && xc <= 5.0 && dval < 0.f) acc += (double)(ht - tval);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (threadIdx.x == 0) (sim ? a.flux_tgt : a.flux_pred)[((long)b * a.steps + s) * a.T + t] = (float)(acc / (double)Wo * (double)a.coef);
+}
+
+// ---------------------------------------------------------------------------- Gaussian KDE and KL(p || q)
+enum { RED_SUM = 0, RED_MIN = 1, RED_MAX = 2 };
+template <int OP> __device__ __forceinline__ double red_op(double a, double b) {
+    if constexpr (OP == RED_SUM) return a + b;
+    else if constexpr (OP == RED_MIN) return fmin(a, b);
+    else return fmax(a, b);
+}
+// every thread gets the reduction of v over the workgroup, formed in a fixed order (butterfly inside a wave, then the waves in order)
+template <int OP> __device__ __forceinline__ double block_reduce(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = red_op<OP>(v, __shfl_xor(v, o, 64));
+    __syncthreads();                                                        // red may still be read from the previous reduction
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+    for (int w = 1; w < NT / 64; ++w) t = red_op<OP>(t, red[w]);
+    return t;
+}
+
+__global__ void __launch_bounds__(NT) kde_stats_kernel(const double* __restrict__ p, const double* __restrict__ q, long n, long m, double* __restrict__ stats) {
+    __shared__ double red[NT / 64];
+    const int set = blockIdx.x, r = blockIdx.y;
+    const long len = set ? m : n;
+    const double* v = (set ? q : p) + (long)r * len;
+    double sum = 0.0, lo = INFINITY, hi = -INFINITY;
+    for (long j = threadIdx.x; j < len; j += NT) { const double x = v[j]; sum += x; lo = fmin(lo, x); hi = fmax(hi, x); }
+    const double mean = block_reduce<RED_SUM>(sum, red) / (double)len;
+    lo = block_reduce<RED_MIN>(lo, red);
+    hi = block_reduce<RED_MAX>(hi, red);
+    double sq = 0.0;
+    for (long j = threadIdx.x; j < len; j += NT) { const double e = v[j] - mean; sq += e * e; }
+    const double var = block_reduce<RED_SUM>(sq, red) / (double)(len - 1);
+    if (threadIdx.x == 0) {
+        double* st = stats + ((long)r * 2 + set) * KDE_STATS;
+        st[0] = mean; st[1] = var; st[2] = lo; st[3] = hi;
+    }
+}
+
+static int kde_slabs(long n) { return (int)std::max<long>(1, std::min<long>(KDE_MAX_SLABS, (n + KDE_SLAB_MIN - 1) / KDE_SLAB_MIN)); }
+
+// grid point i of np.linspace(lo, hi, points): i * step + lo (a product, then a sum: two roundings, not one fused), the last one hi itself
+__device__ __forceinline__ double kde_grid_x(int i, int points, double lo, double hi, double step) {
+#pragma clang fp contract(off)
+    const double prod = (double)i * step;
+    return i == points - 1 ? hi : prod + lo;
+}
+
+__global__ void __launch_bounds__(NT) kde_partial_kernel(const double* __restrict__ p, const double* __restrict__ q, long n, long m, int points, int slabs_p,
+                                                        int slabs_q, double scott_p, double scott_q, const double* __restrict__ stats,
+                                                        double* __restrict__ part) {
+    __shared__ double sm[KDE_CHUNK];
+    const int r = blockIdx.z, slab = blockIdx.y, set = slab >= slabs_p;
+    const int k = set ? slab - slabs_p : slab, nslab = set ? slabs_q : slabs_p;
+    const long len = set ? m : n;
+    const double* v = (set ? q : p) + (long)r * len;
+    const double* st = stats + (long)r * 2 * KDE_STATS;
+    const double lo = fmin(st[2], st[KDE_STATS + 2]), hi = fmax(st[3], st[KDE_STATS + 3]), step = (hi - lo) / (double)(points - 1);
+    const double inv_h = 1.0 / ((set ? scott_q : scott_p) * sqrt(st[set * KDE_STATS + 1]));
+    const long per = (len + nslab - 1) / nslab, j0 = (long)k * per, j1 = min(len, j0 + per);
+    const int i = blockIdx.x * NT + threadIdx.x;
+    const double x = kde_grid_x(min(i, points - 1), points, lo, hi, step);
+    double a0 = 0.0, a1 = 0.0;
+    for (long c0 = j0; c0 < j1; c0 += KDE_CHUNK) {
+        const int cn = (int)min((long)KDE_CHUNK, j1 - c0);
+        __syncthreads();
+        for (int j = threadIdx.x; j < cn; j += NT) sm[j] = v[c0 + j];
+        __syncthreads();
+        int j = 0;
+        for (; j + 1 < cn; j += 2) {
+            const double d0 = (x - sm[j]) * inv_h, d1 = (x - sm[j + 1]) * inv_h;
+            a0 += exp(-0.5 * (d0 * d0));
+            a1 += exp(-0.5 * (d1 * d1));
+        }
+        if (j < cn) { const double d0 = (x - sm[j]) * inv_h; a0 += exp(-0.5 * (d0 * d0)); }
+    }
+    if (i < points) part[((long)r * (slabs_p + slabs_q) + slab) * points + i] = a0 + a1;
+}
+
+__global__ void __launch_bounds__(NT) kde_finish_kernel(long n, long m, int points, int slabs_p, int slabs_q, double scott_p, double scott_q, double eps,
+                                                       const double* __restrict__ stats, const double* __restrict__ part, double* __restrict__ kl,
+                                                       double* __restrict__ xs, double* __restrict__ pdf_p, double* __restrict__ pdf_q) {
+    __shared__ double red[NT / 64];
+    const int r = blockIdx.x;
+    const double* st = stats + (long)r * 2 * KDE_STATS;
+    const double var_p = st[1], var_q = st[KDE_STATS + 1];
+    const bool ok = var_p > 0.0 && var_q > 0.0;                             // a constant set has no bandwidth (scipy raises): NaN
+    const double lo = fmin(st[2], st[KDE_STATS + 2]), hi = fmax(st[3], st[KDE_STATS + 3]), step = (hi - lo) / (double)(points - 1);
+    const double norm_p = (double)n * (scott_p * sqrt(var_p)) * sqrt(2.0 * M_PI), norm_q = (double)m * (scott_q * sqrt(var_q)) * sqrt(2.0 * M_PI);
+    const double* pp = part + (long)r * (slabs_p + slabs_q) * points;
+    const double* pq = pp + (long)slabs_p * points;
+    const int simpson_n = (points & 1) ? points : points - 1;               // even point count: Simpson on the first points - 1, then the last interval
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < points; i += NT) {
+        double sp = 0.0, sq = 0.0;
+        for (int k = 0; k < slabs_p; ++k) sp += pp[(long)k * points + i];
+        for (int k = 0; k < slabs_q; ++k) sq += pq[(long)k * points + i];
+        const double dp = ok ? sp / norm_p : NAN, dq = ok ? sq / norm_q : NAN;
+        if (xs) xs[(long)r * points + i] = kde_grid_x(i, points, lo, hi, step);
+        if (pdf_p) pdf_p[(long)r * points + i] = dp;
+        if (pdf_q) pdf_q[(long)r * points + i] = dq;
+        const double f = dp == 0.0 ? 0.0 : dp * log(dp / (dq == 0.0 ? eps : dq));
+        if (i < simpson_n) s1 += ((i == 0 || i == simpson_n - 1) ? 1.0 : (i & 1) ? 4.0 : 2.0) * f;
+        if (simpson_n != points && i >= points - 3) s2 += (i == points - 1 ? 5.0 : i == points - 2 ? 8.0 : -1.0) * f;
+    }
+    s1 = block_reduce<RED_SUM>(s1, red);
+    s2 = block_reduce<RED_SUM>(s2, red);
+    if (threadIdx.x == 0) kl[r] = step * (s1 / 3.0) + step * (s2 / 12.0);
+}
+}  // namespace
+
+extern "C" int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                                   const int32_t* step, const int32_t* field, const float* diff, const float* div, int dfun_channel, int temp_channel,
+                                   const float* heater_temp, float x_min, float dx, float lc, float conductivity, float* flux_pred, float* flux_tgt,
+                                   int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+    BF_REQUIRE(pred && frames && first && step && field && diff && div && heater_temp && flux_pred && flux_tgt, "bf_rollout_heatflux: null pointer");
+    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && steps > 0 && nfields > 0 && total_frames > 0 &&
+               field_stride >= total_frames * H * W && (int64_t)B * T <= 0x7fffffff, "bf_rollout_heatflux: bad sizes");
+    BF_REQUIRE(dfun_channel >= 0 && dfun_channel < C && temp_channel >= 0 && temp_channel < C,
+               "bf_rollout_heatflux: the signed-distance and the temperature channel must be output channels");
+    BF_REQUIRE(dx > 0.f && lc > 0.f, "bf_rollout_heatflux: dx and lc must be positive");
+    const HeatfluxArgs a{pred, frames, (long)field_stride, (long)total_frames, nfields, (const long*)first, (const int*)step, (const int*)field, diff, div,
+                         dfun_channel, temp_channel, heater_temp, x_min, dx, conductivity / (dx * lc), flux_pred, flux_tgt, B, T, C, H, W, Ho, Wo, steps};
+    hipLaunchKernelGGL(rollout_heatflux_kernel, dim3((unsigned)(B * T), 2), dim3(64), 0, (hipStream_t)stream, a);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t bf_kde_kl_ws_doubles(int R, int64_t n, int64_t m, int points) {
+    if (R <= 0 || n < 2 || m < 2 || points < 3) return 0;
+    return (int64_t)R * (2 * KDE_STATS + (int64_t)(kde_slabs(n) + kde_slabs(m)) * points);
+}
+
+extern "C" int bf_kde_kl(const double* p, const double* q, int R, int64_t n, int64_t m, int points, double eps, double* kl, double* x, double* pdf_p,
+                         double* pdf_q, double* ws, int64_t ws_doubles, bf_stream_t stream) {
+    BF_REQUIRE(p && q && kl && ws, "bf_kde_kl: null pointer");
+    BF_REQUIRE(R > 0 && R <= 65535 && n >= 2 && m >= 2 && points >= 3, "bf_kde_kl: needs 1 <= R <= 65535 rows, n >= 2, m >= 2 samples and points >= 3");
+    BF_REQUIRE(ws_doubles >= bf_kde_kl_ws_doubles(R, n, m, points), "bf_kde_kl: workspace smaller than bf_kde_kl_ws_doubles");
+    BF_REQUIRE(((uintptr_t)p % 8 == 0) && ((uintptr_t)q % 8 == 0) && ((uintptr_t)ws % 8 == 0), "bf_kde_kl: buffers must be 8-byte aligned");
+    const int sp = kde_slabs(n), sq = kde_slabs(m);
+    const double scott_p = pow((double)n, -0.2), scott_q = pow((double)m, -0.2);      // scipy's default factor for one dimension: n^(-1 / (d + 4))
+    double* stats = ws;
+    double* part = ws + (long)R * 2 * KDE_STATS;
+    hipLaunchKernelGGL(kde_stats_kernel, dim3(2, (unsigned)R), dim3(NT), 0, (hipStream_t)stream, p, q, (long)n, (long)m, stats);
+    BF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kde_partial_kernel, dim3((unsigned)bf_cdiv(points, NT), (unsigned)(sp + sq), (unsigned)R), dim3(NT), 0, (hipStream_t)stream, p, q,
+                       (long)n, (long)m, points, sp, sq, scott_p, scott_q, (const double*)stats, part);
+    BF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kde_finish_kernel, dim3((unsigned)R), dim3(NT), 0, (hipStream_t)stream, (long)n, (long)m, points, sp, sq, scott_p, scott_q, eps,
+                       (const double*)stats, (const double*)part, kl, x, pdf_p, pdf_q);
+    BF_CHECK_LAUNCH();
+    return 0;
+}

@@ -952,6 +952,65 @@ def rollout_score(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor,
                                      B, T, Cn, H, W, Ho, Wo, int(steps), _stream()), "bf_rollout_score")
 
 
+def rollout_heatflux(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, dfun_channel: int, temp_channel: int,
+                     heater_temp: torch.Tensor, steps: int, flux_pred: torch.Tensor, flux_tgt: torch.Tensor, x_min: float = -8.0,
+                     dx: float = 1.0 / 32, lc: float = 0.0007, conductivity: float = 0.054) -> None:
+    """The heat-flux rows of one rollout step (bf_rollout_heatflux; include/bubbleformer_hip.h has the contract): row s * T + t of flux_pred /
+    flux_tgt (B, steps*T) from row 0 of the de-normalised prediction and of the stored frame ``first[b] + (s + 1) * T + t``, s = the int32
+    ``step`` tensor ON THE DEVICE, which this call only reads -- issue it BEFORE the step's ``rollout_score``.  heater_temp (B,) fp32 on the
+    device.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(pred)
+    ids, diff, div = table
+    nf, total, H, W = frames.shape
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise L.BubbleformerHipError("rollout_heatflux: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
+    B, T, Cn, Ho, Wo = pred.shape
+    want = {"flux_pred": (flux_pred, (B, steps * T), torch.float32), "flux_tgt": (flux_tgt, (B, steps * T), torch.float32),
+            "heater_temp": (heater_temp, (B,), torch.float32), "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32)}
+    for name, (t, shape, dtype) in want.items():
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device:
+            raise L.BubbleformerHipError(f"rollout_heatflux: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
+    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.device != pred.device:
+        raise L.BubbleformerHipError(f"rollout_heatflux: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
+    if ids.numel() != Cn:
+        raise L.BubbleformerHipError(f"rollout_heatflux: the field table has {ids.numel()} channels, the prediction {Cn}")
+    if not (0 <= int(dfun_channel) < Cn and 0 <= int(temp_channel) < Cn):
+        raise L.BubbleformerHipError(f"rollout_heatflux: channels {dfun_channel} / {temp_channel} are not among the prediction's {Cn}")
+    L.check(L.lib().bf_rollout_heatflux(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(dfun_channel),
+                                        int(temp_channel), _p(heater_temp), float(x_min), float(dx), float(lc), float(conductivity), _p(flux_pred),
+                                        _p(flux_tgt), B, T, Cn, H, W, Ho, Wo, int(steps), _stream()), "bf_rollout_heatflux")
+
+
+def kde_kl_workspace(rows: int, n: int, m: int, points: int, device) -> torch.Tensor:
+    """The fp64 workspace ``kde_kl`` needs (allocate once, outside a graph capture): O(points) per row, whatever n and m."""
+    if int(rows) < 1 or int(n) < 2 or int(m) < 2 or int(points) < 3:
+        raise L.BubbleformerHipError(f"kde_kl_workspace: needs rows >= 1, n >= 2, m >= 2, points >= 3 (got {rows}, {n}, {m}, {points})")
+    return torch.empty(L.lib().bf_kde_kl_ws_doubles(int(rows), int(n), int(m), int(points)), dtype=torch.float64, device=device)
+
+
+def kde_kl(p: torch.Tensor, q: torch.Tensor, points: int, eps: float, ws: torch.Tensor, kl: torch.Tensor, x: Optional[torch.Tensor] = None,
+           pdf_p: Optional[torch.Tensor] = None, pdf_q: Optional[torch.Tensor] = None) -> None:
+    """kl (R,) = KL(p || q) of the Gaussian KDEs of the rows of p (R, n) and q (R, m), fp64 on the device, by Simpson's rule on ``points``
+    grid points (bf_kde_kl; include/bubbleformer_hip.h has the contract); optionally the grid and both densities (R, points).  Allocates nothing."""
+    _require_gpu(p)
+    if p.dim() != 2 or q.dim() != 2 or p.shape[0] != q.shape[0]:
+        raise L.BubbleformerHipError(f"kde_kl: p and q must be (R, n) and (R, m), got {tuple(p.shape)} and {tuple(q.shape)}")
+    R, n, m = int(p.shape[0]), int(p.shape[1]), int(q.shape[1])
+    if n < 2 or m < 2 or int(points) < 3 or R < 1:
+        raise L.BubbleformerHipError(f"kde_kl: needs at least 2 samples per set and 3 grid points (n = {n}, m = {m}, points = {points})")
+    want = {"p": (p, (R, n)), "q": (q, (R, m)), "kl": (kl, (R,)), "x": (x, (R, points)), "pdf_p": (pdf_p, (R, points)), "pdf_q": (pdf_q, (R, points)),
+            "ws": (ws, (ws.numel(),))}
+    for name, (t, shape) in want.items():
+        if name in ("x", "pdf_p", "pdf_q") and t is None:
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != p.device:
+            raise L.BubbleformerHipError(f"kde_kl: {name} must be a contiguous torch.float64 tensor of shape {shape} on {p.device}")
+    if ws.numel() < L.lib().bf_kde_kl_ws_doubles(R, n, m, int(points)):
+        raise L.BubbleformerHipError("kde_kl: the workspace is smaller than kde_kl_workspace(rows, n, m, points)")
+    L.check(L.lib().bf_kde_kl(_p(p), _p(q), R, n, m, int(points), float(eps), _p(kl), _p(x), _p(pdf_p), _p(pdf_q), _p(ws), ws.numel(), _stream()),
+            "bf_kde_kl")
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
           grad_scale: float = 1.0) -> None:
     """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140)."""

@@ -1,5 +1,7 @@
 """Physics metrics of a rollout, on the device (reference: bubbleformer/utils/losses.py:5-15, bubbleformer/utils/heatflux.py)."""
 import ctypes as C
+import dataclasses
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -43,3 +45,85 @@ def heatflux(dfun: torch.Tensor, temp: torch.Tensor, heater_temp: float):
     L.check(L.lib().bf_heatflux_rows(_p(dfun), _p(temp), T, 512 * 512, 512, -8.0, 1.0 / 32, float(heater_temp), 0.0007, _p(flux), _stream()),
             "bf_heatflux_rows")
     return flux.mean(), flux.max()
+
+
+@dataclasses.dataclass(frozen=True)
+class HeaterSpec:
+    """The heater of a pool-boiling study, for the heat flux of utils/heatflux.py.  The defaults are the reference's FC-72 constants
+    (heatflux.py:17-35); ``heater_temp`` is one float, or one float per file of the dataset.  The domain is symmetric about x = 0, as the
+    reference assumes (x in [-8, 8) at dx = 1/32: 512 columns), so a downsampled or coarser dataset needs a spec with its own ``dx``."""
+    heater_temp: Union[float, Sequence[float]]
+    temperature_field: str = "temperature"
+    sdf_field: str = "dfun"
+    x_min: float = -8.0
+    dx: float = 1.0 / 32
+    lc: float = 0.0007
+    conductivity: float = 0.054
+
+    def check_width(self, W: int) -> None:
+        """A frame of W columns is accepted when x_min + W * dx = -x_min to 1e-9 relative (the slack is for a dx that is no binary fraction)."""
+        x_max = self.x_min + int(W) * self.dx
+        if not (self.dx > 0 and self.lc > 0 and abs(x_max + self.x_min) <= 1e-9 * abs(self.x_min)):
+            raise ValueError(f"a frame of {W} columns at dx = {self.dx} ends at x = {x_max}, the symmetric domain of utils/heatflux.py at "
+                             f"{-self.x_min}: give the HeaterSpec the dataset's own dx")
+
+    def temperatures(self, files: Sequence[int], num_files: int) -> list:
+        """heater_temp of every trajectory, from the file each comes from."""
+        if isinstance(self.heater_temp, (int, float)):
+            return [float(self.heater_temp)] * len(files)
+        temps = [float(v) for v in self.heater_temp]
+        if len(temps) != int(num_files):
+            raise ValueError(f"heater_temp has {len(temps)} entries, the dataset {num_files} files: give one float, or one per file")
+        return [temps[int(f)] for f in files]
+
+    def channels(self, fields: Sequence[str]):
+        """(signed-distance channel, temperature channel) among the output fields."""
+        fields = list(fields)
+        for name in (self.sdf_field, self.temperature_field):
+            if name not in fields:
+                raise ValueError(f"the heat flux needs the field {name!r} among the output fields {fields}")
+        return fields.index(self.sdf_field), fields.index(self.temperature_field)
+
+
+def heatflux_series(dfun: torch.Tensor, temp: torch.Tensor, heater_temp: float, spec: Optional[HeaterSpec] = None) -> torch.Tensor:
+    """dfun, temp (T, H, W) device tensors in physical units -> (T,) fp32: the bottom-row heat flux of every frame (the `hfluxes` of
+    utils/heatflux.py:36, which ``heatflux`` reduces to mean and max), for any width the spec accepts."""
+    _require_gpu(dfun)
+    spec = spec if spec is not None else HeaterSpec(heater_temp)
+    if dfun.dim() != 3 or dfun.shape != temp.shape:
+        raise ValueError(f"heatflux_series expects two (T, H, W) fields of one shape, got {tuple(dfun.shape)} and {tuple(temp.shape)}")
+    T, H, W = dfun.shape
+    spec.check_width(W)
+    dfun, temp = dfun.contiguous().float(), temp.contiguous().float()
+    flux = torch.empty(T, dtype=torch.float32, device=dfun.device)
+    # bf_heatflux_rows carries the reference's conductivity 0.054 in its coefficient 0.054 / (dx * lc): another conductivity scales lc
+    # (a factor of exactly 1 at the default, so the default spec has the bits ``heatflux`` reduces)
+    lc = spec.lc * (0.054 / spec.conductivity)
+    L.check(L.lib().bf_heatflux_rows(_p(dfun), _p(temp), T, H * W, W, float(spec.x_min), float(spec.dx), float(heater_temp), float(lc), _p(flux),
+                                     _stream()), "bf_heatflux_rows")
+    return flux
+
+
+def kde_kl_divergence(sim: torch.Tensor, model: torch.Tensor, points: int = 1000, eps: float = 1e-10, return_pdfs: bool = False):
+    """KL(sim || model) of the Gaussian kernel density estimates of two sample sets, as examples/data_visualization.ipynb cell 4 computes it
+    (scipy's gaussian_kde with Scott's bandwidth, a ``points``-point grid over both sets, Simpson's rule), on the device in fp64 without a
+    points x n intermediate.  sim (n,) / model (m,), or batched (R, n) / (R, m), fp32 or fp64 -> a 0-d or (R,) fp64 tensor; with
+    ``return_pdfs`` also (x, pdf_sim, pdf_model), each (points,) or (R, points).  One deviation from the notebook: where the simulated
+    density is exactly 0 the integrand is 0 (its limit) instead of numpy's NaN.  A set of zero variance gives NaN.  Never synchronises."""
+    from .. import ops
+    _require_gpu(sim)
+    if sim.dim() not in (1, 2) or sim.dim() != model.dim() or (sim.dim() == 2 and sim.shape[0] != model.shape[0]):
+        raise ValueError(f"kde_kl_divergence expects (n,) and (m,), or (R, n) and (R, m); got {tuple(sim.shape)} and {tuple(model.shape)}")
+    single = sim.dim() == 1
+    p = sim.reshape(1 if single else sim.shape[0], -1).to(torch.float64).contiguous()
+    q = model.reshape(p.shape[0], -1).to(torch.float64).contiguous()
+    if p.shape[1] < 2 or q.shape[1] < 2 or int(points) < 3:
+        raise ValueError(f"kde_kl_divergence needs at least 2 samples per set and 3 grid points (got {p.shape[1]}, {q.shape[1]}, {points})")
+    R = p.shape[0]
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.device)
+    kl = new(R)
+    extra = (new(R, points), new(R, points), new(R, points)) if return_pdfs else (None, None, None)
+    ops.kde_kl(p, q, int(points), float(eps), ops.kde_kl_workspace(R, p.shape[1], q.shape[1], int(points), p.device), kl, *extra)
+    if not return_pdfs:
+        return kl[0] if single else kl
+    return (kl[0],) + tuple(t[0] for t in extra) if single else (kl,) + extra

@@ -127,6 +127,8 @@ class RolloutReport:
     timesteps: torch.Tensor                         # (B, steps*T)     int64 frame numbers inside the trajectory's file
     fields: List[str]                               # output field names in channel order
     predictions: Optional[torch.Tensor] = None      # (B, steps*T, C, Ho, Wo) if kept
+    heatflux_pred: Optional[torch.Tensor] = None    # (B, steps*T)     heater heat flux of every predicted frame (utils/heatflux.py), or None
+    heatflux_target: Optional[torch.Tensor] = None  # (B, steps*T)     the same of the simulated one
 
     def save(self, path) -> None:
         """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
@@ -135,7 +137,27 @@ class RolloutReport:
             out["preds"] = self.predictions
         if self.eikonal_pred is not None:
             out["eikonal_pred"], out["eikonal_target"] = self.eikonal_pred, self.eikonal_target
+        if self.heatflux_pred is not None:
+            out["heatflux_pred"], out["heatflux_target"] = self.heatflux_pred, self.heatflux_target
         torch.save(out, path)
+
+    def _heatfluxes(self):
+        if self.heatflux_pred is None:
+            raise ValueError("this report has no heat-flux rows: call evaluate_rollouts(..., heatflux=HeaterSpec(...))")
+        return self.heatflux_target, self.heatflux_pred
+
+    def heatflux_kl(self, points: int = 1000, pooled: bool = False) -> torch.Tensor:
+        """KL(simulation || model) of the heat-flux distributions (examples/data_visualization.ipynb cell 4, ``physics.kde_kl_divergence``):
+        (B,) per trajectory, or with ``pooled`` the one divergence of all trajectories' rows together -- the notebook's number for one long
+        series.  On the device; the caller synchronises when it reads the value."""
+        from .physics import kde_kl_divergence
+        sim, model = self._heatfluxes()
+        return kde_kl_divergence(sim.reshape(-1), model.reshape(-1), points) if pooled else kde_kl_divergence(sim, model, points)
+
+    def save_heatfluxes(self, path) -> None:
+        """The file examples/data_visualization.ipynb cell 2 loads: {"sim_hf", "model_hf"} as 1-D CPU float tensors, all trajectories in order."""
+        sim, model = self._heatfluxes()
+        torch.save({"sim_hf": sim.reshape(-1).float().cpu(), "model_hf": model.reshape(-1).float().cpu()}, path)
 
 
 def _to_device(values, dtype, device) -> torch.Tensor:
@@ -144,7 +166,7 @@ def _to_device(values, dtype, device) -> torch.Tensor:
 
 
 def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
-                      keep_predictions: bool = False) -> RolloutReport:
+                      keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.HeaterSpec)
     """Roll ``model`` out over ``B = len(starts)`` test trajectories at once and score every predicted frame against the simulation.
 
     data: a ``BubbleForecast`` (its device store is made on the model's device) or a ``DeviceClipStore``; starts: dataset sample indices.
@@ -152,7 +174,9 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     takes its targets from the store, writes that step's rows of the report, the next step's input and, if kept, the archive, and advances
     a step counter that lives on the device.  With ``use_graph`` both are captured as one linear HIP graph and replayed ``steps`` times with
     no other host work between replays; without, the same two calls run eagerly and give the same bits.  A model whose ``forward`` takes
-    ``fluid_params`` gets the store's fluid row of each trajectory's file.  Never synchronises."""
+    ``fluid_params`` gets the store's fluid row of each trajectory's file.  With ``heatflux`` (a ``physics.HeaterSpec``) the step also leaves
+    the heater heat flux of every predicted and simulated frame (``ops.rollout_heatflux``, issued right before the scoring call and captured
+    with it); ``None`` leaves the launches and the report as they are without it.  Never synchronises."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
@@ -179,12 +203,21 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     archive = new(B, steps * T, C, Ho, Wo) if keep_predictions else None
     counter = torch.zeros(1, dtype=torch.int32, device=device)
     ws = ops.rollout_score_workspace(x)
+    hf_p = hf_t = hf_args = None
+    if heatflux is not None:
+        hf_channels = heatflux.channels(fields)
+        heatflux.check_width(Wo)
+        heater = _to_device(heatflux.temperatures(plan.files, len(ds.traj_lens)), torch.float32, device)
+        hf_p, hf_t = new(B, steps * T), new(B, steps * T)
+        hf_args = (*hf_channels, heater, steps, hf_p, hf_t, heatflux.x_min, heatflux.dx, heatflux.lc, heatflux.conductivity)
 
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
             pred = pred.float().contiguous()
         if pred.shape != x.shape:
             raise ValueError(f"the model returned {tuple(pred.shape)} for an input of {tuple(x.shape)}: it cannot be fed back")
+        if hf_args is not None:                     # reads the step counter the scoring call then advances
+            ops.rollout_heatflux(pred, store.frames, first, step, store.out_tab, *hf_args)
         ops.rollout_score(pred, store.frames, first, step, store.out_tab, sdf, steps, rel_l2, criterion, ws, eik_p, eik_t, next_in, arch)
 
     model.eval()
@@ -208,4 +241,4 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         else:
             for _ in range(steps):
                 score(model(x, *extra), counter, x, archive)
-    return RolloutReport(rel_l2, criterion, eik_p, eik_t, plan.timesteps.to(device, non_blocking=True), fields, archive)
+    return RolloutReport(rel_l2, criterion, eik_p, eik_t, plan.timesteps.to(device, non_blocking=True), fields, archive, hf_p, hf_t)

@@ -33,6 +33,7 @@
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
+ *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  */
 #ifndef BUBBLEFORMER_HIP_H
@@ -378,6 +379,36 @@ int bf_rollout_score(const float* pred, const float* frames, int64_t field_strid
                      int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
                      float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
                      int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+/* The heat-flux rows of ONE rollout step (utils/heatflux.py:3-38 per step of scripts/inference.py:239-252; csrc/physics.hip), for the prediction
+ * and for the simulation; allocation-free, capturable, no atomics (the same bits on every call), never makes the host wait.  pred, frames,
+ * field_stride, total_frames, nfields, first, field / diff / div and the sizes are bf_rollout_score's.  step = one int32 in DEVICE memory, READ and
+ * never written: the call must be issued BEFORE the step's bf_rollout_score, which increments that counter.  With s = *step, row s * T + t of
+ * trajectory b of flux_pred / flux_tgt [B][steps*T] is bf_heatflux_rows' expression on row 0 (the heater row) of frame t:
+ *   mean over ALL Wo cells of [-5 <= x_c <= 5 and dfun < 0] * (heater_temp[b] - temp) * conductivity / (dx * lc),  x_c = x_min + (i + 0.5) * dx in fp64,
+ * the difference in fp32, the sum in fp64 in a fixed order, one rounding; heater_temp [B] fp32 on the DEVICE.
+ *   flux_pred: dfun = pred * div + diff of channel dfun_channel, temp likewise of temp_channel (fp32 multiply, then add, unfused: the physical
+ *              field bf_rollout_score's Eikonal rows see);
+ *   flux_tgt:  the stored raw frame first[b] + (s + 1) * T + t (clamped into the store) of fields field[dfun_channel] / field[temp_channel],
+ *              through bf_clip_gather's nearest-neighbour map when Ho x Wo < H x W.
+ * With s outside [0, steps) nothing is written. */
+int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                        const int32_t* step, const int32_t* field, const float* diff, const float* div, int dfun_channel, int temp_channel,
+                        const float* heater_temp, float x_min, float dx, float lc, float conductivity, float* flux_pred, float* flux_tgt,
+                        int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+/* KL(p || q) of the Gaussian kernel density estimates of two sample sets, for R independent rows (examples/data_visualization.ipynb cell 4:
+ * scipy.stats.gaussian_kde of each set, np.linspace grid, scipy.integrate.simpson; csrc/physics.hip).  Everything fp64 on the device, allocation-free,
+ * capturable, no atomics (the same bits on every call, and a row has the same bits alone and in a batch).  p [R][n] (the simulation), q [R][m]
+ * (the model), n, m >= 2, points >= 3, R <= 65535.  Per row: mean, then unbiased variance from centred squares, min and max of each set;
+ * bandwidth h = n^(-1/5) * sqrt(var) (Scott's factor); grid x_i = lo + i * (hi - lo) / (points - 1), x_{points-1} = hi over the smaller minimum /
+ * larger maximum; pdf(x_i) = sum_j exp(-((x_i - s_j) / h)^2 / 2) / (n * h * sqrt(2 pi)), partial sums per slab of samples added in slab order;
+ * q_i == 0 becomes eps; f_i = p_i * log(p_i / q_i), and f_i = 0 where p_i == 0 (the limit; numpy has 0 * -inf = NaN there, so the notebook
+ * returns NaN for far-apart sets -- the one deliberate deviation); kl[r] = Simpson's rule on the uniform grid as scipy 1.15 applies it: composite
+ * Simpson for odd points, for even points composite Simpson over the first points - 1 nodes plus step * (5 f_{N-1} + 8 f_{N-2} - f_{N-3}) / 12.
+ * A set of zero variance gives kl = NaN (and NaN densities).  x, pdf_p, pdf_q [R][points] are optional (null: not written).
+ * ws: bf_kde_kl_ws_doubles(R, n, m, points) doubles = R * (8 + slabs * points) with at most 128 slabs: O(points) per row, no points x n matrix. */
+int64_t bf_kde_kl_ws_doubles(int R, int64_t n, int64_t m, int points);
+int bf_kde_kl(const double* p, const double* q, int R, int64_t n, int64_t m, int points, double eps, double* kl, double* x, double* pdf_p,
+              double* pdf_q, double* ws, int64_t ws_doubles, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
