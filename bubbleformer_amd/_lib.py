@@ -157,6 +157,11 @@ SIGNATURES = {
     "bf_adamw": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
     "bf_adam": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
     "bf_lion": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, vp]),
+    "bf_grad_norm_ws_doubles": (i64, [i64]),
+    "bf_grad_norm": (C.c_int, [fp, i64, f32, f32, fp, vp, i64, vp]),
+    "bf_adamw_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
+    "bf_adam_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
+    "bf_lion_dev": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, vp]),
     "bf_eikonal_sum": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, vp, vp]),
     "bf_eikonal_l1_frames": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, vp]),
     "bf_heatflux_rows": (C.c_int, [fp, fp, i64, i64, C.c_int, f32, f32, f32, f32, fp, vp]),

@@ -11,6 +11,7 @@
 //
 // This is the generic fp32-VALU form (any d <= 128, any L <= 32, both dtypes).
 #include "bf_common.h"
+#include "param_reduce.h"
 
 namespace {
 
@@ -168,10 +169,14 @@ __global__ void __launch_bounds__(NT) attn_fwd_kernel(const T* __restrict__ qkv,
 template <typename T>
 __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ dout, T* __restrict__ dqkv,
                                                      SeqGeo g, int heads, int d, AttnParams p, AttnGrads gr, float out_scale,
-                                                     int accumulate) {
+                                                     int accumulate, float* __restrict__ ws) {
+    // Parameter gradients: every sum below has ONE writer and a fixed order (the same bits every run) -- a wave keeps its own partials
+    // (bias-table buckets and head scales in LDS, LayerNorm columns in registers), the block adds its waves in wave order and leaves one
+    // row of the workspace for an ordered reduction (param_reduce.h: attn_reduce_block); float atomics only when no workspace is given.
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float s_demb[32 * 16];     // [bucket][head] (heads <= 16), block-reduced
-    __shared__ float s_dhs[16];
+    __shared__ float s_demb[NT / 64][32 * 16];     // [wave][bucket][head] (heads <= 16)
+    __shared__ float s_dhs[NT / 64][16];
+    __shared__ float s_diag[NT / 64][64];          // sums of dS along its 2L - 1 diagonals (the bias table is Toeplitz)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int L = g.L, ldd = d + 1, E = heads * d, lds = L + 1;
     const int per_wave = 6 * L * ldd + 2 * L * lds + 2 * L;
@@ -184,8 +189,8 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
     float* sP = dkn + L * ldd;
     float* sA = sP + L * lds;               // A, later dS
     float* rstd = sA + L * lds;
-    for (int i = threadIdx.x; i < 32 * 16; i += blockDim.x) s_demb[i] = 0.f;
-    if (threadIdx.x < 16) s_dhs[threadIdx.x] = 0.f;
+    for (int i = threadIdx.x; i < (NT / 64) * 32 * 16; i += blockDim.x) (&s_demb[0][0])[i] = 0.f;
+    if (threadIdx.x < (NT / 64) * 16) (&s_dhs[0][0])[threadIdx.x] = 0.f;
     __syncthreads();
     // per-lane LayerNorm parameter gradient accumulators (columns lane, lane + 64)
     float a_qw[2] = {0.f, 0.f}, a_qb[2] = {0.f, 0.f}, a_kw[2] = {0.f, 0.f}, a_kb[2] = {0.f, 0.f};
@@ -246,15 +251,27 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
             for (int j = 0; j < L; ++j) sA[lane * lds + j] = sP[lane * lds + j] * (sA[lane * lds + j] - dot);   // dS
         }
         wave_sync();
-        // bias-table gradient: Toeplitz -> one LDS atomic per (i, j)
-        if (gr.demb)
-            for (int t = lane; t < L * L; t += 64) {
-                const int i = t / L, j = t % L;
-                atomicAdd(&s_demb[t5_bucket(i - j) * 16 + head], sA[i * lds + j]);
+        // bias-table gradient: Toeplitz -> lane q sums diagonal i - j = q - (L - 1) top to bottom (2L - 1 <= 63 diagonals), then lane b adds
+        // the diagonals of bucket b in diagonal order into this wave's table
+        if (gr.demb) {
+            if (lane < 2 * L - 1) {
+                const int dd = lane - (L - 1);
+                float t = 0.f;
+                for (int i = max(0, dd); i < min(L, L + dd); ++i) t += sA[i * lds + (i - dd)];
+                s_diag[wave][lane] = t;
             }
+            wave_sync();
+            if (lane < 32) {
+                float t = 0.f;
+                for (int q = 0; q < 2 * L - 1; ++q)
+                    if (t5_bucket(q - (L - 1)) == lane) t += s_diag[wave][q];
+                s_demb[wave][lane * 16 + head] += t;
+            }
+            wave_sync();
+        }
         if (p.hscale) {
             dhs_part = wave_sum(dhs_part);
-            if (lane == 0 && gr.dhscale) atomicAdd(&s_dhs[head], dhs_part);
+            if (lane == 0 && gr.dhscale) s_dhs[wave][head] += dhs_part;
         }
         // 3) dqn[i][e] = scale * sum_j dS[i][j] kn[j][e];  dkn[j][e] = scale * sum_i dS[i][j] qn[i][e]
         for (int e = lane; e < d; e += 64) {
@@ -316,19 +333,40 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
         }
         wave_sync();
     }
-    // flush parameter gradients
+    // flush parameter gradients: the wave's LayerNorm columns into its own (now idle) tile area, then one value per thread, waves in order
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const int e = lane + 64 * c;
-        if (e < d && gr.dqw) { atomicAdd(gr.dqw + e, a_qw[c]); atomicAdd(gr.dqb + e, a_qb[c]); atomicAdd(gr.dkw + e, a_kw[c]); atomicAdd(gr.dkb + e, a_kb[c]); }
+        if (e < d) { q[e] = a_qw[c]; q[d + e] = a_qb[c]; q[2 * d + e] = a_kw[c]; q[3 * d + e] = a_kb[c]; }
     }
     __syncthreads();
-    if (gr.demb)
-        for (int i = threadIdx.x; i < 32 * heads; i += blockDim.x) {
-            const float val = s_demb[(i / heads) * 16 + (i % heads)];
-            if (val != 0.f) atomicAdd(gr.demb + i, val);
+    const int nvals = 4 * d + 32 * heads + heads;
+    for (int i = threadIdx.x; i < nvals; i += blockDim.x) {
+        float val = 0.f;
+        float* dst;
+        if (i < 4 * d) {
+            for (int w = 0; w < WPB; ++w) val += smem[w * per_wave + i];
+            const int pq = i / d, e = i % d;
+            dst = pq == 0 ? gr.dqw : pq == 1 ? gr.dqb : pq == 2 ? gr.dkw : gr.dkb;
+            if (dst) dst += e;
+        } else if (i < 4 * d + 32 * heads) {
+            const int t = i - 4 * d;
+            for (int w = 0; w < WPB; ++w) val += s_demb[w][(t / heads) * 16 + (t % heads)];
+            dst = gr.demb ? gr.demb + t : nullptr;
+        } else {
+            const int t = i - 4 * d - 32 * heads;
+            for (int w = 0; w < WPB; ++w) val += s_dhs[w][t];
+            dst = gr.dhscale ? gr.dhscale + t : nullptr;
         }
-    if (gr.dhscale && threadIdx.x < heads) atomicAdd(gr.dhscale + threadIdx.x, s_dhs[threadIdx.x]);
+        if (ws) ws[(long)blockIdx.x * nvals + i] = val;
+        else if (dst && val != 0.f) atomicAdd(dst, val);
+    }
+}
+
+// dst += sum over the workspace rows attn_bwd_kernel left, in row order (param_reduce.h)
+__global__ void __launch_bounds__(64 * BF_RED_FL) attn_rows_reduce_kernel(AttnReduceJob j) {
+    __shared__ float red[1][BF_RED_FL][64];
+    attn_reduce_block(j, blockIdx.x, 0, 1, red);
 }
 
 // waves per block so the dynamic LDS plan fits; raises the kernel's dynamic-LDS limit when needed
@@ -477,12 +515,20 @@ static int attn_bwd_impl(int dtype, const void* qkv, const void* dout, void* dqk
     if (int rc = dtype == BF_DTYPE_BF16 ? plan_waves(attn_bwd_kernel<bf16>, fpw, &WPB, &shm) : plan_waves(attn_bwd_kernel<float>, fpw, &WPB, &shm)) return rc;
     const long nprob = nseq * heads;
     BfProfScope prof((hipStream_t)stream, "attn_bwd", 10.0 * nprob * L * L * d, (double)nprob * L * d * bf_esize(dtype) * (accumulate ? 10.0 : 7.0));
-    const int grid = (int)std::min<long>((nprob + WPB - 1) / WPB, 256 * 4);
+    const int full = (int)std::min<long>((nprob + WPB - 1) / WPB, 256 * 4), nvals = 4 * d + 32 * heads + heads;
+    int grid = full;
+    if (ws && ws_floats < (int64_t)full * nvals) { grid = (int)(ws_floats / nvals); if (grid < 1) { ws = nullptr; grid = full; } }
     if (dtype == BF_DTYPE_BF16)
-        hipLaunchKernelGGL(attn_bwd_kernel<bf16>, dim3(grid), dim3(WPB * 64), shm, (hipStream_t)stream, (const bf16*)qkv, (const bf16*)dout, (bf16*)dqkv, g, heads, d, p, gr, out_scale, accumulate);
+        hipLaunchKernelGGL(attn_bwd_kernel<bf16>, dim3(grid), dim3(WPB * 64), shm, (hipStream_t)stream, (const bf16*)qkv, (const bf16*)dout, (bf16*)dqkv, g, heads, d, p, gr, out_scale, accumulate, ws);
     else
-        hipLaunchKernelGGL(attn_bwd_kernel<float>, dim3(grid), dim3(WPB * 64), shm, (hipStream_t)stream, (const float*)qkv, (const float*)dout, (float*)dqkv, g, heads, d, p, gr, out_scale, accumulate);
+        hipLaunchKernelGGL(attn_bwd_kernel<float>, dim3(grid), dim3(WPB * 64), shm, (hipStream_t)stream, (const float*)qkv, (const float*)dout, (float*)dqkv, g, heads, d, p, gr, out_scale, accumulate, ws);
     BF_CHECK_LAUNCH();
+    if (rows_out) { *rows_out = ws ? grid : 0; return 0; }       // the caller reduces the workspace rows later (AttnReduceJob)
+    if (ws) {
+        const AttnReduceJob j{ws, grid, d, heads, dqw, dqb, dkw, dkb, demb, dhscale};
+        hipLaunchKernelGGL(attn_rows_reduce_kernel, dim3(bf_cdiv(nvals, 64)), dim3(64 * BF_RED_FL), 0, (hipStream_t)stream, j);
+        BF_CHECK_LAUNCH();
+    }
     return 0;
 }
 
@@ -494,8 +540,8 @@ extern "C" int bf_attn_bwd(int dtype, const void* qkv, const void* dout, void* d
     return attn_bwd_impl(dtype, qkv, dout, dqkv, nseq, L, inner, outer_stride, inner_stride, tok_stride, heads, d, qw, qb, kw, kb, emb, hscale, dqw,
                          dqb, dkw, dkb, demb, dhscale, out_scale, accumulate, ws, ws_floats, nullptr, stream);
 }
-// Same, but the parameter-gradient rows the MFMA kernel leaves in ws are NOT reduced: *rows = number of rows for a later
-// AttnReduceJob (0 when the kernel accumulated the parameter gradients itself: fp32 / generic path, or no workspace).
+// Same, but the parameter-gradient rows the kernel leaves in ws are NOT reduced: *rows = number of rows for a later
+// AttnReduceJob (0 when the kernel accumulated the parameter gradients itself: no workspace).
 int bf_attn_bwd_partials(int dtype, const void* qkv, const void* dout, void* dqkv, int64_t nseq, int L, int64_t inner, int64_t outer_stride,
                          int64_t inner_stride, int64_t tok_stride, int heads, int d, const float* qw, const float* qb, const float* kw,
                          const float* kb, const float* emb, const float* hscale, float* dqw, float* dqb, float* dkw, float* dkb, float* demb,

@@ -1,0 +1,142 @@
+// Gradient clipping for the training step, without a host round trip:
+//   bf_grad_norm                             -> {norm, coef} of the flat gradient buffer in device memory (torch.nn.utils.clip_grad_norm_,
+//                                               norm_type 2: what Lightning's Trainer(gradient_clip_val=...) calls)
+//   bf_adamw_dev / bf_adam_dev / bf_lion_dev -> the fused optimizers of optim_kernels.h reading that coefficient from device memory, with an
+//                                               optional clamp of the scaled gradient (gradient_clip_algorithm="value")
+//
+// The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
+//   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
+//           sweeps slab s: thread t takes groups t, t + 256, ... of the slab with one 16-byte load each, squares in fp64 into four
+//           accumulators (one per component), adds them as (x + y) + (z + w); the 64 lanes of a wave meet in an xor butterfly (1, 2, .. 32),
+//           the 4 waves are added in wave order.  One fp64 partial per slab; the n % 4 trailing elements join the last slab's partial.
+//   pass 2  one workgroup: thread t adds partials 4t .. 4t + 3 in order, then the same butterfly and wave order.
+//           norm = fp32(gscale * sqrt(sum)) (one rounding), coef = min(max_norm / (norm + 1e-6f), 1) in fp32 with an IEEE divide.
+// At most GN_MAX_SLABS partials, so pass 2 is one load per thread.
+#include "optim_kernels.h"
+
+namespace {
+constexpr int GN_NT = 256;
+constexpr int GN_MAX_SLABS = 1024;
+constexpr long GN_MIN_SLAB_GROUPS = 1024;      // 16 KB: below this a slab is not worth a workgroup
+
+// groups per slab: at least GN_MIN_SLAB_GROUPS, at most GN_MAX_SLABS slabs, a whole number of sweeps of the workgroup
+inline long gn_slab_groups(long G) {
+    const long per = std::max<long>(GN_MIN_SLAB_GROUPS, (G + GN_MAX_SLABS - 1) / GN_MAX_SLABS);
+    return (per + GN_NT - 1) / GN_NT * GN_NT;
+}
+inline int gn_slabs(long G) { return (int)std::max<long>(1, (G + gn_slab_groups(G) - 1) / gn_slab_groups(G)); }
+
+__device__ __forceinline__ double gn_wave_sum(double v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);      // every lane ends with the same tree over the 64 values
+    return v;
+}
+// sum over the workgroup in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double gn_block_sum(double v, double* red) {
+    v = gn_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int w = 1; w < GN_NT / 64; ++w) s += red[w];
+    return s;
+}
+
+__global__ void __launch_bounds__(GN_NT) grad_sumsq_kernel(const float* __restrict__ g, long n, long slab_groups, double* __restrict__ part) {
+    __shared__ double red[GN_NT / 64];
+    const long G = n / 4;
+    const long g0 = (long)blockIdx.x * slab_groups, g1 = min(G, g0 + slab_groups);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+    long i = g0 + threadIdx.x;
+    for (; i + 3 * GN_NT < g1; i += 4 * GN_NT) {          // four loads in flight per thread; the adds stay in group order
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = g4[i + u * GN_NT];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            ax += (double)q[u].x * (double)q[u].x; ay += (double)q[u].y * (double)q[u].y;
+            az += (double)q[u].z * (double)q[u].z; aw += (double)q[u].w * (double)q[u].w;
+        }
+    }
+    for (; i < g1; i += GN_NT) {
+        const float4 q = g4[i];
+        ax += (double)q.x * (double)q.x; ay += (double)q.y * (double)q.y;
+        az += (double)q.z * (double)q.z; aw += (double)q.w * (double)q.w;
+    }
+    double s = gn_block_sum((ax + ay) + (az + aw), red);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == gridDim.x - 1)
+            for (long k = G * 4; k < n; ++k) s += (double)g[k] * (double)g[k];
+        part[blockIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(GN_NT) grad_norm_finish_kernel(const double* __restrict__ part, int nslabs, float gscale, float max_norm,
+                                                                float* __restrict__ out) {
+    __shared__ double red[GN_NT / 64];
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < GN_MAX_SLABS / GN_NT; ++k) {
+        const int s = threadIdx.x * (GN_MAX_SLABS / GN_NT) + k;
+        if (s < nslabs) a += part[s];
+    }
+    const double sum = gn_block_sum(a, red);
+    if (threadIdx.x == 0) {
+        const float norm = (float)((double)gscale * sqrt(sum));
+        const float c = __fdiv_rn(max_norm, norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.f ? 1.f : c;                      // a NaN norm stays a NaN coefficient (torch.clamp)
+    }
+}
+}  // namespace
+
+extern "C" int64_t bf_grad_norm_ws_doubles(int64_t n) { return n > 0 ? gn_slabs((long)(n / 4)) : 0; }
+
+extern "C" int bf_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* out, double* ws, int64_t ws_doubles,
+                            bf_stream_t stream) {
+    BF_REQUIRE(g && n > 0, "bf_grad_norm: bad arguments");
+    BF_REQUIRE(out, "bf_grad_norm: the output {norm, coef} is null");
+    BF_REQUIRE(max_norm > 0.f, "bf_grad_norm: max_norm must be positive");
+    BF_REQUIRE(BF_OPT_ALIGNED(g), "bf_grad_norm: the gradient buffer must be 16-byte aligned");
+    const long G = (long)(n / 4);
+    const int nslabs = gn_slabs(G);
+    BF_REQUIRE(ws && ws_doubles >= nslabs && (uintptr_t)ws % 8 == 0, "bf_grad_norm: the workspace is smaller than bf_grad_norm_ws_doubles(n)");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nslabs), dim3(GN_NT), 0, st, g, (long)n, gn_slab_groups(G), ws);
+    BF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_NT), 0, st, (const double*)ws, nslabs, gscale, max_norm, out);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- the optimizers on a device-resident coefficient
+// clip_value = +inf = no clamp: that variant has no clamp code at all, so its loop body is the host-scale kernel's
+#define BF_OPT_DISPATCH(CALL_DEV, CALL_CLAMP) (isinf(clip_value) ? (CALL_DEV) : (CALL_CLAMP))
+
+extern "C" int bf_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                            float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_dev: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_dev: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    return BF_OPT_DISPATCH(opt_launch_adam<BF_OPT_DEV>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st),
+                           opt_launch_adam<BF_OPT_DEV_CLAMP>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st));
+}
+
+extern "C" int bf_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                           float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_dev: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_dev: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    return BF_OPT_DISPATCH(opt_launch_adam<BF_OPT_DEV>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st),
+                           opt_launch_adam<BF_OPT_DEV_CLAMP>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st));
+}
+
+extern "C" int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
+                           const float* coef_dev, float clip_value, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_dev: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_dev: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    return BF_OPT_DISPATCH(opt_launch_lion<BF_OPT_DEV>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st),
+                           opt_launch_lion<BF_OPT_DEV_CLAMP>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st));
+}

@@ -139,6 +139,7 @@ struct StageHints { bool prepared = false; NextHead head; NextTail tail; NextSca
 struct ReduceJobs {
     static constexpr int IN_CAP = 6, ATTN_CAP = 4;
     int n_in = 0, n_attn = 0; InReduceJob in[IN_CAP]; AttnReduceJob at[ATTN_CAP];
+    bool at_follows[ATTN_CAP] = {};      // set at launch: job i adds into job i - 1's slots and runs behind it in the SAME workgroups (see launch_reduce_jobs)
     bool fits(const ReduceJobs& o) const { return n_in + o.n_in <= IN_CAP && n_attn + o.n_attn <= ATTN_CAP; }
     int push(const InReduceJob& j) { BF_REQUIRE(n_in < IN_CAP, "ReduceJobs: more InstanceNorm reductions than one launch holds"); in[n_in++] = j; return 0; }
     int push(const AttnReduceJob& j) { BF_REQUIRE(n_attn < ATTN_CAP, "ReduceJobs: more attention reductions than one launch holds"); at[n_attn++] = j; return 0; }
@@ -664,15 +665,27 @@ __global__ void __launch_bounds__(64 * BF_RED_FL) stage_param_reduce_kernel(Redu
         const InReduceJob& j = J.in[z];
         if ((int)blockIdx.x < (j.C + 63) / 64 && (int)blockIdx.y < (j.frames + j.rdiv() - 1) / j.rdiv()) in_reduce_block(j, blockIdx.x, blockIdx.y, red);
     } else {
-        const AttnReduceJob& j = J.at[z - J.n_in];
-        const int nvals = 4 * j.D + 32 * j.heads + j.heads;
-        if ((int)blockIdx.x < (nvals + 63) / 64 && blockIdx.y == 0) attn_reduce_block(j, blockIdx.x, 0, 1, red);
+        int a = z - J.n_in;
+        if (J.at_follows[a]) return;             // done by the workgroups of the job it follows
+        for (;; ++a) {
+            const AttnReduceJob& j = J.at[a];
+            const int nvals = 4 * j.D + 32 * j.heads + j.heads;
+            if ((int)blockIdx.x < (nvals + 63) / 64 && blockIdx.y == 0) attn_reduce_block(j, blockIdx.x, 0, 1, red);
+            if (a + 1 >= J.n_attn || !J.at_follows[a + 1]) break;
+            __syncthreads();                     // `red` is reused
+        }
     }
 }
 int launch_reduce_jobs(ReduceJobs& J, hipStream_t st) {
-    int k = 0;                                   // drop attention jobs without rows (fp32 / generic path accumulated directly)
+    int k = 0;                                   // drop attention jobs without rows (no workspace: the kernel accumulated directly)
     for (int i = 0; i < J.n_attn; ++i) if (J.at[i].rows > 0) J.at[k++] = J.at[i];
     J.n_attn = k;
+    // two jobs on the same slots (the W and the H pass of a spatial stage share their LayerNorms and bias table): each value's thread adds
+    // the first job's sum, then the second's -- slot + a + b in that order.  As two concurrent workgroups they were order free only on a
+    // zeroed slot (0 + a + b); under gradient accumulation the slot holds the earlier micro-batches' sum.
+    for (int i = 0; i < J.n_attn; ++i)
+        J.at_follows[i] = i > 0 && J.at[i].D == J.at[i - 1].D && J.at[i].heads == J.at[i - 1].heads &&
+                          ((J.at[i].dqw && J.at[i].dqw == J.at[i - 1].dqw) || (J.at[i].demb && J.at[i].demb == J.at[i - 1].demb));
     if (J.n_in + J.n_attn == 0) return 0;
     int gx = 1, gy = 1;
     for (int i = 0; i < J.n_in; ++i) { gx = std::max(gx, bf_cdiv(J.in[i].C, 64)); gy = std::max(gy, bf_cdiv(J.in[i].frames, J.in[i].rdiv())); }
@@ -1724,11 +1737,16 @@ extern "C" int bf_embed_bwd(const bf_dims* dims, const bf_embed_params* p, const
         const int nrc = sv.Kp == 16 ? bf_tokred_narrow(d.dtype, sv.C[0], sv.P[0], dy, sv.patches, sc.wg, sv.Kp, 0, 0, nullptr, nullptr, 0, sc.tokred_ws, sc.tokred_floats, ss) : 1;
         if (nrc < 0) return nrc;
         if (nrc == 1) {
-            ZERO_ON(ss, sc.wg, (size_t)sv.C[0] * sv.Kp * 4);
             bf_operand A = op_plain(dy, sv.C[0], BF_LAY_XC);
             bf_operand Bo = op_plain(sv.patches, sv.Kp, BF_LAY_XC);
-            bf_epilogue e = epi_atomic(sc.wg, sv.Kp);
-            TRY(bf_gemm(d.dtype, sv.C[0], sv.Kp, (int)sv.P[0], &A, &Bo, &e, splitk_for(sv.C[0], sv.Kp, sv.P[0]), ss));
+            // per-slice images summed in order, as for the later stages above; atomics only where the workspace cannot hold the images
+            const int src = bf_gemm_slabs(d.dtype, sv.C[0], sv.Kp, (int)sv.P[0], &A, &Bo, sc.wg, sv.Kp, 0, splitk_for(sv.C[0], sv.Kp, sv.P[0]), (float*)sc.t1b, sc.t1b_floats, ss);
+            if (src < 0) return src;
+            if (src == 1) {
+                ZERO_ON(ss, sc.wg, (size_t)sv.C[0] * sv.Kp * 4);
+                bf_epilogue e = epi_atomic(sc.wg, sv.Kp);
+                TRY(bf_gemm(d.dtype, sv.C[0], sv.Kp, (int)sv.P[0], &A, &Bo, &e, splitk_for(sv.C[0], sv.Kp, sv.P[0]), ss));
+            }
         }
         TRY(bf_wgrad_unprep(0, sc.wg, g->conv_w[0], sv.C[0], 4 * d.cin, sv.Kp, 0, ss));
         if (dx_in) {
@@ -1859,12 +1877,18 @@ extern "C" int bf_debed_bwd(const bf_dims* dims, const bf_debed_params* p, const
                                                                       sc.tokred_ws, sc.tokred_floats, ss) : 1;
             if (nrc < 0) return nrc;
             if (nrc == 1) {
-                ZERO_ON(ss, sc.wg, (size_t)sv.Np * cin * 4);
                 bf_operand A = op_plain(dpm, sv.Np, BF_LAY_XC);
                 bf_operand Bo = op_plain(ain, cin, BF_LAY_XC);
                 if (i > 0) op_affine(Bo, BF_PRO_AFFINE_GELU, sv.sc[i - 1], sv.sh[i - 1], rpf, cin);
-                bf_epilogue e = epi_atomic(sc.wg, cin);
-                TRY(bf_gemm(d.dtype, sv.Np, cin, (int)sv.Pin[i], &A, &Bo, &e, splitk_for(sv.Np, cin, sv.Pin[i]), ss));
+                // per-slice images summed in order (see bf_embed_bwd); atomics only where the slab form does not apply
+                const int src = cin % 4 == 0 ? bf_gemm_slabs(d.dtype, sv.Np, cin, (int)sv.Pin[i], &A, &Bo, sc.wg, cin, 0, splitk_for(sv.Np, cin, sv.Pin[i]),
+                                                             (float*)sc.t1b, sc.t1b_floats, ss) : 1;
+                if (src < 0) return src;
+                if (src == 1) {
+                    ZERO_ON(ss, sc.wg, (size_t)sv.Np * cin * 4);
+                    bf_epilogue e = epi_atomic(sc.wg, cin);
+                    TRY(bf_gemm(d.dtype, sv.Np, cin, (int)sv.Pin[i], &A, &Bo, &e, splitk_for(sv.Np, cin, sv.Pin[i]), ss));
+                }
             }
             TRY(bf_wgrad_unprep(0, sc.wg, g->conv_w[i], cin, 4 * co, sv.Np, 1, ss));
             if (rc == 1) {   // dact[p][ci] = sum_n dpm[p][n] * wt[ci][n]

@@ -4,11 +4,12 @@
 //   nchw2pm (+ loss backward)  : d(pred) -> patch-major rows for the debed backward GEMMs
 //   wprep / wgrad_unprep       : fp32 state_dict weights -> GEMM operand layout/dtype and back (gradients)
 //   film_net fwd/bwd           : LayerNorm(P) + Linear(P, 2E) on B rows
-//   adamw / adam               : fused flat-buffer AdamW and Adam
+//   adamw / adam / lion        : fused flat-buffer optimizers on a host gradient scale (kernels: optim_kernels.h, shared with gradclip.hip)
 //   rollout_score              : every score of one rollout step against store-resident targets, one pass over the prediction
 // All are bandwidth-bound; each thread moves 8..16 contiguous bytes where the layout allows.
 #include "bf_common.h"
 #include "param_reduce.h"
+#include "optim_kernels.h"
 
 namespace {
 constexpr int NT = 256;
@@ -611,73 +612,6 @@ __global__ void film_net_bwd_kernel(const float* __restrict__ dgb_, const float*
         for (int b = 0; b < B; ++b)
             acc += (double)dgb_[(long)(o / E) * B * E + (long)b * E + (o % E)] * ((double)chat[b * P + i] * lnw[i] + lnb[i]);
         dW[(long)o * P + i] += (float)acc;
-    }
-}
-
-// ---------------------------------------------------------------------------- AdamW (torch.optim.AdamW semantics)
-__global__ void __launch_bounds__(NT) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                  float bc1, float sqrt_bc2, float gscale) {
-    const long n4 = n / 4;
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-#define BF_ADAM1(X)                                                        \
-        { const float gr = gg.X * gscale;                                   \
-          pp.X *= (1.f - lr * wd);                                          \
-          mm.X = b1 * mm.X + (1.f - b1) * gr;                               \
-          vv.X = b2 * vv.X + (1.f - b2) * gr * gr;                          \
-          pp.X -= (lr / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
-        BF_ADAM1(x) BF_ADAM1(y) BF_ADAM1(z) BF_ADAM1(w)
-#undef BF_ADAM1
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
-        const long i = n4 * 4 + threadIdx.x;
-        const float gr = g[i] * gscale;
-        float pp = p[i] * (1.f - lr * wd);
-        const float mm = b1 * m[i] + (1.f - b1) * gr;
-        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
-        p[i] = pp; m[i] = mm; v[i] = vv;
-    }
-}
-
-// ---------------------------------------------------------------------------- Adam (torch.optim.Adam semantics, single-tensor path)
-// Weight decay is an L2 term on the gradient (g += wd*p), so it passes through both moments; AdamW above decays the parameter instead.
-// Zero padding stays zero: p = g = m = v = 0 gives m / (sqrt(v) / sqrt_bc2 + eps) = 0.
-__global__ void __launch_bounds__(NT) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                 float bc1, float sqrt_bc2, float gscale) {
-    const long n4 = n / 4;
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-#define BF_ADAML2(X)                                                       \
-        { float gr = gg.X * gscale;                                         \
-          if (wd != 0.f) gr += wd * pp.X;                                   \
-          mm.X = b1 * mm.X + (1.f - b1) * gr;                               \
-          vv.X = b2 * vv.X + (1.f - b2) * gr * gr;                          \
-          pp.X -= (lr / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
-        BF_ADAML2(x) BF_ADAML2(y) BF_ADAML2(z) BF_ADAML2(w)
-#undef BF_ADAML2
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
-        const long i = n4 * 4 + threadIdx.x;
-        float pp = p[i];
-        float gr = g[i] * gscale;
-        if (wd != 0.f) gr += wd * pp;
-        const float mm = b1 * m[i] + (1.f - b1) * gr;
-        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
-        p[i] = pp; m[i] = mm; v[i] = vv;
     }
 }
 
@@ -1292,61 +1226,24 @@ extern "C" int bf_rollout_score(const float* pred, const float* frames, int64_t 
     return 0;
 }
 
-// ---------------------------------------------------------------------------- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization
-// Algorithms"; the update lion_pytorch.Lion applies at bubbleformer/modules.py:139-140):
-//   p *= 1 - lr*wd;  p -= lr * sign(b1*m + (1-b1)*g);  m = b2*m + (1-b2)*g
-__global__ void __launch_bounds__(NT) lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n, float lr,
-                                                 float b1, float b2, float wd, float gscale) {
-    const long n4 = n / 4;
-    auto sgn = [](float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); };
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-#define BF_LION1(X)                                                        \
-        { const float gr = gg.X * gscale;                                   \
-          pp.X = pp.X * (1.f - lr * wd) - lr * sgn(b1 * mm.X + (1.f - b1) * gr); \
-          mm.X = b2 * mm.X + (1.f - b2) * gr; }
-        BF_LION1(x) BF_LION1(y) BF_LION1(z) BF_LION1(w)
-#undef BF_LION1
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
-        const long i = n4 * 4 + threadIdx.x;
-        const float gr = g[i] * gscale;
-        p[i] = p[i] * (1.f - lr * wd) - lr * sgn(b1 * m[i] + (1.f - b1) * gr);
-        m[i] = b2 * m[i] + (1.f - b2) * gr;
-    }
-}
-
+// ---------------------------------------------------------------------------- fused optimizers: the kernels are in optim_kernels.h
 extern "C" int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
                        bf_stream_t stream) {
     BF_REQUIRE(p && g && m && n > 0, "bf_lion: bad arguments");
     BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0), "bf_lion: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(lion_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, (hipStream_t)stream, p, g, m, (long)n, lr, beta1, beta2, wd, gscale);
-    BF_CHECK_LAUNCH();
-    return 0;
+    return opt_launch_lion<BF_OPT_HOST>(p, g, m, n, lr, beta1, beta2, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
                         float eps, float wd, float gscale, bf_stream_t stream) {
     BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adamw: bad arguments");
     BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adamw: buffers must be 16-byte aligned");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2, gscale);
-    BF_CHECK_LAUNCH();
-    return 0;
+    return opt_launch_adam<BF_OPT_HOST>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
                        float eps, float wd, float gscale, bf_stream_t stream) {
     BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adam: bad arguments");
     BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adam: buffers must be 16-byte aligned");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2, gscale);
-    BF_CHECK_LAUNCH();
-    return 0;
+    return opt_launch_adam<BF_OPT_HOST>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
 }

@@ -4,6 +4,9 @@ driving the native training step from device-resident clips.
 What is kept from the reference's run configuration:
   * one optimizer step per batch, `CosineWarmupLR` stepped per batch (``interval="step"``, modules.py:153-171) with
     ``max_iters = trainer.estimated_stepping_batches`` = max_epochs x batches per epoch (modules.py:63-68);
+  * `Trainer`'s ``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``accumulate_grad_batches`` (off by default, as there): with
+    accumulation the optimizer and the schedule step once per group of k batches and on an epoch's last batch, so
+    ``estimated_stepping_batches`` = max_epochs x ceil(batches per epoch / k);
   * ``limit_train_batches`` / ``limit_val_batches`` (train.py:167-168: 1000 / 25): an epoch is at most that many batches of a
     freshly shuffled pass over the dataset; validation runs after every epoch, unshuffled, no sanity pass (train.py:169);
   * the last, partial batch is kept (DataLoader's ``drop_last=False``);
@@ -19,7 +22,7 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from .trainer import TrainStep
+from .trainer import TrainStep, accumulation_plan
 from .utils.checkpoint import load_checkpoint, save_checkpoint
 from .utils.lr_schedulers import CosineWarmupLR
 
@@ -48,42 +51,61 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         weight_decay: float = 0.1, warmup_iters: Optional[int] = 1000, eta_min: float = 1e-6, limit_train_batches: Optional[int] = 1000,
         limit_val_batches: Optional[int] = 25, seed: int = 42, rank: int = 0, world: int = 1, checkpoint_path: Optional[str] = None,
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
-        criterion: Optional[Callable] = None) -> Dict:
+        criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+        accumulate_grad_batches: int = 1) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
     (config/optim_cfg/adamw.yaml: lr 2.5e-4 wd 1e-2; adam.yaml: lr 2.5e-4 wd 1e-5).  ``resume_from`` takes a file written here or by
     the reference's Lightning run (utils/checkpoint.py: load_checkpoint).  ``warmup_iters=None`` runs at a constant learning rate.  ``criterion``: None = the
     model's fused relative-L2 loss; or a callable (prediction, target) -> scalar tensor that training and validation both use (TrainStep).
-    Returns the history."""
+    ``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``accumulate_grad_batches``: see TrainStep.  The history and `log` keep one
+    loss and one learning rate per batch; with clipping by norm, ``hist["grad_norm"]`` holds the (unclipped) gradient norm of every
+    optimizer step, read from the device at the end of the epoch like the losses, and the `log` dict of a batch that stepped carries
+    it as a device scalar.  Returns the history."""
     dev = next(model.parameters()).device
     store = train_set.device_store(dev)
     vstore = val_set.device_store(dev) if val_set is not None else None
     conditioned = getattr(train_set, "return_fluid_params", False)
     per_epoch = len(batches(epoch_indices(len(train_set), 0, seed, True, rank, world), batch_size, limit_train_batches))
-    sched = CosineWarmupLR(lr, warmup_iters, max_epochs * per_epoch, eta_min) if warmup_iters is not None else None
-    step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion)
+    steps_per_epoch = accumulation_plan(per_epoch, accumulate_grad_batches)[1]
+    sched = CosineWarmupLR(lr, warmup_iters, max_epochs * steps_per_epoch, eta_min) if warmup_iters is not None else None
+    step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion,
+                     gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
+                     accumulate_grad_batches=accumulate_grad_batches)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
+    if step.grad_norm is not None:
+        hist["grad_norm"] = []
     first_epoch = 0
     if resume_from is not None:
         ck = load_checkpoint(resume_from, model, step)
         # an epoch-less file (written by an older version, or by save_checkpoint outside fit) resumes at the epoch its step count implies
-        first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(per_epoch, 1)
+        first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(steps_per_epoch, 1)
     for epoch in range(first_epoch, max_epochs):
         model.train()
-        losses = []
-        for bi, idx in enumerate(batches(epoch_indices(len(train_set), epoch, seed, True, rank, world), batch_size, limit_train_batches)):
+        losses, norms = [], []
+        todo = batches(epoch_indices(len(train_set), epoch, seed, True, rank, world), batch_size, limit_train_batches)
+        for bi, idx in enumerate(todo):
             got = store.gather(idx)
             x, y, c = (got[0], got[1], got[2]) if conditioned else (got[0], got[1], None)
             cur_lr = sched.get_last_lr()[0] if sched is not None else step.lr      # step.lr: a reference checkpoint brings its own
+            before = step.step_no
             loss = step(x, c, y)
+            if bi == len(todo) - 1:
+                step.finish_accumulation()      # an epoch's last batch completes its group, whatever the group holds
             losses.append(loss)
             hist["lr"].append(cur_lr)
+            entry = {"epoch": epoch, "batch_idx": bi, "global_step": step.step_no, "train_loss": loss, "learning_rate": cur_lr}
+            if step.grad_norm is not None and step.step_no != before:
+                norms.append(step.grad_norm[0].clone())      # the next step overwrites the pair
+                entry["grad_norm"] = norms[-1]
             if log is not None:
-                log({"epoch": epoch, "batch_idx": bi, "global_step": step.step_no, "train_loss": loss, "learning_rate": cur_lr})
+                log(entry)
         ep = torch.stack(losses).float()
         hist["train_loss"].extend(ep.tolist())
+        if norms:
+            hist["grad_norm"].extend(torch.stack(norms).tolist())
         hist["epoch_train_loss"].append(float(ep.mean()))
         if vstore is not None:
             hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion))

@@ -1011,31 +1011,82 @@ def kde_kl(p: torch.Tensor, q: torch.Tensor, points: int, eps: float, ws: torch.
             "bf_kde_kl")
 
 
+def grad_norm_workspace(n: int, device) -> torch.Tensor:
+    """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
+    return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)
+
+
+def grad_norm_(grad: torch.Tensor, out: torch.Tensor, max_norm: float, grad_scale: float = 1.0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[0] = grad_scale * ||grad||_2, out[1] = min(max_norm / (out[0] + 1e-6), 1): the norm and the clip coefficient of
+    torch.nn.utils.clip_grad_norm_ over a flat fp32 gradient buffer, left in device memory (`out`: two fp32) for the optimizers'
+    ``coef=``.  fp64 sums in a fixed order (csrc/gradclip.hip): the same bits on every call.  ws: grad_norm_workspace(grad.numel(),
+    device), allocated per call when None."""
+    _require_gpu(grad)
+    if grad.dtype != torch.float32 or not grad.is_contiguous() or grad.dim() != 1:
+        raise L.BubbleformerHipError("grad_norm_: grad must be a contiguous 1-D torch.float32 tensor")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 2 or out.device != grad.device:
+        raise L.BubbleformerHipError(f"grad_norm_: out must be a contiguous torch.float32 tensor of 2 elements on {grad.device}")
+    if ws is None:
+        ws = grad_norm_workspace(grad.numel(), grad.device)
+    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.device != grad.device:
+        raise L.BubbleformerHipError(f"grad_norm_: ws must be a contiguous torch.float64 tensor on {grad.device}")
+    L.check(L.lib().bf_grad_norm(_p(grad), grad.numel(), float(grad_scale), float(max_norm), _p(out), _p(ws), ws.numel(), _stream()), "bf_grad_norm")
+    return out
+
+
+def _coef_ptr(coef: Optional[torch.Tensor], p: torch.Tensor, who: str):
+    if coef is None:
+        return None
+    if coef.dtype != torch.float32 or coef.numel() != 1 or coef.device != p.device:
+        raise L.BubbleformerHipError(f"{who}: coef must be one torch.float32 element on {p.device} (e.g. grad_norm_'s out[1:])")
+    return coef.data_ptr()
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
-          grad_scale: float = 1.0) -> None:
-    """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140)."""
+          grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None) -> None:
+    """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140).  coef: one fp32 on the device
+    that multiplies grad_scale (grad_norm_'s out[1:]); clip_value: the scaled gradient is clamped to +-clip_value first
+    (torch.nn.utils.clip_grad_value_).  Both None: the host-scale kernel."""
     _require_gpu(p)
-    L.check(L.lib().bf_lion(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
-                            float(grad_scale), _stream()), "bf_lion")
+    if coef is None and clip_value is None:
+        L.check(L.lib().bf_lion(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
+                                float(grad_scale), _stream()), "bf_lion")
+    else:
+        L.check(L.lib().bf_lion_dev(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
+                                    float(grad_scale), _coef_ptr(coef, p, "lion_"), float("inf") if clip_value is None else float(clip_value),
+                                    _stream()), "bf_lion_dev")
     _weights_changed()
 
 
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
-           eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0) -> None:
-    """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136)."""
+           eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+           clip_value: Optional[float] = None) -> None:
+    """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value: see lion_."""
     _require_gpu(p)
-    L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                             float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
+    if coef is None and clip_value is None:
+        L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                 float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
+    else:
+        L.check(L.lib().bf_adamw_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adamw_"),
+                                     float("inf") if clip_value is None else float(clip_value), _stream()), "bf_adamw_dev")
     _weights_changed()
 
 
 def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
-          eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> None:
+          eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+          clip_value: Optional[float] = None) -> None:
     """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
-    weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay."""
+    weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay.  coef / clip_value: see lion_
+    (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step())."""
     _require_gpu(p)
-    L.check(L.lib().bf_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                            float(weight_decay), float(grad_scale), _stream()), "bf_adam")
+    if coef is None and clip_value is None:
+        L.check(L.lib().bf_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                float(weight_decay), float(grad_scale), _stream()), "bf_adam")
+    else:
+        L.check(L.lib().bf_adam_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                    float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"),
+                                    float("inf") if clip_value is None else float(clip_value), _stream()), "bf_adam_dev")
     _weights_changed()
 
 

@@ -8,12 +8,14 @@
                       issued per bucket as soon as backward has produced every gradient in it (debed first, then
                       blocks N-1 .. 0, then embed), overlapped with the rest of backward.  One process per GPU.
 * ``TrainStep``    -- forward (+ fused relative-L2 loss, or a caller's criterion on the prediction) -> backward -> bucket wait ->
-                      fused AdamW / Adam / Lion.
+                      [gradient norm and clip coefficient, on the device] -> fused AdamW / Adam / Lion; with
+                      ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only.
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
+import contextlib
 import os
 
 import torch
@@ -70,6 +72,7 @@ class BucketReducer:
         self.handles = []
         self.held = None          # direct-gradient mode: a complete bucket waits until the NEXT one is complete (see stage_ready)
         self.enabled = self.world > 1
+        self.sync = True          # False inside no_sync(): gradients accumulate locally, nothing is counted, launched or held
         self.done = set()         # buckets reduced in this step
         if self.enabled and use_hooks:
             for p, b in zip(flat.params, bucket_of):
@@ -87,7 +90,20 @@ class BucketReducer:
         else:
             self.handles.append((dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group, async_op=True), None, None))
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """A backward under this context launches no collective (DistributedDataParallel.no_sync, which Lightning enters on the
+        micro-batches of ``accumulate_grad_batches`` that do not step): its gradients stay in the flat buffer, and the next backward
+        outside the context reduces the sum."""
+        was, self.sync = self.sync, False
+        try:
+            yield
+        finally:
+            self.sync = was
+
     def _arrived(self, b, hold=False):
+        if not self.sync:
+            return
         self.pending[b] += 1
         if self.pending[b] == self.count[b]:
             self.pending[b] = 0
@@ -155,6 +171,17 @@ def stage_buckets(model: nn.Module, blocks_per_bucket: Optional[int] = None) -> 
     return ids
 
 
+def accumulation_plan(per_epoch: int, k: int) -> Tuple[List[int], int]:
+    """(batch indices of an epoch of `per_epoch` batches after which the optimizer steps under ``accumulate_grad_batches=k``, their number):
+    every k-th batch, and the epoch's last batch whatever the group holds -- ceil(per_epoch / k) steps per epoch, which is what
+    Lightning's ``estimated_stepping_batches`` counts."""
+    if per_epoch < 0 or k < 1:
+        raise ValueError(f"accumulation_plan: per_epoch {per_epoch} must be >= 0 and accumulate_grad_batches {k} >= 1")
+    steps = [i for i in range(per_epoch) if (i + 1) % k == 0 or i == per_epoch - 1]
+    assert len(steps) == -(-per_epoch // k)
+    return steps, len(steps)
+
+
 class TrainStep:
     """optimizer: "adamw" (config/optim_cfg/adamw.yaml; modules.py:135-136), "adam" (config/optim_cfg/adam.yaml, torch.optim.Adam
     with its L2 weight decay; modules.py:137-138) or "lion" (config/optim_cfg/lion.yaml, the reference default; modules.py:139-140).
@@ -162,13 +189,30 @@ class TrainStep:
     object with get_last_lr() / step() (utils.lr_schedulers.CosineWarmupLR), stepped once per optimizer step like the reference's
     ``interval="step"`` (modules.py:166-171).  criterion: None = the model's fused forward_loss (relative L2 as configured at
     modules.py:50); or a callable (prediction, target) -> scalar tensor, e.g. utils.losses.LpLoss(...) plus a physics penalty: the step
-    then runs model(x[, fluid]), the criterion and loss.backward() through the same gradient slots and bucket reducer."""
+    then runs model(x[, fluid]), the criterion and loss.backward() through the same gradient slots and bucket reducer.
+    gradient_clip_val / gradient_clip_algorithm / accumulate_grad_batches: Lightning's `Trainer` arguments of those names.
+      * "norm": the averaged gradient (after the bucket exchange, so identical on every rank) is scaled by
+        min(gradient_clip_val / (its 2-norm + 1e-6), 1) -- torch.nn.utils.clip_grad_norm_.  Norm and coefficient are computed on the
+        device into ``self.grad_norm`` (two fp32: {norm, coef} of the last optimizer step) and the optimizer kernel reads the coefficient
+        from there: no host synchronisation.  "value": every element is clamped to +-gradient_clip_val (clip_grad_value_).
+        None (or 0) = off: the step launches what it launched without these arguments.
+      * accumulate_grad_batches = k: a call that does not complete a group of k only adds its gradient to the flat buffer (no
+        zero_grad, no collective -- BucketReducer.no_sync -- no optimizer, no scheduler step); the completing call exchanges the
+        buckets, applies 1/(world*k) and steps once.  ``step_no`` counts optimizer steps.  finish_accumulation() steps on a partial
+        group with the same factor, as Lightning does on an epoch's last batch."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
-                 optimizer: str = "adamw", scheduler=None, criterion=None):
+                 optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1):
         from . import ops
         if optimizer not in ("adamw", "adam", "lion"):
             raise ValueError(f"Optimizer {optimizer} not supported")
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r} not supported: 'norm' or 'value'")
+        if gradient_clip_val is not None and not gradient_clip_val >= 0:
+            raise ValueError(f"gradient_clip_val {gradient_clip_val!r} must be None or >= 0")
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches {accumulate_grad_batches!r} must be an integer >= 1")
         self.ops = ops
         self.model = model
         self.flat = FlatParams(model)
@@ -183,6 +227,15 @@ class TrainStep:
         self.scheduler = scheduler
         self.criterion = criterion
         self.step_no = 0
+        self.clip_val = float(gradient_clip_val) if gradient_clip_val else None      # Lightning: None and 0 both mean no clipping
+        self.clip_algorithm = gradient_clip_algorithm
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.micro = 0            # micro-batches whose gradient is pending in the flat buffer
+        self.grad_norm = None     # "norm" clipping: device {norm, coef} of the last optimizer step
+        if self.clip_val is not None and gradient_clip_algorithm == "norm":
+            self.grad_norm = torch.zeros(2, dtype=torch.float32, device=self.flat.flat.device)
+            self._coef = self.grad_norm[1:]
+            self._norm_ws = None
         self.sync_from_rank0()
 
     def sync_from_rank0(self) -> None:
@@ -201,27 +254,53 @@ class TrainStep:
         ops._weights_changed()           # the broadcast wrote the flat buffer behind the parameters' version counters: prepared inference weights are stale
 
     def __call__(self, x, fluid, target) -> torch.Tensor:
-        self.flat.zero_grad()
+        final = self.micro + 1 >= self.accumulate_grad_batches
+        if self.micro == 0:
+            self.flat.zero_grad()
         self.reducer.begin_step()
         self.ops.set_direct_grad_slots(self.slots, self.reducer.stage_ready, self.reducer.flush)
         self.ops.set_side_defer(True)       # a stage's weight-gradient GEMMs may run into the next stage; joined below
         try:
-            loss = self._fwd_bwd(x, fluid, target)
+            with contextlib.nullcontext() if final else self.reducer.no_sync():
+                loss = self._fwd_bwd(x, fluid, target)
         finally:
             self.ops.set_side_defer(False)
             self.ops.set_direct_grad_slots(None)
-        gscale = self.reducer.wait()
+        self.micro += 1
+        if final:
+            self._optimizer_step()
+        return loss.detach()
+
+    def finish_accumulation(self) -> bool:
+        """Step on the gradient of a partial group (an epoch's last batches), with the full group's 1/(world*k); nothing to do when no
+        gradient is pending.  The pending micro-batches ran without collectives, so every bucket is exchanged here.  -> stepped or not"""
+        if self.micro == 0:
+            return False
+        self.reducer.begin_step()
+        self._optimizer_step()
+        return True
+
+    def _optimizer_step(self) -> None:
+        gscale = self.reducer.wait() / self.accumulate_grad_batches
+        self.micro = 0
         self.step_no += 1
         lr = self.scheduler.get_last_lr()[0] if self.scheduler is not None else self.lr
+        clip = {}
+        if self.grad_norm is not None:
+            if self._norm_ws is None:
+                self._norm_ws = self.ops.grad_norm_workspace(self.flat.numel, self.flat.grad.device)
+            self.ops.grad_norm_(self.flat.grad, self.grad_norm, self.clip_val, gscale, self._norm_ws)
+            clip = {"coef": self._coef}
+        elif self.clip_val is not None:
+            clip = {"clip_value": self.clip_val}
         if self.optimizer == "adamw":
-            self.ops.adamw_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale)
+            self.ops.adamw_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale, **clip)
         elif self.optimizer == "adam":
-            self.ops.adam_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale)
+            self.ops.adam_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale, **clip)
         else:
-            self.ops.lion_(self.flat.flat, self.flat.grad, self.m, lr, self.betas, self.wd, gscale)
+            self.ops.lion_(self.flat.flat, self.flat.grad, self.m, lr, self.betas, self.wd, gscale, **clip)
         if self.scheduler is not None:
             self.scheduler.step()
-        return loss.detach()
 
     def _fwd_bwd(self, x, fluid, target):
         if self.criterion is None:

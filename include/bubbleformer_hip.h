@@ -35,6 +35,7 @@
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
+ *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
 #ifndef BUBBLEFORMER_HIP_H
 #define BUBBLEFORMER_HIP_H
@@ -429,6 +430,26 @@ int bf_eikonal_bwd(const float* phi, int64_t frames, int H, int W, float dx, con
 /* Lion: p *= 1 - lr*wd; p -= lr*sign(beta1*m + (1-beta1)*g); m = beta2*m + (1-beta2)*g   (g is multiplied by gscale first) */
 int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
             bf_stream_t stream);
+/* Gradient clipping without a host round trip (csrc/gradclip.hip).
+ * bf_grad_norm: out = {norm, coef} (two fp32 in DEVICE memory) of the flat gradient buffer g[n] (fp32, 16-byte aligned, n > 0):
+ *   norm = gscale * sqrt(sum g^2)   squares and sums in fp64, rounded once to fp32; gscale = the factor the optimizer applies to g
+ *   coef = min(max_norm / (norm + 1e-6), 1)   in fp32, IEEE divide; a NaN norm gives a NaN coefficient
+ * i.e. torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False).  A fixed-order two-pass reduction, no float atomics: the
+ * buffer is cut into slabs by a rule that depends on n only, one fp64 partial per slab in ws (at least bf_grad_norm_ws_doubles(n)
+ * doubles, 8-byte aligned, at most 1024), which one workgroup then adds in slab order.  Two calls on one buffer give the same bits on
+ * any device.  max_norm <= 0 or a null out is an error. */
+int64_t bf_grad_norm_ws_doubles(int64_t n);
+int bf_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* out, double* ws, int64_t ws_doubles, bf_stream_t stream);
+/* bf_adamw / bf_adam / bf_lion with the gradient scale completed on the device: the effective gradient is (gscale * coef_dev[0]) * g[i]
+ * (coef_dev = one fp32 in DEVICE memory, e.g. bf_grad_norm's out + 1; NULL = 1), clamped to [-clip_value, clip_value] before any use
+ * (clip_value > 0; +inf = off; a NaN stays a NaN).  Same kernel bodies as the host-scale entry points: with coef_dev[0] == 1.0f and
+ * clip_value = +inf they produce the same bits. */
+int bf_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                 float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream);
+int bf_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream);
+int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
+                const float* coef_dev, float clip_value, bf_stream_t stream);
 
 /* ---------------------------------------------------------------- stage-level entry points (what the nn.Modules call) */
 
