@@ -175,6 +175,11 @@ SIGNATURES = {
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_kde_kl_ws_doubles": (i64, [C.c_int, i64, i64, C.c_int]),
     "bf_kde_kl": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, vp]),
+    "bf_bubble_census_lds_cells": (i64, []),
+    "bf_bubble_census_ws_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
+    "bf_bubble_census": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, fp, vp, vp, vp, i64, vp]),
+    "bf_rollout_bubbles": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_lp_rows_ws_doubles": (i64, [i64, i64]),
     "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
     "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),

@@ -167,6 +167,14 @@ template <typename T> __device__ __forceinline__ float dgelu_t(float x) { if con
 // Source index of F.interpolate(mode="nearest"): floor(dst * float(in / out)) clamped to in - 1 (identity at full resolution)
 __device__ __forceinline__ int nearest_src(int dst, float scale, int n, bool ident) { return ident ? dst : min((int)floorf((float)dst * scale), n - 1); }
 
+// pred * div + diff as torch forms it: an fp32 product, rounded, then an fp32 sum (contraction off: never one fused operation).  The physical
+// field the rollout's heat-flux rows (physics.hip) and bubble census (bubbles.hip) see
+__device__ __forceinline__ float denormalise(float v, float q, float d) {
+#pragma clang fp contract(off)
+    const float prod = v * q;
+    return prod + d;
+}
+
 // ---------------------------------------------------------------- wave / block reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

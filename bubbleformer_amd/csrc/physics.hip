@@ -33,13 +33,7 @@ struct HeatfluxArgs {
     int B, T, C, H, W, Ho, Wo, steps;
 };
 
-// pred * div + diff as torch forms it: an fp32 product, rounded, then an fp32 sum (contraction off: never one fused operation)
-__device__ __forceinline__ float denormalise(float v, float q, float d) {
-#pragma clang fp contract(off)
-    const float prod = v * q;
-    return prod + d;
-}
-
+// (denormalise, pred * div + diff as torch forms it, lives in bf_common.h: bubbles.hip de-normalises the same way)
 __global__ void __launch_bounds__(64) rollout_heatflux_kernel(HeatfluxArgs a) {
     const int s = *a.step;
     if (s < 0 || s >= a.steps) return;                                     // behind the last row: nothing is written

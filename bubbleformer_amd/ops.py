@@ -1011,6 +1011,85 @@ def kde_kl(p: torch.Tensor, q: torch.Tensor, points: int, eps: float, ws: torch.
             "bf_kde_kl")
 
 
+def bubble_census_workspace(frames: int, H: int, W: int, max_bubbles: int, device) -> torch.Tensor:
+    """The workspace ``bubble_census`` (and, with frames = 2 * B * T, ``rollout_bubbles``) needs: allocate once, outside a graph capture.  A frame
+    larger than the library supports is refused here, before any launch."""
+    nbytes = L.lib().bf_bubble_census_ws_bytes(int(frames), int(H), int(W), int(max_bubbles))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"bubble_census_workspace: {frames} frames of {H} x {W} with {max_bubbles} records are not supported "
+                                     "(every size at least 1, at most 2^24 cells per frame)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def bubble_census_lds_cells() -> int:
+    """Frames of at most this many cells are labelled in LDS, larger ones in the workspace (bf_bubble_census_lds_cells)."""
+    return int(L.lib().bf_bubble_census_lds_cells())
+
+
+def bubble_census(phi: torch.Tensor, connectivity: int, max_bubbles: int, ws: torch.Tensor, count: torch.Tensor, vapour_cells: torch.Tensor,
+                  attached: torch.Tensor, area: torch.Tensor, centroid: Optional[torch.Tensor] = None, on_heater: Optional[torch.Tensor] = None,
+                  labels: Optional[torch.Tensor] = None) -> None:
+    """The connected components of phi > 0 of every frame of phi (F, H, W) fp32 (bf_bubble_census; include/bubbleformer_hip.h has the contract):
+    count / vapour_cells / attached (F,) int32, area (F, max_bubbles) int32, and optionally centroid (F, max_bubbles, 2) fp32, on_heater
+    (F, max_bubbles) bool and the label image (F, H, W) int32.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(phi)
+    if phi.dim() != 3 or phi.dtype != torch.float32 or not phi.is_contiguous():
+        raise L.BubbleformerHipError("bubble_census: phi must be a contiguous fp32 (frames, H, W) tensor")
+    F, H, W = phi.shape
+    mb = int(max_bubbles)
+    want = {"count": (count, (F,), torch.int32), "vapour_cells": (vapour_cells, (F,), torch.int32), "attached": (attached, (F,), torch.int32),
+            "area": (area, (F, mb), torch.int32), "centroid": (centroid, (F, mb, 2), torch.float32), "on_heater": (on_heater, (F, mb), torch.bool),
+            "labels": (labels, (F, H, W), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)}
+    for name, (t, shape, dtype) in want.items():
+        if name in ("centroid", "on_heater", "labels") and t is None:
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != phi.device:
+            raise L.BubbleformerHipError(f"bubble_census: {name} must be a contiguous {dtype} tensor of shape {shape} on {phi.device}")
+    need = L.lib().bf_bubble_census_ws_bytes(F, H, W, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("bubble_census: the workspace is smaller than bubble_census_workspace(frames, H, W, max_bubbles)")
+    L.check(L.lib().bf_bubble_census(_p(phi), F, H, W, int(connectivity), mb, _p(count), _p(vapour_cells), _p(attached), _p(area), _p(centroid),
+                                     _p(on_heater), _p(labels), _p(ws), ws.numel(), _stream()), "bf_bubble_census")
+
+
+def rollout_bubbles(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
+                    connectivity: int, max_bubbles: int, ws: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor, cells_pred: torch.Tensor,
+                    cells_tgt: torch.Tensor, attached_pred: torch.Tensor, attached_tgt: torch.Tensor, area_pred: torch.Tensor,
+                    area_tgt: torch.Tensor) -> None:
+    """The bubble census of one rollout step (bf_rollout_bubbles; include/bubbleformer_hip.h has the contract): row s * T + t of the int32 outputs
+    count / cells / attached (B, steps*T) and area (B, steps*T, max_bubbles), for the de-normalised signed-distance channel of the prediction
+    (_pred) and for the stored frame ``first[b] + (s + 1) * T + t`` (_tgt), s = the int32 ``step`` tensor ON THE DEVICE, which this call only
+    reads -- issue it BEFORE the step's ``rollout_score``.  ws: ``bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)``.  Allocates nothing."""
+    _require_gpu(pred)
+    ids, diff, div = table
+    nf, total, H, W = frames.shape
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise L.BubbleformerHipError("rollout_bubbles: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
+    B, T, Cn, Ho, Wo = pred.shape
+    mb = int(max_bubbles)
+    rows, recs = (B, steps * T), (B, steps * T, mb)
+    want = {"count_pred": (count_pred, rows, torch.int32), "count_tgt": (count_tgt, rows, torch.int32), "cells_pred": (cells_pred, rows, torch.int32),
+            "cells_tgt": (cells_tgt, rows, torch.int32), "attached_pred": (attached_pred, rows, torch.int32),
+            "attached_tgt": (attached_tgt, rows, torch.int32), "area_pred": (area_pred, recs, torch.int32), "area_tgt": (area_tgt, recs, torch.int32),
+            "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)}
+    for name, (t, shape, dtype) in want.items():
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device:
+            raise L.BubbleformerHipError(f"rollout_bubbles: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
+    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.device != pred.device:
+        raise L.BubbleformerHipError(f"rollout_bubbles: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
+    if ids.numel() != Cn:
+        raise L.BubbleformerHipError(f"rollout_bubbles: the field table has {ids.numel()} channels, the prediction {Cn}")
+    if not 0 <= int(sdf_channel) < Cn:
+        raise L.BubbleformerHipError(f"rollout_bubbles: channel {sdf_channel} is not among the prediction's {Cn}")
+    need = L.lib().bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_bubbles: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
+    L.check(L.lib().bf_rollout_bubbles(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(sdf_channel),
+                                       int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt), _p(attached_pred),
+                                       _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(ws), ws.numel(), B, T, Cn, H, W, Ho, Wo, int(steps), _stream()),
+            "bf_rollout_bubbles")
+
+
 def grad_norm_workspace(n: int, device) -> torch.Tensor:
     """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
     return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)

@@ -1,6 +1,7 @@
 """Physics metrics of a rollout, on the device (reference: bubbleformer/utils/losses.py:5-15, bubbleformer/utils/heatflux.py)."""
 import ctypes as C
 import dataclasses
+import math
 from typing import Optional, Sequence, Union
 
 import torch
@@ -127,3 +128,85 @@ def kde_kl_divergence(sim: torch.Tensor, model: torch.Tensor, points: int = 1000
     if not return_pdfs:
         return kl[0] if single else kl
     return (kl[0],) + tuple(t[0] for t in extra) if single else (kl,) + extra
+
+
+@dataclasses.dataclass(frozen=True)
+class BubbleSpec:
+    """The bubble census of a rollout (``evaluate_rollouts(..., bubbles=BubbleSpec())``): which output field is the signed distance, how cells
+    connect (4: edges, 8: edges and corners), how many per-bubble records a frame keeps, and the cell size for the equivalent diameters."""
+    sdf_field: str = "dfun"
+    connectivity: int = 4
+    max_bubbles: int = 256
+    dx: float = 1.0 / 32
+
+    def __post_init__(self):
+        _check_census_arguments(self.connectivity, self.max_bubbles)
+        if not self.dx > 0:
+            raise ValueError(f"dx must be positive, got {self.dx}")
+
+    def channel(self, fields: Sequence[str]) -> int:
+        """The signed-distance channel among the output fields."""
+        fields = list(fields)
+        if self.sdf_field not in fields:
+            raise ValueError(f"the bubble census needs the field {self.sdf_field!r} among the output fields {fields}")
+        return fields.index(self.sdf_field)
+
+
+def _check_census_arguments(connectivity, max_bubbles) -> None:
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if int(max_bubbles) != max_bubbles or int(max_bubbles) < 1:
+        raise ValueError(f"max_bubbles must be an integer of at least 1, got {max_bubbles!r}")
+
+
+def equivalent_diameter(area: torch.Tensor, dx: float = 1.0 / 32) -> torch.Tensor:
+    """The diameter of the disc of a bubble's area, 2 * sqrt(area * dx^2 / pi) in fp32; 0 where the area is 0 (an unused slot)."""
+    return 2.0 * torch.sqrt(area.to(torch.float32) * (float(dx) * float(dx) / math.pi))
+
+
+@dataclasses.dataclass
+class BubbleCensus:
+    """What ``bubble_census`` returns; every tensor is on the device and keeps phi's leading dims.  The bubbles of a frame are numbered in raster
+    order of their first cell (scipy.ndimage.label's numbering); slot k of the records is bubble k + 1, slots behind the last bubble are 0."""
+    count: torch.Tensor                             # (...)                 int32: components of the frame, also above max_bubbles
+    vapour_cells: torch.Tensor                      # (...)                 int32: cells with phi > 0
+    attached: torch.Tensor                          # (...)                 int32: components with a cell in row 0 (the heater row)
+    area: torch.Tensor                              # (..., max_bubbles)    int32 cells
+    centroid: torch.Tensor                          # (..., max_bubbles, 2) fp32 (y, x) in cells
+    on_heater: torch.Tensor                         # (..., max_bubbles)    bool
+    shape: tuple                                    # (H, W)
+    labels: Optional[torch.Tensor] = None           # (..., H, W)           int32, 0 = liquid, if asked for
+
+    def vapour_fraction(self) -> torch.Tensor:
+        """vapour_cells / (H * W): the quotient in fp64, rounded once to fp32."""
+        return (self.vapour_cells.to(torch.float64) / float(self.shape[0] * self.shape[1])).to(torch.float32)
+
+    def equivalent_diameter(self, dx: float = 1.0 / 32) -> torch.Tensor:
+        """(..., max_bubbles) fp32: 2 * sqrt(area * dx^2 / pi) of every record, 0 in unused slots."""
+        return equivalent_diameter(self.area, dx)
+
+
+def bubble_census(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int = 256, return_labels: bool = False) -> BubbleCensus:
+    """The bubbles of every frame of phi (..., H, W), a signed-distance field in physical units on the device.  Vapour is phi > 0: an exact
+    zero and a NaN count as liquid.  A bubble is a connected component of vapour cells under ``connectivity`` 4 (edges) or 8 (edges and
+    corners); row 0 is the heater row.  One launch, a workgroup per frame (``ops.bubble_census``); never synchronises; the same bits on every
+    call, and for a frame alone or in a batch.  A frame of more than 2^24 cells raises ``BubbleformerHipError`` before any launch."""
+    _check_census_arguments(connectivity, max_bubbles)
+    if phi.dim() < 2:
+        raise ValueError(f"bubble_census expects (..., H, W), got {tuple(phi.shape)}")
+    from .. import ops
+    _require_gpu(phi)
+    lead, (H, W) = tuple(phi.shape[:-2]), phi.shape[-2:]
+    mb = int(max_bubbles)
+    flat = phi.reshape(-1, H, W).contiguous().float()
+    F = flat.shape[0]
+    if F < 1 or H < 1 or W < 1:
+        raise ValueError(f"bubble_census needs at least one frame of at least one cell, got {tuple(phi.shape)}")
+    ws = ops.bubble_census_workspace(F, H, W, mb, flat.device)
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=flat.device)
+    count, cells, attached, area = new(torch.int32, F), new(torch.int32, F), new(torch.int32, F), new(torch.int32, F, mb)
+    centroid, on_heater = new(torch.float32, F, mb, 2), new(torch.bool, F, mb)
+    labels = new(torch.int32, F, H, W) if return_labels else None
+    ops.bubble_census(flat, int(connectivity), mb, ws, count, cells, attached, area, centroid, on_heater, labels)
+    return BubbleCensus(count.reshape(lead), cells.reshape(lead), attached.reshape(lead), area.reshape(lead + (mb,)), centroid.reshape(lead + (mb, 2)),
+                        on_heater.reshape(lead + (mb,)), (int(H), int(W)), labels.reshape(lead + (int(H), int(W))) if labels is not None else None)

@@ -129,6 +129,15 @@ class RolloutReport:
     predictions: Optional[torch.Tensor] = None      # (B, steps*T, C, Ho, Wo) if kept
     heatflux_pred: Optional[torch.Tensor] = None    # (B, steps*T)     heater heat flux of every predicted frame (utils/heatflux.py), or None
     heatflux_target: Optional[torch.Tensor] = None  # (B, steps*T)     the same of the simulated one
+    bubble_count_pred: Optional[torch.Tensor] = None        # (B, steps*T) int32   bubbles of every predicted frame (physics.bubble_census), or None
+    bubble_count_target: Optional[torch.Tensor] = None      # (B, steps*T) int32   the same of the simulated one
+    bubble_attached_pred: Optional[torch.Tensor] = None     # (B, steps*T) int32   those with a cell in the heater row
+    bubble_attached_target: Optional[torch.Tensor] = None
+    vapour_fraction_pred: Optional[torch.Tensor] = None     # (B, steps*T) fp32    vapour cells / all cells
+    vapour_fraction_target: Optional[torch.Tensor] = None
+    bubble_area_pred: Optional[torch.Tensor] = None         # (B, steps*T, max_bubbles) int32 cells, in raster order of the first cell, then 0
+    bubble_area_target: Optional[torch.Tensor] = None
+    bubble_dx: Optional[float] = None                       # the cell size of the census' BubbleSpec (for the equivalent diameters)
 
     def save(self, path) -> None:
         """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
@@ -139,6 +148,9 @@ class RolloutReport:
             out["eikonal_pred"], out["eikonal_target"] = self.eikonal_pred, self.eikonal_target
         if self.heatflux_pred is not None:
             out["heatflux_pred"], out["heatflux_target"] = self.heatflux_pred, self.heatflux_target
+        if self.bubble_count_pred is not None:
+            for key in _BUBBLE_KEYS:
+                out[key] = getattr(self, key)
         torch.save(out, path)
 
     def _heatfluxes(self):
@@ -159,6 +171,38 @@ class RolloutReport:
         sim, model = self._heatfluxes()
         torch.save({"sim_hf": sim.reshape(-1).float().cpu(), "model_hf": model.reshape(-1).float().cpu()}, path)
 
+    def _bubbles(self):
+        if self.bubble_count_pred is None:
+            raise ValueError("this report has no bubble census: call evaluate_rollouts(..., bubbles=BubbleSpec(...))")
+
+    def vapour_drift(self) -> torch.Tensor:
+        """(B, steps*T) fp32: (predicted - simulated) / simulated vapour fraction of every frame, the mass-conservation curve (inf or NaN
+        where the simulated frame has no vapour).  On the device; never synchronises."""
+        self._bubbles()
+        return (self.vapour_fraction_pred - self.vapour_fraction_target) / self.vapour_fraction_target
+
+    def bubble_diameters(self, dx: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(simulation, model): the equivalent diameters 2 * sqrt(area * dx^2 / pi) of all recorded bubbles of all frames and trajectories, each
+        a 1-D fp32 device tensor in report order.  SYNCHRONISES: dropping the empty slots makes the host wait for their number."""
+        from .physics import equivalent_diameter
+        self._bubbles()
+        dx = self.bubble_dx if dx is None else dx
+        return tuple(equivalent_diameter(a[a > 0], dx) for a in (self.bubble_area_target, self.bubble_area_pred))
+
+    def bubble_size_kl(self, points: int = 1000) -> torch.Tensor:
+        """KL(simulation || model) of the bubble-size distributions: ``physics.kde_kl_divergence`` of ``bubble_diameters()``, a 0-d fp64 device
+        tensor.  NaN when either side has fewer than two recorded bubbles (a model that predicts no vapour: a density needs two samples), as
+        it is for a side whose bubbles all have one size.  Synchronises as ``bubble_diameters`` does."""
+        from .physics import kde_kl_divergence
+        sim, model = self.bubble_diameters()
+        if sim.numel() < 2 or model.numel() < 2:
+            return torch.full((), float("nan"), dtype=torch.float64, device=sim.device)
+        return kde_kl_divergence(sim, model, points)
+
+
+_BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
+                "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
+
 
 def _to_device(values, dtype, device) -> torch.Tensor:
     host = torch.as_tensor(values, dtype=dtype)
@@ -166,7 +210,8 @@ def _to_device(values, dtype, device) -> torch.Tensor:
 
 
 def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
-                      keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.HeaterSpec)
+                      keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None,  # noqa: F821 (physics.HeaterSpec)
+                      bubbles: "Optional[BubbleSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.BubbleSpec)
     """Roll ``model`` out over ``B = len(starts)`` test trajectories at once and score every predicted frame against the simulation.
 
     data: a ``BubbleForecast`` (its device store is made on the model's device) or a ``DeviceClipStore``; starts: dataset sample indices.
@@ -176,7 +221,9 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     no other host work between replays; without, the same two calls run eagerly and give the same bits.  A model whose ``forward`` takes
     ``fluid_params`` gets the store's fluid row of each trajectory's file.  With ``heatflux`` (a ``physics.HeaterSpec``) the step also leaves
     the heater heat flux of every predicted and simulated frame (``ops.rollout_heatflux``, issued right before the scoring call and captured
-    with it); ``None`` leaves the launches and the report as they are without it.  Never synchronises."""
+    with it); ``None`` leaves the launches and the report as they are without it.  With ``bubbles`` (a ``physics.BubbleSpec``) the step
+    likewise leaves the bubble census of every predicted and simulated frame (``ops.rollout_bubbles``, one more launch before the scoring
+    call): the ``bubble_*`` and ``vapour_fraction_*`` rows of the report.  Never synchronises."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
@@ -210,6 +257,13 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         heater = _to_device(heatflux.temperatures(plan.files, len(ds.traj_lens)), torch.float32, device)
         hf_p, hf_t = new(B, steps * T), new(B, steps * T)
         hf_args = (*hf_channels, heater, steps, hf_p, hf_t, heatflux.x_min, heatflux.dx, heatflux.lc, heatflux.conductivity)
+    bub = bub_args = None
+    if bubbles is not None:
+        mb = int(bubbles.max_bubbles)
+        rows = lambda *tail: [torch.empty((B, steps * T) + tail, dtype=torch.int32, device=device) for _ in range(2)]
+        bub = {"count": rows(), "cells": rows(), "attached": rows(), "area": rows(mb)}
+        bub_args = (bubbles.channel(fields), steps, int(bubbles.connectivity), mb, ops.bubble_census_workspace(2 * B * T, Ho, Wo, mb, device),
+                    *bub["count"], *bub["cells"], *bub["attached"], *bub["area"])
 
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
@@ -218,6 +272,8 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
             raise ValueError(f"the model returned {tuple(pred.shape)} for an input of {tuple(x.shape)}: it cannot be fed back")
         if hf_args is not None:                     # reads the step counter the scoring call then advances
             ops.rollout_heatflux(pred, store.frames, first, step, store.out_tab, *hf_args)
+        if bub_args is not None:                    # likewise
+            ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args)
         ops.rollout_score(pred, store.frames, first, step, store.out_tab, sdf, steps, rel_l2, criterion, ws, eik_p, eik_t, next_in, arch)
 
     model.eval()
@@ -241,4 +297,12 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         else:
             for _ in range(steps):
                 score(model(x, *extra), counter, x, archive)
-    return RolloutReport(rel_l2, criterion, eik_p, eik_t, plan.timesteps.to(device, non_blocking=True), fields, archive, hf_p, hf_t)
+    report = RolloutReport(rel_l2, criterion, eik_p, eik_t, plan.timesteps.to(device, non_blocking=True), fields, archive, hf_p, hf_t)
+    if bub is not None:
+        fraction = lambda cells: (cells.to(torch.float64) / float(Ho * Wo)).to(torch.float32)       # the quotient in fp64, rounded once
+        report.bubble_count_pred, report.bubble_count_target = bub["count"]
+        report.bubble_attached_pred, report.bubble_attached_target = bub["attached"]
+        report.vapour_fraction_pred, report.vapour_fraction_target = (fraction(c) for c in bub["cells"])
+        report.bubble_area_pred, report.bubble_area_target = bub["area"]
+        report.bubble_dx = float(bubbles.dx)
+    return report

@@ -34,6 +34,7 @@
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
+ *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
@@ -410,6 +411,38 @@ int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_st
 int64_t bf_kde_kl_ws_doubles(int R, int64_t n, int64_t m, int points);
 int bf_kde_kl(const double* p, const double* q, int R, int64_t n, int64_t m, int points, double eps, double* kl, double* x, double* pdf_p,
               double* pdf_q, double* ws, int64_t ws_doubles, bf_stream_t stream);
+/* The bubble census of `frames` fields phi [frames][H][W] fp32 in physical units (csrc/bubbles.hip; the reference has no program for it).  Vapour is
+ * phi > 0: an exact zero and a NaN are liquid.  A bubble is a connected component of vapour cells under connectivity 4 or 8; the bubbles of a frame
+ * are numbered 1, 2, ... in raster order of their first cell (smallest y * W + x), which is scipy.ndimage.label's numbering.  Per frame:
+ *   count [frames] int32         the number of components, also above max_bubbles; -1 if a bounded loop of the kernel ran out (a corrupted run);
+ *   vapour_cells [frames] int32  the number of vapour cells;
+ *   attached [frames] int32      the number of components with a cell in row 0 (the heater row); they are the first `attached` of the numbering;
+ *   area [frames][max_bubbles] int32, centroid [frames][max_bubbles][2] fp32 (y, x), on_heater [frames][max_bubbles] bytes: the first max_bubbles
+ *                                components in that order, unused slots 0; a centroid is the quotient of exact integer sums, one fp64 division
+ *                                rounded once to fp32; centroid and on_heater are optional (null: not written);
+ *   labels [frames][H][W] int32  optional: the label image, 0 = liquid.
+ * One workgroup owns a frame; integer atomics only: the same bits on every call, and a frame has the same bits alone and in a batch.  Allocation-free,
+ * capturable, never makes the host wait.  Any H, W >= 1 with H * W <= 2^24 (refused beyond, before any launch).  Frames of at most
+ * bf_bubble_census_lds_cells() cells keep the union-find's parents in LDS, larger ones in the workspace.
+ * ws: bf_bubble_census_ws_bytes(frames, H, W, max_bubbles) bytes, 16-byte aligned (0 from the query: sizes out of range). */
+int64_t bf_bubble_census_lds_cells(void);
+int64_t bf_bubble_census_ws_bytes(int64_t frames, int H, int W, int max_bubbles);
+int bf_bubble_census(const float* phi, int64_t frames, int H, int W, int connectivity, int max_bubbles, int32_t* count, int32_t* vapour_cells,
+                     int32_t* attached, int32_t* area, float* centroid, unsigned char* on_heater, int32_t* labels, void* ws, int64_t ws_bytes,
+                     bf_stream_t stream);
+/* The bubble census of ONE rollout step, of the prediction and of the simulation in one call.  pred, frames, field_stride, total_frames, nfields,
+ * first, field / diff / div and the sizes are bf_rollout_score's.  step = one int32 in DEVICE memory, READ and never written: issue the call BEFORE
+ * the step's bf_rollout_score.  With s = *step, row s * T + t of trajectory b of count_* / cells_* / attached_* [B][steps*T] and of
+ * area_* [B][steps*T][max_bubbles] is bf_bubble_census' count / vapour_cells / attached / area of
+ *   *_pred: pred * div + diff of channel sdf_channel (fp32 multiply, then add, unfused), frame t of trajectory b;
+ *   *_tgt:  the stored raw frame first[b] + (s + 1) * T + t (clamped into the store) of field field[sdf_channel] (clamped likewise), through
+ *           bf_clip_gather's nearest-neighbour map when Ho x Wo < H x W: the grid the model sees.
+ * With s outside [0, steps) nothing is written.  ws: bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, max_bubbles) bytes, 16-byte aligned. */
+int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                       const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
+                       int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt, int32_t* attached_pred,
+                       int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W,
+                       int Ho, int Wo, int steps, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
