@@ -163,20 +163,8 @@ __device__ __forceinline__ float dgelu_fast(float x) {
 template <typename T> __device__ __forceinline__ float gelu_t(float x) { if constexpr (sizeof(T) == 2) return gelu_fast(x); else return gelu_f(x); }
 template <typename T> __device__ __forceinline__ float dgelu_t(float x) { if constexpr (sizeof(T) == 2) return dgelu_fast(x); else return dgelu_f(x); }
 
-// ---------------------------------------------------------------- the clip store's downsampling map (patch.hip: gather and scoring; physics.hip)
-// Source index of F.interpolate(mode="nearest"): floor(dst * float(in / out)) clamped to in - 1 (identity at full resolution)
-__device__ __forceinline__ int nearest_src(int dst, float scale, int n, bool ident) { return ident ? dst : min((int)floorf((float)dst * scale), n - 1); }
-
-// pred * div + diff as torch forms it: an fp32 product, rounded, then an fp32 sum (contraction off: never one fused operation).  The physical
-// field the rollout's heat-flux rows (physics.hip) and bubble census (bubbles.hip) see
-__device__ __forceinline__ float denormalise(float v, float q, float d) {
-#pragma clang fp contract(off)
-    const float prod = v * q;
-    return prod + d;
-}
-
 // ---------------------------------------------------------------- wave / block reductions (64 lanes)
-__device__ __forceinline__ float wave_sum(float v) {
+template <class T> __device__ __forceinline__ T wave_sum(T v) {      // float or double: the 32 -> 1 butterfly, every lane gets the sum
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

@@ -19,7 +19,7 @@
 // Every loop is bounded by construction: a root chase must strictly descend (it raises the error flag and stops otherwise), and a union
 // continues only with a strictly smaller pair.  The error flag turns the frame's count into -1.  Integer atomics only: the same bits on every
 // call, and a frame has the same bits alone and in a batch.
-#include "bf_common.h"
+#include "clip_store.h"
 #include <algorithm>
 
 namespace {
@@ -262,33 +262,25 @@ template <class P> __global__ void __launch_bounds__(NT) bubble_census_kernel(Ce
 }
 
 struct RolloutBubbleArgs {
-    const float* pred; const float* src; long field_stride, total_frames; int nfields;
-    const long* first; const int* step; const int* field; const float* diff; const float* dv;
+    RolloutStep v;                                                         // clip_store.h: this step's prediction and its stored target frames
     int sdf_c, conn8, mb;
     int* count[2]; int* cells[2]; int* attached[2]; int* area[2];          // [0] the prediction, [1] the simulation
     char* ws; long slot, parents_off;
-    int B, T, C, H, W, Ho, Wo, steps;
 };
 
 template <class P> __global__ void __launch_bounds__(NT) rollout_bubbles_kernel(RolloutBubbleArgs a) {
-    const int s = *a.step;
-    if (s < 0 || s >= a.steps) return;                                     // behind the last row: nothing is written
-    const int bt = blockIdx.x, t = bt % a.T, b = bt / a.T, side = blockIdx.y;
+    const RolloutStep& v = a.v;
+    const int s = v.current();
+    if (s < 0) return;                                                     // behind the last row: nothing is written
+    const int bt = blockIdx.x, t = bt % v.T, b = bt / v.T, side = blockIdx.y;
     FrameSrc src;
-    if (side == 1) {
-        const int H = a.H, W = a.W;
-        const long frame = min(max(a.first[b] + (long)(s + 1) * a.T + t, 0L), a.total_frames - 1);      // as rollout_score_kernel clamps
-        const float* p = a.src + (long)min(max(a.field[a.sdf_c], 0), a.nfields - 1) * a.field_stride + frame * H * (long)W;
-        src = FrameSrc{p, W, H, W, (float)H / (float)a.Ho, (float)W / (float)a.Wo, a.Ho == H && a.Wo == W, false, 1.f, 0.f};
-    } else {
-        const float* p = a.pred + ((long)bt * a.C + a.sdf_c) * ((long)a.Ho * a.Wo);
-        src = FrameSrc{p, a.Wo, a.Ho, a.Wo, 1.f, 1.f, true, true, a.dv[a.sdf_c], a.diff[a.sdf_c]};
-    }
-    const long row = ((long)b * a.steps + s) * a.T + t;
+    if (side == 1) src = FrameSrc{v.stored(a.sdf_c, v.frame(s, b, t)), v.W, v.H, v.W, v.sy(), v.sx(), v.ident(), false, 1.f, 0.f};
+    else src = FrameSrc{v.predicted(bt, a.sdf_c), v.Wo, v.Ho, v.Wo, 1.f, 1.f, true, true, v.dv[a.sdf_c], v.diff[a.sdf_c]};
+    const long row = v.row(s, b, t);
     char* slot = a.ws + ((long)bt * 2 + side) * a.slot;
     const FrameOut out{a.count[side] + row, a.cells[side] + row, a.attached[side] + row, a.area[side] + row * a.mb, nullptr, nullptr, nullptr,
                        (long long*)slot};
-    census_frame(parents_at<P>(slot, a.parents_off), src, out, a.Ho, a.Wo, a.conn8 != 0, a.mb);
+    census_frame(parents_at<P>(slot, a.parents_off), src, out, v.Ho, v.Wo, a.conn8 != 0, a.mb);
 }
 
 // the LDS kernels ask for more dynamic LDS than the default limit: raised once per device and kernel
@@ -338,19 +330,19 @@ extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_
                                   int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
                                   int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes,
                                   int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
-    BF_REQUIRE(pred && frames && first && step && field && diff && div && count_pred && count_tgt && cells_pred && cells_tgt && attached_pred &&
-               attached_tgt && area_pred && area_tgt && ws, "bf_rollout_bubbles: null pointer");
-    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && steps > 0 && nfields > 0 && total_frames > 0 &&
-               field_stride >= total_frames * H * W && (int64_t)B * T <= 0x3fffffff && max_bubbles > 0, "bf_rollout_bubbles: bad sizes");
+    RolloutStep v;
+    if (const int rc = rollout_step_view(v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
+                                         count_pred && count_tgt && cells_pred && cells_tgt && attached_pred && attached_tgt && area_pred && area_tgt && ws,
+                                         (int64_t)B * T <= 0x3fffffff && max_bubbles > 0, "bf_rollout_bubbles: null pointer", "bf_rollout_bubbles: bad sizes"))
+        return rc;
     BF_REQUIRE(sdf_channel >= 0 && sdf_channel < C, "bf_rollout_bubbles: the signed-distance channel must be an output channel");
     BF_REQUIRE(connectivity == 4 || connectivity == 8, "bf_rollout_bubbles: connectivity must be 4 or 8");
     BF_REQUIRE((int64_t)Ho * Wo <= BUBBLE_MAX_CELLS, "bf_rollout_bubbles: a frame may have at most 2^24 cells");
     BF_REQUIRE(ws_bytes >= bf_bubble_census_ws_bytes(2 * (int64_t)B * T, Ho, Wo, max_bubbles), "bf_rollout_bubbles: workspace smaller than bf_bubble_census_ws_bytes(2 B T, Ho, Wo, max_bubbles)");
     BF_REQUIRE((uintptr_t)ws % 16 == 0, "bf_rollout_bubbles: the workspace must be 16-byte aligned");
     const WsLayout lay(Ho, Wo, max_bubbles);
-    const RolloutBubbleArgs a{pred, frames, (long)field_stride, (long)total_frames, nfields, (const long*)first, (const int*)step, (const int*)field, diff, div,
-                              sdf_channel, connectivity == 8, max_bubbles, {count_pred, count_tgt}, {cells_pred, cells_tgt}, {attached_pred, attached_tgt},
-                              {area_pred, area_tgt}, (char*)ws, lay.slot, lay.parents_off, B, T, C, H, W, Ho, Wo, steps};
+    const RolloutBubbleArgs a{v, sdf_channel, connectivity == 8, max_bubbles, {count_pred, count_tgt}, {cells_pred, cells_tgt}, {attached_pred, attached_tgt},
+                              {area_pred, area_tgt}, (char*)ws, lay.slot, lay.parents_off};
     const long n = (long)Ho * Wo;
     const dim3 grid((unsigned)(B * T), 2);
     if (n <= BUBBLE_LDS_CELLS) {

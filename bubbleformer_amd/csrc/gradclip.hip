@@ -3,6 +3,7 @@
 //                                               norm_type 2: what Lightning's Trainer(gradient_clip_val=...) calls)
 //   bf_adamw_dev / bf_adam_dev / bf_lion_dev -> the fused optimizers of optim_kernels.h reading that coefficient from device memory, with an
 //                                               optional clamp of the scaled gradient (gradient_clip_algorithm="value")
+//   bf_adamw / bf_adam / bf_lion             -> the same optimizers on a host gradient scale (no clipping)
 //
 // The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
 //   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
@@ -108,6 +109,28 @@ extern "C" int bf_grad_norm(const float* g, int64_t n, float gscale, float max_n
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_NT), 0, st, (const double*)ws, nslabs, gscale, max_norm, out);
     BF_CHECK_LAUNCH();
     return 0;
+}
+
+// ---------------------------------------------------------------------------- the optimizers on a host gradient scale
+extern "C" int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
+                       bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && n > 0, "bf_lion: bad arguments");
+    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0), "bf_lion: buffers must be 16-byte aligned");
+    return opt_launch_lion<BF_OPT_HOST>(p, g, m, n, lr, beta1, beta2, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
+                        float eps, float wd, float gscale, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adamw: bad arguments");
+    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adamw: buffers must be 16-byte aligned");
+    return opt_launch_adam<BF_OPT_HOST>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
+                       float eps, float wd, float gscale, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adam: bad arguments");
+    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adam: buffers must be 16-byte aligned");
+    return opt_launch_adam<BF_OPT_HOST>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------- the optimizers on a device-resident coefficient

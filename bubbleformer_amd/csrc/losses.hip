@@ -1,5 +1,5 @@
 // The reference's utils/losses.py as stand-alone kernels: the relative Lp norm per row of LpLoss (utils/losses.py:67-94) forward and
-// backward, and the adjoint of the Eikonal residual (utils/losses.py:5-15; its value is bf_eikonal_sum in patch.hip).
+// backward, and the adjoint of the Eikonal residual (utils/losses.py:5-15; its value is bf_eikonal_sum in physics.hip).
 //
 // Lp rows.  pred, y are [rows][n] fp32.  Forward: S_e = sum |pred - y|^p and S_y = sum |y|^p per row in fp64, ratio = (S_e / S_y)^(1/p)
 // rounded once.  Backward: dpred = coef * sign(e) |e|^(p-1) with coef = g / (S_e^((p-1)/p) * S_y^(1/p)) in fp64.  Two regimes:

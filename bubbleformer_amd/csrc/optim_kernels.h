@@ -1,7 +1,8 @@
-// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates, shared by their two families of entry points:
-//   patch.hip     bf_adamw / bf_adam / bf_lion              gradient scale = a host float                       (BF_OPT_HOST)
-//   gradclip.hip  bf_adamw_dev / bf_adam_dev / bf_lion_dev  gradient scale = gscale * coef_dev[0] (device)      (BF_OPT_DEV)
-//                                                           ... and the scaled gradient clamped to +-clip       (BF_OPT_DEV_CLAMP)
+// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates, shared by their two families of entry points,
+// both in gradclip.hip:
+//   bf_adamw / bf_adam / bf_lion              gradient scale = a host float                       (BF_OPT_HOST)
+//   bf_adamw_dev / bf_adam_dev / bf_lion_dev  gradient scale = gscale * coef_dev[0] (device)      (BF_OPT_DEV)
+//                                             ... and the scaled gradient clamped to +-clip       (BF_OPT_DEV_CLAMP)
 // One body per optimizer: the variants differ in where the scale comes from (read once per thread, before the loop) and in one clamp on
 // the scaled gradient.  BF_OPT_HOST compiles to the kernel the host-scale entry points always launched; BF_OPT_DEV runs the same loop
 // body on gscale * coef_dev[0], which is gscale exactly when the coefficient is 1.0f.

@@ -4,12 +4,10 @@
 //   nchw2pm (+ loss backward)  : d(pred) -> patch-major rows for the debed backward GEMMs
 //   wprep / wgrad_unprep       : fp32 state_dict weights -> GEMM operand layout/dtype and back (gradients)
 //   film_net fwd/bwd           : LayerNorm(P) + Linear(P, 2E) on B rows
-//   adamw / adam / lion        : fused flat-buffer optimizers on a host gradient scale (kernels: optim_kernels.h, shared with gradclip.hip)
-//   rollout_score              : every score of one rollout step against store-resident targets, one pass over the prediction
 // All are bandwidth-bound; each thread moves 8..16 contiguous bytes where the layout allows.
 #include "bf_common.h"
 #include "param_reduce.h"
-#include "optim_kernels.h"
+#include <algorithm>
 
 namespace {
 constexpr int NT = 256;
@@ -820,430 +818,4 @@ extern "C" int bf_film_net_bwd(const float* dgb, const float* chat, const float*
     hipLaunchKernelGGL(film_net_bwd_kernel, dim3(bf_cdiv(E2, 64) + P), dim3(64), 0, (hipStream_t)stream, dgb, chat, lnw, lnb, W, dW, dbias, dlnw, dlnb, B, P, E2);
     BF_CHECK_LAUNCH();
     return 0;
-}
-
-// ---------------------------------------------------------------------------- per-pixel expressions with more than one user
-// The clip gather kernels and the notebook's Eikonal score share these with the rollout scoring kernel (rollout_score_kernel below):
-// one definition each, so that a target built on the fly has the bits a gathered clip has, and both Eikonal scores the same arithmetic.
-// (nearest_src, the gather's source-index map, lives in bf_common.h: physics.hip reads the store through it too)
-__device__ __forceinline__ float clip_norm(float v, float d, float q) { return (v - d) / q; }
-// | |grad phi| - 1 | at pixel (x, y) of an H x W frame read through at(row, column): central differences, replicate-padded borders
-template <class At>
-__device__ __forceinline__ float eikonal_l1_px(At at, int x, int y, int H, int W, float inv_2dx) {
-    const int xi = min(max(x, 1), W - 2), yi = min(max(y, 1), H - 2);
-    const float gx = (at(y, xi + 1) - at(y, xi - 1)) * inv_2dx;
-    const float gy = (at(yi + 1, x) - at(yi - 1, x)) * inv_2dx;
-    return fabsf(sqrtf(gx * gx + gy * gy) - 1.f);
-}
-
-// ---------------------------------------------------------------------------- physics metrics of a rollout
-// Eikonal residual of a signed-distance field (utils/losses.py:5-15): torch.gradient(edge_order=1, spacing=dx) along H and W
-// (central differences inside, one-sided at the borders), out += sum over pixels of (|grad phi| - 1)^2   (caller divides by the count)
-__global__ void __launch_bounds__(NT) eikonal_kernel(const float* __restrict__ phi, long frames, int H, int W, float inv_dx, double* __restrict__ out) {
-    __shared__ double red[NT / 64];
-    const long total = frames * H * W;
-    double acc = 0.0;
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const float* p = phi + i;
-        float gy, gx;
-        if (H == 1) gy = 0.f;
-        else if (y == 0) gy = (p[W] - p[0]) * inv_dx;
-        else if (y == H - 1) gy = (p[0] - p[-W]) * inv_dx;
-        else gy = (p[W] - p[-W]) * (0.5f * inv_dx);
-        if (W == 1) gx = 0.f;
-        else if (x == 0) gx = (p[1] - p[0]) * inv_dx;
-        else if (x == W - 1) gx = (p[0] - p[-1]) * inv_dx;
-        else gx = (p[1] - p[-1]) * (0.5f * inv_dx);
-        const float r = sqrtf(gy * gy + gx * gx) - 1.f;
-        acc += (double)(r * r);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < NT / 64; ++i) t += red[i];
-        atomicAdd(out, t);
-    }
-}
-// The rollout notebook's Eikonal score (scripts/inference_autoregressive.ipynb, `get_eikonal_loss`): per frame, the mean of
-// | |grad phi| - 1 | with central differences at spacing dx in the interior and the border taking its neighbour's gradient
-// (replicate padding).  One workgroup per frame.
-__global__ void __launch_bounds__(NT) eikonal_l1_kernel(const float* __restrict__ phi, int H, int W, float inv_2dx, float* __restrict__ out) {
-    __shared__ double red[NT / 64];
-    const float* f = phi + (long)blockIdx.x * H * W;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < H * W; i += NT) {
-        acc += (double)eikonal_l1_px([&](int yy, int xx) { return f[yy * W + xx]; }, i % W, i / W, H, W, inv_2dx);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < NT / 64; ++i) t += red[i];
-        out[blockIdx.x] = (float)(t / ((double)H * W));
-    }
-}
-// Heater heat flux of FC-72 pool boiling per frame (utils/heatflux.py:17-38): bottom row y = 0 of a W-column grid spanning
-// x in [x_min, x_min + W*dx); flux[t] = mean_x( [ |x| <= 5 and dfun < 0 ] * (heater_temp - temp) ) * 0.054 / (dx * lc)
-__global__ void __launch_bounds__(64) heatflux_kernel(const float* __restrict__ dfun, const float* __restrict__ temp, long frame_stride, int W,
-                                                     float x_min, float dx, float heater_temp, float coef, float* __restrict__ flux) {
-    const float* d = dfun + (long)blockIdx.x * frame_stride;
-    const float* t = temp + (long)blockIdx.x * frame_stride;
-    double acc = 0.0;
-    for (int x = threadIdx.x; x < W; x += 64) {
-        const double xc = (double)x_min + ((double)x + 0.5) * (double)dx;
-        if (xc >= -5.0 && xc <= 5.0 && d[x] < 0.f) acc += (double)(heater_temp - t[x]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (threadIdx.x == 0) flux[blockIdx.x] = (float)(acc / (double)W * (double)coef);
-}
-
-extern "C" int bf_eikonal_sum(const float* phi, int64_t frames, int H, int W, float dx, double* out, bf_stream_t stream) {
-    BF_REQUIRE(phi && out && frames > 0 && H > 0 && W > 0 && dx > 0.f, "bf_eikonal_sum: bad arguments");
-    hipLaunchKernelGGL(eikonal_kernel, dim3(grid_for(frames * H * W)), dim3(NT), 0, (hipStream_t)stream, phi, (long)frames, H, W, 1.f / dx, out);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int bf_eikonal_l1_frames(const float* phi, int64_t frames, int H, int W, float dx, float* out, bf_stream_t stream) {
-    BF_REQUIRE(phi && out && frames > 0 && H >= 3 && W >= 3 && dx > 0.f, "bf_eikonal_l1_frames: bad arguments (central differences need >= 3 points per axis)");
-    hipLaunchKernelGGL(eikonal_l1_kernel, dim3((unsigned)frames), dim3(NT), 0, (hipStream_t)stream, phi, H, W, 0.5f / dx, out);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int bf_heatflux_rows(const float* dfun, const float* temp, int64_t frames, int64_t frame_stride, int W, float x_min, float dx,
-                                float heater_temp, float lc, float* flux, bf_stream_t stream) {
-    BF_REQUIRE(dfun && temp && flux && frames > 0 && W > 0 && dx > 0.f && lc > 0.f, "bf_heatflux_rows: bad arguments");
-    hipLaunchKernelGGL(heatflux_kernel, dim3((unsigned)frames), dim3(64), 0, (hipStream_t)stream, dfun, temp, (long)frame_stride, W, x_min, dx,
-                       heater_temp, 0.054f / (dx * lc), flux);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- field statistics of device-resident trajectories
-// The normalisation constants of the dataset (bubbleformer/data/dataset.py:74-117: mean / std / min / max of every full field of every file,
-// which the reference reads through h5py and reduces on the host) from the trajectories ALREADY resident in HBM: one launch over all
-// (field, file) segments.  Pass 1: every workgroup sweeps a contiguous share of one segment (16-byte loads) and leaves {sum, sum of squares,
-// min, max} in fp64; pass 2: one wave per segment adds the workgroup rows in row order (bit-reproducible; no atomics).
-constexpr int FS_ROWS = 64;      // workgroups per segment
-__global__ void __launch_bounds__(NT) field_stats_kernel(const float* __restrict__ src, const long* __restrict__ seg_begin, const long* __restrict__ seg_len,
-                                                        double* __restrict__ part) {
-    __shared__ double red[NT / 64][4];
-    const int seg = blockIdx.y;
-    const float* p = src + seg_begin[seg];
-    const long n = seg_len[seg];
-    const long per = ((n + FS_ROWS - 1) / FS_ROWS + 3) & ~3L;                      // a multiple of 4 floats: whole 16-byte groups when the segment is aligned
-    const long lo = (long)blockIdx.x * per, hi = min(n, lo + per);
-    double s1 = 0.0, s2 = 0.0, mn = 1.0 / 0.0, mx = -1.0 / 0.0;
-    auto take = [&](float v) { const double d = (double)v; s1 += d; s2 += d * d; mn = fmin(mn, d); mx = fmax(mx, d); };
-    const bool vec = (((uintptr_t)p) & 15) == 0;
-    long i = lo + 4L * threadIdx.x;
-    if (vec)
-        for (; i + 3 < hi; i += 4L * NT) { const float4 v = *reinterpret_cast<const float4*>(p + i); take(v.x); take(v.y); take(v.z); take(v.w); }
-    else
-        for (; i + 3 < hi; i += 4L * NT) { take(p[i]); take(p[i + 1]); take(p[i + 2]); take(p[i + 3]); }
-    for (long j = i; j < hi && j < i + 4; ++j) take(p[j]);                            // the share's ragged end (at most one thread has one)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); mn = fmin(mn, __shfl_xor(mn, o, 64)); mx = fmax(mx, __shfl_xor(mx, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { double* r = red[threadIdx.x >> 6]; r[0] = s1; r[1] = s2; r[2] = mn; r[3] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0, c = 1.0 / 0.0, e = -1.0 / 0.0;
-        for (int w = 0; w < NT / 64; ++w) { a += red[w][0]; b += red[w][1]; c = fmin(c, red[w][2]); e = fmax(e, red[w][3]); }
-        double* o = part + ((long)seg * FS_ROWS + blockIdx.x) * 4;
-        o[0] = a; o[1] = b; o[2] = c; o[3] = e;
-    }
-}
-__global__ void __launch_bounds__(64) field_stats_finish_kernel(const double* __restrict__ part, double* __restrict__ out) {
-    const int seg = blockIdx.x;
-    if (threadIdx.x != 0) return;
-    double a = 0.0, b = 0.0, c = 1.0 / 0.0, e = -1.0 / 0.0;
-    for (int r = 0; r < FS_ROWS; ++r) { const double* q = part + ((long)seg * FS_ROWS + r) * 4; a += q[0]; b += q[1]; c = fmin(c, q[2]); e = fmax(e, q[3]); }
-    out[seg * 4] = a; out[seg * 4 + 1] = b; out[seg * 4 + 2] = c; out[seg * 4 + 3] = e;
-}
-extern "C" int64_t bf_field_stats_ws_doubles(int nseg) { return nseg > 0 ? (int64_t)nseg * FS_ROWS * 4 : 0; }
-extern "C" int bf_field_stats(const float* src, const int64_t* seg_begin, const int64_t* seg_len, int nseg, double* out, double* ws, bf_stream_t stream) {
-    BF_REQUIRE(src && seg_begin && seg_len && out && ws && nseg > 0 && nseg <= 65535, "bf_field_stats: bad arguments");
-    hipLaunchKernelGGL(field_stats_kernel, dim3(FS_ROWS, (unsigned)nseg), dim3(NT), 0, (hipStream_t)stream, src, (const long*)seg_begin, (const long*)seg_len, ws);
-    BF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(field_stats_finish_kernel, dim3((unsigned)nseg), dim3(64), 0, (hipStream_t)stream, (const double*)ws, out);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- clip gather (device-resident trajectories -> batch)
-// out[b][t][c][yo][xo] = (src[field[c]][first[b] + t0 + t][ys(yo)][xs(xo)] - diff[c]) / div[c]
-// ys / xs: identity, or torch's F.interpolate(mode="nearest") source index floor(dst * float(in / out)) clamped to in - 1
-// (bubbleformer/data/dataset.py:138-148).  One thread per 4 output pixels of a row; reads of a full-resolution row are 16-byte.
-__global__ void __launch_bounds__(NT) clip_gather_kernel(const float* __restrict__ src, long field_stride, const int* __restrict__ field,
-                                                        const long* __restrict__ first, int t0, const float* __restrict__ diff,
-                                                        const float* __restrict__ dv, float* __restrict__ out, int B, int T, int C, int H, int W,
-                                                        int Ho, int Wo) {
-    const int wq = (Wo + 3) / 4;
-    const long total = (long)B * T * C * Ho * wq;
-    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    const bool ident = Ho == H && Wo == W;
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
-        const int xq = (int)(i % wq);
-        long r = i / wq;
-        const int yo = (int)(r % Ho); r /= Ho;
-        const int c = (int)(r % C); r /= C;
-        const int t = (int)(r % T);
-        const int b = (int)(r / T);
-        const int ys = nearest_src(yo, sy, H, ident);
-        const float* row = src + (long)field[c] * field_stride + ((first[b] + t0 + t) * H + ys) * (long)W;
-        float* dst = out + ((((long)b * T + t) * C + c) * Ho + yo) * (long)Wo + 4 * xq;
-        const float d = diff[c], q = dv[c];
-        if (ident && (W & 3) == 0) {
-            const float4 v = *reinterpret_cast<const float4*>(row + 4 * xq);
-            *reinterpret_cast<float4*>(dst) = make_float4(clip_norm(v.x, d, q), clip_norm(v.y, d, q), clip_norm(v.z, d, q), clip_norm(v.w, d, q));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int xo = 4 * xq + j;
-                if (xo < Wo) {
-                    const int xs = nearest_src(xo, sx, W, ident);
-                    dst[j] = clip_norm(row[xs], d, q);
-                }
-            }
-        }
-    }
-}
-
-extern "C" int bf_clip_gather(const float* src, int64_t field_stride, const int32_t* field, const int64_t* first, int t0,
-                              const float* diff, const float* div, float* out, int B, int T, int C, int H, int W, int Ho, int Wo,
-                              bf_stream_t stream) {
-    BF_REQUIRE(src && field && first && diff && div && out, "bf_clip_gather: null pointer");
-    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && t0 >= 0, "bf_clip_gather: bad sizes");
-    BF_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0), "bf_clip_gather: buffers must be 16-byte aligned");
-    const long total = (long)B * T * C * Ho * ((Wo + 3) / 4);
-    hipLaunchKernelGGL(clip_gather_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, src, (long)field_stride, (const int*)field,
-                       (const long*)first, t0, diff, div, out, B, T, C, H, W, Ho, Wo);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-
-// A training batch in ONE launch: the input clips (frames first .. first + Tin - 1), the target clips (the Tout frames behind them) and the
-// per-sample fluid-parameter rows, all indexed by SAMPLE number on the device (first_tab / file_tab: absolute first frame and file of every
-// sample of the dataset) -- what took two launches and three index kernels of the host framework (first_tab[idx], file_tab[idx], fluid[...]).
-struct ClipSeg { const int* field; const float* diff; const float* dv; float* out; int T, C, t0; };
-__global__ void __launch_bounds__(NT) clip_gather_batch_kernel(const float* __restrict__ src, long field_stride, const long* __restrict__ idx, long nsamples,
-                                                              const long* __restrict__ first_tab, ClipSeg a, ClipSeg b,
-                                                              const float* __restrict__ fluid_tab, const long* __restrict__ file_tab, int P,
-                                                              float* __restrict__ fluid_out, int B, int H, int W, int Ho, int Wo) {
-    const int wq = (Wo + 3) / 4;
-    const long per_a = (long)a.T * a.C * Ho * wq, per_b = (long)b.T * b.C * Ho * wq, per = per_a + per_b;
-    const long total = (long)B * per;
-    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    const bool ident = Ho == H && Wo == W;
-    if (fluid_out && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < B * P; i += NT) fluid_out[i] = fluid_tab[file_tab[min(max(idx[i / P], 0L), nsamples - 1)] * P + i % P];
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
-        const int bb = (int)(i / per);
-        long r = i - (long)bb * per;
-        const bool second = r >= per_a;
-        if (second) r -= per_a;
-        const ClipSeg& sg = second ? b : a;
-        const int xq = (int)(r % wq); r /= wq;
-        const int yo = (int)(r % Ho); r /= Ho;
-        const int c = (int)(r % sg.C);
-        const int t = (int)(r / sg.C);
-        const int ys = nearest_src(yo, sy, H, ident);
-        const long smp = min(max(idx[bb], 0L), nsamples - 1);      // an index out of range reads a valid sample, never past a table
-        const float* row = src + (long)sg.field[c] * field_stride + ((first_tab[smp] + sg.t0 + t) * H + ys) * (long)W;
-        float* dst = sg.out + ((((long)bb * sg.T + t) * sg.C + c) * Ho + yo) * (long)Wo + 4 * xq;
-        const float d = sg.diff[c], q = sg.dv[c];
-        if (ident && (W & 3) == 0) {
-            const float4 v = *reinterpret_cast<const float4*>(row + 4 * xq);
-            *reinterpret_cast<float4*>(dst) = make_float4(clip_norm(v.x, d, q), clip_norm(v.y, d, q), clip_norm(v.z, d, q), clip_norm(v.w, d, q));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int xo = 4 * xq + j;
-                if (xo < Wo) {
-                    const int xs = nearest_src(xo, sx, W, ident);
-                    dst[j] = clip_norm(row[xs], d, q);
-                }
-            }
-        }
-    }
-}
-extern "C" int bf_clip_gather_batch(const float* src, int64_t field_stride, const int64_t* idx, int64_t nsamples, const int64_t* first_tab, const int32_t* in_field,
-                                    const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out, const int32_t* out_field,
-                                    const float* out_diff, const float* out_div, int Cout, int Tout, float* out_out, const float* fluid_tab,
-                                    const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo, bf_stream_t stream) {
-    BF_REQUIRE(src && idx && first_tab && in_field && in_diff && in_div && in_out && out_field && out_diff && out_div && out_out,
-               "bf_clip_gather_batch: null pointer");
-    BF_REQUIRE(nsamples > 0 && B > 0 && Tin > 0 && Tout > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W, "bf_clip_gather_batch: bad sizes");
-    BF_REQUIRE(!fluid_out || (fluid_tab && file_tab && P > 0), "bf_clip_gather_batch: the fluid rows need their table, the file table and P > 0");
-    BF_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)in_out % 16 == 0) && ((uintptr_t)out_out % 16 == 0), "bf_clip_gather_batch: buffers must be 16-byte aligned");
-    const ClipSeg a{(const int*)in_field, in_diff, in_div, in_out, Tin, Cin, 0}, b{(const int*)out_field, out_diff, out_div, out_out, Tout, Cout, Tin};
-    const long total = (long)B * ((long)Tin * Cin + (long)Tout * Cout) * Ho * ((Wo + 3) / 4);
-    hipLaunchKernelGGL(clip_gather_batch_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, src, (long)field_stride, (const long*)idx, (long)nsamples,
-                       (const long*)first_tab, a, b, fluid_tab, (const long*)file_tab, P, fluid_out, B, H, W, Ho, Wo);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- rollout scoring (one call per autoregressive step)
-// Everything scripts/inference.py:230-266 and the rollout notebook report about one predicted clip, from ONE pass over the prediction:
-// per (trajectory, frame, field) the relative L2 error against the simulation (utils/plot_utils.py:30-33), their mean (the LpLoss the script
-// prints), the notebook's Eikonal score of the predicted and of the simulated signed-distance field, plus the two copies the loop needs (the
-// next step's input and the archive row).  The target is never materialised: it is read where it lies in the store, through the gather's own
-// index map and normalisation (nearest_src / clip_norm above), so it has the bits bf_clip_gather returns.  The step number is read from DEVICE
-// memory and incremented by the last launch, so a captured graph replays without new arguments.
-// Pass 1: grid (rows, B*T*C); a workgroup sweeps a contiguous share of one (b, t, c) frame in 4-pixel groups of a row and leaves
-// {sum (pred - y)^2, sum y^2, Eikonal sum of the prediction, of the target} in fp64.  Pass 2: one workgroup adds the rows of every frame in
-// row order (no atomics: two runs give the same bits), takes quotient, root and means in fp64 and rounds once at the store.
-struct ScoreArgs {
-    const float* pred; const float* src; long field_stride, total_frames; int nfields;
-    const long* first; const int* step; const int* field; const float* diff; const float* dv;
-    int sdf; float inv_2dx; float* next_in; float* archive; double* part;
-    int B, T, C, H, W, Ho, Wo, steps, rows;
-};
-constexpr int RS_QUADS = 1024, RS_MAX_ROWS = 64;      // 4-pixel groups per workgroup (4 per thread) until RS_MAX_ROWS workgroups share a frame
-static int score_rows(int Ho, int Wo) { return (int)std::max<long>(1, std::min<long>(RS_MAX_ROWS, ((long)Ho * ((Wo + 3) / 4) + RS_QUADS - 1) / RS_QUADS)); }
-
-__global__ void __launch_bounds__(NT) rollout_score_kernel(ScoreArgs a) {
-    __shared__ double red[NT / 64][4];
-    const int s = *a.step;
-    if (s < 0 || s >= a.steps) return;                                     // a step behind the last row: nothing is written (pass 2 leaves the counter alone)
-    const int fc = blockIdx.y, H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;     // fc = (b * T + t) * C + c
-    const int c = fc % a.C, t = (fc / a.C) % a.T, b = fc / (a.C * a.T);
-    const int wq = (Wo + 3) / 4, quads = Ho * wq, per = (quads + a.rows - 1) / a.rows;
-    const int lo = blockIdx.x * per, hi = min(quads, lo + per);
-    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    const bool ident = Ho == H && Wo == W;
-    const long frame = min(max(a.first[b] + (long)(s + 1) * a.T + t, 0L), a.total_frames - 1);      // a start too close to the end reads a valid frame
-    const float* tf = a.src + (long)min(max(a.field[c], 0), a.nfields - 1) * a.field_stride + frame * H * (long)W;
-    const long px = (long)Ho * Wo;
-    const float* pf = a.pred + fc * px;
-    float* nf = a.next_in ? a.next_in + fc * px : nullptr;
-    float* af = a.archive ? a.archive + ((((long)b * a.steps + s) * a.T + t) * a.C + c) * px : nullptr;
-    const float d = a.diff[c], q = a.dv[c], inv_2dx = a.inv_2dx;
-    const bool eik = c == a.sdf, vec_p = (Wo & 3) == 0, vec_t = ident && (W & 3) == 0;
-    auto phi_at = [&](int yy, int xx) { return __fadd_rn(__fmul_rn(pf[yy * Wo + xx], q), d); };      // physical units, unfused: torch's pred * div + diff
-    auto tgt_at = [&](int yy, int xx) { return tf[(long)nearest_src(yy, sy, H, ident) * W + nearest_src(xx, sx, W, ident)]; };
-    double n2 = 0.0, y2 = 0.0, ep = 0.0, et = 0.0;
-    for (int i = lo + threadIdx.x; i < hi; i += NT) {
-        const int xq = i % wq, yo = i / wq, nv = min(4, Wo - 4 * xq);
-        const float* row = tf + (long)nearest_src(yo, sy, H, ident) * W;
-        const long o = (long)yo * Wo + 4 * xq;
-        float p[4] = {0.f, 0.f, 0.f, 0.f}, y[4] = {0.f, 0.f, 0.f, 0.f};
-        if (vec_p) { const float4 v = *reinterpret_cast<const float4*>(pf + o); p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
-        else for (int j = 0; j < nv; ++j) p[j] = pf[o + j];
-        if (vec_t) {
-            const float4 v = *reinterpret_cast<const float4*>(row + 4 * xq);
-            y[0] = clip_norm(v.x, d, q); y[1] = clip_norm(v.y, d, q); y[2] = clip_norm(v.z, d, q); y[3] = clip_norm(v.w, d, q);
-        } else
-            for (int j = 0; j < nv; ++j) y[j] = clip_norm(row[nearest_src(4 * xq + j, sx, W, ident)], d, q);
-        for (int j = 0; j < nv; ++j) { const double yy = (double)y[j], e = (double)p[j] - yy; n2 += e * e; y2 += yy * yy; }
-        if (eik)
-            for (int j = 0; j < nv; ++j) {
-                ep += (double)eikonal_l1_px(phi_at, 4 * xq + j, yo, Ho, Wo, inv_2dx);
-                et += (double)eikonal_l1_px(tgt_at, 4 * xq + j, yo, Ho, Wo, inv_2dx);
-            }
-        if (vec_p) {
-            const float4 v = make_float4(p[0], p[1], p[2], p[3]);
-            if (nf) *reinterpret_cast<float4*>(nf + o) = v;
-            if (af) *reinterpret_cast<float4*>(af + o) = v;
-        } else
-            for (int j = 0; j < nv; ++j) { if (nf) nf[o + j] = p[j]; if (af) af[o + j] = p[j]; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { n2 += __shfl_xor(n2, o, 64); y2 += __shfl_xor(y2, o, 64); ep += __shfl_xor(ep, o, 64); et += __shfl_xor(et, o, 64); }
-    if ((threadIdx.x & 63) == 0) { double* r = red[threadIdx.x >> 6]; r[0] = n2; r[1] = y2; r[2] = ep; r[3] = et; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double v = 0.0;
-        for (int w = 0; w < NT / 64; ++w) v += red[w][threadIdx.x];
-        a.part[((long)fc * a.rows + blockIdx.x) * 4 + threadIdx.x] = v;
-    }
-}
-// part [B*T*C][rows][4] -> rel_l2 [B][steps*T][C], criterion [B][steps], eik_pred / eik_tgt [B][steps*T] at the rows of step *step; then ++*step.
-// ratio [B*T*C]: the fp64 quotients of this step, kept for the mean (LpLoss reduce_dims=[0, 1], reductions=["mean", "mean"]: over T, then over C)
-__global__ void __launch_bounds__(NT) rollout_score_finish_kernel(const double* __restrict__ part, double* ratio, int* step, float* __restrict__ rel_l2,
-                                                                 float* __restrict__ criterion, float* __restrict__ eik_pred, float* __restrict__ eik_tgt,
-                                                                 int B, int T, int C, int steps, int rows, int sdf, double px) {
-    const int s = *step;
-    if (s < 0 || s >= steps) return;
-    for (int fc = threadIdx.x; fc < B * T * C; fc += NT) {
-        const int c = fc % C, t = (fc / C) % T, b = fc / (C * T);
-        double n2 = 0.0, y2 = 0.0, ep = 0.0, et = 0.0;
-        for (int r = 0; r < rows; ++r) { const double* q = part + ((long)fc * rows + r) * 4; n2 += q[0]; y2 += q[1]; ep += q[2]; et += q[3]; }
-        const double rr = sqrt(n2 / y2);                                   // a target frame of zeros: inf or NaN, as torch.norm(a) / torch.norm(b) gives
-        const long fr = ((long)b * steps + s) * T + t;
-        ratio[fc] = rr;
-        rel_l2[fr * C + c] = (float)rr;
-        if (c == sdf) { eik_pred[fr] = (float)(ep / px); eik_tgt[fr] = (float)(et / px); }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < B; b += NT) {
-        double m = 0.0;
-        for (int c = 0; c < C; ++c) {
-            double mc = 0.0;
-            for (int t = 0; t < T; ++t) mc += ratio[((long)b * T + t) * C + c];
-            m += mc / (double)T;
-        }
-        criterion[(long)b * steps + s] = (float)(m / (double)C);
-    }
-    __syncthreads();                                                       // every thread has read *step
-    if (threadIdx.x == 0) *step = s + 1;
-}
-
-extern "C" int64_t bf_rollout_score_ws_doubles(int B, int T, int C, int Ho, int Wo) {
-    if (B <= 0 || T <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return 0;
-    return (int64_t)B * T * C * (score_rows(Ho, Wo) * 4 + 1);
-}
-extern "C" int bf_rollout_score(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
-                                float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
-                                int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
-    BF_REQUIRE(pred && frames && first && step && field && diff && div && rel_l2 && criterion && ws, "bf_rollout_score: null pointer");
-    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && steps > 0 && nfields > 0 && total_frames > 0 &&
-               field_stride >= total_frames * H * W && (int64_t)B * T * C <= 65535, "bf_rollout_score: bad sizes");
-    BF_REQUIRE(sdf_channel >= -1 && sdf_channel < C, "bf_rollout_score: the signed-distance channel is -1 (none) or an output channel");
-    BF_REQUIRE(sdf_channel < 0 || (eik_pred && eik_tgt && Ho >= 3 && Wo >= 3 && dx > 0.f),
-               "bf_rollout_score: the Eikonal rows need their outputs, dx > 0 and >= 3 points per axis (central differences)");
-    BF_REQUIRE(pred != next_in && pred != archive, "bf_rollout_score: the copies cannot alias the prediction");
-    BF_REQUIRE(((uintptr_t)pred % 16 == 0) && ((uintptr_t)frames % 16 == 0) && ((uintptr_t)next_in % 16 == 0) && ((uintptr_t)archive % 16 == 0) &&
-               ((uintptr_t)ws % 8 == 0), "bf_rollout_score: prediction, frames and copies must be 16-byte aligned");
-    BF_REQUIRE(ws_doubles >= bf_rollout_score_ws_doubles(B, T, C, Ho, Wo), "bf_rollout_score: workspace smaller than bf_rollout_score_ws_doubles");
-    const int rows = score_rows(Ho, Wo);
-    double* ratio = ws + (long)B * T * C * rows * 4;
-    const ScoreArgs a{pred, frames, (long)field_stride, (long)total_frames, nfields, (const long*)first, (const int*)step, (const int*)field, diff, div,
-                      sdf_channel, sdf_channel >= 0 ? 0.5f / dx : 0.f, next_in, archive, ws, B, T, C, H, W, Ho, Wo, steps, rows};
-    hipLaunchKernelGGL(rollout_score_kernel, dim3((unsigned)rows, (unsigned)(B * T * C)), dim3(NT), 0, (hipStream_t)stream, a);
-    BF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rollout_score_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)ws, ratio, (int*)step, rel_l2, criterion,
-                       eik_pred, eik_tgt, B, T, C, steps, rows, sdf_channel, (double)Ho * (double)Wo);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- fused optimizers: the kernels are in optim_kernels.h
-extern "C" int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                       bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && n > 0, "bf_lion: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0), "bf_lion: buffers must be 16-byte aligned");
-    return opt_launch_lion<BF_OPT_HOST>(p, g, m, n, lr, beta1, beta2, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
-}
-
-extern "C" int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                        float eps, float wd, float gscale, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adamw: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adamw: buffers must be 16-byte aligned");
-    return opt_launch_adam<BF_OPT_HOST>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
-}
-
-extern "C" int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                       float eps, float wd, float gscale, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adam: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adam: buffers must be 16-byte aligned");
-    return opt_launch_adam<BF_OPT_HOST>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
 }

@@ -1,10 +1,7 @@
-// The reference's heat-flux evaluation inside a rollout: utils/heatflux.py per step of scripts/inference.py:239-252, and the comparison of
-// the two flux series that examples/data_visualization.ipynb (cell 4) makes: a Gaussian KDE of each, KL(sim || model) by Simpson's rule.
-//
-// rollout_heatflux_kernel: the expression of heatflux_kernel (patch.hip) on row 0 of the two fields of ONE rollout step, once on the
-// prediction (de-normalised as rollout_score_kernel de-normalises its Eikonal rows: fp32 multiply, then add, unfused) and once on the
-// stored simulation frame (through nearest_src, the gather's own map).  A wave per (trajectory, frame, side); 64 lanes stride over the row,
-// fp64 sum by the butterfly heatflux_kernel uses, one rounding.  The step number is READ from device memory, never written.
+// Physics metrics of a clip, and the comparison of two flux series:
+//   eikonal (sum of squares) / eikonal_l1 (the notebook's per-frame score) of a signed-distance field, heatflux_rows of a clip's heater rows.
+//   Their per-pixel and per-row expressions are clip_store.h's, shared with the per-step rollout kernels (rollout.hip);
+//   kde_kl: what examples/data_visualization.ipynb (cell 4) makes of two flux series: a Gaussian KDE of each, KL(sim || model) by Simpson's rule.
 //
 // KDE / KL, everything in fp64, three launches per call, no atomics (two calls give the same bits), O(n + m + points) memory:
 //   kde_stats_kernel  grid (2 sets, R rows): count is n; mean, then centred squares (np.cov(ddof=1)), min and max, each reduced in a fixed order;
@@ -14,7 +11,7 @@
 //                     slabs depends on n alone (at most KDE_MAX_SLABS), so a row has the same bits alone and in a batch;
 //   kde_finish_kernel grid (R): adds the slabs in slab order, divides by n h sqrt(2 pi), forms f = p log(p / q) (q == 0 -> eps; f = 0 where
 //                     p == 0, the limit -- numpy has NaN there) and applies scipy.integrate.simpson's rule for a uniform grid.
-#include "bf_common.h"
+#include "clip_store.h"
 #include <algorithm>
 #include <math.h>
 
@@ -25,53 +22,9 @@ constexpr int KDE_SLAB_MIN = 256;      // a set is not cut into slabs shorter th
 constexpr int KDE_MAX_SLABS = 64;      // bounds the workspace at 2 * 64 * points doubles per row, whatever n
 constexpr int KDE_STATS = 4;           // {mean, unbiased variance, min, max} per (row, set)
 
-struct HeatfluxArgs {
-    const float* pred; const float* src; long field_stride, total_frames; int nfields;
-    const long* first; const int* step; const int* field; const float* diff; const float* dv;
-    int dfun_c, temp_c; const float* heater_temp; float x_min, dx, coef;
-    float* flux_pred; float* flux_tgt;
-    int B, T, C, H, W, Ho, Wo, steps;
-};
+int grid_for(long total) { return (int)std::max<long>(1, std::min<long>((total + NT - 1) / NT, 256L * 16)); }
 
-// (denormalise, pred * div + diff as torch forms it, lives in bf_common.h: bubbles.hip de-normalises the same way)
-__global__ void __launch_bounds__(64) rollout_heatflux_kernel(HeatfluxArgs a) {
-    const int s = *a.step;
-    if (s < 0 || s >= a.steps) return;                                     // behind the last row: nothing is written
-    const int bt = blockIdx.x, t = bt % a.T, b = bt / a.T, Wo = a.Wo;
-    const bool sim = blockIdx.y == 1;
-    const float ht = a.heater_temp[b];
-    const float* d;
-    const float* tp;
-    float dq = 1.f, dd = 0.f, tq = 1.f, td = 0.f, sx = 1.f;
-    bool ident = true;
-    if (sim) {
-        const int H = a.H, W = a.W;
-        ident = a.Ho == H && Wo == W;
-        sx = (float)W / (float)Wo;
-        const long frame = min(max(a.first[b] + (long)(s + 1) * a.T + t, 0L), a.total_frames - 1);      // as rollout_score_kernel clamps
-        const long off = frame * H * (long)W + (long)nearest_src(0, (float)H / (float)a.Ho, H, ident) * W;
-        d = a.src + (long)min(max(a.field[a.dfun_c], 0), a.nfields - 1) * a.field_stride + off;
-        tp = a.src + (long)min(max(a.field[a.temp_c], 0), a.nfields - 1) * a.field_stride + off;
-    } else {
-        const long px = (long)a.Ho * Wo;
-        d = a.pred + ((long)bt * a.C + a.dfun_c) * px;                     // row 0 of the frame: the heater row ([:, 0, :])
-        tp = a.pred + ((long)bt * a.C + a.temp_c) * px;
-        dq = a.dv[a.dfun_c]; dd = a.diff[a.dfun_c]; tq = a.dv[a.temp_c]; td = a.diff[a.temp_c];
-    }
-    double acc = 0.0;
-    for (int x = threadIdx.x; x < Wo; x += 64) {
-        const double xc = (double)a.x_min + ((double)x + 0.5) * (double)a.dx;
-        float dval, tval;
-        if (sim) { const int xs = nearest_src(x, sx, a.W, ident); dval = d[xs]; tval = tp[xs]; }
-        else { dval = denormalise(d[x], dq, dd); tval = denormalise(tp[x], tq, td); }
-        if (xc >= -5.0 && xc <= 5.0 && dval < 0.f) acc += (double)(ht - tval);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (threadIdx.x == 0) (sim ? a.flux_tgt : a.flux_pred)[((long)b * a.steps + s) * a.T + t] = (float)(acc / (double)Wo * (double)a.coef);
-}
-
-// ---------------------------------------------------------------------------- Gaussian KDE and KL(p || q)
+// ---------------------------------------------------------------------------- workgroup reductions in a fixed order
 enum { RED_SUM = 0, RED_MIN = 1, RED_MAX = 2 };
 template <int OP> __device__ __forceinline__ double red_op(double a, double b) {
     if constexpr (OP == RED_SUM) return a + b;
@@ -90,6 +43,53 @@ template <int OP> __device__ __forceinline__ double block_reduce(double v, doubl
     return t;
 }
 
+// ---------------------------------------------------------------------------- physics metrics of a clip
+// Eikonal residual of a signed-distance field (utils/losses.py:5-15): torch.gradient(edge_order=1, spacing=dx) along H and W
+// (central differences inside, one-sided at the borders), out += sum over pixels of (|grad phi| - 1)^2   (caller divides by the count)
+__global__ void __launch_bounds__(NT) eikonal_kernel(const float* __restrict__ phi, long frames, int H, int W, float inv_dx, double* __restrict__ out) {
+    __shared__ double red[NT / 64];
+    const long total = frames * H * W;
+    double acc = 0.0;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const float* p = phi + i;
+        float gy, gx;
+        if (H == 1) gy = 0.f;
+        else if (y == 0) gy = (p[W] - p[0]) * inv_dx;
+        else if (y == H - 1) gy = (p[0] - p[-W]) * inv_dx;
+        else gy = (p[W] - p[-W]) * (0.5f * inv_dx);
+        if (W == 1) gx = 0.f;
+        else if (x == 0) gx = (p[1] - p[0]) * inv_dx;
+        else if (x == W - 1) gx = (p[0] - p[-1]) * inv_dx;
+        else gx = (p[1] - p[-1]) * (0.5f * inv_dx);
+        const float r = sqrtf(gy * gy + gx * gx) - 1.f;
+        acc += (double)(r * r);
+    }
+    const double t = block_reduce<RED_SUM>(acc, red);
+    if (threadIdx.x == 0) atomicAdd(out, t);
+}
+// The rollout notebook's Eikonal score (scripts/inference_autoregressive.ipynb, `get_eikonal_loss`): per frame, the mean of
+// | |grad phi| - 1 | with central differences at spacing dx in the interior and the border taking its neighbour's gradient
+// (replicate padding).  One workgroup per frame.
+__global__ void __launch_bounds__(NT) eikonal_l1_kernel(const float* __restrict__ phi, int H, int W, float inv_2dx, float* __restrict__ out) {
+    __shared__ double red[NT / 64];
+    const float* f = phi + (long)blockIdx.x * H * W;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < H * W; i += NT)
+        acc += (double)eikonal_l1_px([&](int yy, int xx) { return f[yy * W + xx]; }, i % W, i / W, H, W, inv_2dx);
+    const double t = block_reduce<RED_SUM>(acc, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(t / ((double)H * W));
+}
+// Heater heat flux per frame (utils/heatflux.py:17-38): heater_row_flux of the bottom row y = 0, coef = 0.054 / (dx * lc).  A wave per frame.
+__global__ void __launch_bounds__(64) heatflux_kernel(const float* __restrict__ dfun, const float* __restrict__ temp, long frame_stride, int W,
+                                                     float x_min, float dx, float heater_temp, float coef, float* __restrict__ flux) {
+    const float* d = dfun + (long)blockIdx.x * frame_stride;
+    const float* t = temp + (long)blockIdx.x * frame_stride;
+    const float f = heater_row_flux([&](int x) { return d[x]; }, [&](int x) { return t[x]; }, W, x_min, dx, heater_temp, coef);
+    if (threadIdx.x == 0) flux[blockIdx.x] = f;
+}
+
+// ---------------------------------------------------------------------------- Gaussian KDE and KL(p || q)
 __global__ void __launch_bounds__(NT) kde_stats_kernel(const double* __restrict__ p, const double* __restrict__ q, long n, long m, double* __restrict__ stats) {
     __shared__ double red[NT / 64];
     const int set = blockIdx.x, r = blockIdx.y;
@@ -181,19 +181,23 @@ __global__ void __launch_bounds__(NT) kde_finish_kernel(long n, long m, int poin
 }
 }  // namespace
 
-extern "C" int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                   const int32_t* step, const int32_t* field, const float* diff, const float* div, int dfun_channel, int temp_channel,
-                                   const float* heater_temp, float x_min, float dx, float lc, float conductivity, float* flux_pred, float* flux_tgt,
-                                   int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
-    BF_REQUIRE(pred && frames && first && step && field && diff && div && heater_temp && flux_pred && flux_tgt, "bf_rollout_heatflux: null pointer");
-    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && steps > 0 && nfields > 0 && total_frames > 0 &&
-               field_stride >= total_frames * H * W && (int64_t)B * T <= 0x7fffffff, "bf_rollout_heatflux: bad sizes");
-    BF_REQUIRE(dfun_channel >= 0 && dfun_channel < C && temp_channel >= 0 && temp_channel < C,
-               "bf_rollout_heatflux: the signed-distance and the temperature channel must be output channels");
-    BF_REQUIRE(dx > 0.f && lc > 0.f, "bf_rollout_heatflux: dx and lc must be positive");
-    const HeatfluxArgs a{pred, frames, (long)field_stride, (long)total_frames, nfields, (const long*)first, (const int*)step, (const int*)field, diff, div,
-                         dfun_channel, temp_channel, heater_temp, x_min, dx, conductivity / (dx * lc), flux_pred, flux_tgt, B, T, C, H, W, Ho, Wo, steps};
-    hipLaunchKernelGGL(rollout_heatflux_kernel, dim3((unsigned)(B * T), 2), dim3(64), 0, (hipStream_t)stream, a);
+extern "C" int bf_eikonal_sum(const float* phi, int64_t frames, int H, int W, float dx, double* out, bf_stream_t stream) {
+    BF_REQUIRE(phi && out && frames > 0 && H > 0 && W > 0 && dx > 0.f, "bf_eikonal_sum: bad arguments");
+    hipLaunchKernelGGL(eikonal_kernel, dim3(grid_for(frames * H * W)), dim3(NT), 0, (hipStream_t)stream, phi, (long)frames, H, W, 1.f / dx, out);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int bf_eikonal_l1_frames(const float* phi, int64_t frames, int H, int W, float dx, float* out, bf_stream_t stream) {
+    BF_REQUIRE(phi && out && frames > 0 && H >= 3 && W >= 3 && dx > 0.f, "bf_eikonal_l1_frames: bad arguments (central differences need >= 3 points per axis)");
+    hipLaunchKernelGGL(eikonal_l1_kernel, dim3((unsigned)frames), dim3(NT), 0, (hipStream_t)stream, phi, H, W, 0.5f / dx, out);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int bf_heatflux_rows(const float* dfun, const float* temp, int64_t frames, int64_t frame_stride, int W, float x_min, float dx,
+                                float heater_temp, float lc, float* flux, bf_stream_t stream) {
+    BF_REQUIRE(dfun && temp && flux && frames > 0 && W > 0 && dx > 0.f && lc > 0.f, "bf_heatflux_rows: bad arguments");
+    hipLaunchKernelGGL(heatflux_kernel, dim3((unsigned)frames), dim3(64), 0, (hipStream_t)stream, dfun, temp, (long)frame_stride, W, x_min, dx,
+                       heater_temp, 0.054f / (dx * lc), flux);
     BF_CHECK_LAUNCH();
     return 0;
 }

@@ -4,7 +4,7 @@
 (bubbleformer/data/dataset.py:17-184) but reads the trajectory files with the in-tree HDF5 reader (no h5py), and adds the
 MI355X-side path: ``device_store()`` puts every trajectory in HBM once (a BubbleML study is a few GB; one GPU has 288 GB) and
 ``DeviceClipStore.gather`` builds a whole batch of normalised (input, target) clips with ONE HIP kernel (`bf_clip_gather`,
-csrc/patch.hip) -- no host-side slicing, stacking or H2D copy per step.
+csrc/clip_store.hip) -- no host-side slicing, stacking or H2D copy per step.
 """
 import json
 from typing import Dict, List, Optional, Sequence, Tuple

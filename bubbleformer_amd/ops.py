@@ -918,6 +918,31 @@ def clip_gather_batch(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch.
     return inp, out, fl
 
 
+def _check_tensors(who: str, device, want: dict, optional=()) -> None:
+    """want = {name: (tensor, shape, dtype)}: every tensor contiguous, of that shape and dtype, on ``device``; the names in ``optional`` may be None."""
+    for name, (t, shape, dtype) in want.items():
+        if t is None and name in optional:
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != device:
+            raise L.BubbleformerHipError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
+
+
+def _rollout_step_args(who: str, pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int):
+    """The three per-step rollout bindings' checks of prediction, store, first / step and field table -> their entry points' leading and trailing arguments."""
+    _require_gpu(pred)
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise L.BubbleformerHipError(f"{who}: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
+    ids, diff, div = table
+    nf, total, H, W = frames.shape
+    B, T, Cn, Ho, Wo = pred.shape
+    _check_tensors(who, pred.device, {"first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32)})
+    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.device != pred.device:
+        raise L.BubbleformerHipError(f"{who}: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
+    if ids.numel() != Cn:
+        raise L.BubbleformerHipError(f"{who}: the field table has {ids.numel()} channels, the prediction {Cn}")
+    return (_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div)), (B, T, Cn, H, W, Ho, Wo, int(steps), _stream())
+
+
 def rollout_score_workspace(pred: torch.Tensor) -> torch.Tensor:
     """The fp64 workspace ``rollout_score`` needs for predictions of this shape (allocate once, outside a graph capture)."""
     B, T, Cn, Ho, Wo = pred.shape
@@ -932,24 +957,14 @@ def rollout_score(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor,
     frames ``first[b] + (s + 1) * T + t`` of the store, s = the int32 ``step`` tensor ON THE DEVICE, which the call increments.  Writes row
     s * T + t of rel_l2 (B, steps*T, C), criterion (B, steps), eik_pred / eik_tgt (B, steps*T) (sdf_channel >= 0), and the optional copies
     next_in (like pred) and archive (B, steps*T, C, Ho, Wo).  Allocates nothing: capturable in a HIP graph."""
-    _require_gpu(pred)
-    ids, diff, div = table
-    nf, total, H, W = frames.shape
+    lead, tail = _rollout_step_args("rollout_score", pred, frames, first, step, table, steps)
     B, T, Cn, Ho, Wo = pred.shape
-    if pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise L.BubbleformerHipError("rollout_score: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
-    want = {"rel_l2": (rel_l2, (B, steps * T, Cn), torch.float32), "criterion": (criterion, (B, steps), torch.float32),
-            "eik_pred": (eik_pred, (B, steps * T), torch.float32), "eik_tgt": (eik_tgt, (B, steps * T), torch.float32),
-            "next_in": (next_in, (B, T, Cn, Ho, Wo), torch.float32), "archive": (archive, (B, steps * T, Cn, Ho, Wo), torch.float32),
-            "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32), "ws": (ws, (ws.numel(),), torch.float64)}
-    for name, (t, shape, dtype) in want.items():
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device):
-            raise L.BubbleformerHipError(f"rollout_score: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
-    if ids.numel() != Cn:
-        raise L.BubbleformerHipError(f"rollout_score: the field table has {ids.numel()} channels, the prediction {Cn}")
-    L.check(L.lib().bf_rollout_score(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(sdf_channel),
-                                     float(dx), _p(rel_l2), _p(criterion), _p(eik_pred), _p(eik_tgt), _p(next_in), _p(archive), _p(ws), ws.numel(),
-                                     B, T, Cn, H, W, Ho, Wo, int(steps), _stream()), "bf_rollout_score")
+    f32 = torch.float32
+    _check_tensors("rollout_score", pred.device, {"rel_l2": (rel_l2, (B, steps * T, Cn), f32), "criterion": (criterion, (B, steps), f32),
+                   "eik_pred": (eik_pred, (B, steps * T), f32), "eik_tgt": (eik_tgt, (B, steps * T), f32), "next_in": (next_in, (B, T, Cn, Ho, Wo), f32),
+                   "archive": (archive, (B, steps * T, Cn, Ho, Wo), f32), "ws": (ws, (ws.numel(),), torch.float64)}, ("eik_pred", "eik_tgt", "next_in", "archive"))
+    L.check(L.lib().bf_rollout_score(*lead, int(sdf_channel), float(dx), _p(rel_l2), _p(criterion), _p(eik_pred), _p(eik_tgt), _p(next_in), _p(archive),
+                                     _p(ws), ws.numel(), *tail), "bf_rollout_score")
 
 
 def rollout_heatflux(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, dfun_channel: int, temp_channel: int,
@@ -959,26 +974,14 @@ def rollout_heatflux(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tens
     flux_tgt (B, steps*T) from row 0 of the de-normalised prediction and of the stored frame ``first[b] + (s + 1) * T + t``, s = the int32
     ``step`` tensor ON THE DEVICE, which this call only reads -- issue it BEFORE the step's ``rollout_score``.  heater_temp (B,) fp32 on the
     device.  Allocates nothing: capturable in a HIP graph."""
-    _require_gpu(pred)
-    ids, diff, div = table
-    nf, total, H, W = frames.shape
-    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise L.BubbleformerHipError("rollout_heatflux: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
-    B, T, Cn, Ho, Wo = pred.shape
-    want = {"flux_pred": (flux_pred, (B, steps * T), torch.float32), "flux_tgt": (flux_tgt, (B, steps * T), torch.float32),
-            "heater_temp": (heater_temp, (B,), torch.float32), "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32)}
-    for name, (t, shape, dtype) in want.items():
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device:
-            raise L.BubbleformerHipError(f"rollout_heatflux: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
-    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.device != pred.device:
-        raise L.BubbleformerHipError(f"rollout_heatflux: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
-    if ids.numel() != Cn:
-        raise L.BubbleformerHipError(f"rollout_heatflux: the field table has {ids.numel()} channels, the prediction {Cn}")
+    lead, tail = _rollout_step_args("rollout_heatflux", pred, frames, first, step, table, steps)
+    B, T, Cn = pred.shape[:3]
+    _check_tensors("rollout_heatflux", pred.device, {"flux_pred": (flux_pred, (B, steps * T), torch.float32), "flux_tgt": (flux_tgt, (B, steps * T), torch.float32),
+                                                     "heater_temp": (heater_temp, (B,), torch.float32)})
     if not (0 <= int(dfun_channel) < Cn and 0 <= int(temp_channel) < Cn):
         raise L.BubbleformerHipError(f"rollout_heatflux: channels {dfun_channel} / {temp_channel} are not among the prediction's {Cn}")
-    L.check(L.lib().bf_rollout_heatflux(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(dfun_channel),
-                                        int(temp_channel), _p(heater_temp), float(x_min), float(dx), float(lc), float(conductivity), _p(flux_pred),
-                                        _p(flux_tgt), B, T, Cn, H, W, Ho, Wo, int(steps), _stream()), "bf_rollout_heatflux")
+    L.check(L.lib().bf_rollout_heatflux(*lead, int(dfun_channel), int(temp_channel), _p(heater_temp), float(x_min), float(dx), float(lc),
+                                        float(conductivity), _p(flux_pred), _p(flux_tgt), *tail), "bf_rollout_heatflux")
 
 
 def kde_kl_workspace(rows: int, n: int, m: int, points: int, device) -> torch.Tensor:
@@ -1000,11 +1003,7 @@ def kde_kl(p: torch.Tensor, q: torch.Tensor, points: int, eps: float, ws: torch.
         raise L.BubbleformerHipError(f"kde_kl: needs at least 2 samples per set and 3 grid points (n = {n}, m = {m}, points = {points})")
     want = {"p": (p, (R, n)), "q": (q, (R, m)), "kl": (kl, (R,)), "x": (x, (R, points)), "pdf_p": (pdf_p, (R, points)), "pdf_q": (pdf_q, (R, points)),
             "ws": (ws, (ws.numel(),))}
-    for name, (t, shape) in want.items():
-        if name in ("x", "pdf_p", "pdf_q") and t is None:
-            continue
-        if t is None or tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != p.device:
-            raise L.BubbleformerHipError(f"kde_kl: {name} must be a contiguous torch.float64 tensor of shape {shape} on {p.device}")
+    _check_tensors("kde_kl", p.device, {k: (t, shape, torch.float64) for k, (t, shape) in want.items()}, optional=("x", "pdf_p", "pdf_q"))
     if ws.numel() < L.lib().bf_kde_kl_ws_doubles(R, n, m, int(points)):
         raise L.BubbleformerHipError("kde_kl: the workspace is smaller than kde_kl_workspace(rows, n, m, points)")
     L.check(L.lib().bf_kde_kl(_p(p), _p(q), R, n, m, int(points), float(eps), _p(kl), _p(x), _p(pdf_p), _p(pdf_q), _p(ws), ws.numel(), _stream()),
@@ -1037,14 +1036,10 @@ def bubble_census(phi: torch.Tensor, connectivity: int, max_bubbles: int, ws: to
         raise L.BubbleformerHipError("bubble_census: phi must be a contiguous fp32 (frames, H, W) tensor")
     F, H, W = phi.shape
     mb = int(max_bubbles)
-    want = {"count": (count, (F,), torch.int32), "vapour_cells": (vapour_cells, (F,), torch.int32), "attached": (attached, (F,), torch.int32),
-            "area": (area, (F, mb), torch.int32), "centroid": (centroid, (F, mb, 2), torch.float32), "on_heater": (on_heater, (F, mb), torch.bool),
-            "labels": (labels, (F, H, W), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)}
-    for name, (t, shape, dtype) in want.items():
-        if name in ("centroid", "on_heater", "labels") and t is None:
-            continue
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != phi.device:
-            raise L.BubbleformerHipError(f"bubble_census: {name} must be a contiguous {dtype} tensor of shape {shape} on {phi.device}")
+    i32 = torch.int32
+    _check_tensors("bubble_census", phi.device, {"count": (count, (F,), i32), "vapour_cells": (vapour_cells, (F,), i32), "attached": (attached, (F,), i32),
+                   "area": (area, (F, mb), i32), "centroid": (centroid, (F, mb, 2), torch.float32), "on_heater": (on_heater, (F, mb), torch.bool),
+                   "labels": (labels, (F, H, W), i32), "ws": (ws, (ws.numel(),), torch.uint8)}, ("centroid", "on_heater", "labels"))
     need = L.lib().bf_bubble_census_ws_bytes(F, H, W, mb)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("bubble_census: the workspace is smaller than bubble_census_workspace(frames, H, W, max_bubbles)")
@@ -1060,34 +1055,20 @@ def rollout_bubbles(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tenso
     count / cells / attached (B, steps*T) and area (B, steps*T, max_bubbles), for the de-normalised signed-distance channel of the prediction
     (_pred) and for the stored frame ``first[b] + (s + 1) * T + t`` (_tgt), s = the int32 ``step`` tensor ON THE DEVICE, which this call only
     reads -- issue it BEFORE the step's ``rollout_score``.  ws: ``bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)``.  Allocates nothing."""
-    _require_gpu(pred)
-    ids, diff, div = table
-    nf, total, H, W = frames.shape
-    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise L.BubbleformerHipError("rollout_bubbles: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
+    lead, tail = _rollout_step_args("rollout_bubbles", pred, frames, first, step, table, steps)
     B, T, Cn, Ho, Wo = pred.shape
     mb = int(max_bubbles)
-    rows, recs = (B, steps * T), (B, steps * T, mb)
-    want = {"count_pred": (count_pred, rows, torch.int32), "count_tgt": (count_tgt, rows, torch.int32), "cells_pred": (cells_pred, rows, torch.int32),
-            "cells_tgt": (cells_tgt, rows, torch.int32), "attached_pred": (attached_pred, rows, torch.int32),
-            "attached_tgt": (attached_tgt, rows, torch.int32), "area_pred": (area_pred, recs, torch.int32), "area_tgt": (area_tgt, recs, torch.int32),
-            "first": (first, (B,), torch.int64), "step": (step, (1,), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)}
-    for name, (t, shape, dtype) in want.items():
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != pred.device:
-            raise L.BubbleformerHipError(f"rollout_bubbles: {name} must be a contiguous {dtype} tensor of shape {shape} on {pred.device}")
-    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.device != pred.device:
-        raise L.BubbleformerHipError(f"rollout_bubbles: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
-    if ids.numel() != Cn:
-        raise L.BubbleformerHipError(f"rollout_bubbles: the field table has {ids.numel()} channels, the prediction {Cn}")
+    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
+    _check_tensors("rollout_bubbles", pred.device, {"count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32), "cells_pred": (cells_pred, rows, i32),
+                   "cells_tgt": (cells_tgt, rows, i32), "attached_pred": (attached_pred, rows, i32), "attached_tgt": (attached_tgt, rows, i32),
+                   "area_pred": (area_pred, recs, i32), "area_tgt": (area_tgt, recs, i32), "ws": (ws, (ws.numel(),), torch.uint8)})
     if not 0 <= int(sdf_channel) < Cn:
         raise L.BubbleformerHipError(f"rollout_bubbles: channel {sdf_channel} is not among the prediction's {Cn}")
     need = L.lib().bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, mb)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("rollout_bubbles: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
-    L.check(L.lib().bf_rollout_bubbles(_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div), int(sdf_channel),
-                                       int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt), _p(attached_pred),
-                                       _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(ws), ws.numel(), B, T, Cn, H, W, Ho, Wo, int(steps), _stream()),
-            "bf_rollout_bubbles")
+    L.check(L.lib().bf_rollout_bubbles(*lead, int(sdf_channel), int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt),
+                                       _p(attached_pred), _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(ws), ws.numel(), *tail), "bf_rollout_bubbles")
 
 
 def grad_norm_workspace(n: int, device) -> torch.Tensor:

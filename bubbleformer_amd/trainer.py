@@ -1,7 +1,7 @@
 """Data-parallel training step for the native FiLMAViT path.
 
 * ``FlatParams``   -- re-homes every parameter (and its gradient) of a module into ONE fp32 buffer each, in
-                      registration order, so the optimizer is a single fused kernel (csrc/patch.hip: adamw_kernel)
+                      registration order, so the optimizer is a single fused kernel (csrc/optim_kernels.h: adamw_kernel)
                       and gradient buckets are contiguous slices.
 * ``BucketReducer``-- the data-parallel exchange (reference: Lightning's ``strategy="ddp"``, scripts/train.py:158-172):
                       mean all-reduce of gradient buckets over ``torch.distributed`` (backend "nccl" = RCCL over xGMI),

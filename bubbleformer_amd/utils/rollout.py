@@ -250,30 +250,31 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     archive = new(B, steps * T, C, Ho, Wo) if keep_predictions else None
     counter = torch.zeros(1, dtype=torch.int32, device=device)
     ws = ops.rollout_score_workspace(x)
-    hf_p = hf_t = hf_args = None
+    before_score = []                               # (pred, step) calls that read the step counter the scoring call then advances, in launch order
+    hf_p = hf_t = None
     if heatflux is not None:
         hf_channels = heatflux.channels(fields)
         heatflux.check_width(Wo)
         heater = _to_device(heatflux.temperatures(plan.files, len(ds.traj_lens)), torch.float32, device)
         hf_p, hf_t = new(B, steps * T), new(B, steps * T)
-        hf_args = (*hf_channels, heater, steps, hf_p, hf_t, heatflux.x_min, heatflux.dx, heatflux.lc, heatflux.conductivity)
-    bub = bub_args = None
+        before_score.append(lambda pred, step: ops.rollout_heatflux(pred, store.frames, first, step, store.out_tab, *hf_channels, heater, steps, hf_p, hf_t,
+                                                                    heatflux.x_min, heatflux.dx, heatflux.lc, heatflux.conductivity))
+    bub = None
     if bubbles is not None:
         mb = int(bubbles.max_bubbles)
         rows = lambda *tail: [torch.empty((B, steps * T) + tail, dtype=torch.int32, device=device) for _ in range(2)]
         bub = {"count": rows(), "cells": rows(), "attached": rows(), "area": rows(mb)}
         bub_args = (bubbles.channel(fields), steps, int(bubbles.connectivity), mb, ops.bubble_census_workspace(2 * B * T, Ho, Wo, mb, device),
                     *bub["count"], *bub["cells"], *bub["attached"], *bub["area"])
+        before_score.append(lambda pred, step: ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args))
 
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
             pred = pred.float().contiguous()
         if pred.shape != x.shape:
             raise ValueError(f"the model returned {tuple(pred.shape)} for an input of {tuple(x.shape)}: it cannot be fed back")
-        if hf_args is not None:                     # reads the step counter the scoring call then advances
-            ops.rollout_heatflux(pred, store.frames, first, step, store.out_tab, *hf_args)
-        if bub_args is not None:                    # likewise
-            ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args)
+        for call in before_score:
+            call(pred, step)
         ops.rollout_score(pred, store.frames, first, step, store.out_tab, sdf, steps, rel_l2, criterion, ws, eik_p, eik_t, next_in, arch)
 
     model.eval()

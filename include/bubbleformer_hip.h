@@ -381,7 +381,7 @@ int bf_rollout_score(const float* pred, const float* frames, int64_t field_strid
                      int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
                      float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
                      int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
-/* The heat-flux rows of ONE rollout step (utils/heatflux.py:3-38 per step of scripts/inference.py:239-252; csrc/physics.hip), for the prediction
+/* The heat-flux rows of ONE rollout step (utils/heatflux.py:3-38 per step of scripts/inference.py:239-252; csrc/rollout.hip), for the prediction
  * and for the simulation; allocation-free, capturable, no atomics (the same bits on every call), never makes the host wait.  pred, frames,
  * field_stride, total_frames, nfields, first, field / diff / div and the sizes are bf_rollout_score's.  step = one int32 in DEVICE memory, READ and
  * never written: the call must be issued BEFORE the step's bf_rollout_score, which increments that counter.  With s = *step, row s * T + t of

@@ -135,9 +135,20 @@ def test_entry_points_are_declared_and_bound():
         assert len(declared) == len(_lib.SIGNATURES[name][1]), name                   # one ctypes entry per declared parameter
     src = open(os.path.join(REPO, "bubbleformer_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS :=.*\bbubbles\.hip\b", src, flags=re.M)
-    common = open(os.path.join(REPO, "bubbleformer_amd", "csrc", "bf_common.h")).read()
-    physics = open(os.path.join(REPO, "bubbleformer_amd", "csrc", "physics.hip")).read()
-    assert "float denormalise(" in common and "float denormalise(" not in physics    # one definition, as nearest_src has
+    csrc = os.path.join(REPO, "bubbleformer_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip"))}
+    for sig in ("float denormalise(", "int nearest_src(", "float clip_norm(", "float eikonal_l1_px("):      # one definition each, in clip_store.h
+        assert {f: t.count(sig) for f, t in texts.items() if sig in t} == {"clip_store.h": 1}, sig
+
+
+def test_makefile_builds_every_hip_file():
+    """SRCS names exactly the *.hip files of csrc/: a file that is not listed would be left out of the library without a build error."""
+    csrc = os.path.join(REPO, "bubbleformer_amd", "csrc")
+    m = re.search(r"^SRCS :=(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
+    assert m
+    listed = m.group(1).split()
+    assert len(listed) == len(set(listed))
+    assert sorted(listed) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
 
 
 def test_workspace_query_and_size_limit():

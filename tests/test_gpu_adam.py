@@ -1,4 +1,4 @@
-"""GPU: the fused Adam kernel (csrc/patch.hip: bf_adam, torch.optim.Adam semantics) against torch.optim.Adam, and TrainStep(optimizer="adam")
+"""GPU: the fused Adam kernel (csrc/gradclip.hip: bf_adam, torch.optim.Adam semantics) against torch.optim.Adam, and TrainStep(optimizer="adam")
 (config/optim_cfg/adam.yaml) on FiLMAViT against the oracle and on the classic U-Net."""
 import numpy as np
 import pytest

@@ -101,6 +101,72 @@ def test_targets_are_the_stores_and_copies_are_exact(factor):
     assert int(past["counter"]) == steps and torch.isnan(past["rel_l2"]).all() and torch.isnan(past["next_in"]).all()
 
 
+def test_the_three_step_calls_read_the_same_store_frame():
+    """`rollout_score`, `rollout_heatflux` and `rollout_bubbles` of one step all report on the stored frame clamp(first[b] + (s + 1) * T + t,
+    0, total - 1), computed here in Python, including starts that need the clamp at either end of the store (`plan_rollouts` refuses those,
+    so no other test gets there), with a channel that is not its own field id, at full resolution and through `nearest_src`.  A synthetic
+    store inside a larger buffer: an unclamped index would read allocated memory and show up as a wrong value."""
+    from bubbleformer_amd import ops
+    from bubbleformer_amd.utils import physics
+    from tests import heatflux_restatement as H_
+    nf, total, H, W, C, T, steps, B, mb = 3, 12, 6, 10, 2, 2, 3, 3, 32
+    margin = (steps + 1) * T * H * W                                                  # floats: a multiple of 4, so the store stays 16-byte aligned
+    g = torch.Generator().manual_seed(7)
+    flat = torch.randn(2 * margin + nf * total * H * W, generator=g).cuda()
+    frames = flat[margin:margin + nf * total * H * W].view(nf, total, H, W)
+    frames[0] += 3.0                                                                  # the temperature field: heater_temp - temp does not vanish
+    assert frames.is_contiguous() and frames.data_ptr() % 16 == 0
+    dev = frames.device
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    table = (i32([2, 0]), f32([0.3, -0.2]), f32([1.7, 0.6]))                         # channel 0 = field 2 (signed distance), channel 1 = field 0 (temperature)
+    identity = (i32([0, 1, 2]), f32([0.0, 0.0, 0.0]), f32([1.0, 1.0, 1.0]))
+    first_host = [-5, 3, total - 1]                                                   # clamped at 0, in range, clamped at total - 1
+    first = torch.tensor(first_host, dtype=torch.int64, device=dev)
+    temps = [1.0, 1.3, 1.15]
+    heater = f32(temps)
+    for Ho, Wo in ((6, 10), (3, 5)):
+        spec = physics.HeaterSpec(1.0, x_min=-8.0, dx=16.0 / Wo)
+        for s in (0, steps - 1):
+            e = [[min(max(first_host[b] + (s + 1) * T + t, 0), total - 1) for t in range(T)] for b in range(B)]
+            if s == 0:
+                assert e[0][0] == 0 and e[2] == [total - 1] * T and e[1] == [3 + T, 3 + T + 1]      # both clamps and an in-range start are in play
+            gather = lambda tab: torch.stack([torch.cat([ops.clip_gather(frames, torch.tensor([e[b][t]], dtype=torch.int64, device=dev), 0, 1, tab, Ho, Wo)[0]
+                                                         for t in range(T)]) for b in range(B)])
+            pred, raw = gather(table), gather(identity)                               # (B, T, C, Ho, Wo) normalised, (B, T, nf, Ho, Wo) as stored
+            rows = slice(s * T, (s + 1) * T)
+            counter = lambda: torch.full((1,), s, dtype=torch.int32, device=dev)
+            nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+            # the scoring call: a prediction that IS the gathered frames e scores exactly 0, and is copied exactly
+            rel, crit, ep, et, nxt, arch = nan(B, steps * T, C), nan(B, steps), nan(B, steps * T), nan(B, steps * T), nan(B, T, C, Ho, Wo), nan(B, steps * T, C, Ho, Wo)
+            ops.rollout_score(pred, frames, first, counter(), table, 0, steps, rel, crit, ops.rollout_score_workspace(pred), ep, et, nxt, arch)
+            print(f"{Ho}x{Wo} step {s}: frames {e}, rel_l2 max {float(rel[:, rows].max()):.3e}")
+            assert torch.equal(rel[:, rows], torch.zeros_like(rel[:, rows]))
+            assert torch.equal(nxt, pred) and torch.equal(arch[:, rows], pred)
+            # the heat-flux call: its simulation rows against bf_heatflux_rows of the same raw frames
+            fp, ft = nan(B, steps * T), nan(B, steps * T)
+            ops.rollout_heatflux(pred, frames, first, counter(), table, 0, 1, heater, steps, fp, ft, x_min=spec.x_min, dx=spec.dx, lc=spec.lc,
+                                 conductivity=spec.conductivity)
+            liquid, vapour = H_.heater_cells(raw[:, :, 2, 0].cpu().numpy(), spec.x_min, spec.dx)
+            assert liquid > 0 and vapour > 0, (liquid, vapour)                        # otherwise the mask is not exercised
+            want = torch.stack([physics.heatflux_series(raw[b, :, 2].contiguous(), raw[b, :, 0].contiguous(), temps[b], spec) for b in range(B)])
+            got = ft[:, rows]
+            diff = (got.double() - want.double()).abs()                                # a heater row without a liquid cell has flux 0 on both sides
+            print(f"{Ho}x{Wo} step {s}: flux_tgt worst relative error {float((diff / want.double().abs())[want != 0].max()):.2e} (bound 2e-6), "
+                  f"bit-equal {torch.equal(got, want)}, {liquid} liquid / {vapour} vapour cells")
+            assert bool(want.isfinite().all()) and bool((want != 0).any()) and bool((diff <= 2e-6 * want.double().abs()).all())
+            # the census call: its simulation side against bf_bubble_census of the same raw frames
+            bub = {k: [torch.full((B, steps * T) + tail, -9, dtype=torch.int32, device=dev) for _ in range(2)]
+                   for k, tail in (("count", ()), ("cells", ()), ("attached", ()), ("area", (mb,)))}
+            ops.rollout_bubbles(pred, frames, first, counter(), table, 0, steps, 4, mb, ops.bubble_census_workspace(2 * B * T, Ho, Wo, mb, dev),
+                                *bub["count"], *bub["cells"], *bub["attached"], *bub["area"])
+            census = physics.bubble_census(raw[:, :, 2], connectivity=4, max_bubbles=mb)
+            print(f"{Ho}x{Wo} step {s}: bubbles per target frame {census.count.tolist()}")
+            assert int(census.count.min()) > 0
+            for k, want_k in (("count", census.count), ("cells", census.vapour_cells), ("attached", census.attached), ("area", census.area)):
+                assert torch.equal(bub[k][1][:, rows], want_k), k
+
+
 def _report_tensors(r):
     out = {"rel_l2": r.rel_l2, "criterion": r.criterion, "timesteps": r.timesteps}
     if r.eikonal_pred is not None:
