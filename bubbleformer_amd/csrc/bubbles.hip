@@ -266,6 +266,7 @@ struct RolloutBubbleArgs {
     int sdf_c, conn8, mb;
     int* count[2]; int* cells[2]; int* attached[2]; int* area[2];          // [0] the prediction, [1] the simulation
     char* ws; long slot, parents_off;
+    int* ring;                                                             // null, or the label images [2 sides][2 halves][B][T][Ho][Wo]: half s & 1
 };
 
 template <class P> __global__ void __launch_bounds__(NT) rollout_bubbles_kernel(RolloutBubbleArgs a) {
@@ -278,7 +279,8 @@ template <class P> __global__ void __launch_bounds__(NT) rollout_bubbles_kernel(
     else src = FrameSrc{v.predicted(bt, a.sdf_c), v.Wo, v.Ho, v.Wo, 1.f, 1.f, true, true, v.dv[a.sdf_c], v.diff[a.sdf_c]};
     const long row = v.row(s, b, t);
     char* slot = a.ws + ((long)bt * 2 + side) * a.slot;
-    const FrameOut out{a.count[side] + row, a.cells[side] + row, a.attached[side] + row, a.area[side] + row * a.mb, nullptr, nullptr, nullptr,
+    int* const labels = a.ring ? a.ring + ((((long)side * 2 + (s & 1)) * v.B + b) * v.T + t) * ((long)v.Ho * v.Wo) : nullptr;
+    const FrameOut out{a.count[side] + row, a.cells[side] + row, a.attached[side] + row, a.area[side] + row * a.mb, nullptr, nullptr, labels,
                        (long long*)slot};
     census_frame(parents_at<P>(slot, a.parents_off), src, out, v.Ho, v.Wo, a.conn8 != 0, a.mb);
 }
@@ -325,11 +327,12 @@ extern "C" int bf_bubble_census(const float* phi, int64_t frames, int H, int W, 
     return 0;
 }
 
-extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                  const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
-                                  int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
-                                  int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes,
-                                  int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+// bf_rollout_bubbles (ring = null) and bf_rollout_bubbles_labelled: one launch either way
+static int rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                           const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
+                           int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
+                           int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, int32_t* ring, void* ws, int64_t ws_bytes,
+                           int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
     RolloutStep v;
     if (const int rc = rollout_step_view(v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
                                          count_pred && count_tgt && cells_pred && cells_tgt && attached_pred && attached_tgt && area_pred && area_tgt && ws,
@@ -342,7 +345,7 @@ extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_
     BF_REQUIRE((uintptr_t)ws % 16 == 0, "bf_rollout_bubbles: the workspace must be 16-byte aligned");
     const WsLayout lay(Ho, Wo, max_bubbles);
     const RolloutBubbleArgs a{v, sdf_channel, connectivity == 8, max_bubbles, {count_pred, count_tgt}, {cells_pred, cells_tgt}, {attached_pred, attached_tgt},
-                              {area_pred, area_tgt}, (char*)ws, lay.slot, lay.parents_off};
+                              {area_pred, area_tgt}, (char*)ws, lay.slot, lay.parents_off, ring};
     const long n = (long)Ho * Wo;
     const dim3 grid((unsigned)(B * T), 2);
     if (n <= BUBBLE_LDS_CELLS) {
@@ -354,4 +357,26 @@ extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_
     }
     BF_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                                  const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
+                                  int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
+                                  int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes,
+                                  int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+    return rollout_bubbles(pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, sdf_channel, connectivity, max_bubbles, count_pred,
+                           count_tgt, cells_pred, cells_tgt, attached_pred, attached_tgt, area_pred, area_tgt, nullptr, ws, ws_bytes, B, T, C, H, W, Ho, Wo,
+                           steps, stream);
+}
+
+extern "C" int bf_rollout_bubbles_labelled(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields,
+                                           const int64_t* first, const int32_t* step, const int32_t* field, const float* diff, const float* div,
+                                           int sdf_channel, int connectivity, int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred,
+                                           int32_t* cells_tgt, int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt,
+                                           int32_t* labels, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps,
+                                           bf_stream_t stream) {
+    BF_REQUIRE(labels, "bf_rollout_bubbles_labelled: null pointer");
+    return rollout_bubbles(pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, sdf_channel, connectivity, max_bubbles, count_pred,
+                           count_tgt, cells_pred, cells_tgt, attached_pred, attached_tgt, area_pred, area_tgt, labels, ws, ws_bytes, B, T, C, H, W, Ho, Wo,
+                           steps, stream);
 }

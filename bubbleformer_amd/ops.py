@@ -1071,6 +1071,133 @@ def rollout_bubbles(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tenso
                                        _p(attached_pred), _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(ws), ws.numel(), *tail), "bf_rollout_bubbles")
 
 
+def bubble_links_workspace(pairs: int, max_bubbles: int, device) -> torch.Tensor:
+    """The workspace ``bubble_links`` (and, with pairs = 2 * B * T, ``rollout_bubble_links``) needs: allocate once, outside a graph capture.  It holds
+    the overlap tables that do not fit ``bubble_links_lds_entries()``; more records than the library supports are refused here, before any launch."""
+    nbytes = L.lib().bf_bubble_links_ws_bytes(int(pairs), int(max_bubbles))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"bubble_links_workspace: {pairs} pairs with {max_bubbles} records are not supported (at least one pair, "
+                                     "1 to 2^15 records per frame)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def bubble_links_lds_entries() -> int:
+    """A pair whose overlap table min(count_a, max_bubbles) x min(count_b, max_bubbles) has at most this many entries keeps it in LDS, a larger
+    one in the workspace (bf_bubble_links_lds_entries)."""
+    return int(L.lib().bf_bubble_links_lds_entries())
+
+
+def _link_rows(lead: tuple, mb: int) -> dict:
+    """name -> shape of the six outputs of a link call whose pair axes are ``lead``."""
+    return {"successor": lead + (mb,), "n_successors": lead + (mb,), "predecessor": lead + (mb,), "n_predecessors": lead + (mb,),
+            "departure_area": lead + (mb,), "events": lead + (5,)}
+
+
+def bubble_links(labels: torch.Tensor, count: torch.Tensor, attached: torch.Tensor, area: torch.Tensor, ws: torch.Tensor, successor: torch.Tensor,
+                 n_successors: torch.Tensor, predecessor: torch.Tensor, n_predecessors: torch.Tensor, departure_area: torch.Tensor,
+                 events: torch.Tensor) -> None:
+    """The links between the consecutive frames of N sequences (bf_bubble_links; include/bubbleformer_hip.h has the contract): labels (N, T, H, W),
+    count / attached (N, T) and area (N, T, max_bubbles) int32 as ``bubble_census`` left them -> successor, n_successors, predecessor,
+    n_predecessors, departure_area (N, T - 1, max_bubbles) and events (N, T - 1, 5) int32.  T = 1 launches nothing.  ws:
+    ``bubble_links_workspace(N * (T - 1), max_bubbles)``.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(labels)
+    i32 = torch.int32
+    if labels.dim() != 4 or labels.dtype != i32 or not labels.is_contiguous():
+        raise L.BubbleformerHipError("bubble_links: labels must be a contiguous int32 (sequences, T, H, W) tensor")
+    if area.dim() != 3:
+        raise L.BubbleformerHipError("bubble_links: area must be a (sequences, T, max_bubbles) tensor")
+    N, T, H, W = labels.shape
+    mb = int(area.shape[-1])
+    outs = dict(successor=successor, n_successors=n_successors, predecessor=predecessor, n_predecessors=n_predecessors, departure_area=departure_area,
+                events=events)
+    want = {"count": (count, (N, T), i32), "attached": (attached, (N, T), i32), "area": (area, (N, T, mb), i32), "ws": (ws, (ws.numel(),), torch.uint8)}
+    want.update({k: (outs[k], shape, i32) for k, shape in _link_rows((N, T - 1), mb).items()})
+    _check_tensors("bubble_links", labels.device, want)
+    if N < 1 or T < 1 or H < 1 or W < 1 or mb < 1:
+        raise L.BubbleformerHipError(f"bubble_links: needs at least one sequence of at least one frame of at least one cell, got {tuple(labels.shape)}")
+    if T == 1:
+        return
+    need = L.lib().bf_bubble_links_ws_bytes(N * (T - 1), mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("bubble_links: the workspace is smaller than bubble_links_workspace(sequences * (T - 1), max_bubbles)")
+    L.check(L.lib().bf_bubble_links(_p(labels), _p(count), _p(attached), _p(area), N, T, H, W, mb, _p(successor), _p(n_successors), _p(predecessor),
+                                    _p(n_predecessors), _p(departure_area), _p(events), _p(ws), ws.numel(), _stream()), "bf_bubble_links")
+
+
+def bubble_track_ids(count: torch.Tensor, successor: torch.Tensor, predecessor: torch.Tensor, track_id: torch.Tensor, n_tracks: torch.Tensor) -> None:
+    """Track ids of N sequences from their links (bf_bubble_track_ids; include/bubbleformer_hip.h has the contract): count (N, T), successor /
+    predecessor (N, T - 1, max_bubbles) int32 -> track_id (N, T, max_bubbles), 0 in unused slots, and n_tracks (N,) int32.  Allocates nothing."""
+    _require_gpu(count)
+    i32 = torch.int32
+    if count.dim() != 2 or track_id.dim() != 3:
+        raise L.BubbleformerHipError("bubble_track_ids: count must be (sequences, T) and track_id (sequences, T, max_bubbles)")
+    N, T = count.shape
+    mb = int(track_id.shape[-1])
+    _check_tensors("bubble_track_ids", count.device, {"count": (count, (N, T), i32), "successor": (successor, (N, T - 1, mb), i32),
+                   "predecessor": (predecessor, (N, T - 1, mb), i32), "track_id": (track_id, (N, T, mb), i32), "n_tracks": (n_tracks, (N,), i32)})
+    if N < 1 or T < 1 or mb < 1:
+        raise L.BubbleformerHipError(f"bubble_track_ids: needs at least one sequence, one frame and one record, got {tuple(track_id.shape)}")
+    L.check(L.lib().bf_bubble_track_ids(_p(count), _p(successor) if T > 1 else None, _p(predecessor) if T > 1 else None, N, T, mb, _p(track_id),
+                                        _p(n_tracks), _stream()), "bf_bubble_track_ids")
+
+
+def rollout_bubbles_labelled(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
+                             connectivity: int, max_bubbles: int, ws: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor,
+                             cells_pred: torch.Tensor, cells_tgt: torch.Tensor, attached_pred: torch.Tensor, attached_tgt: torch.Tensor,
+                             area_pred: torch.Tensor, area_tgt: torch.Tensor, labels: torch.Tensor) -> None:
+    """``rollout_bubbles`` that also leaves its label images (bf_rollout_bubbles_labelled): labels (2, 2, B, T, Ho, Wo) int32 is a ring of two
+    steps, [0] the prediction and [1] the simulation; step s writes half ``s & 1`` and leaves the other, which ``rollout_bubble_links`` still needs.
+    Everything else as ``rollout_bubbles``.  Allocates nothing."""
+    lead, tail = _rollout_step_args("rollout_bubbles_labelled", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    mb = int(max_bubbles)
+    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
+    _check_tensors("rollout_bubbles_labelled", pred.device, {"count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32),
+                   "cells_pred": (cells_pred, rows, i32), "cells_tgt": (cells_tgt, rows, i32), "attached_pred": (attached_pred, rows, i32),
+                   "attached_tgt": (attached_tgt, rows, i32), "area_pred": (area_pred, recs, i32), "area_tgt": (area_tgt, recs, i32),
+                   "labels": (labels, (2, 2, B, T, Ho, Wo), i32), "ws": (ws, (ws.numel(),), torch.uint8)})
+    if not 0 <= int(sdf_channel) < Cn:
+        raise L.BubbleformerHipError(f"rollout_bubbles_labelled: channel {sdf_channel} is not among the prediction's {Cn}")
+    need = L.lib().bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_bubbles_labelled: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
+    L.check(L.lib().bf_rollout_bubbles_labelled(*lead, int(sdf_channel), int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt),
+                                                _p(attached_pred), _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(labels), _p(ws), ws.numel(), *tail),
+            "bf_rollout_bubbles_labelled")
+
+
+def rollout_bubble_links(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int, max_bubbles: int,
+                         ws: torch.Tensor, labels: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor, attached_pred: torch.Tensor,
+                         attached_tgt: torch.Tensor, area_pred: torch.Tensor, area_tgt: torch.Tensor, links_pred: dict, links_tgt: dict) -> None:
+    """The links of one rollout step (bf_rollout_bubble_links; include/bubbleformer_hip.h has the contract), on the ring and the census rows the
+    step's ``rollout_bubbles_labelled`` wrote: per side and trajectory the pairs that end in a frame of step s = the int32 ``step`` tensor ON THE
+    DEVICE, which this call only reads -- issue it after ``rollout_bubbles_labelled`` and BEFORE the step's ``rollout_score``.  links_pred /
+    links_tgt: dicts of successor, n_successors, predecessor, n_predecessors, departure_area (B, steps*T - 1, max_bubbles) and events
+    (B, steps*T - 1, 5) int32; the pair that ends in frame t of step s is row s * T + t - 1.  ws: ``bubble_links_workspace(2 * B * T, max_bubbles)``.
+    A rollout of one frame (steps * T = 1) has no pair and launches nothing.  Allocates nothing."""
+    lead, tail = _rollout_step_args("rollout_bubble_links", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    mb = int(max_bubbles)
+    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
+    want = {"labels": (labels, (2, 2, B, T, Ho, Wo), i32), "count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32),
+            "attached_pred": (attached_pred, rows, i32), "attached_tgt": (attached_tgt, rows, i32), "area_pred": (area_pred, recs, i32),
+            "area_tgt": (area_tgt, recs, i32), "ws": (ws, (ws.numel(),), torch.uint8)}
+    shapes = _link_rows((B, steps * T - 1), mb)
+    for side, given in (("pred", links_pred), ("tgt", links_tgt)):
+        if sorted(given) != sorted(shapes):
+            raise L.BubbleformerHipError(f"rollout_bubble_links: links_{side} must hold exactly {sorted(shapes)}")
+        want.update({f"{k}_{side}": (given[k], shape, i32) for k, shape in shapes.items()})
+    _check_tensors("rollout_bubble_links", pred.device, want)
+    need = L.lib().bf_bubble_links_ws_bytes(2 * B * T, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_bubble_links: the workspace is smaller than bubble_links_workspace(2 * B * T, max_bubbles)")
+    if steps * T < 2:
+        return
+    both = [_p(side[k]) for k in ("successor", "n_successors", "predecessor", "n_predecessors", "departure_area", "events") for side in (links_pred, links_tgt)]
+    L.check(L.lib().bf_rollout_bubble_links(*lead, mb, _p(labels), _p(count_pred), _p(count_tgt), _p(attached_pred), _p(attached_tgt), _p(area_pred),
+                                            _p(area_tgt), *both, _p(ws), ws.numel(), *tail), "bf_rollout_bubble_links")
+
+
 def grad_norm_workspace(n: int, device) -> torch.Tensor:
     """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
     return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)

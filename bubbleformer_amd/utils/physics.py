@@ -133,14 +133,20 @@ def kde_kl_divergence(sim: torch.Tensor, model: torch.Tensor, points: int = 1000
 @dataclasses.dataclass(frozen=True)
 class BubbleSpec:
     """The bubble census of a rollout (``evaluate_rollouts(..., bubbles=BubbleSpec())``): which output field is the signed distance, how cells
-    connect (4: edges, 8: edges and corners), how many per-bubble records a frame keeps, and the cell size for the equivalent diameters."""
+    connect (4: edges, 8: edges and corners), how many per-bubble records a frame keeps, and the cell size for the equivalent diameters.  With
+    ``track`` the bubbles are also followed from frame to frame (``bubble_tracks``): the report gains the link, event and departure rows."""
     sdf_field: str = "dfun"
     connectivity: int = 4
     max_bubbles: int = 256
     dx: float = 1.0 / 32
+    track: bool = False
 
     def __post_init__(self):
         _check_census_arguments(self.connectivity, self.max_bubbles)
+        if not isinstance(self.track, bool):
+            raise ValueError(f"track must be True or False, got {self.track!r}")
+        if self.track and int(self.max_bubbles) > MAX_TRACKED_BUBBLES:
+            raise ValueError(f"tracking keeps at most {MAX_TRACKED_BUBBLES} records per frame, got max_bubbles = {self.max_bubbles}")
         if not self.dx > 0:
             raise ValueError(f"dx must be positive, got {self.dx}")
 
@@ -150,6 +156,9 @@ class BubbleSpec:
         if self.sdf_field not in fields:
             raise ValueError(f"the bubble census needs the field {self.sdf_field!r} among the output fields {fields}")
         return fields.index(self.sdf_field)
+
+
+MAX_TRACKED_BUBBLES = 1 << 15          # bf_bubble_links' limit: an overlap table of max_bubbles^2 int32 indices
 
 
 def _check_census_arguments(connectivity, max_bubbles) -> None:
@@ -210,3 +219,73 @@ def bubble_census(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int 
     ops.bubble_census(flat, int(connectivity), mb, ws, count, cells, attached, area, centroid, on_heater, labels)
     return BubbleCensus(count.reshape(lead), cells.reshape(lead), attached.reshape(lead), area.reshape(lead + (mb,)), centroid.reshape(lead + (mb, 2)),
                         on_heater.reshape(lead + (mb,)), (int(H), int(W)), labels.reshape(lead + (int(H), int(W))) if labels is not None else None)
+
+
+def departure_diameters(departure_area: torch.Tensor, dx: float = 1.0 / 32) -> torch.Tensor:
+    """The equivalent diameters of the bubbles that leave the heater, a 1-D fp32 device tensor in row order, from ``departure_area`` rows (area at
+    the departing bubble's slot, 0 elsewhere, -1 in an invalid pair).  SYNCHRONISES: dropping the empty slots makes the host wait for their number."""
+    return equivalent_diameter(departure_area[departure_area > 0], dx)
+
+
+def departure_frequency(events: torch.Tensor) -> torch.Tensor:
+    """events (..., pairs, 5) -> (...) fp64: departures per frame pair, over the valid pairs (NaN without one).  On the device; never synchronises."""
+    departures = events[..., 4]
+    valid = departures >= 0
+    return departures.clamp(min=0).sum(-1).to(torch.float64) / valid.sum(-1).to(torch.float64)
+
+
+@dataclasses.dataclass
+class BubbleTracks:
+    """What ``bubble_tracks`` returns; every tensor is int32 on the device and keeps phi's leading dims.  Pair t is frames t and t + 1; slot k of a
+    row is bubble k + 1 of the pair's earlier (successor, n_successors, departure_area) or later (predecessor, n_predecessors) frame; 0 means none."""
+    census: BubbleCensus                            # of every frame, label images included
+    successor: torch.Tensor                         # (..., T-1, max_bubbles)  the later frame's bubble that shares most cells, ties to the smallest
+    n_successors: torch.Tensor                      # (..., T-1, max_bubbles)  how many share a cell
+    predecessor: torch.Tensor                       # (..., T-1, max_bubbles)
+    n_predecessors: torch.Tensor                    # (..., T-1, max_bubbles)
+    departure_area: torch.Tensor                    # (..., T-1, max_bubbles)  cells of a bubble that leaves the heater row in this pair, else 0
+    events: torch.Tensor                            # (..., T-1, 5)            births, deaths, merges, splits, departures
+    track_id: torch.Tensor                          # (..., T, max_bubbles)    1, 2, ... per sequence by first appearance, 0 in unused slots
+    n_tracks: torch.Tensor                          # (...)
+
+    def departure_diameters(self, dx: float = 1.0 / 32) -> torch.Tensor:
+        """The equivalent diameters of all departing bubbles, a 1-D fp32 device tensor in pair order.  SYNCHRONISES (it compacts)."""
+        return departure_diameters(self.departure_area, dx)
+
+    def lifetimes(self) -> torch.Tensor:
+        """Frames every track lives, a 1-D int64 device tensor: the tracks of the first sequence in id order, then the next one's.  SYNCHRONISES
+        (it compacts).  A track cut by the first or last frame counts the frames it was seen."""
+        mb = self.track_id.shape[-1]
+        T = self.track_id.shape[-2]
+        ids = self.track_id.reshape(-1, T * mb).to(torch.int64)
+        seen = torch.zeros(ids.shape[0], T * mb + 1, dtype=torch.int64, device=ids.device).scatter_add_(1, ids, torch.ones_like(ids))[:, 1:]
+        return seen[seen > 0]
+
+    def departure_frequency(self) -> torch.Tensor:
+        """(...) fp64: departures per frame pair of every sequence.  On the device; never synchronises."""
+        return departure_frequency(self.events)
+
+
+def bubble_tracks(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int = 256) -> BubbleTracks:
+    """The bubbles of phi (..., T, H, W), a signed-distance field in physical units on the device, followed along axis -3: the census of every
+    frame with its label images (``bubble_census``), the links of every consecutive pair and their events (``ops.bubble_links``, a workgroup per
+    pair) and the track ids (``ops.bubble_track_ids``, a workgroup per sequence).  Three launches (one for T = 1: its pair tensors are empty);
+    never synchronises; the same bits on every call, and for a sequence alone or in a batch."""
+    _check_census_arguments(connectivity, max_bubbles)
+    if phi.dim() < 3:
+        raise ValueError(f"bubble_tracks expects (..., T, H, W), got {tuple(phi.shape)}")
+    if int(max_bubbles) > MAX_TRACKED_BUBBLES:
+        raise ValueError(f"tracking keeps at most {MAX_TRACKED_BUBBLES} records per frame, got max_bubbles = {max_bubbles}")
+    from .. import ops
+    census = bubble_census(phi, connectivity=connectivity, max_bubbles=max_bubbles, return_labels=True)
+    lead, (T, H, W), mb = tuple(phi.shape[:-3]), phi.shape[-3:], int(max_bubbles)
+    N = census.count.numel() // T
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=phi.device)
+    rows = {k: new(*shape) for k, shape in ops._link_rows((N, T - 1), mb).items()}
+    if T > 1:
+        ops.bubble_links(census.labels.reshape(N, T, H, W), census.count.reshape(N, T), census.attached.reshape(N, T), census.area.reshape(N, T, mb),
+                         ops.bubble_links_workspace(N * (T - 1), mb, phi.device), **rows)
+    track_id, n_tracks = new(N, T, mb), new(N)
+    ops.bubble_track_ids(census.count.reshape(N, T), rows["successor"], rows["predecessor"], track_id, n_tracks)
+    return BubbleTracks(census, **{k: v.reshape(lead + v.shape[1:]) for k, v in rows.items()}, track_id=track_id.reshape(lead + (T, mb)),
+                        n_tracks=n_tracks.reshape(lead))

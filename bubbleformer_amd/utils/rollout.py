@@ -138,6 +138,15 @@ class RolloutReport:
     bubble_area_pred: Optional[torch.Tensor] = None         # (B, steps*T, max_bubbles) int32 cells, in raster order of the first cell, then 0
     bubble_area_target: Optional[torch.Tensor] = None
     bubble_dx: Optional[float] = None                       # the cell size of the census' BubbleSpec (for the equivalent diameters)
+    # with BubbleSpec(track=True): row s * T + t - 1 is the pair of frames that ends in frame t of step s (physics.bubble_tracks), else None
+    bubble_events_pred: Optional[torch.Tensor] = None           # (B, steps*T-1, 5) int32   births, deaths, merges, splits, departures
+    bubble_events_target: Optional[torch.Tensor] = None
+    bubble_successor_pred: Optional[torch.Tensor] = None        # (B, steps*T-1, max_bubbles) int32
+    bubble_successor_target: Optional[torch.Tensor] = None
+    bubble_predecessor_pred: Optional[torch.Tensor] = None      # (B, steps*T-1, max_bubbles) int32
+    bubble_predecessor_target: Optional[torch.Tensor] = None
+    bubble_departure_area_pred: Optional[torch.Tensor] = None   # (B, steps*T-1, max_bubbles) int32 cells of a bubble that leaves the heater, else 0
+    bubble_departure_area_target: Optional[torch.Tensor] = None
 
     def save(self, path) -> None:
         """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
@@ -150,6 +159,9 @@ class RolloutReport:
             out["heatflux_pred"], out["heatflux_target"] = self.heatflux_pred, self.heatflux_target
         if self.bubble_count_pred is not None:
             for key in _BUBBLE_KEYS:
+                out[key] = getattr(self, key)
+        if self.bubble_events_pred is not None:
+            for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
         torch.save(out, path)
 
@@ -200,6 +212,51 @@ class RolloutReport:
         return kde_kl_divergence(sim, model, points)
 
 
+    def _tracks(self):
+        if self.bubble_events_pred is None:
+            raise ValueError("this report has no bubble tracking: call evaluate_rollouts(..., bubbles=BubbleSpec(track=True))")
+
+    def bubble_track_ids(self) -> Tuple[Tuple[torch.Tensor, torch.Tensor], Tuple[torch.Tensor, torch.Tensor]]:
+        """((track_id, n_tracks) of the simulation, the same of the model): track_id (B, steps*T, max_bubbles) and n_tracks (B,) int32, every
+        trajectory one sequence (``ops.bubble_track_ids``, one launch per side, after the rollout).  On the device; never synchronises."""
+        from .. import ops
+        self._tracks()
+        out = []
+        for count, succ, pred in ((self.bubble_count_target, self.bubble_successor_target, self.bubble_predecessor_target),
+                                  (self.bubble_count_pred, self.bubble_successor_pred, self.bubble_predecessor_pred)):
+            B, F = count.shape
+            ids = torch.empty((B, F, succ.shape[-1]), dtype=torch.int32, device=count.device)
+            n = torch.empty(B, dtype=torch.int32, device=count.device)
+            ops.bubble_track_ids(count, succ, pred, ids, n)
+            out.append((ids, n))
+        return tuple(out)
+
+    def departure_diameters(self, dx: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(simulation, model): the equivalent diameters of the bubbles that leave the heater, each a 1-D fp32 device tensor in report order.
+        SYNCHRONISES, as ``bubble_diameters`` does."""
+        from .physics import departure_diameters
+        self._tracks()
+        dx = self.bubble_dx if dx is None else dx
+        return departure_diameters(self.bubble_departure_area_target, dx), departure_diameters(self.bubble_departure_area_pred, dx)
+
+    def departure_frequency(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(simulation, model): (B,) fp64 departures per frame pair of every trajectory.  On the device; never synchronises."""
+        from .physics import departure_frequency
+        self._tracks()
+        return departure_frequency(self.bubble_events_target), departure_frequency(self.bubble_events_pred)
+
+    def departure_diameter_kl(self, points: int = 1000) -> torch.Tensor:
+        """KL(simulation || model) of the departure-diameter distributions: ``physics.kde_kl_divergence`` of ``departure_diameters()``, a 0-d fp64
+        device tensor; NaN when either side has fewer than two departures, as ``bubble_size_kl``.  Synchronises as ``departure_diameters`` does."""
+        from .physics import kde_kl_divergence
+        sim, model = self.departure_diameters()
+        if sim.numel() < 2 or model.numel() < 2:
+            return torch.full((), float("nan"), dtype=torch.float64, device=sim.device)
+        return kde_kl_divergence(sim, model, points)
+
+
+_TRACK_KEYS = ("bubble_events_pred", "bubble_events_target", "bubble_successor_pred", "bubble_successor_target", "bubble_predecessor_pred",
+               "bubble_predecessor_target", "bubble_departure_area_pred", "bubble_departure_area_target")
 _BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
                 "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
 
@@ -223,7 +280,9 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     the heater heat flux of every predicted and simulated frame (``ops.rollout_heatflux``, issued right before the scoring call and captured
     with it); ``None`` leaves the launches and the report as they are without it.  With ``bubbles`` (a ``physics.BubbleSpec``) the step
     likewise leaves the bubble census of every predicted and simulated frame (``ops.rollout_bubbles``, one more launch before the scoring
-    call): the ``bubble_*`` and ``vapour_fraction_*`` rows of the report.  Never synchronises."""
+    call): the ``bubble_*`` and ``vapour_fraction_*`` rows of the report; with ``BubbleSpec(track=True)`` that launch also leaves its label
+    images and one more (``ops.rollout_bubble_links``) follows the bubbles into this step's frames: the ``bubble_events_*``, ``bubble_successor_*``,
+    ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows.  Never synchronises."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
@@ -266,7 +325,16 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         bub = {"count": rows(), "cells": rows(), "attached": rows(), "area": rows(mb)}
         bub_args = (bubbles.channel(fields), steps, int(bubbles.connectivity), mb, ops.bubble_census_workspace(2 * B * T, Ho, Wo, mb, device),
                     *bub["count"], *bub["cells"], *bub["attached"], *bub["area"])
-        before_score.append(lambda pred, step: ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args))
+        if not bubbles.track:
+            before_score.append(lambda pred, step: ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args))
+        else:                                       # the labelled census in its place, then the links of the pairs that end in this step
+            ring = torch.empty((2, 2, B, T, Ho, Wo), dtype=torch.int32, device=device)
+            link_rows = [{k: torch.empty((B,) + shape, dtype=torch.int32, device=device) for k, shape in ops._link_rows((steps * T - 1,), mb).items()}
+                         for _ in range(2)]
+            link_ws = ops.bubble_links_workspace(2 * B * T, mb, device)
+            before_score.append(lambda pred, step: ops.rollout_bubbles_labelled(pred, store.frames, first, step, store.out_tab, *bub_args, ring))
+            before_score.append(lambda pred, step: ops.rollout_bubble_links(pred, store.frames, first, step, store.out_tab, steps, mb, link_ws, ring,
+                                                                            *bub["count"], *bub["attached"], *bub["area"], *link_rows))
 
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
@@ -306,4 +374,8 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         report.vapour_fraction_pred, report.vapour_fraction_target = (fraction(c) for c in bub["cells"])
         report.bubble_area_pred, report.bubble_area_target = bub["area"]
         report.bubble_dx = float(bubbles.dx)
+        if bubbles.track:
+            for key in ("events", "successor", "predecessor", "departure_area"):
+                setattr(report, f"bubble_{key}_pred", link_rows[0][key])
+                setattr(report, f"bubble_{key}_target", link_rows[1][key])
     return report

@@ -35,6 +35,7 @@
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
+ *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
@@ -443,6 +444,55 @@ int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_str
                        int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt, int32_t* attached_pred,
                        int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W,
                        int Ho, int Wo, int steps, bf_stream_t stream);
+/* bf_rollout_bubbles that also leaves its label images: labels [2 sides][2 halves][B][T][Ho][Wo] int32 is a ring of two steps, side 0 the prediction,
+ * side 1 the simulation; the call for step s = *step writes bf_bubble_census' label image of frame (b, t) into half s & 1 and touches nothing of the
+ * other half, which still holds step s - 1 for bf_rollout_bubble_links.  Everything else, the step counter included, is bf_rollout_bubbles'. */
+int bf_rollout_bubbles_labelled(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                                const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
+                                int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt, int32_t* attached_pred,
+                                int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, int32_t* labels, void* ws, int64_t ws_bytes, int B, int T,
+                                int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+/* Bubbles followed from frame to frame (csrc/bubble_tracks.hip; the reference has no program for it).  labels [sequences][T][H][W], count / attached
+ * [sequences][T] and area [sequences][T][max_bubbles] are what bf_bubble_census left for sequences * T frames; a pair is two consecutive frames a, b
+ * of one sequence, pair row q = sequence * (T - 1) + t for frames t, t + 1.  With ka = min(count_a, max_bubbles), kb likewise (labels above them count
+ * as liquid) and overlap[i][j] = the number of cells with La == i and Lb == j, per pair:
+ *   successor [pairs][max_bubbles] int32       slot i - 1: the j of the largest overlap[i][j] > 0, ties to the smallest j, 0 if none;
+ *   n_successors                               the number of j with overlap[i][j] > 0;
+ *   predecessor, n_predecessors                the same per bubble j of b over the bubbles i of a (ties to the smallest i);
+ *   departure_area                             area_a[i] when bubble i departs, else 0: i <= attached_a, j = successor[i] > attached_b, predecessor[j] == i;
+ *   events [pairs][5] int32                    births (j without predecessor), deaths (i without successor), merges (n_predecessors >= 2),
+ *                                              splits (n_successors >= 2), departures.
+ * Slots behind ka / kb hold 0.  A pair with a frame whose count is -1 holds -1 in every output.  T == 1 launches nothing.  One workgroup owns a pair;
+ * its ka x kb table is in LDS when ka * kb <= bf_bubble_links_lds_entries(), in its slice of the workspace otherwise (a workgroup-uniform branch on the
+ * device).  Integer adds only: the same bits on every call, and for a pair alone or in a batch.  Any H, W >= 1 with H * W <= 2^24, max_bubbles <= 2^15.
+ * Allocation-free, capturable, never makes the host wait.  ws: bf_bubble_links_ws_bytes(pairs, max_bubbles) bytes, 16-byte aligned, contents
+ * irrelevant before and after (0 from the query: sizes out of range). */
+int64_t bf_bubble_links_lds_entries(void);
+int64_t bf_bubble_links_ws_bytes(int64_t pairs, int max_bubbles);
+int bf_bubble_links(const int32_t* labels, const int32_t* count, const int32_t* attached, const int32_t* area, int64_t sequences, int T, int H, int W,
+                    int max_bubbles, int32_t* successor, int32_t* n_successors, int32_t* predecessor, int32_t* n_predecessors, int32_t* departure_area,
+                    int32_t* events, void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* Track ids from the links: bubble j of frame t + 1 continues bubble i of frame t iff predecessor[j] == i and successor[i] == j; every other bubble
+ * (every bubble of frame 0, and of the later frame of a pair that holds -1) starts a new track.  Tracks are numbered 1, 2, ... per sequence in order of
+ * (frame, bubble number) of their first member.  count [sequences][T]; successor, predecessor [sequences][T - 1][max_bubbles] (unread when T == 1);
+ * track_id [sequences][T][max_bubbles] int32, 0 in unused slots; n_tracks [sequences] int32.  One workgroup per sequence walks the frames in order. */
+int bf_bubble_track_ids(const int32_t* count, const int32_t* successor, const int32_t* predecessor, int64_t sequences, int T, int max_bubbles,
+                        int32_t* track_id, int32_t* n_tracks, bf_stream_t stream);
+/* bf_bubble_links for ONE rollout step, both sides in one call, on the ring bf_rollout_bubbles_labelled filled and the census rows it wrote.  step is
+ * READ and never written: issue the call after the step's bf_rollout_bubbles_labelled and BEFORE its bf_rollout_score.  With s = *step, per side and
+ * trajectory b the pairs that end in a frame of step s: (t - 1, t) for t = 1 .. T - 1 from half s & 1, and for s > 0 the pair (frame T - 1 of half
+ * (s - 1) & 1, frame 0 of half s & 1).  The pair that ends in frame t goes to row s * T + t - 1 of [B][steps*T - 1][max_bubbles] (events:
+ * [B][steps*T - 1][5]); no other row is touched, and with s outside [0, steps) nothing is written.  count_* / attached_* [B][steps*T] and
+ * area_* [B][steps*T][max_bubbles] are the census rows.  pred, frames, ..., div and the sizes are bf_rollout_score's (checked, the fields unread);
+ * steps * T >= 2.  ws: bf_bubble_links_ws_bytes(2 * B * T, max_bubbles) bytes, 16-byte aligned. */
+int bf_rollout_bubble_links(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                            const int32_t* step, const int32_t* field, const float* diff, const float* div, int max_bubbles, const int32_t* labels,
+                            const int32_t* count_pred, const int32_t* count_tgt, const int32_t* attached_pred, const int32_t* attached_tgt,
+                            const int32_t* area_pred, const int32_t* area_tgt, int32_t* successor_pred, int32_t* successor_tgt, int32_t* n_successors_pred,
+                            int32_t* n_successors_tgt, int32_t* predecessor_pred, int32_t* predecessor_tgt, int32_t* n_predecessors_pred,
+                            int32_t* n_predecessors_tgt, int32_t* departure_area_pred, int32_t* departure_area_tgt, int32_t* events_pred,
+                            int32_t* events_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps,
+                            bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
