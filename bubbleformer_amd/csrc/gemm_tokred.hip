@@ -548,7 +548,7 @@ extern "C" int64_t bf_gemm_tokred_ws_floats(int Nout, int Kin, int64_t M) {
 }
 
 // Returns 0 when done, 1 when the shape is not covered (the caller then runs bf_gemm's token-reduction form), < 0 on error.
-// ---- deferred slab sums (library-internal, model.hip): bf_gemm_tokred_deferred leaves its slab sum PENDING -- the next deferred call on the
+// ---- deferred slab sums (library-internal, model.hip; flushed by model_common.h's Fork): bf_gemm_tokred_deferred leaves its slab sum PENDING -- the next deferred call on the
 // same stream carries it in extra workgroups of its own launch (FoldRed), bf_gemm_tokred_flush runs what is left as a launch of its own.
 // The caller alternates nothing: the two halves of `ws` are used in turn, so a pending sum's slabs are never the next launch's target.
 // One record per device, looked up once per call.  It remembers the stream that produced the slabs: a pending sum is only ever folded into,

@@ -47,6 +47,6 @@ class FiLMMLP(nn.Module):
 
     def forward(self, x: torch.Tensor, cond) -> torch.Tensor:
         """gamma * x + beta with (gamma, beta) = film_net(cond).chunk(2), x (B, T, C, h, w) (linear_layers.py:63-77), on native kernels.
-        In the model the modulation rides inside the fused patch embed (csrc/model.hip: bf_embed_fwd) instead."""
+        In the model the modulation rides inside the fused patch embed (csrc/embed_debed.hip: bf_embed_fwd) instead."""
         from .. import ops
         return ops.film(x, cond, *self.film_params())

@@ -378,7 +378,12 @@ def test_training_mode_draws_masks_and_eval_is_deterministic():
 def test_batched_stage_preparation_is_bit_identical(monkeypatch):
     """bf_prep_stages (all trunk stages' bf16 weight copies, out-projection folds and stochastic-depth tables in one launch per 12
     stages) against the per-stage preparation launches it replaces: same prediction bit for bit in eval and in training mode under a
-    fixed seed, same loss, and the prepared records are consumed (nothing left for a later call)."""
+    fixed seed, same loss, and the prepared records are consumed (nothing left for a later call).  Both arms take the per-stage Python
+    path (BF_TRUNK_NATIVE=0): the native trunk call always prepares in batches, so only there does BF_PREP_AHEAD choose between the two
+    preparations.  The training-mode run also takes the backward: the operands only it reads (the alpha-scaled out-projection weight,
+    the transposed fc2 copy, the stochastic-depth table) are compared through every parameter gradient -- the slab-summed weight
+    gradients bit for bit, the rest within four times what two identical runs differ by (the convention of
+    test_native_trunk_call_and_folded_slab_sums_change_no_bit)."""
     from bubbleformer_amd import ops
     spec, z, model = build_product_model("tiny_d64", torch.bfloat16)
     from bubbleformer_amd.layers.attention import DropPath
@@ -394,15 +399,34 @@ def test_batched_stage_preparation_is_bit_identical(monkeypatch):
         torch.manual_seed(5)
         loss, pred = model.forward_loss(x, c, y)
         assert not ops._LINKS.prepared
-        return float(loss), pred.clone()
+        grads = None
+        if train:
+            model.zero_grad(set_to_none=True)
+            loss.backward()
+            torch.cuda.synchronize()
+            grads = {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+        return float(loss), pred.clone(), grads
 
+    monkeypatch.setenv("BF_TRUNK_NATIVE", "0")
     got = {}
     for mode in ("1", "0"):
         monkeypatch.setenv("BF_PREP_AHEAD", mode)
         got[mode] = (run(False), run(True))
+    again = run(True)[2]                             # BF_PREP_AHEAD=0 once more: what two identical runs differ by
     for a, b in zip(got["1"], got["0"]):
         assert a[0] == b[0] and torch.equal(a[1], b[1])
     assert got["1"][0][0] != got["1"][1][0]          # the training-mode run really dropped something
+    g1, g0 = got["1"][1][2], got["0"][1][2]
+    exact = ("input_head.weight", "input_head.bias", "output_head.weight", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+    noise = max(float((g0[k] - again[k]).abs().max()) for k in g0)
+    print("run-to-run noise of the parameter gradients: %.3e" % noise)
+    assert set(g1) == set(g0) and any(k.startswith("blocks.") and k.endswith(exact) for k in g0)
+    for k in g0:
+        if k.startswith("blocks.") and k.endswith(exact):
+            assert torch.equal(g1[k], g0[k]), k
+        else:
+            diff = float((g1[k] - g0[k]).abs().max())
+            assert diff <= max(noise, 1e-30) * 4 + 1e-12, (k, diff, noise)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
