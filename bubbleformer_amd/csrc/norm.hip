@@ -687,6 +687,7 @@ static int in_stats_impl(int dtype, const void* x, int frames, int S, int C, con
 extern "C" int bf_in_stats_merge_slices(int dtype, int frames, int S, int C, int rows, const float* w, const float* b, const float* g, int gdiv,
                                         const float* gb, float* mean, float* rstd, float* sc, float* sh, float* ws, bf_stream_t stream) {
     BF_REQUIRE(w && b && mean && rstd && sc && sh && ws && frames > 0 && S > 0 && C > 0 && rows > 0, "bf_in_stats_merge_slices: bad arguments");
+    BF_REQUIRE(C % (dtype == BF_DTYPE_BF16 ? 8 : 4) == 0, "bf_in_stats_merge_slices: C must be a multiple of the 16-byte chunk");
     const SliceCfg cfg = slice_cfg(dtype, S, C);
     if (!cfg.sliced || bf_cdiv(S, rows) > bf_cdiv(S, cfg.rows)) return 1;
     if (gdiv < 1) gdiv = 1;
@@ -757,6 +758,8 @@ static int in_bwd_impl(int dtype, const void* dy, const void* x, const void* add
     BF_REQUIRE(dy && x && dx && mean && rstd && w && b, "bf_in_bwd: null pointer");
     const int ch = dtype == BF_DTYPE_BF16 ? 8 : 4;
     BF_REQUIRE(C % ch == 0, "bf_in_bwd: C must be a multiple of the 16-byte chunk");
+    // dg / dgb are the gradients of y = (xhat * w + b) * g + gb; behind a GELU they are sum dy * gelu(z) and sum dy, which {s1, s2} do not give
+    BF_REQUIRE(!(gelu && (dg || dgb)), "bf_in_bwd: dg / dgb are not available with gelu");
     dim3 grid(frames, bf_cdiv(C, CPB));
     if (gdiv < 1) gdiv = 1;
     hipStream_t st = (hipStream_t)stream;

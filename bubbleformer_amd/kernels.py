@@ -36,24 +36,25 @@ def gemm_tokred(dy, x, out, accumulate=False, colsum=None):
     return True
 
 
-def in_stats(x, frames, S, Cc, w, b, g=None, gdiv=1, gb=None):
+def in_stats(x, frames, S, Cc, w, b, g=None, gdiv=1, gb=None, use_ws=True):
     dev = x.device
     mean, rstd, sc, sh = (torch.empty(frames, Cc, dtype=torch.float32, device=dev) for _ in range(4))
-    ws = torch.empty(L.lib().bf_in_ws_floats(_dt(x.dtype), frames, S, Cc), dtype=torch.float32, device=dev)
+    ws = torch.empty(L.lib().bf_in_ws_floats(_dt(x.dtype), frames, S, Cc), dtype=torch.float32, device=dev) if use_ws else None
     L.check(L.lib().bf_in_stats(_dt(x.dtype), _p(x), frames, S, Cc, _p(w), _p(b), _p(g), gdiv, _p(gb), _p(mean), _p(rstd), _p(sc),
                                 _p(sh), _p(ws), _stream()), "bf_in_stats")
     return mean, rstd, sc, sh
 
 
-def in_bwd(dy, x, frames, S, Cc, mean, rstd, w, b, add=None, g=None, gdiv=1, gelu=False, use_ws=True):
-    """InstanceNorm backward through the C ABI: returns (dx, dw, db)."""
+def in_bwd(dy, x, frames, S, Cc, mean, rstd, w, b, add=None, g=None, gdiv=1, gelu=False, use_ws=True, dw=None, db=None, dg=None, dgb=None):
+    """InstanceNorm backward through the C ABI: returns (dx, dw, db).  dw / db (given: accumulated into, as they are; default: fresh zeros)
+    and dg / dgb ([ceil(frames / gdiv)][C], accumulated into where given, not computed otherwise) are the caller's tensors."""
     dev = x.device
     dx = torch.empty_like(x)
-    dw = torch.zeros(Cc, dtype=torch.float32, device=dev)
-    db = torch.zeros(Cc, dtype=torch.float32, device=dev)
+    dw = torch.zeros(Cc, dtype=torch.float32, device=dev) if dw is None else dw
+    db = torch.zeros(Cc, dtype=torch.float32, device=dev) if db is None else db
     ws = torch.empty(L.lib().bf_in_ws_floats(_dt(x.dtype), frames, S, Cc), dtype=torch.float32, device=dev) if use_ws else None
     L.check(L.lib().bf_in_bwd(_dt(x.dtype), _p(dy), _p(x), _p(add), _p(dx), frames, S, Cc, _p(mean), _p(rstd), _p(w), _p(b), _p(g), gdiv,
-                              int(gelu), _p(dw), _p(db), None, None, _p(ws), _stream()), "bf_in_bwd")
+                              int(gelu), _p(dw), _p(db), _p(dg), _p(dgb), _p(ws), _stream()), "bf_in_bwd")
     return dx, dw, db
 
 

@@ -185,7 +185,8 @@ int64_t bf_in_ws_floats(int dtype, int frames, int S, int C);
 /* out = [resid +] z * sc[f,c] + sh[f,c]   (sh may be NULL = 0) */
 int bf_affine_apply(int dtype, const void* z, const void* resid, const float* sc, const float* sh, void* out, int64_t nrows,
                     int S, int C, bf_stream_t stream);
-/* backward of y = act(xhat*w + b) [*g]; dx = ... [+ add]; dw/db/dg/dgb accumulate (fp32 atomics) */
+/* backward of y = act(xhat*w + b) [*g]; dx = ... [+ add]; dw/db/dg/dgb accumulate (fp32 atomics).  dg / dgb [ceil(frames/gdiv)][C] are the
+ * gradients of the post scale / shift of an identity act (dg = w*s2 + b*s1, dgb = s1); with gelu they are refused (an error is returned). */
 int bf_in_bwd(int dtype, const void* dy, const void* x, const void* add, void* dx, int frames, int S, int C, const float* mean,
               const float* rstd, const float* w, const float* b, const float* g, int gdiv, int gelu, float* dw, float* db,
               float* dg, float* dgb, float* ws /* optional, bf_in_ws_floats(): per-frame partials + reduce instead of atomics */,
