@@ -187,6 +187,10 @@ SIGNATURES = {
     "bf_bubble_links": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "bf_bubble_track_ids": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp]),
     "bf_rollout_bubble_links": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int] + [vp] * 20 + [i64] + [C.c_int] * 8 + [vp]),
+    "bf_field_errors_ws_bytes": (i64, [i64, C.c_int, C.c_int]),
+    "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp, fp, fp, vp, i64, vp]),
+    "bf_rollout_errors": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp,
+                                    fp, fp, vp, i64] + [C.c_int] * 8 + [vp]),
     "bf_lp_rows_ws_doubles": (i64, [i64, i64]),
     "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
     "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),

@@ -1198,6 +1198,79 @@ def rollout_bubble_links(pred: torch.Tensor, frames: torch.Tensor, first: torch.
                                             _p(area_tgt), *both, _p(ws), ws.numel(), *tail), "bf_rollout_bubble_links")
 
 
+_ERROR_ROWS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
+               "spectrum_target")
+
+
+def field_errors_workspace(frames: int, H: int, W: int, device) -> torch.Tensor:
+    """The workspace ``field_errors`` (and, with frames = B * T * C, ``rollout_errors``) needs: allocate once, outside a graph capture.  It holds the
+    fp64 row-to-column intermediate of the transforms; a side above 1024 is refused here, before any launch."""
+    nbytes = L.lib().bf_field_errors_ws_bytes(int(frames), int(H), int(W))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"field_errors_workspace: {frames} frames of {H} x {W} are not supported (at least one frame, sides from 1 to 1024)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _error_rows(who: str, device, lead: tuple, K: int, rows: dict, ws: torch.Tensor):
+    """The nine optional outputs of the error calls, checked -> their pointers in the entry points' order."""
+    unknown = set(rows) - set(_ERROR_ROWS)
+    if unknown:
+        raise L.BubbleformerHipError(f"{who}: unknown outputs {sorted(unknown)}")
+    f32 = torch.float32
+    shapes = {"rmse": (lead, f32), "max_error": (lead, f32), "boundary_rmse": (lead, f32), "interface_rmse": (lead, f32),
+              "interface_cells": (lead, torch.int32), "spectral_error": (lead + (3,), f32), "spectrum_error": (lead + (K,), f32),
+              "spectrum_pred": (lead + (K,), f32), "spectrum_target": (lead + (K,), f32)}
+    want = {k: (rows.get(k), shape, dtype) for k, (shape, dtype) in shapes.items()}
+    want["ws"] = (ws, (ws.numel(),), torch.uint8)
+    _check_tensors(who, device, want, _ERROR_ROWS)
+    return [_p(rows.get(k)) for k in _ERROR_ROWS]
+
+
+def shell_count(H: int, W: int) -> int:
+    """K = isqrt(S * S // 2) + 1 shells for S = min(H, W): every mode of an H x W frame falls in one of them."""
+    import math
+    S = min(int(H), int(W))
+    return math.isqrt(S * S // 2) + 1
+
+
+def field_errors(pred: torch.Tensor, target: torch.Tensor, sdf: Optional[torch.Tensor], ws: torch.Tensor, interface_radius: int = 1, lo: int = 4,
+                 hi: int = 12, want_spectra: bool = True, **rows: Optional[torch.Tensor]) -> None:
+    """The error rows of pred against target (F, H, W) fp32 (bf_field_errors; include/bubbleformer_hip.h has the contract); sdf (F, H, W) fp32 in
+    physical units or None.  rows: any of rmse, max_error, boundary_rmse, interface_rmse (F,) fp32, interface_cells (F,) int32, spectral_error
+    (F, 3), spectrum_error / spectrum_pred / spectrum_target (F, shell_count(H, W)) fp32; what is left out is not computed.  ws:
+    ``field_errors_workspace(F, H, W)``.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(pred)
+    if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise L.BubbleformerHipError("field_errors: pred must be a contiguous fp32 (frames, H, W) tensor")
+    F, H, W = pred.shape
+    _check_tensors("field_errors", pred.device, {"target": (target, (F, H, W), torch.float32), "sdf": (sdf, (F, H, W), torch.float32)}, ("sdf",))
+    ptrs = _error_rows("field_errors", pred.device, (F,), shell_count(H, W), rows, ws)
+    need = L.lib().bf_field_errors_ws_bytes(F, H, W)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("field_errors: the workspace is smaller than field_errors_workspace(frames, H, W)")
+    L.check(L.lib().bf_field_errors(_p(pred), _p(target), _p(sdf), F, H, W, int(interface_radius), int(lo), int(hi), int(bool(want_spectra)), *ptrs,
+                                    _p(ws), ws.numel(), _stream()), "bf_field_errors")
+
+
+def rollout_errors(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
+                   ws: torch.Tensor, interface_radius: int = 1, lo: int = 4, hi: int = 12, want_spectra: bool = True,
+                   **rows: Optional[torch.Tensor]) -> None:
+    """The error rows of one rollout step (bf_rollout_errors; include/bubbleformer_hip.h has the contract): rows (b, s * T + t, c) of the outputs
+    ``field_errors`` names, here (B, steps*T, C) with the same tails, for the prediction against the stored frame ``first[b] + (s + 1) * T + t``,
+    s = the int32 ``step`` tensor ON THE DEVICE, which this call only reads -- issue it BEFORE the step's ``rollout_score``.  The interface mask
+    comes from the raw stored frame of ``sdf_channel`` (-1: none).  ws: ``field_errors_workspace(B * T * C, Ho, Wo)``.  Allocates nothing."""
+    lead, tail = _rollout_step_args("rollout_errors", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    ptrs = _error_rows("rollout_errors", pred.device, (B, steps * T, Cn), shell_count(Ho, Wo), rows, ws)
+    if not -1 <= int(sdf_channel) < Cn:
+        raise L.BubbleformerHipError(f"rollout_errors: channel {sdf_channel} is not among the prediction's {Cn}")
+    need = L.lib().bf_field_errors_ws_bytes(B * T * Cn, Ho, Wo)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_errors: the workspace is smaller than field_errors_workspace(B * T * C, Ho, Wo)")
+    L.check(L.lib().bf_rollout_errors(*lead, int(sdf_channel), int(interface_radius), int(lo), int(hi), int(bool(want_spectra)), *ptrs, _p(ws),
+                                      ws.numel(), *tail), "bf_rollout_errors")
+
+
 def grad_norm_workspace(n: int, device) -> torch.Tensor:
     """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
     return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)

@@ -1,3 +1,4 @@
 from .lr_schedulers import CosineWarmupLR  # noqa: F401
 from .losses import LpLoss, eikonal_loss  # noqa: F401
 from .physics import BubbleCensus, BubbleSpec, BubbleTracks, HeaterSpec, bubble_census, bubble_tracks, heatflux_series, kde_kl_divergence  # noqa: F401
+from .physics import ErrorSpec, FieldErrors, field_errors, shell_count  # noqa: F401

@@ -289,3 +289,84 @@ def bubble_tracks(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int 
     ops.bubble_track_ids(census.count.reshape(N, T), rows["successor"], rows["predecessor"], track_id, n_tracks)
     return BubbleTracks(census, **{k: v.reshape(lead + v.shape[1:]) for k, v in rows.items()}, track_id=track_id.reshape(lead + (T, mb)),
                         n_tracks=n_tracks.reshape(lead))
+
+
+@dataclasses.dataclass(frozen=True)
+class ErrorSpec:
+    """The error rows of a rollout (``evaluate_rollouts(..., errors=ErrorSpec())``) or of ``field_errors``: how far from a cell the window that
+    decides "at the interface" reaches, the shells (lo, hi) that split the low, mid and high band, whether the spectra are taken at all, and
+    which output field is the signed distance."""
+    interface_radius: int = 1
+    bands: tuple = (4, 12)
+    spectra: bool = True
+    sdf_field: str = "dfun"
+
+    def __post_init__(self):
+        if int(self.interface_radius) != self.interface_radius or int(self.interface_radius) < 1:
+            raise ValueError(f"interface_radius must be an integer of at least 1, got {self.interface_radius!r}")
+        try:
+            lo, hi = self.bands
+            ok = int(lo) == lo and int(hi) == hi and 0 <= lo <= hi
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"bands must be two integers 0 <= lo <= hi, got {self.bands!r}")
+
+
+def shell_count(H: int, W: int) -> int:
+    """The number of shells of an H x W frame's spectrum: isqrt(S * S // 2) + 1 with S = min(H, W)."""
+    from ..ops import shell_count as count
+    return count(H, W)
+
+
+@dataclasses.dataclass
+class FieldErrors:
+    """What ``field_errors`` returns; every tensor is on the device and keeps the leading dims of the prediction.  e = pred - target in fp64."""
+    rmse: torch.Tensor                              # (...)     fp32  sqrt(mean e^2)
+    max_error: torch.Tensor                         # (...)     fp32  max |e|; NaN if any e is NaN
+    boundary_rmse: torch.Tensor                     # (...)     fp32  the root mean square over the outer ring of cells
+    interface_rmse: Optional[torch.Tensor]          # (...)     fp32  the same over the interface cells of sdf (NaN where there is none), or None
+    interface_cells: Optional[torch.Tensor]         # (...)     int32 their number
+    spectral_error: Optional[torch.Tensor]          # (..., 3)  fp32  band-limited RMSE of e: low, mid, high; None without spectra
+    spectrum_error: Optional[torch.Tensor]          # (..., K)  fp32  shell power of e
+    spectrum_pred: Optional[torch.Tensor]           # (..., K)  fp32  shell power of the prediction
+    spectrum_target: Optional[torch.Tensor]         # (..., K)  fp32  shell power of the target
+
+    def spectral_ratio(self) -> torch.Tensor:
+        """spectrum_pred / spectrum_target per shell: the blurring curve (below 1 where the prediction lost power).  Never synchronises."""
+        if self.spectrum_pred is None:
+            raise ValueError("these errors have no spectra: use ErrorSpec(spectra=True)")
+        return self.spectrum_pred / self.spectrum_target
+
+
+def field_errors(pred: torch.Tensor, target: torch.Tensor, sdf: Optional[torch.Tensor] = None, *, spec: ErrorSpec = ErrorSpec()) -> FieldErrors:
+    """Where ``pred`` (..., H, W) differs from ``target`` and at which scales, per frame, on the device (``ops.field_errors``).
+
+    Pointwise rows: RMSE, maximum error, RMSE over the outer ring, and -- with ``sdf`` (same shape, physical units: vapour is sdf > 0) -- RMSE
+    over the cells whose (2 r + 1)^2 window holds both vapour and liquid, with their number.  Spectra: the power of e, pred and target per
+    shell of the unnormalised 2-D DFT divided by (H W)^2, so a field's shells add up to its mean square, and ``spectral_error``, the
+    band-limited RMSE sqrt(sum of the error's shell power over the band) for the bands [0, lo), [lo, hi), [hi, K): low^2 + mid^2 + high^2 =
+    rmse^2.  This is NOT PDEBench's fRMSE, which is the mean over a band of the per-shell roots.  fp64 arithmetic, one rounding, the same
+    bits on every call and for a frame alone or in a batch; never synchronises."""
+    if pred.dim() < 2 or pred.shape != target.shape or (sdf is not None and sdf.shape != pred.shape):
+        raise ValueError(f"field_errors expects pred, target (and sdf) of one shape (..., H, W), got {tuple(pred.shape)} and {tuple(target.shape)}")
+    from .. import ops
+    _require_gpu(pred)
+    lead, (H, W) = tuple(pred.shape[:-2]), pred.shape[-2:]
+    flat = lambda t: t.reshape(-1, H, W).contiguous().float()
+    p, y, phi = flat(pred), flat(target), flat(sdf) if sdf is not None else None
+    F = p.shape[0]
+    if F < 1 or H < 1 or W < 1:
+        raise ValueError(f"field_errors needs at least one frame of at least one cell, got {tuple(pred.shape)}")
+    K = shell_count(H, W)
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=p.device)
+    rows = {"rmse": new(torch.float32, F), "max_error": new(torch.float32, F), "boundary_rmse": new(torch.float32, F)}
+    if phi is not None:
+        rows["interface_rmse"], rows["interface_cells"] = new(torch.float32, F), new(torch.int32, F)
+    if spec.spectra:
+        rows["spectral_error"] = new(torch.float32, F, 3)
+        for key in ("spectrum_error", "spectrum_pred", "spectrum_target"):
+            rows[key] = new(torch.float32, F, K)
+    ops.field_errors(p, y, phi, ops.field_errors_workspace(F, H, W, p.device), int(spec.interface_radius), int(spec.bands[0]), int(spec.bands[1]),
+                     spec.spectra, **rows)
+    return FieldErrors(**{k: (rows[k].reshape(lead + tuple(rows[k].shape[1:])) if k in rows else None) for k in ops._ERROR_ROWS})

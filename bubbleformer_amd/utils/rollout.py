@@ -147,6 +147,17 @@ class RolloutReport:
     bubble_predecessor_target: Optional[torch.Tensor] = None
     bubble_departure_area_pred: Optional[torch.Tensor] = None   # (B, steps*T-1, max_bubbles) int32 cells of a bubble that leaves the heater, else 0
     bubble_departure_area_target: Optional[torch.Tensor] = None
+    # with errors=ErrorSpec(): e = prediction - target in fp64 (physics.field_errors), else None.  Attributes that evaluate_rollouts sets, not
+    # constructor arguments: the dataclass fields end at the tracking rows, so positional callers and dataclasses.fields() stay as they are
+    rmse = None                                         # (B, steps*T, C)     fp32 sqrt(mean e^2)
+    max_error = None                                    # (B, steps*T, C)     fp32 max |e|
+    boundary_rmse = None                                # (B, steps*T, C)     fp32 the root mean square over the outer ring of cells
+    interface_rmse = None                               # (B, steps*T, C)     fp32 the same over the interface cells of the simulated frame
+    interface_cells = None                              # (B, steps*T, C)     int32 their number (one mask for all C channels)
+    spectral_error = None                               # (B, steps*T, C, 3)  fp32 band-limited RMSE of e: low, mid, high (ErrorSpec(spectra=True))
+    spectrum_error = None                               # (B, steps*T, C, K)  fp32 shell power of e
+    spectrum_pred = None                                # (B, steps*T, C, K)  fp32 shell power of the prediction
+    spectrum_target = None                              # (B, steps*T, C, K)  fp32 shell power of the target
 
     def save(self, path) -> None:
         """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
@@ -163,7 +174,17 @@ class RolloutReport:
         if self.bubble_events_pred is not None:
             for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
+        for key in _ERROR_KEYS:
+            if getattr(self, key) is not None:
+                out[key] = getattr(self, key)
         torch.save(out, path)
+
+    def spectral_ratio(self) -> torch.Tensor:
+        """(B, steps*T, C, K) fp32: spectrum_pred / spectrum_target per shell, the blurring curve (below 1 where the prediction lost power; inf
+        or NaN where the simulation has none).  On the device; never synchronises."""
+        if self.spectrum_pred is None:
+            raise ValueError("this report has no spectra: call evaluate_rollouts(..., errors=ErrorSpec(spectra=True))")
+        return self.spectrum_pred / self.spectrum_target
 
     def _heatfluxes(self):
         if self.heatflux_pred is None:
@@ -257,6 +278,8 @@ class RolloutReport:
 
 _TRACK_KEYS = ("bubble_events_pred", "bubble_events_target", "bubble_successor_pred", "bubble_successor_target", "bubble_predecessor_pred",
                "bubble_predecessor_target", "bubble_departure_area_pred", "bubble_departure_area_target")
+_ERROR_KEYS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
+               "spectrum_target")
 _BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
                 "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
 
@@ -268,7 +291,8 @@ def _to_device(values, dtype, device) -> torch.Tensor:
 
 def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
                       keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None,  # noqa: F821 (physics.HeaterSpec)
-                      bubbles: "Optional[BubbleSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.BubbleSpec)
+                      bubbles: "Optional[BubbleSpec]" = None,  # noqa: F821 (physics.BubbleSpec)
+                      errors: "Optional[ErrorSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.ErrorSpec)
     """Roll ``model`` out over ``B = len(starts)`` test trajectories at once and score every predicted frame against the simulation.
 
     data: a ``BubbleForecast`` (its device store is made on the model's device) or a ``DeviceClipStore``; starts: dataset sample indices.
@@ -282,7 +306,10 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     likewise leaves the bubble census of every predicted and simulated frame (``ops.rollout_bubbles``, one more launch before the scoring
     call): the ``bubble_*`` and ``vapour_fraction_*`` rows of the report; with ``BubbleSpec(track=True)`` that launch also leaves its label
     images and one more (``ops.rollout_bubble_links``) follows the bubbles into this step's frames: the ``bubble_events_*``, ``bubble_successor_*``,
-    ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows.  Never synchronises."""
+    ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows.  With ``errors`` (a ``physics.ErrorSpec``) one more call before the scoring
+    call (``ops.rollout_errors``) leaves ``physics.field_errors``' rows of every predicted frame and field against the stored target: ``rmse``,
+    ``max_error``, ``boundary_rmse``, the interface rows when the signed-distance field is among the outputs, and with ``spectra`` the shell
+    spectra and the band-limited errors; ``None`` leaves the launches and the report as they are without it.  Never synchronises."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
@@ -335,6 +362,22 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
             before_score.append(lambda pred, step: ops.rollout_bubbles_labelled(pred, store.frames, first, step, store.out_tab, *bub_args, ring))
             before_score.append(lambda pred, step: ops.rollout_bubble_links(pred, store.frames, first, step, store.out_tab, steps, mb, link_ws, ring,
                                                                             *bub["count"], *bub["attached"], *bub["area"], *link_rows))
+    err_rows = None
+    if errors is not None:
+        err_sdf = fields.index(errors.sdf_field) if errors.sdf_field in fields else -1
+        K = ops.shell_count(Ho, Wo)
+        err_rows = {key: new(B, steps * T, C) for key in ("rmse", "max_error", "boundary_rmse")}
+        if err_sdf >= 0:
+            err_rows["interface_rmse"] = new(B, steps * T, C)
+            err_rows["interface_cells"] = torch.empty((B, steps * T, C), dtype=torch.int32, device=device)
+        if errors.spectra:
+            err_rows["spectral_error"] = new(B, steps * T, C, 3)
+            for key in ("spectrum_error", "spectrum_pred", "spectrum_target"):
+                err_rows[key] = new(B, steps * T, C, K)
+        err_ws = ops.field_errors_workspace(B * T * C, Ho, Wo, device)
+        before_score.append(lambda pred, step: ops.rollout_errors(pred, store.frames, first, step, store.out_tab, err_sdf, steps, err_ws,
+                                                                  int(errors.interface_radius), int(errors.bands[0]), int(errors.bands[1]),
+                                                                  errors.spectra, **err_rows))
 
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
@@ -378,4 +421,7 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
             for key in ("events", "successor", "predecessor", "departure_area"):
                 setattr(report, f"bubble_{key}_pred", link_rows[0][key])
                 setattr(report, f"bubble_{key}_target", link_rows[1][key])
+    if err_rows is not None:
+        for key, rows in err_rows.items():
+            setattr(report, key, rows)
     return report

@@ -36,6 +36,7 @@
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
  *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
+ *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
@@ -494,6 +495,33 @@ int bf_rollout_bubble_links(const float* pred, const float* frames, int64_t fiel
                             int32_t* n_predecessors_tgt, int32_t* departure_area_pred, int32_t* departure_area_tgt, int32_t* events_pred,
                             int32_t* events_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps,
                             bf_stream_t stream);
+/* Where a prediction is wrong and at which scales (csrc/spectra.hip; the reference has no program for it).  pred, target
+ * [frames][H][W] fp32, e = pred - target in fp64; sdf (optional) [frames][H][W] fp32 in physical units.  Any output may be NULL and is then not computed:
+ *   rmse, max_error, boundary_rmse [frames] fp32   sqrt(mean e^2); max |e| (NaN if any e is NaN); the root mean square over the outer ring of cells;
+ *   interface_rmse [frames] fp32, interface_cells [frames] int32   the same over the cells whose (2 r + 1)^2 window (r = interface_radius >= 1, clipped to
+ *     the frame) holds both vapour (sdf > 0) and liquid (anything else: zero and NaN too), and their number; NaN where there is none.  Both need sdf;
+ *   spectrum_error / spectrum_pred / spectrum_target [frames][K] fp32   shell power of e / pred / target: the sum of |X|^2 / (H W)^2 over the modes of
+ *     shell q, X the unnormalised 2-D DFT, q the largest integer with q^2 H^2 W^2 <= S^2 (fy^2 W^2 + fx^2 H^2) for the signed frequencies fy, fx and
+ *     S = min(H, W) (decided in int64), K = isqrt(S * S / 2) + 1 shells; the K values of a field add up to its mean square;
+ *   spectral_error [frames][3] fp32   sqrt of spectrum_error summed over the shells [0, lo), [lo, hi), [hi, K) (lo, hi clipped to K; 0 <= lo <= hi).
+ * want_spectra == 0 skips the transforms: the four spectral outputs are then left untouched.  fp64 arithmetic, fixed-order sums, one rounding: the same
+ * bits on every call and for a frame alone or in a batch; e == 0 everywhere gives exact zeros.  H, W in [1, 1024].  Allocation-free, capturable, never
+ * makes the host wait.  ws: bf_field_errors_ws_bytes(frames, H, W) bytes, 16-byte aligned (0 from the query: sizes out of range). */
+int64_t bf_field_errors_ws_bytes(int64_t frames, int H, int W);
+int bf_field_errors(const float* pred, const float* target, const float* sdf, int64_t frames, int H, int W, int interface_radius, int lo, int hi,
+                    int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse, int32_t* interface_cells,
+                    float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target, void* ws, int64_t ws_bytes,
+                    bf_stream_t stream);
+/* bf_field_errors of ONE rollout step: frame (b, t, c) of the prediction against the stored frame first[b] + (s + 1) * T + t of field[c], read where it
+ * lies with the bits bf_clip_gather returns; the interface mask from the raw stored frame of channel sdf_channel (-1: none, the interface rows must be
+ * NULL), one mask for all C channels of (b, t).  Rows (b, s * T + t, c) of [B][steps*T][C]([K] or [3]) are written and no other; with s = *step outside
+ * [0, steps) nothing is written.  step is READ and never written: issue the call BEFORE the step's bf_rollout_score.  pred, frames, ..., div and the
+ * sizes are bf_rollout_score's.  ws: bf_field_errors_ws_bytes(B * T * C, Ho, Wo) bytes, 16-byte aligned. */
+int bf_rollout_errors(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
+                      const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int interface_radius, int lo,
+                      int hi, int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse, int32_t* interface_cells,
+                      float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target, void* ws, int64_t ws_bytes, int B, int T,
+                      int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
