@@ -80,6 +80,21 @@ class ConvGeo(C.Structure):
 
 BF_CONV_PRO_NONE, BF_CONV_PRO_AFFINE_GELU, BF_CONV_PRO_GELU = 0, 1, 2
 
+
+class RenderTile(C.Structure):
+    """bf_render_tile: what one slot of an image shows (bf_render_tiles)."""
+    _fields_ = [("a", fp), ("b", fp), ("mask", fp), ("frame_stride", i64), ("slot_stride", i64), ("mask_frame_stride", i64), ("mask_slot_stride", i64),
+                ("range", vp), ("kind", i32)]
+
+
+class RenderGeom(C.Structure):
+    _fields_ = [(n, i32) for n in ("H", "W", "scale", "rows", "cols", "ox", "oy", "pitch_x", "pitch_y", "bar_dx", "bar_w", "img_h", "img_w", "stride")] + [
+        ("stroke", C.c_double)]
+
+
+BF_RENDER_SDF, BF_RENDER_TEMP, BF_RENDER_SPEED = 0, 1, 2
+BF_RENDER_MAX_TILES = 6
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # bf_stage_done_fn
 P = C.POINTER
 # name -> (restype, argtypes); mirrors include/bubbleformer_hip.h one to one
@@ -191,6 +206,9 @@ SIGNATURES = {
     "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp, fp, fp, vp, i64, vp]),
     "bf_rollout_errors": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp,
                                     fp, fp, vp, i64] + [C.c_int] * 8 + [vp]),
+    "bf_render_ranges_ws_doubles": (i64, []),
+    "bf_render_ranges": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "bf_render_tiles": (C.c_int, [P(RenderTile), C.c_int, P(RenderGeom), i64, vp, vp, vp, vp]),
     "bf_lp_rows_ws_doubles": (i64, [i64, i64]),
     "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
     "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),

@@ -52,7 +52,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         limit_val_batches: Optional[int] = 25, seed: int = 42, rank: int = 0, world: int = 1, checkpoint_path: Optional[str] = None,
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
-        accumulate_grad_batches: int = 1) -> Dict:
+        accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -62,7 +62,9 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     ``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``accumulate_grad_batches``: see TrainStep.  The history and `log` keep one
     loss and one learning rate per batch; with clipping by norm, ``hist["grad_norm"]`` holds the (unclipped) gradient norm of every
     optimizer step, read from the device at the end of the epoch like the losses, and the `log` dict of a batch that stepped carries
-    it as a device scalar.  Returns the history."""
+    it as a device scalar.  ``panel_dir``: after every validation, the picture strips ForecastModule.on_validation_epoch_end logs
+    (modules.py:191-250) of sample 0 of validation batch 0 as ``epoch_<e>_{sdf,temp,vel}_{target,pred}.png`` (utils/plot_utils.py; a field the
+    dataset does not output is skipped); None renders and writes nothing.  Returns the history."""
     dev = next(model.parameters()).device
     store = train_set.device_store(dev)
     vstore = val_set.device_store(dev) if val_set is not None else None
@@ -108,7 +110,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             hist["grad_norm"].extend(torch.stack(norms).tolist())
         hist["epoch_train_loss"].append(float(ep.mean()))
         if vstore is not None:
-            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion))
+            sample = [] if panel_dir is not None and rank == 0 else None
+            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, sample))
+            if sample:
+                write_validation_strips(panel_dir, epoch, list(val_set.output_fields), *sample)
             if log is not None:
                 log({"epoch": epoch, "val_loss": hist["val_loss"][-1]})
         if checkpoint_path is not None and rank == 0:
@@ -117,8 +122,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
 
 
 @torch.no_grad()
-def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optional[int], rank: int = 0, world: int = 1, criterion=None) -> float:
-    """Mean over the (limited) validation batches of the training criterion, as `validation_step` logs it on epoch end."""
+def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optional[int], rank: int = 0, world: int = 1, criterion=None,
+             sample: Optional[list] = None) -> float:
+    """Mean over the (limited) validation batches of the training criterion, as `validation_step` logs it on epoch end.  A list passed as
+    ``sample`` receives (target, prediction) of sample 0 of batch 0, (T, C, H, W) each (`validation_sample` of modules.py:185-189)."""
     was_training = model.training
     model.eval()
     conditioned = getattr(val_set, "return_fluid_params", False)
@@ -126,10 +133,35 @@ def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optiona
     for idx in batches(epoch_indices(len(val_set), 0, 0, False, rank, world), batch_size, limit_val_batches):
         got = vstore.gather(idx)
         if criterion is None:
-            loss, _ = model.forward_loss(got[0], got[2], got[1]) if conditioned else model.forward_loss(got[0], got[1])
+            loss, pred = model.forward_loss(got[0], got[2], got[1]) if conditioned else model.forward_loss(got[0], got[1])
         else:
-            loss = criterion(model(got[0], got[2]) if conditioned else model(got[0]), got[1])
+            pred = model(got[0], got[2]) if conditioned else model(got[0])
+            loss = criterion(pred, got[1])
+        if sample is not None and n == 0:
+            sample.extend((got[1][0].detach().float().clone(), pred[0].detach().float().clone()))
         tot += float(loss)
         n += 1
     model.train(was_training)
     return tot / max(n, 1)
+
+
+def write_validation_strips(panel_dir: str, epoch: int, fields: List[str], target: torch.Tensor, pred: torch.Tensor) -> List[str]:
+    """The six strips of one validation sample (T, C, H, W): each field that is among ``fields`` as target and as prediction, every strip
+    scaled to its own data as the reference's plotters are.  Returns the files written."""
+    import os
+    from .utils import plot_utils as P
+    os.makedirs(panel_dir, exist_ok=True)
+    spec = P.RenderSpec()
+    T, _, H, W = target.shape
+    layout = spec.layout(H, W, 1, T)
+    written = []
+    for name, title, needs, strip in (("sdf", "SDF", ("dfun",), P.sdf_strip), ("temp", "TEMP", ("temperature",), P.temp_strip),
+                                      ("vel", "VEL", ("velx", "vely"), P.vel_strip)):
+        if any(n not in fields for n in needs):
+            continue                                  # the reference's `except ValueError: pass`
+        idx = [fields.index(n) for n in needs]
+        for side, clip in (("target", target), ("pred", pred)):
+            frames = clip[:, idx] if len(idx) == 2 else clip[:, idx[0]]
+            written.append(os.path.join(panel_dir, f"epoch_{epoch}_{name}_{side}.png"))
+            P.write_strip(written[-1], strip(frames, spec=spec), title, layout)
+    return written

@@ -2030,3 +2030,72 @@ def unet_upconv2(x, w, b, port=None):
 def classic_final(c, T, g, b, bn, w, bias, target=None):
     """-> (pred (B, T, C, H, W) fp32, loss) of conv(gelu(bn(c))); only ``loss`` carries gradient when ``target`` is given."""
     return _ClassicFinalFn.apply(c, target, T, g, b, bn, w, bias)
+
+
+# ---------------------------------------------------------------------------- pictures (csrc/render.hip; utils/plot_utils.py is the user's side)
+_RENDER_LUTS = {}
+
+
+def _render_luts(device):
+    """The two 256 x 3 colour tables on ``device`` (utils/colormaps.py), uploaded once."""
+    key = (device.type, device.index)
+    if key not in _RENDER_LUTS:
+        from .utils import colormaps
+        _RENDER_LUTS[key] = tuple(torch.from_numpy(t.copy()).to(device) for t in (colormaps.BLUES, colormaps.TURBO))
+    return _RENDER_LUTS[key]
+
+
+def render_ranges(frames: torch.Tensor, channels: Sequence[int]) -> torch.Tensor:
+    """frames (F, C, H, W) fp32 on the device, channels = (sdf, temperature, velx, vely) with -1 for an absent one -> (3, 5) fp64 on the
+    device: {n, sum, sum of squares, min, max} of the signed distance, the temperature and the speed (bf_render_ranges).  Never synchronises."""
+    _require_gpu(frames)
+    if frames.dim() != 4 or frames.dtype != torch.float32 or not frames.is_contiguous():
+        raise L.BubbleformerHipError("render_ranges: the frames must be a contiguous fp32 (F, C, H, W) tensor")
+    ch = [int(c) for c in channels]
+    if len(ch) != 4 or any(c < -1 or c >= frames.shape[1] for c in ch):
+        raise L.BubbleformerHipError(f"render_ranges: channels must be four indices into the {frames.shape[1]} channels, -1 for an absent field")
+    Fn, Cn, H, W = frames.shape
+    out = torch.empty((3, 5), dtype=torch.float64, device=frames.device)
+    ws = torch.empty(L.lib().bf_render_ranges_ws_doubles(), dtype=torch.float64, device=frames.device)
+    L.check(L.lib().bf_render_ranges(_p(frames), Fn, Cn, H, W, *ch, _p(out), _p(ws), _stream()), "bf_render_ranges")
+    return out
+
+
+def render_tiles(tiles: Sequence[dict], layout, images: int) -> torch.Tensor:
+    """One launch for all images of a call (bf_render_tiles) -> (images, img_h, img_w, 3) uint8 on the device.
+
+    tiles: one dict per description, slot k of an image showing description k % len(tiles): ``kind`` (L.BF_RENDER_*), ``a`` (and ``b`` for a
+    speed tile, ``mask`` optionally) fp32 views of shape (images, rounds, H, W) whose last two axes are contiguous, ``range`` two fp64 values
+    {vmin, vmax} on the device.  layout: a ``plot_utils.RenderLayout``."""
+    g = layout
+    rounds, rem = divmod(g.rows * g.cols, len(tiles))
+    if not 1 <= len(tiles) <= L.BF_RENDER_MAX_TILES or rem:
+        raise L.BubbleformerHipError(f"render_tiles: {len(tiles)} descriptions do not tile {g.rows} x {g.cols} slots")
+    device = tiles[0]["a"].device
+    desc = (L.RenderTile * len(tiles))()
+    for d, t in zip(desc, tiles):
+        views = [t["a"], t.get("b"), t.get("mask")]
+        for v in views:
+            if v is None:
+                continue
+            _require_gpu(v)
+            if (v.dtype != torch.float32 or v.device != device or tuple(v.shape) != (images, rounds, g.H, g.W)
+                    or (g.W > 1 and v.stride(3) != 1) or (g.H > 1 and v.stride(2) != g.W)):
+                raise L.BubbleformerHipError(f"render_tiles: a field must be an fp32 view of shape {(images, rounds, g.H, g.W)} with contiguous frames on {device}")
+        rng = t["range"]
+        if rng.dtype != torch.float64 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != device:
+            raise L.BubbleformerHipError("render_tiles: a range is two contiguous fp64 values on the fields' device")
+        if t["kind"] == L.BF_RENDER_SPEED and views[1] is None:
+            raise L.BubbleformerHipError("render_tiles: a speed tile needs both velocity components")
+        d.a, d.b, d.mask = _p(views[0]), _p(views[1]), _p(views[2])
+        d.frame_stride, d.slot_stride = views[0].stride(0), views[0].stride(1)
+        if views[1] is not None and (views[1].stride(0), views[1].stride(1)) != (views[0].stride(0), views[0].stride(1)):
+            raise L.BubbleformerHipError("render_tiles: both velocity components must have the same strides")
+        if views[2] is not None:
+            d.mask_frame_stride, d.mask_slot_stride = views[2].stride(0), views[2].stride(1)
+        d.range, d.kind = _p(rng), int(t["kind"])
+    geom = L.RenderGeom(g.H, g.W, g.scale, g.rows, g.cols, g.ox, g.oy, g.pitch_x, g.pitch_y, g.bar_dx, g.bar_w, g.img_h, g.img_w, g.stride, float(g.stroke))
+    blues, turbo = _render_luts(device)
+    out = torch.empty((images, g.img_h, g.img_w, 3), dtype=torch.uint8, device=device)
+    L.check(L.lib().bf_render_tiles(desc, len(tiles), C.byref(geom), images, _p(blues), _p(turbo), _p(out), _stream()), "bf_render_tiles")
+    return out

@@ -425,3 +425,36 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
         for key, rows in err_rows.items():
             setattr(report, key, rows)
     return report
+
+
+FIELD_ROLES = ("dfun", "temperature", "velx", "vely")          # the fields plot_bubbleml draws, in its channel order
+
+
+def render_rollouts(report: RolloutReport, data, starts: Sequence[int], save_dir, trajectories: Optional[Sequence[int]] = None, **kw) -> dict:
+    """Pictures of a report made with ``evaluate_rollouts(..., keep_predictions=True)`` on the same ``data`` and ``starts``: for every chosen
+    trajectory b (all by default) the simulated frames at ``report.timesteps[b]`` are gathered from the store as the scoring call reads them
+    (``ops.clip_gather``) and ``plot_utils.plot_bubbleml`` writes ``save_dir/traj_<b>/plots/0000.png ...`` and ``relative_l2_error.csv``.
+    Keyword arguments go to ``plot_bubbleml``; the channels follow the report's field names unless given.  Returns {b: its result}."""
+    import os
+    from .. import ops
+    from ..data.dataset import DeviceClipStore
+    from .plot_utils import plot_bubbleml
+    if report.predictions is None:
+        raise ValueError("this report kept no predictions: call evaluate_rollouts(..., keep_predictions=True)")
+    device = report.predictions.device
+    store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
+    B, frames, _, Ho, Wo = report.predictions.shape
+    T = int(store.ds.time_window)
+    plan = plan_rollouts(store.ds, starts, frames // T)
+    if len(plan.first) != B or not torch.equal(plan.timesteps, report.timesteps.cpu()):
+        raise ValueError("data and starts do not give the report's trajectories")
+    kw.setdefault("channels", tuple(report.fields.index(n) if n in report.fields else -1 for n in FIELD_ROLES))
+    chosen = list(range(B)) if trajectories is None else [int(b) for b in trajectories]
+    out = {}
+    for b in chosen:
+        if not 0 <= b < B:
+            raise IndexError(f"trajectory {b} is outside the report (0 .. {B - 1})")
+        first = _to_device([plan.first[b]], torch.int64, device)
+        targets = ops.clip_gather(store.frames, first, T, frames, store.out_tab, Ho, Wo)[0]      # the frames behind the first input clip
+        out[b] = plot_bubbleml(report.predictions[b], targets, plan.timesteps[b], os.path.join(str(save_dir), f"traj_{b}"), **kw)
+    return out

@@ -37,6 +37,7 @@
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
  *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
  *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
+ *   bf_render_ranges / bf_render_tiles .. plot_bubbleml and the wandb_*_plotter strips: utils/plot_utils.py:12-228 (no matplotlib, no cv2)
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
@@ -758,6 +759,40 @@ int bf_bn_act(int dtype, const void* x, int B, int H, int W, int C, const float*
 int bf_bn_bwd(int dtype, const float* dA, int64_t ldA, int offA, const void* dP, const uint8_t* idx, const void* x, int B, int H, int W, int C,
               const float* gamma, const float* mean, const float* rstd, const float* sc, const float* sh, void* dx, float* dgamma, float* dbeta,
               int accumulate, float* ws, bf_stream_t stream);
+
+/* Pictures of fields (plot_bubbleml and the wandb_*_plotter strips of bubbleformer/utils/plot_utils.py), fields in, uint8 RGB out.
+ * bf_render_ranges: src (frames, C, H, W) fp32; out[q] = {n, sum, sum of squares, min, max} in fp64 for q = 0 the channel c_sdf, 1 the channel
+ * c_temp, 2 the speed sqrt(velx^2 + vely^2) formed in fp64; a quantity with a channel of -1 is skipped (n = 0).  A NaN propagates into the sums,
+ * min and max ignore it.  Summed in a fixed order (bit-reproducible, no atomics).  ws: bf_render_ranges_ws_doubles() doubles. */
+enum { BF_RENDER_SDF = 0 /* Blues, interface outline */, BF_RENDER_TEMP = 1 /* turbo */, BF_RENDER_SPEED = 2 /* turbo of the speed, arrows */ };
+#define BF_RENDER_MAX_TILES 6
+typedef struct bf_render_tile {
+    const float* a;                 /* the field; BF_RENDER_SPEED: the x velocity */
+    const float* b;                 /* BF_RENDER_SPEED: the y velocity */
+    const float* mask;              /* BF_RENDER_SPEED: a signed distance whose positive cells carry no arrow, or NULL */
+    int64_t frame_stride;           /* floats from one image's field to the next image's (a and b) */
+    int64_t slot_stride;            /* floats from one round of slots to the next (a and b) */
+    int64_t mask_frame_stride, mask_slot_stride;
+    const double* range;            /* {vmin, vmax} on the device */
+    int32_t kind;                   /* BF_RENDER_* */
+} bf_render_tile;
+/* An image is rows x cols slots; slot (r, c) has its tile's top-left pixel at (oy + r * pitch_y, ox + c * pitch_x), the tile is H * scale x
+ * W * scale pixels and its colour bar is bar_w pixels wide from bar_dx pixels right of the tile's left edge. */
+typedef struct bf_render_geom {
+    int32_t H, W, scale, rows, cols, ox, oy, pitch_x, pitch_y, bar_dx, bar_w, img_h, img_w, stride;
+    double stroke;                  /* half-width of an arrow stroke in pixels */
+} bf_render_geom;
+int64_t bf_render_ranges_ws_doubles(void);
+int bf_render_ranges(const float* src, int64_t frames, int C, int H, int W, int c_sdf, int c_temp, int c_velx, int c_vely, double* out, double* ws,
+                     bf_stream_t stream);
+/* out (images, img_h, img_w, 3) uint8, img_w a multiple of 4.  Slot k = r * cols + c of image f is drawn from description k % ntiles at
+ * a + f * frame_stride + (k / ntiles) * slot_stride: a 2 x 3 panel has six descriptions, a strip one.  Tile pixel (py, px) shows field cell
+ * (H - 1 - py / scale, px / scale).  Colour: idx = clamp(floor(256 (x - vmin) / (vmax - vmin)), 0, 255) in fp64 into the 256 x 3 table (NaN: white;
+ * vmax == vmin: 0).  SDF tiles: black on the 3 x 3 dilation of the liquid cells (sdf < 0) that have an in-range 4-neighbour which is not liquid.
+ * Speed tiles: white within `stroke` pixels of an arrow (shaft and two head strokes) anchored at the cells i % stride == j % stride == stride / 2.
+ * The bar shows the table from vmin (bottom) to vmax (top); everything else is white. */
+int bf_render_tiles(const bf_render_tile* tiles, int ntiles, const bf_render_geom* geom, int64_t images, const uint8_t* lut_blues,
+                    const uint8_t* lut_turbo, uint8_t* out, bf_stream_t stream);
 
 /* Optional per-launch HIP-event timing on the launch stream (bench.py's roofline leg); off by default. */
 void bf_prof_enable(int on);
