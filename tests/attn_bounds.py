@@ -1,5 +1,5 @@
-"""fp64 reference and per-element error bounds for the attention kernels (csrc/attn_mfma.hip, csrc/attn.hip; 1 <= L <= 32 -- the
-reference part also serves csrc/attn_long.hip up to L = 128).
+"""fp64 reference and per-element error bounds for the attention kernels (csrc/attn_mfma.hip, csrc/attn.hip; 1 <= L <= 32) and for
+csrc/attn_long.hip (33 <= L <= 128: the modes LONG_BF16 / LONG_FP32, "Long axes" below).
 
 Given the stored values a kernel reads (qkv, dout, the fp32 parameters, the prior content of an accumulated output), the functions below
 return for every output the fp64 value `ref` of bf_attn_fwd / bf_attn_bwd's contract and an elementwise `bnd` such that a correct kernel
@@ -50,7 +50,40 @@ addends of the whole sum (problems x rows, or x pairs of a bucket): valid for th
 atomics alike.  dkb is structurally zero (sum_j dS_ij = 0) and gets its absolute bound from the same formula.
 The InstanceNorm bf_attn_axial_norm_fwd appends reads the bf16 values it has just stored, so `instance_norm` takes the kernel's own
 `out` as exact input: fp32 two-pass statistics over the S tokens (gamma_{S+2}), one bf16 store.
+
+Long axes (attn_long.hip; Mode.long): LONG_BF16 = (2^-8, 2^-8, long), LONG_FP32 = (0, 2^-24, long).  u_op is the rounding of pack4, which
+turns every MFMA operand to bf16 as it leaves LDS; in the fp32 mode all six products are plain fp32 sums (fused or not: gamma_n covers
+either) and u_op = 0.  Everything not restated here is as above.  Where the kernel rounds differently (row_stats, stage, scores,
+softmax_rows, mm_block, attn_fwd_long, attn_bwd_long):
+  term counts  O = A V, dV = A^T g, dqn = dS kn, dkn = dS^T qn sum over the L keys (queries): the MFMA path runs to LP = 16 ceil(L / 16) with
+             exact zeros (staged rows >= L are zero, P is zero in padded rows and keys), so gamma_L, not gamma_32.  S and dA sum over d
+             (columns >= d staged as zero): gamma_d.
+  operands   d^-1/2 is not folded into q: qn = xhat qw + qb and kn are staged as they stand, eq = exh |w| + 2 u (|xhat w| + |b|), then
+             rounded: eq (1 + u_op) + u_op |qn|.
+  scores     S = acc * rsqrtf(d) + emb: rsqrtf within 2 ulp = 4 u, the product u: e = e_acc d^-1/2 (1 + 5 u) + 5 u |S|, then u |S + emb|.
+             dqn and dkn are both acc * rsqrtf(d) in the same way, their operand being the unscaled kn / qn.
+  softmax    one thread per row, keys in order: max, __expf(s - m) (the shift D as above), an fp32 sum of L terms, inv = 1.f / sum, e * inv:
+             L - 1 additions, the division, the product <= gamma_{L+6} as above.  ASSUMED: the fp32 division 1.f / x is within 2 ulp
+             (4 u; the compiler's default is the correctly rounded one).  The rescale is done in fp32 in place: eA as above.
+  P V        the forward rounds A in mm_block: (1 + u_op) eA + u_op |A|.  The computed row is P~ (1 + theta), P~ = e_j / sum e exactly
+             normalised and within the enclosure of P, |theta| <= gamma_{L+6}; the P~ - P sum to zero over the keys, so that part of the
+             error only meets V's deviation from a constant c (the per-channel mean over the keys is used):
+             eO = [encl |V - c| + gamma_{L+6} (P + encl) |V|] |hs| + 3 u (1/L + |P - 1/L| |hs|) |V|, times (1 + u_op), + u_op |A| |V| +
+             gamma_L |A| |V|.  (Without this a V of 48 .. 150 would carry the whole softmax perturbation times |V|.)
+  dA         stage forms g = dO out_scale in fp32, and pack4 rounds it: e_g = u |g| (1 + u_op) + u_op |g|, or 0 when out_scale = +-2^k
+             (both steps exact).  dP0 = g V^T: e = e_g |V|^T + gamma_d |g| |V|^T, no product afterwards.  dV = A^T g uses the same
+             staged operand and A rescaled anew from P in fp32 (the same three roundings), rounded: eAb^T (|g| + e_g) + |A|^T e_g +
+             gamma_L |A|^T |g|.
+  dS         dh = sum (P - 1/L) dA, dot = sum P dP and dS = P (dP - dot) are fp32, one thread per row in key order (dot: gamma_{L+1},
+             dh: 2 u per term beside param_total's gamma_n); dS stays fp32 in LDS and is rounded once, as an operand of dqn / dkn.
+  LayerNorm backward  m1, m2: one thread per row over d; dx, dw, db: one thread per column over the L rows; as ln_backward.
+  parameter gradients  a workgroup adds its problems in order in LDS, its row goes through attn_reduce_block or float atomics:
+             param_total with n = nseq heads L addends for dqw .. dkb, n = nseq L^2 for demb and dhscale, whatever the order.
+  raw modes  only bf16 with d % 32 == 0.  Mode 2 stores bf16(dqn), bf16(dkn) and adds nothing to them (bit 0 is clear); mode 5 adds the
+             stored values in front of the one LayerNorm backward and accumulates dV: as axial_pair, which takes a pair of modes when one
+             pass is a short axis (attn_mfma.hip) and the other a long one.
 """
+import math
 import os
 from collections import namedtuple
 from types import SimpleNamespace as NS
@@ -62,8 +95,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = ("dqw", "dqb", "dkw", "dkb", "demb", "dhscale")
 U32, U16 = 2.0 ** -24, 2.0 ** -8
 EPS = 1e-5
-Mode = namedtuple("Mode", "u_op u_st")
+Mode = namedtuple("Mode", "u_op u_st long", defaults=(False,))
 MFMA, GENERIC_BF16, FP32 = Mode(U16, U16), Mode(0.0, U16), Mode(0.0, U32)
+LONG_BF16, LONG_FP32 = Mode(U16, U16, True), Mode(0.0, U32, True)        # csrc/attn_long.hip, 33 <= L <= 128
 
 
 def gamma(n):
@@ -87,8 +121,15 @@ def t5_bucket(n):
     return int(_TABLE[0][i][i - n])
 
 
+_MATRIX = {}
+
+
 def bucket_matrix(L, device="cpu"):
-    return torch.tensor([[t5_bucket(i - j) for j in range(L)] for i in range(L)], device=device)
+    """[query][key] -> bucket; built once per (L, device) and shared: callers must not write to it."""
+    key = (L, str(device))
+    if key not in _MATRIX:
+        _MATRIX[key] = torch.tensor([[t5_bucket(i - j) for j in range(L)] for i in range(L)], device=device)
+    return _MATRIX[key]
 
 
 def geometry(kind, L, n_outer=3, inner=5):
@@ -186,10 +227,11 @@ def _layer_norm(x):
     return NS(xh=xh, exh=exh, r=r, er=er)
 
 
-def _operand(n, w, b, mul, u_op):
+def _operand(n, w, b, mul, u_op, post=3):
+    """post: the roundings charged after the affine (3: the product by rsqrtf(d); 0: the long kernels stage xhat w + b as it stands)"""
     lin = n.xh * w + b
     v = lin * mul
-    e = (n.exh * w.abs() + 2 * U32 * ((n.xh * w).abs() + b.abs())) * mul + 3 * U32 * v.abs()
+    e = (n.exh * w.abs() + 2 * U32 * ((n.xh * w).abs() + b.abs())) * mul + post * U32 * v.abs()
     return v, e * (1 + u_op) + u_op * v.abs()
 
 
@@ -210,11 +252,17 @@ def forward(qkv, geo, heads, d, prm, with_emb, with_hs, mode):
     x = to_problems(qkv, idx, heads, 3, d)
     nq, nk, v = _layer_norm(x[..., 0, :]), _layer_norm(x[..., 1, :]), x[..., 2, :]
     scale = d ** -0.5
-    qn, eq = _operand(nq, qw, qb, scale, mode.u_op)
-    kn, ek = _operand(nk, kw, kb, 1.0, mode.u_op)
     T = lambda z: z.transpose(-1, -2)
-    S = qn @ T(kn)
-    eS = qn.abs() @ T(ek) + eq @ T(kn.abs()) + eq @ T(ek) + gamma(d) * (qn.abs() @ T(kn.abs()))
+    if mode.long:             # unscaled operands; the fp32 accumulator times rsqrtf(d) (2 ulp = 4 u) and that product's rounding: 5 u
+        qn, eq = _operand(nq, qw, qb, 1.0, mode.u_op, 0)
+        kn, ek = _operand(nk, kw, kb, 1.0, mode.u_op, 0)
+        S = (qn @ T(kn)) * scale
+        eS = (qn.abs() @ T(ek) + eq @ T(kn.abs()) + eq @ T(ek) + gamma(d) * (qn.abs() @ T(kn.abs()))) * scale * (1 + 5 * U32) + 5 * U32 * S.abs()
+    else:
+        qn, eq = _operand(nq, qw, qb, scale, mode.u_op)
+        kn, ek = _operand(nk, kw, kb, 1.0, mode.u_op)
+        S = qn @ T(kn)
+        eS = qn.abs() @ T(ek) + eq @ T(kn.abs()) + eq @ T(ek) + gamma(d) * (qn.abs() @ T(kn.abs()))
     bk = bucket_matrix(L, dev)
     if with_emb:
         bias = emb[bk].permute(2, 0, 1).unsqueeze(0)                        # [1][h][i][j]
@@ -224,8 +272,8 @@ def forward(qkv, geo, heads, d, prm, with_emb, with_hs, mode):
         eS = eS + 2 * U32 * S.abs()
     a = S - S.max(-1, keepdim=True).values
     P = torch.softmax(S, -1)
-    eP = _softmax_enclosure(P, eS + U32 * (3 * a.abs() + 2))
-    eP = eP * (1 + gamma(L + 6)) + gamma(L + 6) * P
+    encl = _softmax_enclosure(P, eS + U32 * (3 * a.abs() + 2))
+    eP = encl * (1 + gamma(L + 6)) + gamma(L + 6) * P
     invL = float(np.float32(1.0) / np.float32(L))
     if with_hs:
         hv = hs.view(1, heads, 1, 1)
@@ -235,7 +283,14 @@ def forward(qkv, geo, heads, d, prm, with_emb, with_hs, mode):
         hv, A, eA = None, P, eP
     eAb = eA * (1 + mode.u_op) + mode.u_op * A.abs()
     O = A @ v
-    eO = eAb @ v.abs() + gamma(32) * (A.abs() @ v.abs())
+    if mode.long:             # the normalised row sums to one: its perturbation only sees V's deviation from a per-channel constant
+        dev_v = (v - v.mean(-2, keepdim=True)).abs()
+        eO = encl @ dev_v + gamma(L + 6) * ((P + encl) @ v.abs())
+        if with_hs:
+            eO = eO * hv.abs() + 3 * U32 * ((invL + (P - invL).abs() * hv.abs()) @ v.abs())
+        eO = eO * (1 + mode.u_op) + mode.u_op * (A.abs() @ v.abs()) + gamma(L) * (A.abs() @ v.abs())
+    else:
+        eO = eAb @ v.abs() + gamma(32) * (A.abs() @ v.abs())
     return NS(idx=idx, L=L, heads=heads, d=d, N=qkv.shape[0], nq=nq, nk=nk, v=v, qn=qn, eq=eq, kn=kn, ek=ek, P=P, eP=eP, A=A, eAb=eAb, O=O, eO=eO,
               hv=hv, invL=invL, bk=bk, scale=scale, qw=qw, kw=kw, with_emb=with_emb, with_hs=with_hs, mode=mode)
 
@@ -255,6 +310,8 @@ def out_bound(F, out_scale, old=None, e_old=0.0):
 
 def backward(F, dO, out_scale):
     """Gradients up to the LayerNorm outputs: dv (unstored), dqn, dkn, per-problem demb / dhscale, each with its bound."""
+    if F.mode.long:
+        return _backward_long(F, dO, out_scale)
     u_op, L, d, os_ = F.mode.u_op, F.L, F.d, abs(out_scale)
     T = lambda z: z.transpose(-1, -2)
     dO = dO.double()
@@ -283,6 +340,41 @@ def backward(F, dO, out_scale):
     B.e_dkn = T(e_dSb) @ (F.qn.abs() + F.eq) + T(dS.abs()) @ F.eq + gamma(32) * (T(dS.abs()) @ F.qn.abs())
     B.dqn = (dS @ F.kn) * F.scale
     B.e_dqn = (e_dSb @ (F.kn.abs() + F.ek) + dS.abs() @ F.ek + gamma(32) * (dS.abs() @ F.kn.abs())) * F.scale + 2 * U32 * B.dqn.abs()
+    return B
+
+
+def _backward_long(F, dO, out_scale):
+    """backward() for csrc/attn_long.hip (the module docstring, "Long axes"): the same outputs."""
+    u_op, L, d = F.mode.u_op, F.L, F.d
+    T = lambda z: z.transpose(-1, -2)
+    g = dO.double() * out_scale                                             # staged dO out_scale: fp32 product, then the operand type
+    exact = out_scale == 0 or math.frexp(abs(out_scale))[0] == 0.5          # +-2^k: no rounding at either step
+    e_g = 0.0 * g.abs() if exact else U32 * g.abs() * (1 + u_op) + u_op * g.abs()
+    va = F.v.abs()
+    dP0 = g @ T(F.v)
+    e_dP0 = e_g @ T(va) + gamma(d) * (g.abs() @ T(va))
+    B = NS()
+    if F.with_hs:
+        c = F.P - F.invL
+        B.dhs = (c * dP0).sum((-1, -2))
+        B.m_dhs = (c * dP0).abs().sum((-1, -2))
+        B.e_dhs = (F.eP * dP0.abs() + (c.abs() + F.eP) * e_dP0).sum((-1, -2)) + 2 * U32 * B.m_dhs      # P - 1/L and the product, per term
+        dP, e_dP = dP0 * F.hv, e_dP0 * F.hv.abs() + U32 * (dP0 * F.hv).abs()
+    else:
+        dP, e_dP = dP0, e_dP0
+    dot = (F.P * dP).sum(-1, keepdim=True)
+    e_dot = (F.eP * dP.abs() + (F.P + F.eP) * e_dP).sum(-1, keepdim=True) + gamma(L + 1) * (F.P * dP.abs()).sum(-1, keepdim=True)
+    dS = F.P * (dP - dot)
+    e_dS = F.eP * (dP - dot).abs() + (F.P + F.eP) * (e_dP + e_dot) + 2 * U32 * dS.abs()
+    if F.with_emb:
+        flat = lambda z: torch.zeros(z.shape[0], z.shape[1], 32, dtype=z.dtype, device=z.device).index_add(2, F.bk.flatten(), z.flatten(-2))
+        B.demb, B.e_demb, B.m_demb = flat(dS), flat(e_dS), flat(dS.abs())
+    e_dSb = e_dS * (1 + u_op) + u_op * dS.abs()                             # fp32 in LDS, one rounding as an operand of dqn / dkn
+    B.dv = T(F.A) @ g
+    B.e_dv = T(F.eAb) @ (g.abs() + e_g) + T(F.A.abs()) @ e_g + gamma(L) * (T(F.A.abs()) @ g.abs())
+    post = lambda acc, e: (acc * F.scale, e * F.scale * (1 + 5 * U32) + 5 * U32 * (acc * F.scale).abs())     # acc * rsqrtf(d), as the scores
+    B.dkn, B.e_dkn = post(T(dS) @ F.qn, T(e_dSb) @ (F.qn.abs() + F.eq) + T(dS.abs()) @ F.eq + gamma(L) * (T(dS.abs()) @ F.qn.abs()))
+    B.dqn, B.e_dqn = post(dS @ F.kn, e_dSb @ (F.kn.abs() + F.ek) + dS.abs() @ F.ek + gamma(L) * (dS.abs() @ F.kn.abs()))
     return B
 
 
@@ -353,11 +445,14 @@ def plain(qkv, dout, geo, heads, d, prm, with_emb, with_hs, out_scale, mode, old
 def axial_pair(qkv, dout, frames, h, w, heads, d, prm, mode, with_emb=True, with_hs=True):
     """The W pass then the H pass accumulated (out_scale 0.5 each): forward accumulate 0 then 1 (or the one-launch kernel, which
     rounds its intermediate the same way), backward accumulate 2 then 5.  prm = (qw, qb, kw, kb, emb, hscale_x, hscale_y).
+    mode: one Mode, or (the W pass's, the H pass's) when the axes run in different kernels.
     -> {name: (ref, bnd)}: out, dq, dk, dv in token layout [N][heads][d]; dqw .. dkb [d]; demb (both passes) [32][heads];
     dhscale_x, dhscale_y [heads]."""
     N = frames * h * w
     gW, gH = axial_geos(frames, h, w)
-    FW = forward(qkv, gW, heads, d, list(prm[:5]) + [prm[5]], with_emb, with_hs, mode)
+    modeW, mode = mode if isinstance(mode[0], tuple) else (mode, mode)      # (W pass's mode, H pass's mode): a short and a long axis
+    assert modeW.u_st == mode.u_st
+    FW = forward(qkv, gW, heads, d, list(prm[:5]) + [prm[5]], with_emb, with_hs, modeW)
     FH = forward(qkv, gH, heads, d, list(prm[:5]) + [prm[6]], with_emb, with_hs, mode)
     tokW = lambda z: to_tokens(z, FW.idx, N)
     tokH = lambda z: to_tokens(z, FH.idx, N)
