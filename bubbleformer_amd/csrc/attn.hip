@@ -10,37 +10,15 @@
 // LayerNorm / bias-table / scale-factor gradients (block-reduced, then fp32 atomics).
 //
 // This is the generic fp32-VALU form (any d <= 128, any L <= 32, both dtypes).
-#include "bf_common.h"
+#include "lane_ops.h"
 #include "param_reduce.h"
 
 namespace {
 
 constexpr int NT = 256;           // at most 4 waves per block; fewer when a problem's LDS plan is large
-__device__ __forceinline__ void wave_sync() {
-    // the wave's own LDS traffic is in order; this only pins the compiler's ordering of it
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 constexpr int LMAX = 32;           // this file's kernels and attn_mfma.hip; 33..128 run in attn_long.hip
 constexpr int LONG_LMAX = 128;
 constexpr int DMAX = 128;
-
-// one-sided T5 bucket for |offset| (num_buckets 32 -> 16 per side, max_exact 8, max_distance 32);
-// restated from the reference formula, checked against the reference's tables in the tests.
-__device__ __forceinline__ int t5_bucket(int n) {
-    const int a = n < 0 ? -n : n;
-    int b;
-    if (a < 8) b = a;
-    else if (a < 10) b = 8;
-    else if (a < 12) b = 9;
-    else if (a < 14) b = 10;
-    else if (a < 16) b = 11;
-    else if (a < 20) b = 12;
-    else if (a < 23) b = 13;
-    else if (a < 27) b = 14;
-    else b = 15;
-    return b + (n < 0 ? 16 : 0);   // n = query - key; key after query -> upper half
-}
 
 struct SeqGeo {
     long nseq; int L; long inner; long outer_stride; long inner_stride; long tok_stride;
@@ -109,7 +87,7 @@ __device__ __forceinline__ void scores_softmax(const float* qh, const float* kh,
         if (p.emb) s += p.emb[t5_bucket(i - j) * heads + head];
         sP[i * lds + j] = s;
     }
-    wave_sync();
+    wsync();
     if (lane < L) {
         float* row = sP + lane * lds;
         float m = -INFINITY;
@@ -125,7 +103,7 @@ __device__ __forceinline__ void scores_softmax(const float* qh, const float* kh,
             sA[lane * lds + j] = p.hscale ? (invL + (pr - invL) * hs) : pr;
         }
     }
-    wave_sync();
+    wsync();
 }
 
 template <typename T>
@@ -148,9 +126,9 @@ __global__ void __launch_bounds__(NT) attn_fwd_kernel(const T* __restrict__ qkv,
         const int head = (int)(pr % heads);
         const long tok0 = seq_base(g, s);
         load_rows<T>(qkv + head * 3 * d, 3L * E, q, L, 3 * d, ldd, d, tok0, g.tok_stride, lane, 1.f);
-        wave_sync();
+        wsync();
         ln_rows(q, k, rstd, L, d, ldd, lane);
-        wave_sync();
+        wsync();
         scores_softmax(q, k, p, head, heads, L, d, ldd, sA, sA, lane);
         for (int e = lane; e < d; e += 64) {
             for (int i = 0; i < L; ++i) {
@@ -162,7 +140,7 @@ __global__ void __launch_bounds__(NT) attn_fwd_kernel(const T* __restrict__ qkv,
                 out[o] = from_f<T>(r);
             }
         }
-        wave_sync();
+        wsync();
     }
 }
 
@@ -203,9 +181,9 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
         const long tok0 = seq_base(g, s);
         load_rows<T>(qkv + head * 3 * d, 3L * E, q, L, 3 * d, ldd, d, tok0, g.tok_stride, lane, 1.f);
         load_rows<T>(dout + head * d, (long)E, dO, L, d, ldd, d, tok0, g.tok_stride, lane, out_scale);
-        wave_sync();
+        wsync();
         ln_rows(q, k, rstd, L, d, ldd, lane);
-        wave_sync();
+        wsync();
         scores_softmax(q, k, p, head, heads, L, d, ldd, sP, sA, lane);
         // dV[j][e] = sum_i A[i][j] dO[i][e]   -> stored into dkn temporarily? no: write straight to global later; keep in regs
         // dA[i][j] = sum_e dO[i][e] v[j][e]
@@ -220,7 +198,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 for (int i = 0; i < L; ++i) acc += sA[i * lds + j] * dO[i * ldd + e];
                 dqn[j * ldd + e] = acc;          // dV parked in the dqn plane
             }
-        wave_sync();
+        wsync();
         // write dV now (frees the plane)
         {
             constexpr int CH = Chunk<T>::N;
@@ -235,7 +213,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 o.store(dst);
             }
         }
-        wave_sync();
+        wsync();
         // 2) dA -> dP -> dS (into sA)
         for (int t = lane; t < L * L; t += 64) {
             const int i = t / L, j = t % L;
@@ -244,13 +222,13 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
             if (p.hscale) { dhs_part += (sP[i * lds + j] - invL) * acc; acc *= hs; }
             sA[i * lds + j] = acc;               // dP
         }
-        wave_sync();
+        wsync();
         if (lane < L) {
             float dot = 0.f;
             for (int j = 0; j < L; ++j) dot += sP[lane * lds + j] * sA[lane * lds + j];
             for (int j = 0; j < L; ++j) sA[lane * lds + j] = sP[lane * lds + j] * (sA[lane * lds + j] - dot);   // dS
         }
-        wave_sync();
+        wsync();
         // bias-table gradient: Toeplitz -> lane q sums diagonal i - j = q - (L - 1) top to bottom (2L - 1 <= 63 diagonals), then lane b adds
         // the diagonals of bucket b in diagonal order into this wave's table
         if (gr.demb) {
@@ -260,14 +238,14 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 for (int i = max(0, dd); i < min(L, L + dd); ++i) t += sA[i * lds + (i - dd)];
                 s_diag[wave][lane] = t;
             }
-            wave_sync();
+            wsync();
             if (lane < 32) {
                 float t = 0.f;
                 for (int q = 0; q < 2 * L - 1; ++q)
                     if (t5_bucket(q - (L - 1)) == lane) t += s_diag[wave][q];
                 s_demb[wave][lane * 16 + head] += t;
             }
-            wave_sync();
+            wsync();
         }
         if (p.hscale) {
             dhs_part = wave_sum(dhs_part);
@@ -286,7 +264,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 dkn[i * ldd + e] = a2 * scale;
             }
         }
-        wave_sync();
+        wsync();
         // LayerNorm parameter grads (per column) ...
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -300,7 +278,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 a_qw[c] += sw; a_qb[c] += sb; a_kw[c] += tw; a_kb[c] += tb;
             }
         }
-        wave_sync();
+        wsync();
         // ... and LayerNorm input grads, row per lane, in place: dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dn * w
         if (lane < 2 * L) {
             const bool isq = lane < L;
@@ -314,7 +292,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
             const float rs = rstd[lane];
             for (int e = 0; e < d; ++e) dn[e] = rs * (dn[e] * w[e] - m1 - xh[e] * m2);
         }
-        wave_sync();
+        wsync();
         // write dq, dk
         {
             constexpr int CH = Chunk<T>::N;
@@ -331,7 +309,7 @@ __global__ void __launch_bounds__(NT) attn_bwd_kernel(const T* __restrict__ qkv,
                 o.store(dst);
             }
         }
-        wave_sync();
+        wsync();
     }
     // flush parameter gradients: the wave's LayerNorm columns into its own (now idle) tile area, then one value per thread, waves in order
 #pragma unroll

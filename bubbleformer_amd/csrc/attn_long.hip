@@ -15,7 +15,7 @@
 // the LDS that P held.  Parameter gradients (q / k LayerNorm affine, T5 table, head scale) are summed per workgroup in LDS by ONE
 // thread per value in problem order, and each workgroup leaves one row in the AttnReduceJob layout of param_reduce.h: the step stays
 // bit-reproducible (no float atomics on shared addresses; with no workspace the rows are added to the gradients with atomics instead).
-#include "bf_common.h"
+#include "lane_ops.h"
 #include "param_reduce.h"
 
 namespace {
@@ -23,22 +23,6 @@ namespace {
 constexpr int NTL = 256;            // threads per workgroup
 constexpr int CW = 16, CLD = CW + 1;     // columns per staged slice, its LDS row pitch
 constexpr int LONG_LMAX = 128, LONG_DMAX = 128;
-
-// one-sided T5 bucket for |offset| (num_buckets 32, max_exact 8, max_distance 32): every |offset| >= 27 is bucket 15 (attn.hip's table)
-__device__ __forceinline__ int t5_bucket_long(int n) {
-    const int a = n < 0 ? -n : n;
-    int b;
-    if (a < 8) b = a;
-    else if (a < 10) b = 8;
-    else if (a < 12) b = 9;
-    else if (a < 14) b = 10;
-    else if (a < 16) b = 11;
-    else if (a < 20) b = 12;
-    else if (a < 23) b = 13;
-    else if (a < 27) b = 14;
-    else b = 15;
-    return b + (n < 0 ? 16 : 0);
-}
 
 struct LGeo { long nseq; int L; long inner, outer_stride, inner_stride, tok_stride; };
 struct LPar { const float *qw, *qb, *kw, *kb, *emb, *hscale; };
@@ -189,7 +173,7 @@ __device__ __forceinline__ void scores(const T* __restrict__ qkv, long tok0, lon
                 for (int r = 0; r < 4; ++r) {
                     const int i = 16 * (b / NA) + 4 * (lane >> 4) + r, j = 16 * (b % NA) + (lane & 15);
                     float s = acc[t][r] * scale;
-                    if (has_emb) s += s_emb[t5_bucket_long(i - j)];
+                    if (has_emb) s += s_emb[t5_bucket(i - j)];
                     M[i * LDM + j] = j < L ? s : -INFINITY;
                 }
             }
@@ -216,7 +200,7 @@ __device__ __forceinline__ void scores(const T* __restrict__ qkv, long tok0, lon
         for (int b = 0; b < NA; ++b) {
             const int i = ti + 16 * a, j = tj + 16 * b;
             float s = acc[a][b] * scale;
-            if (has_emb) s += s_emb[t5_bucket_long(i - j)];
+            if (has_emb) s += s_emb[t5_bucket(i - j)];
             M[i * LDM + j] = j < L ? s : -INFINITY;
         }
     __syncthreads();
@@ -445,7 +429,7 @@ __global__ void __launch_bounds__(NTL) attn_bwd_long(const T* __restrict__ qkv, 
             if (t < 32) {
                 float sum = 0.f;
                 for (int u = 0; u < 2 * L - 1; ++u)
-                    if (t5_bucket_long(u - (L - 1)) == t) sum += diag[u];
+                    if (t5_bucket(u - (L - 1)) == t) sum += diag[u];
                 a_emb[t * 16 + head] += sum;
             }
         }

@@ -14,55 +14,12 @@
 //     dKn^T[e][j] = sum_i Qn[i][e] dS[i][j]         A = Qn^T (tr read), B = dS^T through a small LDS transpose
 //     dV^T[e][j]  = sum_i dO[i][e] A[i][j]          A = dO^T (tr read), B = A^T through the same transpose
 // and finishes LayerNorm backward in the operand layout after one LDS re-layout (16-byte global stores).
-#include "bf_common.h"
+#include "lane_ops.h"
 #include "param_reduce.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
-
-// All outstanding vector-memory operations complete, as an s_waitcnt the compiler's wait-count pass models (an inline-asm wait is opaque to
-// it).  In front of a loop that prefetches the next problem's rows: the pass merges the loop header's pending-load state from the preheader
-// and the back edge, and with the first problem's loads still pending there it counts every use of `cur` at the top of the body against
-// them -- vmcnt(7), vmcnt(6), ... right behind the eight NEW loads, i.e. a full memory round trip per problem and no look-ahead at all.
-__device__ __forceinline__ void drain_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // vmcnt(0), expcnt / lgkmcnt untouched
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ int t5b(int n) {   // n = query - key  (see attn.hip)
-    const int a = n < 0 ? -n : n;
-    int b;
-    if (a < 8) b = a; else if (a < 10) b = 8; else if (a < 12) b = 9; else if (a < 14) b = 10; else if (a < 16) b = 11;
-    else if (a < 20) b = 12; else if (a < 23) b = 13; else if (a < 27) b = 14; else b = 15;
-    return b + (n < 0 ? 16 : 0);
-}
-// Reductions over a lane quad {l, l+16, l+32, l+48} with the gfx950 row-swap VALU ops (no LDS crossbar round trip):
-// v_permlane16_swap(a, b) exchanges the odd 16-lane rows of a with the even rows of b, v_permlane32_swap the upper half of a
-// with the lower half of b; with a = b = v the two results are v and its xor-16 / xor-32 partner in every lane.
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float quad_sum(float v) {
-    u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// total of a 16-lane row in every lane of the row: xor-1 / xor-2 quad permutes, then the half-row and row mirrors (DPP, no LDS)
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-    return v;
-}
-__device__ __forceinline__ float quad_max(float v) {
-    u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
 
 struct Geo { long nseq; int L; long inner, outer_stride, inner_stride, tok_stride; };
 // Where problem pr = sequence * heads + head starts.  pr is wave-uniform (the wave index comes through readfirstlane), so this is scalar
@@ -78,10 +35,6 @@ __device__ __forceinline__ Prob locate(const Geo& g, int heads, long pr) {
 // Totals over the 16 lanes of a row of sixteen values, value v landing in lane v of the row: four halving exchange steps (mirror,
 // half-mirror, xor 2, xor 1 -- one DPP add per surviving value: 8 + 4 + 2 + 1) instead of sixteen full row sums and sixteen selects.
 // In each step a lane keeps the half of its values whose index bit matches its own lane bit and receives its partner's copy of it.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float keep, float send) {
-    return keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float row16_scatter_sum(const float (&p)[16], int i16) {
     // The two wide steps (8 + 4 survivors) as bank-masked DPP adds: lanes whose index bit is 0 take own + partner's copy of the low half of the
     // values, lanes whose bit is 1 the same of the high half -- both halves of a result register written by one v_add_f32_dpp each, no select,
@@ -111,17 +64,6 @@ __device__ __forceinline__ float row16_scatter_sum(const float (&p)[16], int i16
 struct Par { const float *qw, *qb, *kw, *kb, *emb, *hscale; };
 struct Grd { float *dqw, *dqb, *dkw, *dkb, *demb, *dhscale; };
 
-// transposing read of a 4-row x 16-col block of a bf16 LDS tile (row stride ld elements): lane i16 of the 16-lane group gets
-// column c0 + i16 of rows r0..r0+3
-__device__ __forceinline__ s16x4 tr4(const bf16* tile, int ld, int r0, int c0, int lane) {
-    const int i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tile + (r0 + q) * ld + c0 + 4 * p));
-}
-__device__ __forceinline__ bf16x8 cat(s16x4 lo, s16x4 hi) {
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ short bfbits(float x) { return __builtin_bit_cast(short, (bf16)x); }
 
 // Load one 16-row block of q (part 0) / k (1) / v (2) rows as fp32 in the operand layout:
 // lane (i = l & 15, g = l >> 4) gets channels 32*s + 8*g + jj of row i.
@@ -230,7 +172,7 @@ __device__ __forceinline__ void lane_masks(int L, int lane, float (&mk)[NB][NB][
                 const int i = 16 * ib + i16, j = 16 * jb + 4 * gq + r;
                 mk[jb][ib][r] = (i < L && j < L) ? 1.f : 0.f;
                 mneg[jb][ib][r] = j < L ? 0.f : -INFINITY;
-                eidx[jb][ib][r] = t5b(i - j) * 16;
+                eidx[jb][ib][r] = t5_bucket(i - j) * 16;
             }
 }
 // registers (key blocks x 4) of one query block -> the B operand whose k-slot (g, jj) is key 4g+jj / 16+4g+jj-4
@@ -944,7 +886,7 @@ __global__ void __launch_bounds__(256, ((NB == 1 && KS <= 2) ? 2 : 1)) attn_bwd_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = 16 * ib + i16, j = 16 * jb + 4 * gq + r;
-                    if (gr.demb && i < L && j < L) atomicAdd(&s_demb[t5b(i - j) * 16 + head], a_emb[jb][ib][r]);
+                    if (gr.demb && i < L && j < L) atomicAdd(&s_demb[t5_bucket(i - j) * 16 + head], a_emb[jb][ib][r]);
                 }
         if (p.hscale && gr.dhscale) {
             a_dhs = wave_sum(a_dhs);

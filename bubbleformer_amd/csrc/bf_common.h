@@ -137,6 +137,12 @@ __device__ __forceinline__ float dgelu_f(float x) {
     const float cdf = 0.5f * (1.0f + copysignf(1.0f - poly * e, x));
     return cdf + x * (0.39894228040143267794f * e);
 }
+// The U-Net kernels (conv.hip, bn.hip) take the library erff instead, in every mode: the conv prologue must agree bit for bit between
+// forward, weight gradient and the GroupNorm / BatchNorm backward that recomputes it.  Not gelu_f: erf_fast and erff differ in the last bits.
+__device__ __forceinline__ float gelu_erff(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+__device__ __forceinline__ float dgelu_erff(float x) {
+    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
+}
 
 // bf16-storage kernels: Phi(x) and gelu'(x) as odd polynomials around 1/2 on |x| <= 4 (clamped beyond: Phi(4) = 1 - 3.2e-5), no
 // transcendentals -- 11-13 plain VALU operations instead of ~20 with a reciprocal and an exponential.  |error| <= 2.5e-5 (Phi) and

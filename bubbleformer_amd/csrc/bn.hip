@@ -19,12 +19,6 @@ namespace {
 constexpr int BN_THREADS = 256;
 constexpr int BN_TARGET_WGS = 2048;
 
-// exact-erf GELU and its derivative, the same expressions as conv.hip's prologue
-__device__ __forceinline__ float gelu_e(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float dgelu_e(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
-}
-
 template <typename T>
 __device__ __forceinline__ float ld(const T* p, int64_t i) { return (float)p[i]; }
 
@@ -121,7 +115,7 @@ __global__ void bn_act_kernel(const T* __restrict__ x, int C, int64_t total, con
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % C);
-    a[i] = (T)gelu_e(fmaf(ld(x, i), sc[c], sh[c]));
+    a[i] = (T)gelu_erff(fmaf(ld(x, i), sc[c], sh[c]));
 }
 
 // one thread per (2x2 window, channel), windows covering the frame (the last row / column of an odd frame forms partial windows that
@@ -144,7 +138,7 @@ __global__ void bn_act_pool_kernel(const T* __restrict__ x, int H, int W, int C,
         const int y = 2 * wy + (j >> 1), xx = 2 * wx + (j & 1);
         if (y >= H || xx >= W) continue;
         const int64_t o = (((int64_t)f * H + y) * W + xx) * C + c;
-        const T v = (T)gelu_e(fmaf(ld(x, o), s, h));
+        const T v = (T)gelu_erff(fmaf(ld(x, o), s, h));
         a[o] = v;
         const float vf = (float)v;
         if (j == 0 || vf > best || isnan(vf)) { best = vf; bi = j; }
@@ -168,7 +162,7 @@ __device__ __forceinline__ float bn_grad_in(const float* dA, int64_t ldA, const 
             if (idx[o] == ((y & 1) << 1 | (x & 1))) g += ld(dP, o);
         }
     }
-    return g * dgelu_e(u);
+    return g * dgelu_erff(u);
 }
 
 // ws[z][c] = {sum g, sum g*xhat} over slab z.  grid (ceil(C/CW), slabs)

@@ -19,6 +19,7 @@
 // predecessor / successor) or new, a block-wide exclusive scan numbers the new tracks in bubble order, and one drained barrier closes the frame
 // (the next frame reads this frame's ids back through the L2).
 #include "clip_store.h"
+#include "lane_ops.h"
 #include <algorithm>
 
 namespace {
@@ -32,11 +33,6 @@ typedef __attribute__((address_space(1))) int gint;
 #define BF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 #define BF_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
 
-// all waves' global stores and atomics have reached the L2 before anybody goes on
-__device__ __forceinline__ void drain_and_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
 // a value another thread of this workgroup left in global memory before the last drained barrier, and such a value's store: both through the L2
 __device__ __forceinline__ int ld_l2(const int* p) { return __hip_atomic_load((gint*)p, BF_RLX_AGENT); }
 __device__ __forceinline__ void st_l2(int* p, int v) { __hip_atomic_store((gint*)p, v, BF_RLX_AGENT); }

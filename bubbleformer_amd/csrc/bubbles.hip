@@ -20,6 +20,7 @@
 // continues only with a strictly smaller pair.  The error flag turns the frame's count into -1.  Integer atomics only: the same bits on every
 // call, and a frame has the same bits alone and in a batch.
 #include "clip_store.h"
+#include "lane_ops.h"
 #include <algorithm>
 
 namespace {
@@ -33,11 +34,6 @@ typedef __attribute__((address_space(1))) long long glong;
 #define BF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 #define BF_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
 
-// all waves' global stores and atomics have reached the L2 before anybody goes on
-__device__ __forceinline__ void drain_and_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
 
 struct LdsParents {
     int* L;

@@ -52,13 +52,6 @@ __device__ __forceinline__ void src_st(const Src& s, int f, int y, int x, int c,
     else reinterpret_cast<T*>(const_cast<void*>(s.p))[o] = (T)v;
 }
 
-// exact-erf GELU and its derivative in every mode: the prologue must agree bit for bit between forward, weight gradient and the
-// GroupNorm backward that recomputes it
-__device__ __forceinline__ float gelu_x(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float dgelu_x(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
-}
-
 struct Gather {
     Src s0, s1;
     int C0, Cin;               // Cin = C0 + s1.C
@@ -85,8 +78,8 @@ __device__ __forceinline__ float gather(const Gather& g, int f, int oy, int ox, 
     }
     if (iy >= g.Hi || ix >= g.Wi) return 0.f;
     float v = c < g.C0 ? src_ld<T>(g.s0, f, iy, ix, c, g.Hi, g.Wi) : src_ld<T>(g.s1, f, iy, ix, c - g.C0, g.Hi, g.Wi);
-    if (g.pro == BF_CONV_PRO_AFFINE_GELU) v = gelu_x(fmaf(v, g.sc[(int64_t)f * g.Cin + c], g.sh[(int64_t)f * g.Cin + c]));
-    else if (g.pro == BF_CONV_PRO_GELU) v = gelu_x(v);
+    if (g.pro == BF_CONV_PRO_AFFINE_GELU) v = gelu_erff(fmaf(v, g.sc[(int64_t)f * g.Cin + c], g.sh[(int64_t)f * g.Cin + c]));
+    else if (g.pro == BF_CONV_PRO_GELU) v = gelu_erff(v);
     return v;
 }
 
@@ -374,7 +367,7 @@ __global__ void __launch_bounds__(256) gn_bwd_partial_kernel(const float* __rest
         for (int pix = b + rl; pix < e; pix += 4) {
             const int y = pix / W, x = pix - y * W;
             const float v = c < C0 ? src_ld<T>(s0, f, y, x, c, HW / W, W) : src_ld<T>(s1, f, y, x, c - C0, HW / W, W);
-            const float gv = dA[((int64_t)f * HW + pix) * Cin + c] * dgelu_x(fmaf(v, a, s));
+            const float gv = dA[((int64_t)f * HW + pix) * Cin + c] * dgelu_erff(fmaf(v, a, s));
             a1 += gv; a2 += (double)gv * ((v - mu) * r);
         }
     }
@@ -436,11 +429,11 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ dA, Src s0, Src s1
     float gv;
     if (gamma) {
         const int gi = c / (Cin / G);
-        const float g = dA[i] * dgelu_x(fmaf(v, sc[f * Cin + c], sh[f * Cin + c]));
+        const float g = dA[i] * dgelu_erff(fmaf(v, sc[f * Cin + c], sh[f * Cin + c]));
         const float r = rstd[f * G + gi], xh = (v - mean[f * G + gi]) * r;
         gv = r * (gamma[c] * g - coef[2 * (f * G + gi)] - xh * coef[2 * (f * G + gi) + 1]);
     } else {
-        gv = dA[i] * dgelu_x(v);
+        gv = dA[i] * dgelu_erff(v);
     }
     if (add.p) gv += src_ld<T>(add, f, y, x, c, H, W);
     if (c < C0) src_st<T>(d0, f, y, x, c, H, W, gv);

@@ -21,38 +21,13 @@
 // tile pass through a wave-private LDS tile so that the transposing read returns them in the accumulator layout (lane = channel,
 // four consecutive pixels) -- which is also the MFMA A-operand layout of the pixel contraction, so dd goes from the accumulators
 // into the next MFMA without leaving the lane.  Waves never meet between the weight load and the final reduction.
-#include "bf_common.h"
+#include "lane_ops.h"
 #include <algorithm>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-// sum over the lane quad {l, l+16, l+32, l+48} (v_permlane16_swap / v_permlane32_swap), in every lane
-__device__ __forceinline__ float quad_sum(float v) {
-    u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// transposing read of a 4-row x 16-col block of a bf16 LDS tile: lane i16 of the 16-lane group gets column c0 + i16 of rows r0..r0+3
-__device__ __forceinline__ s16x4 tr4(const bf16* tile, int ld, int r0, int c0, int lane) {
-    const int i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tile + (r0 + q) * ld + c0 + 4 * p));
-}
-__device__ __forceinline__ bf16x8 cat(s16x4 lo, s16x4 hi) {
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ float bf_bits_f(short b) { return __uint_as_float(((unsigned)(unsigned short)b) << 16); }
-__device__ __forceinline__ short f_bf_bits(float x) { return __builtin_bit_cast(short, (bf16)x); }
 
 struct TailArgs {
     const bf16 *dy1, *w1, *y0, *patches, *w0;     // y0 may be null: the stage-0 rows are then rebuilt from the patch rows (y0 = W0 . patch)
@@ -206,7 +181,7 @@ __global__ void __launch_bounds__(64 * TWAVES, 2) embed_tail_bwd_kernel(TailArgs
                     const float dd = acc[rb][cb][r] * dgelu_fast(fmaf(y, k4.x, k4.y));
                     s1[cb] += dd;
                     s2[cb] = fmaf(dd, fmaf(y, k4.z, k4.w), s2[cb]);
-                    ddp[4 * rb + r] = f_bf_bits(dd);
+                    ddp[4 * rb + r] = bfbits(dd);
                 }
             accG[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ddp), pf, accG[cb], 0, 0, 0);
         }

@@ -36,29 +36,6 @@ struct FrameArgs {
     const float* xw; const float* xb; bf16* xn; long ldx;        // second output: the NEXT layer's InstanceNorm of `out` (its norm1), xn = IN(out) * xw + xb
 };
 
-__device__ __forceinline__ void wait_vm_n(int n) {      // n is wave-uniform; a smaller count than asked for is always safe (in-order retirement)
-    if (n >= 16) { wait_vm<16>(); return; }
-    switch (n) {
-        case 0: wait_vm<0>(); break;   case 1: wait_vm<1>(); break;   case 2: wait_vm<2>(); break;   case 3: wait_vm<3>(); break;
-        case 4: wait_vm<4>(); break;   case 5: wait_vm<5>(); break;   case 6: wait_vm<6>(); break;   case 7: wait_vm<7>(); break;
-        case 8: wait_vm<8>(); break;   case 9: wait_vm<9>(); break;   case 10: wait_vm<10>(); break; case 11: wait_vm<11>(); break;
-        case 12: wait_vm<12>(); break; case 13: wait_vm<13>(); break; case 14: wait_vm<14>(); break; default: wait_vm<15>(); break;
-    }
-}
-// 8-byte load the compiler does not count (it would drain the DMA queue at the first use): completion by the caller's wait
-__device__ __forceinline__ void gload8(uint2& dst, const void* p) { asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dst) : "v"(p) : "memory"); }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
-
-// v + (v of lane ^ o), o = 8 / 16 / 32: VALU only (norm.hip's reduction steps)
-__device__ __forceinline__ float lane_xor_add(float v, int o) {
-    if (o == 8) return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));   // row_ror:8
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(v);
-    const u2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float rg8_sum(float v) { return lane_xor_add(lane_xor_add(lane_xor_add(v, 8), 16), 32); }
-
 // one DMA piece: rows 8p .. 8p+7 of a [rows][64] block; lane -> row 8p + (lane >> 3), LDS chunk (lane & 7) = global chunk
 // (lane & 7) ^ ((row >> 1) & 7) of that row (lds_off<bf16, false, 64>)
 __device__ __forceinline__ void dma_piece(const bf16* g0, long ld, unsigned lds_blk, int p, int lane) {
@@ -69,6 +46,7 @@ __device__ __forceinline__ void dma_piece(const bf16* g0, long ld, unsigned lds_
 // One frame's column statistics in in_stats_kernel's summation order (norm.hip: 32 row groups of rows rg + 32 q, eight row groups per
 // wave reduced by lane ^ 8, 16, 32, the four waves added in order).  A lane holds row group residue `lane >> 3` of 8 channels:
 // x[w4][qq][j] = row 8 w4 + (lane >> 3) + 32 qq (w4 < 4; qq < 5 where that row is < 144), channel j.  Returns mean and 1/sqrt(var + eps).
+// (no twin of gemm_frame.hip's frame_stats: that one takes packed bf16 rows 16 i + li)
 template <int NJ>
 __device__ __forceinline__ void frame_stats(const float (&x)[4][5][NJ], float (&mu)[NJ], float (&rs)[NJ]) {
     float tot[NJ];

@@ -10,25 +10,13 @@
 // consecutive channels: 16-byte loads, one 2x2 position ahead of the products), applies f there -- each element exactly once --
 // and leaves through v_permlane16_swap with 8 consecutive output columns per lane (16-byte stores).  Waves never meet after the
 // weight load.
-#include "bf_common.h"
+#include "lane_ops.h"
 #include <algorithm>
 #include <stdint.h>
 
 namespace {
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
 constexpr int GW = 4;                                   // waves per workgroup
-// transposing read of a 4-row x 16-col block of a bf16 LDS tile: lane i16 of the 16-lane group gets column c0 + i16 of rows r0..r0+3
-__device__ __forceinline__ s16x4 tr4g(const bf16* tile, int ld, int r0, int c0, int lane) {
-    const int i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tile + (r0 + q) * ld + c0 + 4 * p));
-}
-__device__ __forceinline__ bf16x8 cat8(s16x4 lo, s16x4 hi) {
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
 
 struct GatherArgs {
     const bf16 *patches, *w0; // REB: the fine map is W0 . patch ([pixels][16] x [C0][16]) and is rebuilt per tile instead of read
@@ -141,7 +129,7 @@ __global__ void __launch_bounds__(64 * GW, 2) gather_gemm_kernel(GatherArgs a) {
 #pragma unroll
                 for (int nb = 0; nb < NNB; ++nb) {
                     const bf16* wrow = Wt + (16 * nb + i16) * LDK + C0 * q + 32 * s;
-                    const bf16x8 aw = REB ? cat8(*reinterpret_cast<const s16x4*>(wrow + 4 * g), *reinterpret_cast<const s16x4*>(wrow + 16 + 4 * g))
+                    const bf16x8 aw = REB ? cat(*reinterpret_cast<const s16x4*>(wrow + 4 * g), *reinterpret_cast<const s16x4*>(wrow + 16 + 4 * g))
                                           : *reinterpret_cast<const bf16x8*>(wrow + 8 * g);
 #pragma unroll
                     for (int rb = 0; rb < 2; ++rb) acc[nb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw, fb[rb], acc[nb][rb], 0, 0, 0);
@@ -186,14 +174,6 @@ struct ScatterArgs {
     int w_kn, F, gh, gw, tiles;
 };
 template <int NKB, int NCB> constexpr int scatter_lds_bytes() { return 4 * 16 * NCB * (32 * NKB + 8) * 2; }
-
-__device__ __forceinline__ float row16_total(float v) {      // sum over the 16 lanes of a row, in every lane (DPP: xor 1, xor 2, half mirror, mirror)
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
 
 template <int NKB, int NCB, bool PRO>
 __global__ void __launch_bounds__(64 * GW, 2) scatter_gemm_kernel(ScatterArgs a) {
@@ -296,7 +276,7 @@ __global__ void __launch_bounds__(64 * GW, 2) scatter_gemm_kernel(ScatterArgs a)
             for (int pp = 0; pp < NCB / 2; ++pp)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float t1 = row16_total(ssum[pp][j]), t2 = row16_total(ssq[pp][j]);
+                    const float t1 = row16_sum(ssum[pp][j]), t2 = row16_sum(ssq[pp][j]);
                     const float mu = t1 * (1.0f / 128.0f);
                     if (i16 == 0) o2[32 * pp + j] = make_float2(mu, fmaxf(t2 - t1 * mu, 0.f));
                 }
@@ -413,10 +393,10 @@ __global__ void __launch_bounds__(64 * WW, 4) gather_wgrad_kernel(WgradArgs a) {
         // k-slot (g, jj) := row 4g + jj (jj < 4) / row 16 + 4g + jj - 4: the same order on both operands
         bf16x8 fa[3];
 #pragma unroll
-        for (int cb = 0; cb < 3; ++cb) fa[cb] = cat8(tr4g(ftile, LDF, 4 * g, 16 * cb, lane), tr4g(ftile, LDF, 16 + 4 * g, 16 * cb, lane));
+        for (int cb = 0; cb < 3; ++cb) fa[cb] = cat(tr4(ftile, LDF, 4 * g, 16 * cb, lane), tr4(ftile, LDF, 16 + 4 * g, 16 * cb, lane));
 #pragma unroll
         for (int kb = 0; kb < 6; ++kb) {
-            const bf16x8 fbk = cat8(tr4g(ct, LDC, 4 * g, 16 * kb, lane), tr4g(ct, LDC, 16 + 4 * g, 16 * kb, lane));
+            const bf16x8 fbk = cat(tr4(ct, LDC, 4 * g, 16 * kb, lane), tr4(ct, LDC, 16 + 4 * g, 16 * kb, lane));
 #pragma unroll
             for (int cb = 0; cb < 3; ++cb) acc[cb][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[cb], fbk, acc[cb][kb], 0, 0, 0);
         }

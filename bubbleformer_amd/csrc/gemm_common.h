@@ -1,6 +1,7 @@
-// Device helpers shared by the GEMM kernels (gemm.hip tile kernel, gemm_frame.hip whole-frame tiles, gemm_stream.hip / gemm_tokred.hip LDS-DMA kernels).
+// Device helpers shared by the GEMM kernels (gemm.hip tile kernel, gemm_frame.hip whole-frame tiles, gemm_stream.hip / gemm_tokred.hip LDS-DMA kernels):
+// what knows a GEMM tile.  The LDS-DMA, wait-count and lane primitives they are built from come with lane_ops.h.
 #pragma once
-#include "bf_common.h"
+#include "lane_ops.h"
 
 namespace bfgemm {
 
@@ -86,12 +87,8 @@ __device__ __forceinline__ bf16x8 frag_bf16(const bf16* t, int outer, int k0, in
         // tile is [k][outer]; transposing read: lane 4q+p of a 16-lane group supplies row q, cols 4p..4p+3,
         // lane i receives column i of the 4 rows.
         const int q = i >> 2, p = i & 3;
-        typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(t + lds_off<bf16, true, LDT>(k0 + 8 * g + q, outer + 4 * p)));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(t + lds_off<bf16, true, LDT>(k0 + 8 * g + q + 4, outer + 4 * p)));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, r);
+        return cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(t + lds_off<bf16, true, LDT>(k0 + 8 * g + q, outer + 4 * p))),
+                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(t + lds_off<bf16, true, LDT>(k0 + 8 * g + q + 4, outer + 4 * p))));
     }
 }
 template <bool XC, int LDT>
@@ -109,21 +106,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     const int q = nwg / 8, r = nwg % 8, x = bid % 8;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
 }
-
-// ----------------------------------------------------------------------------- LDS-DMA (global -> LDS, no staging registers)
-// One global_load_lds_dwordx4: lane l copies the 16 bytes at its OWN source address to LDS byte lds_dst + 16 * l (lds_dst wave-uniform).
-// Written as inline asm on purpose: hipcc models the builtin's LDS write and then drains vmcnt(0) before the next ds_read of the same
-// array, which serialises every K-step; hidden from it, the DMA is ordered for readers by the counted s_waitcnt vmcnt + s_barrier the
-// kernels place themselves (cdna_hip_programming.md section 5.7 item 1).  M0 (the DMA's LDS base) is saved and restored.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // The linear epilogue of the streaming and the frame-pair kernels, written once (explicit fma) so that they agree bit for bit:
 //   v = acc + bias;  scaled: v = (v * cs + ch) * rs;  with a residual: v = (v * cs + ch) * rs + aux  (one fma: rs = 1 makes it a plain add)

@@ -39,14 +39,6 @@ struct FrameArgs {
     const float* fscale; int fdiv;      // optional per-frame-group factor on dy (stochastic depth: the branch gradient of frame f is scaled by fscale[f / fdiv])
 };
 
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-    return v;
-}
-
 __global__ void __launch_bounds__(FNT, 3) gemm_inbwd_frames_kernel(FrameArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16* lds = reinterpret_cast<bf16*>(smem);
@@ -287,20 +279,10 @@ struct PairArgs {
     bf16* out_s; const float* fscale_s; int fdiv_s;
 };
 
-// LDS-DMA with a wave-uniform 64-bit base in SGPRs and a per-lane 32-bit byte offset: one offset register serves every piece of a wave
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
 // ---- InstanceNorm statistics of the frame columns a wave of the frame-pair kernel holds, summed in EXACTLY the order in_stats_kernel (norm.hip)
 // sums a 144-token frame -- so that a norm folded into a producer's epilogue leaves the bits a separate launch would.  There thread (rg, lc) of 32
 // row groups adds its rows rg, rg + 32, .. in order, the row groups meet by a butterfly over rg bits 0, 1, 2 inside a wave, and the four waves
 // (rg >> 3) are added in wave order.  Here lane li holds rows 16 i + li: the even i are row group li, the odd i row group li + 16.
-template <int CTRL> __device__ __forceinline__ float dpp_get(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float stats_tree(float pe, float po, bool lo) {
     pe = pe + dpp_get<0xB1>(pe); po = po + dpp_get<0xB1>(po);        // rg bit 0 (lane xor 1)
     pe = pe + dpp_get<0x4E>(pe); po = po + dpp_get<0x4E>(po);        // rg bit 1 (lane xor 2)
@@ -315,6 +297,7 @@ __device__ __forceinline__ float stats_tree(float pe, float po, bool lo) {
 }
 __device__ __forceinline__ float bfq(const uint4& v, int q) { return (float)__builtin_bit_cast(bf16x8, v)[q]; }
 // mean and 1 / sqrt(var + eps) of 8 columns over the frame's 144 rows (y[i]: row 16 i + li, packed bf16), two passes
+// (no twin of frame_fwd.hip's frame_stats: that one takes fp32 rows in a [4][5][NJ] layout)
 __device__ __forceinline__ void frame_stats(const uint4 (&y)[9], bool lo, float (&mu)[8], float (&r)[8]) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -489,7 +472,6 @@ __device__ __forceinline__ void pair_body(const PairArgs& a, unsigned char* smem
     for (int i = 0; i < 9; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
             const u32x2 sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][0][r]), __float_as_uint(acc[i][1][r]), false, false);
             v[i][r] = __uint_as_float(sw[0]); v[i][4 + r] = __uint_as_float(sw[1]);
         }

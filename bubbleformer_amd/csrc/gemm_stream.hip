@@ -40,20 +40,6 @@ struct StreamArgs {
     int dbg;      // timing experiments (BF_STREAM_DEBUG): 1 no DMA waits, 2 every tile reads the rows of tile 0, 4 no LDS reads / MFMA, 8 no stores
 };
 
-__device__ __forceinline__ void wait_vm_n(int n) {      // n is wave-uniform; a smaller count than asked for is always safe (in-order retirement)
-    if (n >= 16) { wait_vm<16>(); return; }
-    switch (n) {
-        case 0: wait_vm<0>(); break;   case 1: wait_vm<1>(); break;   case 2: wait_vm<2>(); break;   case 3: wait_vm<3>(); break;
-        case 4: wait_vm<4>(); break;   case 5: wait_vm<5>(); break;   case 6: wait_vm<6>(); break;   case 7: wait_vm<7>(); break;
-        case 8: wait_vm<8>(); break;   case 9: wait_vm<9>(); break;   case 10: wait_vm<10>(); break; case 11: wait_vm<11>(); break;
-        case 12: wait_vm<12>(); break; case 13: wait_vm<13>(); break; case 14: wait_vm<14>(); break; default: wait_vm<15>(); break;
-    }
-}
-// 16-byte load the compiler does not count (it would drain the DMA queue at the first use): completion by the caller's wait_vm_n
-__device__ __forceinline__ void gload16(uint4& dst, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory"); }
-
-__device__ __forceinline__ void gload4(float& dst, const void* p) { asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory"); }
-
 template <int AUX, bool GELU2, bool CS>        // AUX: BF_AUX_*; GELU2: second output gelu(value); CS: column scale / shift and per-row-group factor
 __global__ void __launch_bounds__(512) stream_gemm_kernel(StreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -243,7 +229,6 @@ __global__ void __launch_bounds__(512) stream_gemm_kernel(StreamArgs a) {
                 float v[8];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                     const u32x2 sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pp][r]), __float_as_uint(acc[i][2 * pp + 1][r]), false, false);
                     v[r] = __uint_as_float(sw[0]); v[4 + r] = __uint_as_float(sw[1]);
                 }
@@ -315,15 +300,6 @@ __global__ void __launch_bounds__(512) stream_gemm_kernel(StreamArgs a) {
 //    next tile's first steps: the DMAs those steps wait for are OLDER than the stores in the in-order vmcnt queue) and stagger again.
 constexpr int PSLOT = (ACHUNK + CHUNK) * 2;   // bytes of one ring slot: token chunk + weight chunk
 constexpr int PNSLOT = 3;
-
-__device__ __forceinline__ void wait_vm_wide(int n) {      // as wait_vm_n, up to 40 outstanding operations (epilogue stores + look-ahead DMAs)
-    if (n < 16) { wait_vm_n(n); return; }
-    if (n >= 40) { wait_vm<40>(); return; }
-    switch ((n - 16) >> 2) {          // steps of 4: a smaller count than asked for is always safe
-        case 0: wait_vm<16>(); break; case 1: wait_vm<20>(); break; case 2: wait_vm<24>(); break;
-        case 3: wait_vm<28>(); break; case 4: wait_vm<32>(); break; default: wait_vm<36>(); break;
-    }
-}
 
 template <int AUX, bool GELU2, bool CS>
 __global__ void __launch_bounds__(512) stream_pp_kernel(StreamArgs a) {
@@ -513,7 +489,6 @@ __global__ void __launch_bounds__(512) stream_pp_kernel(StreamArgs a) {
                 float v[8];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                     const u32x2 sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pp][r]), __float_as_uint(acc[i][2 * pp + 1][r]), false, false);
                     v[r] = __uint_as_float(sw[0]); v[4 + r] = __uint_as_float(sw[1]);
                 }

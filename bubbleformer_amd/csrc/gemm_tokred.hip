@@ -48,23 +48,9 @@ template <int NI> struct PPGeom {
     static constexpr int TM = 64 * NI, HALFB = (NI + NSB) * SUBB, TILES = NI * 6, TILE_FLOATS = TM * PTN;
 };
 
-// LDS-DMA with an immediate byte offset (one source pointer serves the same rows of several sub-chunks).  The instruction adds its
-// immediate to BOTH addresses -- the global source and the LDS destination (M0 + offset + 16 * lane) -- so M0 is given the
-// destination minus the offset.
-template <int OFF>
-__device__ __forceinline__ void glds16_off(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off offset:%3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst - (unsigned)OFF), "n"(OFF) : "memory");
-}
-
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 __device__ __forceinline__ bf16x8 tr_frag(unsigned addr) {       // addr: LDS byte address of the lane's "lo" block row; "hi" = 4 rows on
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)addr);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)(addr + 512u));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)addr),
+               __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)(addr + 512u)));
 }
 
 // GRP 0: waves 0-3 (start in the load segment), GRP 1: waves 4-7 (one barrier behind).  Same program, different DMA pieces.
@@ -325,11 +311,8 @@ __global__ void __launch_bounds__(256) tokred_narrow_kernel(const bf16* __restri
     const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
     const unsigned offD = (unsigned)((8 * g + q) * (C * 2) + 8 * pp), offX = (unsigned)(DYB + (8 * g + q) * 32 + 8 * pp);
     auto trf = [&](unsigned addr, unsigned hi_off) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)addr);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)(addr + hi_off));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, r);
+        return cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)addr),
+                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)(addr + hi_off)));
     };
     // The tile loop waits by COUNT for its own LDS-DMA pieces, so nothing else may sit in the vector-memory queue while it runs: the
     // frame's scale / shift (ordinary loads to registers) are fetched BETWEEN loops -- a wave's tile range is cut at frame boundaries, and

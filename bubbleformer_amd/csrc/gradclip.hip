@@ -27,6 +27,7 @@ inline long gn_slab_groups(long G) {
 }
 inline int gn_slabs(long G) { return (int)std::max<long>(1, (G + gn_slab_groups(G) - 1) / gn_slab_groups(G)); }
 
+// not bf_common.h's wave_sum: that butterfly runs o = 32..1, this one 1..32 -- in fp64 another association, other bits
 __device__ __forceinline__ double gn_wave_sum(double v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);      // every lane ends with the same tree over the 64 values

@@ -116,11 +116,6 @@ template <int MODE> __device__ __forceinline__ double lp_coef(double g, double s
     else if constexpr (MODE == LP_P2) return g / sqrt(se * sy);
     else return g / (pow(se, (p - 1.0) / p) * pow(sy, 1.0 / p));
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ long lp_span_len(long n, int chunks) { return ((n + chunks - 1) / chunks + 3) & ~3L; }
 
 // ---- long rows: workgroup (row, span).  Span 0 also takes the row's head.
@@ -138,7 +133,7 @@ __global__ void __launch_bounds__(NT) lp_long_fwd_kernel(const float* __restrict
     double se = 0.0, sy = 0.0;
     if (c == 0 && (long)threadIdx.x < h) { se += lp_err_term<MODE>(p[threadIdx.x], q[threadIdx.x], pw); sy += lp_term<MODE>(q[threadIdx.x], pw); }
     lp_span_sums<MODE>(p + h, q + h, lo, hi, threadIdx.x, NT, vec, pw, se, sy);
-    se = wave_sum_d(se); sy = wave_sum_d(sy);
+    se = wave_sum(se); sy = wave_sum(sy);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = se; red[threadIdx.x >> 6][1] = sy; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -2,7 +2,7 @@
 // element-wise affine / residual kernels of the token-major FiLMAViT path.
 // All statistics and reductions are fp32 whatever the activation dtype; global access is in 16-byte
 // chunks (8 bf16 / 4 f32) so a 64-channel slab row is one 128-/256-byte coalesced segment.
-#include "bf_common.h"
+#include "lane_ops.h"
 #include "param_reduce.h"
 
 namespace {
@@ -20,13 +20,6 @@ template <typename T, int CPB_ = CPB, int NT_ = NT> struct Geo {
 // When the chunk lanes tile a wavefront (LC a power of two <= 32) the row groups inside a wave are folded with lane permutes
 // (row rotate by 8, then the gfx950 row / half swaps for lanes ^16 and ^32 -- VALU only), and the waves meet once in LDS: two
 // barriers per reduction instead of two per tree level.
-__device__ __forceinline__ float lane_xor_add(float v, int o) {
-    if (o == 8) return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));   // row_ror:8
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(v);
-    const u2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 template <typename T, int NV, int CPB_ = CPB, int NT_ = NT>
 __device__ __forceinline__ void reduce_rows(float (&v)[NV][Chunk<T>::N], float* sm) {
     constexpr int CH = Chunk<T>::N, LC = Geo<T, CPB_, NT_>::LC, RG = Geo<T, CPB_, NT_>::RG;

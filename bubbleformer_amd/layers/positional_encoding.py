@@ -1,7 +1,7 @@
 """Relative position bias tables (mirror of bubbleformer/layers/positional_encoding.py).
 
 ``RelativePositionBias`` only OWNS the (num_buckets, heads) embedding; the attention kernels index it directly
-with the T5 bucket of (query - key) (csrc/attn.hip: t5_bucket).  ``forward`` materialises the (1, heads, q, k)
+with the T5 bucket of (query - key) (csrc/lane_ops.h: t5_bucket).  ``forward`` materialises the (1, heads, q, k)
 tensor for callers that want it (host-side table lookup of the same integer buckets).
 """
 import torch

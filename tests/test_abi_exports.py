@@ -42,6 +42,19 @@ def test_register_audit_no_spills_beside_counted_waits():
     assert not bad, [(k["kernel"], k.get("vgpr_spill"), k.get("scratch")) for k in bad]
 
 
+def test_register_audit_counted_set_survives_the_shared_header(tmp_path):
+    """The counted-wait helpers live in csrc/lane_ops.h, so a file that orders memory by count may hold no `s_waitcnt` text of its own:
+    counted_wait_files() knows the helpers by call name.  The set is the one the files' local copies used to give -- the LDS-DMA GEMM
+    families, and the two label kernels whose global passes drain by `s_waitcnt vmcnt(0)` (drain_and_sync)."""
+    from tools import register_audit
+    assert register_audit.counted_wait_files() == {"frame_fwd", "gemm_frame", "gemm_stream", "gemm_tokred", "bubbles", "bubble_tracks"}
+    (tmp_path / "calls.hip").write_text('#include "lane_ops.h"\n__global__ void k(int n) { wait_vm_n(3); }\n')
+    (tmp_path / "drains.hip").write_text('#include "lane_ops.h"\n__global__ void k() { drain_and_sync(); }\n')
+    (tmp_path / "gemm_like.hip").write_text('#include "gemm_common.h"\n__global__ void k() { __syncthreads(); }\n')      # the include alone does not count
+    (tmp_path / "lane_ops.h").write_text(open(os.path.join(register_audit.CSRC, "lane_ops.h")).read())
+    assert register_audit.counted_wait_files(str(tmp_path)) == {"calls", "drains"}
+
+
 def test_no_cpu_fallback():
     from bubbleformer_amd import _lib
     from bubbleformer_amd.models import get_model

@@ -705,7 +705,8 @@ def test_axial_attention_backward_raw_pair_of_passes(h, w, d, heads):
 @pytest.mark.parametrize("path", ["mfma_bf16", "generic_f32"])
 @pytest.mark.parametrize("L", [4, 6, 8, 12, 16, 24, 32])
 def test_attention_t5_buckets_bit_exact_on_device(K, path, L):
-    """The device copies of the T5 bucket function (csrc/attn_mfma.hip: t5b, csrc/attn.hip: t5_bucket) against the reference's integer
+    """The device T5 bucket function (csrc/lane_ops.h: t5_bucket, one definition), as the short-axis MFMA kernels (csrc/attn_mfma.hip) and the
+    generic kernels (csrc/attn.hip) reach it -- the long-axis family has its own test -- against the reference's integer
     tables (tests/golden/relpos_tables.npz), read back through the attention forward itself: with q = k = 0 the scores are the bias
     alone, with V = one-hot(key) the output row is the softmax row, and with emb[b] = log(1 + b) the ratio P[q][k] / P[q][q] is
     1 + bucket(q - k) -- an integer, recovered exactly."""

@@ -193,7 +193,8 @@ def _bucket_table(L):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("L", [40, 64, 100, 128])
 def test_long_attention_t5_buckets_bit_exact_on_device(dtype, L):
-    """The long kernel's T5 bucket function against the reference's integer tables, read back through the forward as in
+    """The one device T5 bucket function (csrc/lane_ops.h: t5_bucket) as the long kernels (csrc/attn_long.hip, the third family that calls it)
+    reach it, against the reference's integer tables, read back through the forward as in
     test_gpu_kernels.py: test_attention_t5_buckets_bit_exact_on_device (q = k = 0, V = one-hot(key), emb[b] = log(1 + b): the ratio
     P[q][k] / P[q][q] is 1 + bucket(q - k))."""
     from bubbleformer_amd import _lib as Lb

@@ -66,8 +66,8 @@ def test_bucket_tables_bit_exact():
 
 def test_product_layer_bucket_tables_bit_exact():
     """The PRODUCT's host-side copy of the T5 table (bubbleformer_amd/layers/positional_encoding.py: bucket_matrix / forward) against the
-    reference's own integer tables and bias tensors (tests/golden/relpos_tables.npz) -- integer work: bit-exact.  The device copies
-    are checked the same way in tests/test_gpu_kernels.py::test_attention_t5_buckets_bit_exact_on_device."""
+    reference's own integer tables and bias tensors (tests/golden/relpos_tables.npz) -- integer work: bit-exact.  The device function
+    is checked the same way, through each kernel family that calls it, in tests/test_gpu_kernels.py::test_attention_t5_buckets_bit_exact_on_device."""
     from bubbleformer_amd.layers import RelativePositionBias
     z = np.load(f"{GOLDEN}/relpos_tables.npz")
     rpb = RelativePositionBias(n_heads=z["emb"].shape[1])

@@ -5,8 +5,8 @@ The ring / pair / stream / token-reduction GEMM families order their LDS-DMA tra
 a register spill inside such a kernel adds scratch loads / stores to the same counter and silently changes what a counted wait
 covers (EXPERIMENTS.md records a fault from exactly that).  This script reads the per-kernel resource remarks the Makefile leaves
 in csrc/build/<file>.remarks (hipcc -Rpass-analysis=kernel-resource-usage) and FAILS when a kernel compiled from a source file
-that uses counted waits (`wait_vm<`, or `s_waitcnt vmcnt` in inline asm) reports spilled VGPRs or scratch.  Spills in other
-kernels (compiler-ordered waits only) are reported as warnings.  It also reads the device assembly the Makefile leaves in
+that uses counted waits (a call of lane_ops.h's `wait_vm<`, `wait_vm_n(`, `wait_vm_wide(` or `drain_and_sync(`, or `s_waitcnt vmcnt` in
+inline asm) reports spilled VGPRs or scratch.  Spills in other kernels (compiler-ordered waits only) are reported as warnings.  It also reads the device assembly the Makefile leaves in
 csrc/build/<file>.s and FAILS when hipcc-issued loads sit inside a loop that waits for LDS-DMA by count (`foreign_loads`), or when a
 packed-fp32 instruction takes its LOW lane's src1 / src2 from the HIGH half of a register pair (`packed_high_select`).  --table
 prints every kernel (VGPRs, spills, scratch, LDS, occupancy).
@@ -68,12 +68,17 @@ def parse(path):
     return kernels
 
 
-def counted_wait_files():
+# the counted-wait helpers of csrc/lane_ops.h by call name: a file that only calls one holds no `s_waitcnt` text of its own
+COUNTED_WAIT_CALLS = re.compile(r"\b(?:wait_vm<|wait_vm_n\(|wait_vm_wide\(|drain_and_sync\()")
+
+
+def counted_wait_files(csrc=None):
+    csrc = csrc or CSRC
     out = set()
-    for f in sorted(os.listdir(CSRC)):
+    for f in sorted(os.listdir(csrc)):
         if f.endswith(".hip"):
-            s = open(os.path.join(CSRC, f)).read()
-            if "wait_vm<" in s or re.search(r'asm[^;]*s_waitcnt vmcnt', s):
+            s = open(os.path.join(csrc, f)).read()
+            if COUNTED_WAIT_CALLS.search(s) or re.search(r'asm[^;]*s_waitcnt vmcnt', s):
                 out.add(f[:-4])
     return out
 
