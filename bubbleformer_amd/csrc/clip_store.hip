@@ -94,6 +94,45 @@ __global__ void __launch_bounds__(NT) clip_gather_batch_kernel(const float* __re
         gather_quad(row, dst, xq, d, q, sx, W, Wo, ident);
     }
 }
+// Its sibling for a training step unrolled through its own predictions: segment b holds `unroll` consecutive target clips of Tc = b.T / unroll
+// frames each, written as (unroll, B, Tc, C, Ho, Wo) so that every clip is contiguous (one per pass).  The same index map and normalisation;
+// a frame index is held below `nframes`, so that a device-side sample number whose later clips lie behind its file (the host path refuses
+// those) reads the frames that follow on the store's frame axis -- the next file's -- and the store's last frame where the store ends,
+// never past it.  A kernel of its own: sharing one body through a template made the compiler
+// address the single-clip kernel's two segments differently (18 more instructions), and that one runs in every training step.
+__global__ void __launch_bounds__(NT) clip_gather_unroll_kernel(const float* __restrict__ src, long field_stride, const long* __restrict__ idx, long nsamples,
+                                                               const long* __restrict__ first_tab, ClipSeg a, ClipSeg b,
+                                                               const float* __restrict__ fluid_tab, const long* __restrict__ file_tab, int P,
+                                                               float* __restrict__ fluid_out, int B, int H, int W, int Ho, int Wo, int unroll, long nframes) {
+    const int wq = (Wo + 3) / 4;
+    const long per_a = (long)a.T * a.C * Ho * wq, per_b = (long)b.T * b.C * Ho * wq, per = per_a + per_b;
+    const long total = (long)B * per;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const bool ident = Ho == H && Wo == W;
+    const int Tc = b.T / unroll;
+    if (fluid_out && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < B * P; i += NT) fluid_out[i] = fluid_tab[file_tab[min(max(idx[i / P], 0L), nsamples - 1)] * P + i % P];
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const int bb = (int)(i / per);
+        long r = i - (long)bb * per;
+        const bool second = r >= per_a;
+        if (second) r -= per_a;
+        const ClipSeg& sg = second ? b : a;
+        const int xq = (int)(r % wq); r /= wq;
+        const int yo = (int)(r % Ho); r /= Ho;
+        const int c = (int)(r % sg.C);
+        const int t = (int)(r / sg.C);
+        const int ys = nearest_src(yo, sy, H, ident);
+        const long smp = min(max(idx[bb], 0L), nsamples - 1);
+        const long frame = min(first_tab[smp] + sg.t0 + t, nframes - 1);
+        const int j = second ? t / Tc : 0;
+        const long orow = second ? ((long)j * B + bb) * Tc + (t - j * Tc) : (long)bb * sg.T + t;      // (unroll, B, Tc, ..) row (j, b, t'), or (B, T, ..) row (b, t)
+        const float* row = src + (long)sg.field[c] * field_stride + (frame * H + ys) * (long)W;
+        float* dst = sg.out + ((orow * sg.C + c) * Ho + yo) * (long)Wo + 4 * xq;
+        const float d = sg.diff[c], q = sg.dv[c];
+        gather_quad(row, dst, xq, d, q, sx, W, Wo, ident);
+    }
+}
 extern "C" int bf_clip_gather_batch(const float* src, int64_t field_stride, const int64_t* idx, int64_t nsamples, const int64_t* first_tab, const int32_t* in_field,
                                     const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out, const int32_t* out_field,
                                     const float* out_diff, const float* out_div, int Cout, int Tout, float* out_out, const float* fluid_tab,
@@ -107,6 +146,26 @@ extern "C" int bf_clip_gather_batch(const float* src, int64_t field_stride, cons
     const long total = (long)B * ((long)Tin * Cin + (long)Tout * Cout) * Ho * ((Wo + 3) / 4);
     hipLaunchKernelGGL(clip_gather_batch_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, src, (long)field_stride, (const long*)idx, (long)nsamples,
                        (const long*)first_tab, a, b, fluid_tab, (const long*)file_tab, P, fluid_out, B, H, W, Ho, Wo);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ... and with `unroll` target clips behind the input clip, out_out (unroll, B, Tout, Cout, Ho, Wo): clip j = frames first + Tin + j * Tout ..
+extern "C" int bf_clip_gather_unroll(const float* src, int64_t field_stride, int64_t nframes, const int64_t* idx, int64_t nsamples, const int64_t* first_tab,
+                                     const int32_t* in_field, const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out,
+                                     const int32_t* out_field, const float* out_diff, const float* out_div, int Cout, int Tout, int unroll, float* out_out,
+                                     const float* fluid_tab, const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo,
+                                     bf_stream_t stream) {
+    BF_REQUIRE(src && idx && first_tab && in_field && in_diff && in_div && in_out && out_field && out_diff && out_div && out_out,
+               "bf_clip_gather_unroll: null pointer");
+    BF_REQUIRE(nsamples > 0 && B > 0 && Tin > 0 && Tout > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W, "bf_clip_gather_unroll: bad sizes");
+    BF_REQUIRE(unroll >= 1 && unroll <= 1024 && nframes > 0 && field_stride >= nframes * (int64_t)H * W, "bf_clip_gather_unroll: bad unroll count or frame count");
+    BF_REQUIRE(!fluid_out || (fluid_tab && file_tab && P > 0), "bf_clip_gather_unroll: the fluid rows need their table, the file table and P > 0");
+    BF_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)in_out % 16 == 0) && ((uintptr_t)out_out % 16 == 0), "bf_clip_gather_unroll: buffers must be 16-byte aligned");
+    const ClipSeg a{(const int*)in_field, in_diff, in_div, in_out, Tin, Cin, 0}, b{(const int*)out_field, out_diff, out_div, out_out, unroll * Tout, Cout, Tin};
+    const long total = (long)B * ((long)Tin * Cin + (long)unroll * Tout * Cout) * Ho * ((Wo + 3) / 4);
+    hipLaunchKernelGGL(clip_gather_unroll_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, src, (long)field_stride, (const long*)idx, (long)nsamples,
+                       (const long*)first_tab, a, b, fluid_tab, (const long*)file_tab, P, fluid_out, B, H, W, Ho, Wo, unroll, (long)nframes);
     BF_CHECK_LAUNCH();
     return 0;
 }

@@ -370,6 +370,9 @@ extern "C" int bf_debed_bwd(const bf_dims* dims, const bf_debed_params* p, const
     D d; TRY(get_dims(dims, &d));
     BF_REQUIRE(p && g && x && dx && saved && scratch && d.nst >= 1, "bf_debed_bwd: bad arguments");
     BF_REQUIRE(dpred || (pred && target), "bf_debed_bwd: need dpred or (pred, target) of the fused loss");
+    BF_REQUIRE(!pred == !target, "bf_debed_bwd: pred and target of the fused loss come together");
+    // dpred AND (pred, target): both go through to the last stage's kernels, which add the two in registers (an unrolled training step:
+    // the gradient that came back through the fed-back prediction, plus this pass's own loss term)
     hipStream_t st = (hipStream_t)s;
     TrunkLinks& L = links();
     L.clear(false);

@@ -217,7 +217,12 @@ __global__ void __launch_bounds__(NT) debed_last_kernel(const bf16* __restrict__
 // consecutive input channels of its pixel and the four lanes of a pixel with 32 (tile pair q, lane group lg  <->  ci = 32 q + 8 lg + ..):
 // each store instruction writes 64 contiguous bytes of 16 rows, a wave 16 complete rows (BF_DL_PERM=0: 4T consecutive channels per
 // lane, 16-byte pieces 8T bytes apart -- 0.13 % slower end to end).  Replaces bf_nchw2pm + a 128-wide GEMM tile with K = 16.
-template <int T>
+// BOTH: the third source mode, an explicit gradient AND the fused loss (a training step unrolled through its own predictions):
+// d pred = dpred + coef[f][co] * gscale * (pred - y), formed in the same registers.  A template parameter, not a run-time branch: only
+// its instantiations carry the third pair of float2 in the prefetch registers (about 10 VGPRs: one or two waves per SIMD fewer at T = 2, 4, 8), and this kernel
+// is also bf_embed_first's, in the timed step.
+__device__ __forceinline__ float loss_plus_given(float cf, float p, float t, float d) { return fmaf(cf, p - t, d); }      // the one expression all three entry points share (bit-identical dpm)
+template <int T, bool BOTH>
 __global__ void __launch_bounds__(NT) debed_last_bwd_kernel(const float* __restrict__ dpred, const float* __restrict__ pred, const float* __restrict__ y,
                                                            const float* __restrict__ coef, const float* __restrict__ gscale,
                                                            const bf16* __restrict__ wc, bf16* __restrict__ dpm, bf16* __restrict__ dact,
@@ -242,10 +247,18 @@ __global__ void __launch_bounds__(NT) debed_last_bwd_kernel(const float* __restr
         const int ci = perm ? 32 * (t >> 1) + 8 * (li >> 2) + 4 * (t & 1) + (li & 3) : 4 * T * (li >> 2) + 4 * t + (li & 3);
         wf[t] = *reinterpret_cast<const s16x4*>(wc + ci * 16 + 4 * lg);
     }
-    const float cf = (!dpred && live) ? coef[(long)f * Co + lg] * (gscale ? gscale[0] : 1.f) : 0.f;
-    auto fetch = [&](int g, float2 (&r)[4]) {
+    constexpr int NR = BOTH ? 6 : 4;
+    const float cf = ((BOTH || !dpred) && live) ? coef[(long)f * Co + lg] * (gscale ? gscale[0] : 1.f) : 0.f;
+    auto fetch = [&](int g, float2 (&r)[NR]) {
         const int px = g * 16 + li, yo = px / w, xo = px - yo * w;
         const long o = (((long)f * Co + lg) * H + 2 * yo) * W + 2 * xo;
+        if constexpr (BOTH) {
+            if (!live) { r[0] = r[1] = r[2] = r[3] = r[4] = r[5] = make_float2(0.f, 0.f); return; }
+            r[0] = *reinterpret_cast<const float2*>(pred + o); r[1] = *reinterpret_cast<const float2*>(pred + o + W);
+            r[2] = *reinterpret_cast<const float2*>(y + o); r[3] = *reinterpret_cast<const float2*>(y + o + W);
+            r[4] = *reinterpret_cast<const float2*>(dpred + o); r[5] = *reinterpret_cast<const float2*>(dpred + o + W);
+            return;
+        }
         if (!live) { r[0] = r[1] = r[2] = r[3] = make_float2(0.f, 0.f); return; }
         if (dpred) { r[0] = *reinterpret_cast<const float2*>(dpred + o); r[1] = *reinterpret_cast<const float2*>(dpred + o + W); r[2] = r[3] = make_float2(0.f, 0.f); }
         else {
@@ -253,7 +266,7 @@ __global__ void __launch_bounds__(NT) debed_last_bwd_kernel(const float* __restr
             r[2] = *reinterpret_cast<const float2*>(y + o); r[3] = *reinterpret_cast<const float2*>(y + o + W);
         }
     };
-    float2 cur[4], nxt[4];
+    float2 cur[NR], nxt[NR];
     fetch(g0, cur);
     float s1[4 * T], s2[4 * T];       // optional InstanceNorm statistics of the rows written (this wave's 16 DL_GPW rows = one slice)
 #pragma unroll
@@ -261,7 +274,10 @@ __global__ void __launch_bounds__(NT) debed_last_bwd_kernel(const float* __restr
     for (int g = g0; g < g1; ++g) {
         if (g + 1 < g1) fetch(g + 1, nxt);
         float v[4];
-        if (dpred) { v[0] = cur[0].x; v[1] = cur[0].y; v[2] = cur[1].x; v[3] = cur[1].y; }
+        if constexpr (BOTH) {
+            v[0] = loss_plus_given(cf, cur[0].x, cur[2].x, cur[NR - 2].x); v[1] = loss_plus_given(cf, cur[0].y, cur[2].y, cur[NR - 2].y);
+            v[2] = loss_plus_given(cf, cur[1].x, cur[3].x, cur[NR - 1].x); v[3] = loss_plus_given(cf, cur[1].y, cur[3].y, cur[NR - 1].y);
+        } else if (dpred) { v[0] = cur[0].x; v[1] = cur[0].y; v[2] = cur[1].x; v[3] = cur[1].y; }
         else { v[0] = cf * (cur[0].x - cur[2].x); v[1] = cf * (cur[0].y - cur[2].y); v[2] = cf * (cur[1].x - cur[3].x); v[3] = cf * (cur[1].y - cur[3].y); }
         const bf16x4v b = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
         const long p = (long)f * h * w + g * 16 + li;
@@ -290,7 +306,7 @@ __global__ void __launch_bounds__(NT) debed_last_bwd_kernel(const float* __restr
             }
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
+        for (int q = 0; q < NR; ++q) cur[q] = nxt[q];
     }
     if (part) {      // {slice mean, centred second moment} in in_stats_slice_kernel's layout: in_stats_merge_kernel finishes the frame
         const float n = (float)((g1 - g0) * 16);
@@ -320,7 +336,7 @@ struct DlInb {
     const float* tot;                   // PASS 2: {s1, s2} per (frame, channel)
     float inv_s;                        // 1 / rows per frame
 };
-template <int T, int PASS>
+template <int T, int PASS, bool BOTH = false>      // BOTH (PASS 1 only): dpred and the fused loss together, as in debed_last_bwd_kernel
 __global__ void __launch_bounds__(NT) debed_last_inbwd_kernel(const float* __restrict__ dpred, const float* __restrict__ pred, const float* __restrict__ y,
                                                              const float* __restrict__ coef, const float* __restrict__ gscale,
                                                              const bf16* __restrict__ wc, bf16* __restrict__ dpm, bf16* __restrict__ dx,
@@ -350,8 +366,10 @@ __global__ void __launch_bounds__(NT) debed_last_inbwd_kernel(const float* __res
         const int ci = 32 * (t >> 1) + 8 * (li >> 2) + 4 * (t & 1) + (li & 3);      // lane (pixel li, group lg) gets channel 32 (k / 8) + 8 lg + k % 8 in slot k = 4 t + j
         wf[t] = *reinterpret_cast<const s16x4*>(wc + ci * 16 + 4 * lg);
     }
-    const float cf = (PASS == 1 && !dpred && live) ? coef[(long)f * Co + lg] * (gscale ? gscale[0] : 1.f) : 0.f;
-    struct Row { float2 r[4]; bf16x8 yv[T / 2]; bf16x4v d; };
+    static_assert(!BOTH || PASS == 1, "the second pass reads the stored rows: it has no source mode");
+    constexpr int NR = BOTH ? 6 : 4;
+    const float cf = (PASS == 1 && (BOTH || !dpred) && live) ? coef[(long)f * Co + lg] * (gscale ? gscale[0] : 1.f) : 0.f;
+    struct Row { float2 r[NR]; bf16x8 yv[T / 2]; bf16x4v d; };
     auto fetch = [&](int g, Row& o) __attribute__((always_inline)) {
         const long p = (long)f * h * w + g * 16 + li;
 #pragma unroll
@@ -359,6 +377,13 @@ __global__ void __launch_bounds__(NT) debed_last_inbwd_kernel(const float* __res
         if (PASS == 2) { o.d = *reinterpret_cast<const bf16x4v*>(dpm + p * 16 + 4 * lg); return; }
         const int px = g * 16 + li, yo = px / w, xo = px - yo * w;
         const long oo = (((long)f * Co + lg) * H + 2 * yo) * W + 2 * xo;
+        if constexpr (BOTH) {
+            if (!live) { o.r[0] = o.r[1] = o.r[2] = o.r[3] = o.r[NR - 2] = o.r[NR - 1] = make_float2(0.f, 0.f); return; }
+            o.r[0] = *reinterpret_cast<const float2*>(pred + oo); o.r[1] = *reinterpret_cast<const float2*>(pred + oo + W);
+            o.r[2] = *reinterpret_cast<const float2*>(y + oo); o.r[3] = *reinterpret_cast<const float2*>(y + oo + W);
+            o.r[NR - 2] = *reinterpret_cast<const float2*>(dpred + oo); o.r[NR - 1] = *reinterpret_cast<const float2*>(dpred + oo + W);
+            return;
+        }
         if (!live) { o.r[0] = o.r[1] = o.r[2] = o.r[3] = make_float2(0.f, 0.f); return; }
         if (dpred) { o.r[0] = *reinterpret_cast<const float2*>(dpred + oo); o.r[1] = *reinterpret_cast<const float2*>(dpred + oo + W); o.r[2] = o.r[3] = make_float2(0.f, 0.f); }
         else {
@@ -380,7 +405,10 @@ __global__ void __launch_bounds__(NT) debed_last_inbwd_kernel(const float* __res
         bf16x4v b;
         if (PASS == 1) {
             float v[4];
-            if (dpred) { v[0] = cur.r[0].x; v[1] = cur.r[0].y; v[2] = cur.r[1].x; v[3] = cur.r[1].y; }
+            if constexpr (BOTH) {
+                v[0] = loss_plus_given(cf, cur.r[0].x, cur.r[2].x, cur.r[NR - 2].x); v[1] = loss_plus_given(cf, cur.r[0].y, cur.r[2].y, cur.r[NR - 2].y);
+                v[2] = loss_plus_given(cf, cur.r[1].x, cur.r[3].x, cur.r[NR - 1].x); v[3] = loss_plus_given(cf, cur.r[1].y, cur.r[3].y, cur.r[NR - 1].y);
+            } else if (dpred) { v[0] = cur.r[0].x; v[1] = cur.r[0].y; v[2] = cur.r[1].x; v[3] = cur.r[1].y; }
             else { v[0] = cf * (cur.r[0].x - cur.r[2].x); v[1] = cf * (cur.r[0].y - cur.r[2].y); v[2] = cf * (cur.r[1].x - cur.r[3].x); v[3] = cf * (cur.r[1].y - cur.r[3].y); }
             b = bf16x4v{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
             *reinterpret_cast<bf16x4v*>(dpm + p * 16 + 4 * lg) = b;
@@ -460,8 +488,8 @@ __global__ void lploss_finalize_kernel(const float* __restrict__ lossbuf, int F,
     for (int s = NT / 2; s > 0; s >>= 1) { if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s]; __syncthreads(); }
     if (threadIdx.x == 0) loss[0] = red[0] / (float)F;
 }
-// dpm[p][n] = dpred[f][co][2y+ky][2x+kx]   with dpred either given, or coef[f][co] * gscale * (pred - y)
-template <typename T>
+// dpm[p][n] = dpred[f][co][2y+ky][2x+kx]   with dpred either given, or coef[f][co] * gscale * (pred - y), or (BOTH) the sum of the two
+template <typename T, bool BOTH>
 __global__ void __launch_bounds__(NT) nchw2pm_kernel(const float* __restrict__ dpred, const float* __restrict__ pred, const float* __restrict__ y,
                                                     const float* __restrict__ coef, const float* __restrict__ gscale, T* __restrict__ dpm,
                                                     int Co, int h, int w, int Np, long P) {
@@ -479,7 +507,14 @@ __global__ void __launch_bounds__(NT) nchw2pm_kernel(const float* __restrict__ d
             const int yo = (int)(t % h);
             const long f = t / h;
             const long o = ((f * Co + co) * H + 2 * yo) * (long)W + 2 * xo;
-            if (dpred) {
+            if constexpr (BOTH) {
+                const float cf = coef[f * Co + co] * gs;
+                const float2 a = *reinterpret_cast<const float2*>(pred + o), b = *reinterpret_cast<const float2*>(pred + o + W);
+                const float2 c = *reinterpret_cast<const float2*>(y + o), d = *reinterpret_cast<const float2*>(y + o + W);
+                const float2 e = *reinterpret_cast<const float2*>(dpred + o), g = *reinterpret_cast<const float2*>(dpred + o + W);
+                v0 = loss_plus_given(cf, a.x, c.x, e.x); v1 = loss_plus_given(cf, a.y, c.y, e.y);
+                v2 = loss_plus_given(cf, b.x, d.x, g.x); v3 = loss_plus_given(cf, b.y, d.y, g.y);
+            } else if (dpred) {
                 const float2 a = *reinterpret_cast<const float2*>(dpred + o), b = *reinterpret_cast<const float2*>(dpred + o + W);
                 v0 = a.x; v1 = a.y; v2 = b.x; v3 = b.y;
             } else {
@@ -670,10 +705,14 @@ extern "C" int bf_debed_last(int dtype, const void* act, const float* sc, const 
     return 0;
 }
 
+// the source mode of the last debed stage's backward: dpred alone, (pred, y, coef) alone, or -- all of them given -- their sum
+static inline bool dl_both(const float* dpred, const float* pred, const float* y) { return dpred && pred && y; }
 static int debed_last_bwd_launch(int dtype, const float* dpred, const float* pred, const float* y, const float* coef, const float* gscale,
                                  const void* wc, void* dpm, void* dact, int frames, int Ci, int Co, int h, int w, int Np, float* part,
                                  bf_stream_t stream) {
     BF_REQUIRE(wc && dpm && (dact || part) && (dpred || (pred && y && coef)) && frames > 0 && Ci > 0 && Co > 0 && h > 0 && w > 0, "bf_debed_last_bwd: bad arguments");
+    const bool both = dl_both(dpred, pred, y);
+    BF_REQUIRE(!both || coef, "bf_debed_last_bwd: dpred beside (pred, y) adds the fused loss term and needs coef");
     if (dtype != BF_DTYPE_BF16 || Np != 16 || Co > 4 || Ci % 32 != 0 || Ci > 128 || w % 16 != 0) return 1;      // caller keeps bf_nchw2pm + GEMM
     static const bool off = bf_knob("BF_DEBED_LAST_BWD", 1) == 0;
     if (off) return 1;
@@ -682,9 +721,10 @@ static int debed_last_bwd_launch(int dtype, const float* dpred, const float* pre
     hipStream_t st = (hipStream_t)stream;
     static const int perm = bf_knob("BF_DL_PERM", 1);
     const double P = (double)frames * h * w;
-    BfProfScope prof(st, "patch16", 2.0 * P * Ci * 16, P * (2.0 * Ci + 32.0 + 16.0 * Co * (dpred ? 1 : 2)));
-#define DLB(T) hipLaunchKernelGGL(debed_last_bwd_kernel<T>, grid, dim3(NT), 0, st, dpred, pred, y, coef, gscale, (const bf16*)wc, (bf16*)dpm, (bf16*)dact, Co, h, w, part, perm)
-    switch (Ci / 32) { case 1: DLB(2); break; case 2: DLB(4); break; case 3: DLB(6); break; default: DLB(8); break; }
+    BfProfScope prof(st, both ? "patch16<both>" : "patch16", 2.0 * P * Ci * 16, P * (2.0 * Ci + 32.0 + 16.0 * Co * (both ? 3 : dpred ? 1 : 2)));
+#define DLB(T, B) hipLaunchKernelGGL((debed_last_bwd_kernel<T, B>), grid, dim3(NT), 0, st, dpred, pred, y, coef, gscale, (const bf16*)wc, (bf16*)dpm, (bf16*)dact, Co, h, w, part, perm)
+    if (both) switch (Ci / 32) { case 1: DLB(2, true); break; case 2: DLB(4, true); break; case 3: DLB(6, true); break; default: DLB(8, true); break; }
+    else switch (Ci / 32) { case 1: DLB(2, false); break; case 2: DLB(4, false); break; case 3: DLB(6, false); break; default: DLB(8, false); break; }
 #undef DLB
     BF_CHECK_LAUNCH();
     return 0;
@@ -708,6 +748,8 @@ extern "C" int bf_debed_last_bwd_norm(int dtype, const float* dpred, const float
     if (off) return bf_decline("bf_debed_last_bwd_norm: switched off (BF_DEBED_LAST_NORM=0)");
     BF_REQUIRE(wc && dpm && ymap && mean && rstd && in_w && in_b && dx && ws && (dpred || (pred && y && coef)) && frames > 0 && Co > 0 && h > 0 && w > 0,
                "bf_debed_last_bwd_norm: bad arguments");
+    const bool both = dl_both(dpred, pred, y);
+    BF_REQUIRE(!both || coef, "bf_debed_last_bwd_norm: dpred beside (pred, y) adds the fused loss term and needs coef");
     const int GF = h * w / 16, nsl = bf_cdiv(GF, DL_GPW);
     if (ws_floats < (int64_t)2 * frames * Ci * (1 + nsl))
         return bf_decline("bf_debed_last_bwd_norm: workspace smaller than 2 * frames * Ci * (1 + slices) floats (bf_in_ws_floats)");
@@ -719,9 +761,10 @@ extern "C" int bf_debed_last_bwd_norm(int dtype, const float* dpred, const float
     const DlInb nb1{(const bf16*)ymap, mean, rstd, in_w, in_b, nullptr, 0.f};
     const DlInb nb2{(const bf16*)ymap, mean, rstd, in_w, in_b, tot, 1.0f / (float)(h * w)};
     {
-        BfProfScope prof(st, "debed_last_bwd<stats>", 2.0 * P * Ci * 16, P * (2.0 * Ci + 32.0 + 16.0 * Co * (dpred ? 1 : 2)));
-#define DLN(T) hipLaunchKernelGGL((debed_last_inbwd_kernel<T, 1>), grid, dim3(NT), 0, st, dpred, pred, y, coef, gscale, (const bf16*)wc, (bf16*)dpm, (bf16*)dx, Co, h, w, part, nb1)
-        switch (Ci / 32) { case 1: DLN(2); break; case 2: DLN(4); break; case 3: DLN(6); break; default: DLN(8); break; }
+        BfProfScope prof(st, both ? "debed_last_bwd<stats,both>" : "debed_last_bwd<stats>", 2.0 * P * Ci * 16, P * (2.0 * Ci + 32.0 + 16.0 * Co * (both ? 3 : dpred ? 1 : 2)));
+#define DLN(T, B) hipLaunchKernelGGL((debed_last_inbwd_kernel<T, 1, B>), grid, dim3(NT), 0, st, dpred, pred, y, coef, gscale, (const bf16*)wc, (bf16*)dpm, (bf16*)dx, Co, h, w, part, nb1)
+        if (both) switch (Ci / 32) { case 1: DLN(2, true); break; case 2: DLN(4, true); break; case 3: DLN(6, true); break; default: DLN(8, true); break; }
+        else switch (Ci / 32) { case 1: DLN(2, false); break; case 2: DLN(4, false); break; case 3: DLN(6, false); break; default: DLN(8, false); break; }
 #undef DLN
         BF_CHECK_LAUNCH();
     }
@@ -764,9 +807,13 @@ extern "C" int bf_lploss_finalize(const float* lossbuf, int frames, int Co, floa
 extern "C" int bf_nchw2pm(int dtype, const float* dpred, const float* pred, const float* y, const float* coef, const float* gscale,
                           void* dpm, int frames, int Co, int h, int w, int Np, bf_stream_t stream) {
     BF_REQUIRE(dpm && (dpred || (pred && y && coef)) && Np >= 4 * Co && Np % 4 == 0, "bf_nchw2pm: bad arguments");
+    const bool both = dl_both(dpred, pred, y);
+    BF_REQUIRE(!both || coef, "bf_nchw2pm: dpred beside (pred, y) adds the fused loss term and needs coef");
     const long P = (long)frames * h * w;
-    if (dtype == BF_DTYPE_BF16) hipLaunchKernelGGL(nchw2pm_kernel<bf16>, dim3(grid_for(P * (Np / 4))), dim3(NT), 0, (hipStream_t)stream, dpred, pred, y, coef, gscale, (bf16*)dpm, Co, h, w, Np, P);
-    else hipLaunchKernelGGL(nchw2pm_kernel<float>, dim3(grid_for(P * (Np / 4))), dim3(NT), 0, (hipStream_t)stream, dpred, pred, y, coef, gscale, (float*)dpm, Co, h, w, Np, P);
+#define N2P(T, B) hipLaunchKernelGGL((nchw2pm_kernel<T, B>), dim3(grid_for(P * (Np / 4))), dim3(NT), 0, (hipStream_t)stream, dpred, pred, y, coef, gscale, (T*)dpm, Co, h, w, Np, P)
+    if (dtype == BF_DTYPE_BF16) { if (both) N2P(bf16, true); else N2P(bf16, false); }
+    else { if (both) N2P(float, true); else N2P(float, false); }
+#undef N2P
     BF_CHECK_LAUNCH();
     return 0;
 }

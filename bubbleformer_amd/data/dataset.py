@@ -117,6 +117,18 @@ class BubbleForecast(Dataset):
         start = idx + self.start_time - (int(cumulative[file_idx - 1]) if file_idx > 0 else 0)
         return file_idx, int(start)
 
+    def unrollable(self, k: int) -> List[int]:
+        """Sample indices whose ``k`` consecutive target clips all lie in the sample's own file -- what a training step unrolled through
+        ``k`` of its own predictions can be fed: of a file of ``n`` frames the first ``n - start_time - (k + 1) * time_window + 1`` samples
+        (none when that is <= 0; utils.rollout.plan_rollouts counts the same way for evaluation).  ``k = 1`` is every sample."""
+        if int(k) != k or k < 1:
+            raise ValueError(f"unrollable: k {k!r} must be an integer >= 1")
+        out, base = [], 0
+        for per, n, t in zip(self._per_traj(), self.num_trajs, self.traj_lens):
+            out.extend(range(base, base + max(0, min(per, n * (t - self.start_time - (int(k) + 1) * self.time_window + 1)))))
+            base += per
+        return out
+
     def _field_clip(self, file_idx: int, field: str, sl: slice) -> torch.Tensor:
         item = torch.from_numpy(np.array(self.data[file_idx][field][sl], dtype=np.float32))
         if self.downsample_factor > 1:
@@ -160,6 +172,7 @@ class DeviceClipStore:
             for ci, name in enumerate(self.fields):
                 host[ci, self.frame0[fi]:self.frame0[fi + 1]] = torch.from_numpy(np.array(f[name][...], dtype=np.float32))
         self.frames = host.to(self.device)
+        self._unroll_masks = {}       # per (dataset geometry, k): which samples are in ds.unrollable(k)
         self.fluid = None
         if ds.return_fluid_params:
             self.fluid = torch.tensor([_fluid_vector(fp) for fp in ds.fluid_params], dtype=torch.float32, device=self.device)
@@ -221,12 +234,32 @@ class DeviceClipStore:
             self._tab_key = key
         return self._first_all, self._file_all
 
-    def gather(self, indices):
+    def _unrollable_mask(self, k: int) -> np.ndarray:
+        """[len(ds)] bool: sample i is in ``ds.unrollable(k)`` (kept per k: the host-index check of gather(..., unroll=k))."""
+        ds = self.ds
+        key = (len(ds), ds.time_window, ds.start_time, int(k))
+        cache = self._unroll_masks
+        if key not in cache:
+            mask = np.zeros(len(ds), dtype=bool)
+            mask[np.asarray(ds.unrollable(k), dtype=np.int64)] = True
+            cache[key] = mask
+        return cache[key]
+
+    def gather(self, indices, unroll: Optional[int] = None):
         """indices: sample indices as a sequence of ints or an integer tensor -- a DEVICE tensor (e.g. a slice of
         ``torch.randperm(len(ds), device=...)``) keeps the whole step free of host-device synchronisation; host indices are staged
-        through pinned memory."""
+        through pinned memory.
+        ``unroll=k``: the batch of a training step unrolled through k of its own predictions, ``(inp, targets[, fluid])`` with ``targets``
+        shaped ``(k, B, T, C_out, H', W')`` -- ``targets[j]`` contiguous, frames ``first + (j + 1) T .. first + (j + 2) T - 1`` -- still from
+        one launch.  Host indices outside ``ds.unrollable(k)`` raise IndexError.  Device indices cannot be checked without a host
+        synchronisation: they are clamped into the sample range, as without ``unroll``, and with ``unroll`` every frame number is also
+        held below the store's frame count (bf_clip_gather_unroll; the single-clip launch needs no such clamp) -- a sample whose later
+        clips lie behind its own file then yields the frames that follow on the store's frame axis, those of the next file, and the
+        store's last frame where the store ends; so draw device indices from ``ds.unrollable(k)``.  ``unroll=None`` is the call it always was."""
         from .. import ops
         ds = self.ds
+        if unroll is not None and (int(unroll) != unroll or unroll < 1):
+            raise ValueError(f"gather: unroll {unroll!r} must be None or an integer >= 1")
         first_all, file_all = self._index_tables()
         if isinstance(indices, torch.Tensor) and indices.device == self.device:
             idx = indices.to(torch.int64)
@@ -234,9 +267,15 @@ class DeviceClipStore:
             host = torch.as_tensor(np.asarray(indices, dtype=np.int64) if not isinstance(indices, torch.Tensor) else indices.to(torch.int64).cpu())
             if host.numel() and (int(host.min()) < 0 or int(host.max()) >= len(ds)):
                 raise IndexError("sample index out of range")
+            if unroll is not None and host.numel() and not bool(self._unrollable_mask(int(unroll))[host.numpy()].all()):
+                raise IndexError(f"sample index outside unrollable({int(unroll)}): its target clips run past the end of its file")
             idx = host.pin_memory().to(self.device, non_blocking=True) if self.device.type == "cuda" else host.to(self.device)
         tw, f = ds.time_window, ds.downsample_factor
         ho, wo = (self.H // f, self.W // f) if f > 1 else (self.H, self.W)
+        if unroll is not None:               # one launch: the input clip, all `unroll` target clips and the fluid rows
+            inp, out, fl = ops.clip_gather_unroll(self.frames, idx.contiguous(), first_all, tw, int(unroll), self.in_tab, self.out_tab, ho, wo,
+                                                  self.fluid, file_all if self.fluid is not None else None)
+            return (inp, out, fl) if self.fluid is not None else (inp, out)
         if self.device.type == "cuda":       # one launch: both clips and the fluid rows, indexed by sample number on the device
             inp, out, fl = ops.clip_gather_batch(self.frames, idx.contiguous(), first_all, tw, self.in_tab, self.out_tab, ho, wo,
                                                  self.fluid, file_all if self.fluid is not None else None)

@@ -52,7 +52,8 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         limit_val_batches: Optional[int] = 25, seed: int = 42, rank: int = 0, world: int = 1, checkpoint_path: Optional[str] = None,
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
-        accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None) -> Dict:
+        accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
+        unroll_backprop: bool = True) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -64,21 +65,38 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     optimizer step, read from the device at the end of the epoch like the losses, and the `log` dict of a batch that stepped carries
     it as a device scalar.  ``panel_dir``: after every validation, the picture strips ForecastModule.on_validation_epoch_end logs
     (modules.py:191-250) of sample 0 of validation batch 0 as ``epoch_<e>_{sdf,temp,vel}_{target,pred}.png`` (utils/plot_utils.py; a field the
-    dataset does not output is skipped); None renders and writes nothing.  Returns the history."""
+    dataset does not output is skipped); None renders and writes nothing.
+    ``unroll_steps = k > 1`` / ``unroll_weights`` / ``unroll_backprop``: every training batch is a step unrolled through k of the model's
+    own predictions (TrainStep): an epoch then shuffles ``train_set.unrollable(k)`` -- the samples whose k target clips lie in their own
+    file -- under the same seeding and rank split, the clips come from ``gather(idx, unroll=k)``, ``train_loss`` is the weighted sum and
+    ``hist["unroll_loss"]`` keeps the k per-pass losses of every batch.  Validation stays the single-step criterion; checkpoints and
+    resume are unchanged.  The training set's input and output fields must be the same list (ValueError, as plan_rollouts refuses it).
+    Returns the history."""
     dev = next(model.parameters()).device
+    conditioned = getattr(train_set, "return_fluid_params", False)
+    k = int(unroll_steps)
+    if k > 1 and list(train_set.input_fields) != list(train_set.output_fields):
+        raise ValueError(f"an unrolled step feeds predictions back as inputs: input fields {list(train_set.input_fields)} and output fields "
+                         f"{list(train_set.output_fields)} must be the same")
+    pool = train_set.unrollable(k) if k > 1 else None      # the samples an epoch draws from; None = all of them, as range(len)
+    if pool is not None and not pool:
+        raise ValueError(f"unroll_steps = {k}: no sample of the training set has {k} target clips inside its own file")
+    n_pool = len(train_set) if pool is None else len(pool)
+    per_epoch = len(batches(epoch_indices(n_pool, 0, seed, True, rank, world), batch_size, limit_train_batches))
     store = train_set.device_store(dev)
     vstore = val_set.device_store(dev) if val_set is not None else None
-    conditioned = getattr(train_set, "return_fluid_params", False)
-    per_epoch = len(batches(epoch_indices(len(train_set), 0, seed, True, rank, world), batch_size, limit_train_batches))
     steps_per_epoch = accumulation_plan(per_epoch, accumulate_grad_batches)[1]
     sched = CosineWarmupLR(lr, warmup_iters, max_epochs * steps_per_epoch, eta_min) if warmup_iters is not None else None
     step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion,
                      gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
-                     accumulate_grad_batches=accumulate_grad_batches)
+                     accumulate_grad_batches=accumulate_grad_batches, unroll_steps=unroll_steps, unroll_weights=unroll_weights,
+                     unroll_backprop=unroll_backprop)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
     if step.grad_norm is not None:
         hist["grad_norm"] = []
+    if k > 1:
+        hist["unroll_loss"] = []
     first_epoch = 0
     if resume_from is not None:
         ck = load_checkpoint(resume_from, model, step)
@@ -86,10 +104,11 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(steps_per_epoch, 1)
     for epoch in range(first_epoch, max_epochs):
         model.train()
-        losses, norms = [], []
-        todo = batches(epoch_indices(len(train_set), epoch, seed, True, rank, world), batch_size, limit_train_batches)
+        losses, norms, per_pass = [], [], []
+        order = epoch_indices(n_pool, epoch, seed, True, rank, world)
+        todo = batches(order if pool is None else [pool[i] for i in order], batch_size, limit_train_batches)
         for bi, idx in enumerate(todo):
-            got = store.gather(idx)
+            got = store.gather(idx) if k == 1 else store.gather(idx, unroll=k)
             x, y, c = (got[0], got[1], got[2]) if conditioned else (got[0], got[1], None)
             cur_lr = sched.get_last_lr()[0] if sched is not None else step.lr      # step.lr: a reference checkpoint brings its own
             before = step.step_no
@@ -97,6 +116,8 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             if bi == len(todo) - 1:
                 step.finish_accumulation()      # an epoch's last batch completes its group, whatever the group holds
             losses.append(loss)
+            if k > 1:
+                per_pass.append(step.unroll_losses)
             hist["lr"].append(cur_lr)
             entry = {"epoch": epoch, "batch_idx": bi, "global_step": step.step_no, "train_loss": loss, "learning_rate": cur_lr}
             if step.grad_norm is not None and step.step_no != before:
@@ -108,6 +129,8 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         hist["train_loss"].extend(ep.tolist())
         if norms:
             hist["grad_norm"].extend(torch.stack(norms).tolist())
+        if per_pass:
+            hist["unroll_loss"].extend(torch.stack(per_pass).tolist())
         hist["epoch_train_loss"].append(float(ep.mean()))
         if vstore is not None:
             sample = [] if panel_dir is not None and rank == 0 else None

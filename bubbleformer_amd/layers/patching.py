@@ -85,9 +85,9 @@ class HMLPDebed(nn.Module):
         """(B, T, h, w, E) -> (B, T, C, H, W) fp32."""
         return ops.debed(tok, self.patch_size, self.out_channels, *self.stage_params())
 
-    def loss_from_tokens(self, tok: torch.Tensor, target: torch.Tensor):
-        """Fused debed + relative-L2 loss: returns (loss, prediction)."""
-        return ops.debed_with_loss(tok, target, self.patch_size, self.out_channels, *self.stage_params())
+    def loss_from_tokens(self, tok: torch.Tensor, target: torch.Tensor, pred_grad: bool = False):
+        """Fused debed + relative-L2 loss: returns (loss, prediction); ``pred_grad`` keeps the prediction in the graph (ops.debed_with_loss)."""
+        return ops.debed_with_loss(tok, target, self.patch_size, self.out_channels, *self.stage_params(), pred_grad=pred_grad)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, E, h, w) -> (B, C, H, W)."""

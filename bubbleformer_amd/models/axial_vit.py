@@ -135,8 +135,10 @@ class AViT(_AxialBase):
         """x: (B, T, C, H, W) -> (B, T, C_out, H, W)."""
         return self.debed.from_tokens(self.tokens(x))
 
-    def forward_loss(self, x, target):
-        return self.debed.loss_from_tokens(self.tokens(x), target)
+    def forward_loss(self, x, target, pred_grad: bool = False):
+        """Fused debed + relative-L2 loss: (loss, prediction).  ``pred_grad=True`` keeps the prediction in the graph, so that a training
+        step unrolled through its own predictions can send a gradient back through it beside the loss's (ops.debed_with_loss)."""
+        return self.debed.loss_from_tokens(self.tokens(x), target, pred_grad=pred_grad)
 
 
 @register_model("filmavit")
@@ -158,6 +160,7 @@ class FiLMConditionedAViT(_AxialBase):
         """x: (B, T, C, H, W), fluid_params: (B, num_fluid_params) -> (B, T, C_out, H, W)."""
         return self.debed.from_tokens(self.tokens(x, fluid_params))
 
-    def forward_loss(self, x, fluid_params, target):
-        """Fused debed + relative-L2 loss (utils/losses.py:67-94 as configured at modules.py:50): (loss, prediction)."""
-        return self.debed.loss_from_tokens(self.tokens(x, fluid_params), target)
+    def forward_loss(self, x, fluid_params, target, pred_grad: bool = False):
+        """Fused debed + relative-L2 loss (utils/losses.py:67-94 as configured at modules.py:50): (loss, prediction).  ``pred_grad``: as
+        AViT.forward_loss."""
+        return self.debed.loss_from_tokens(self.tokens(x, fluid_params), target, pred_grad=pred_grad)

@@ -152,6 +152,15 @@ def set_side_defer(on: bool) -> None:
         _DEFER["keep"].clear()
 
 
+def release_deferred() -> None:
+    """Deferred mode, between two backward passes inside one set_side_defer(True) window (a training step unrolled through several passes):
+    order what the stages put on the side stream before the current stream's next work and drop the tensors kept alive for it, so that a
+    finished pass's saved activations go back to the allocator before the next pass runs instead of at the end of the window."""
+    if _DEFER["on"]:
+        L.check(L.lib().bf_side_join(_stream()), "bf_side_join")
+        _DEFER["keep"].clear()
+
+
 def _joined() -> None:
     """Deferred mode, before the patch-embedding backward (the last, long stage of a backward pass): join the side stream here, on
     the Python side, so that the gradient buckets of the processor blocks can be handed to the all-reduce BEFORE that stage's kernels
@@ -708,10 +717,11 @@ def embed(x, fluid, compute_dtype, patch, embed_dim, conv_w, in_w, in_b, film_pa
 
 
 class _DebedFn(torch.autograd.Function):
-    """tokens -> (B, T, Cout, H, W) fp32; with ``target`` also the fused relative-L2 loss."""
+    """tokens -> (B, T, Cout, H, W) fp32; with ``target`` also the fused relative-L2 loss.  ``pred_grad``: beside the fused loss the
+    prediction stays differentiable (a training step unrolled through its own predictions feeds it back)."""
 
     @staticmethod
-    def forward(ctx, x, target, patch, cout, nst, *params):
+    def forward(ctx, x, target, patch, cout, nst, pred_grad, *params):
         _require_gpu(x)
         x = x.contiguous()
         B, T, h, w, E = x.shape
@@ -730,7 +740,7 @@ class _DebedFn(torch.autograd.Function):
                 raise L.BubbleformerHipError(f"target shape {tuple(target.shape)} != prediction shape {tuple(pred.shape)}")
         L.check(lib.bf_debed_fwd(C.byref(d), C.byref(st), _p(x), _p(pred), _p(target), _p(loss) if target is not None else None,
                                  _p(saved), _p(scratch_for(d, x.device)), _stream()), "bf_debed_fwd")
-        ctx.cfg = (patch, cout, nst, target is not None)
+        ctx.cfg = (patch, cout, nst, target is not None, bool(pred_grad))
         ctx.save_for_backward(x, saved, pred, target if target is not None else pred, *params)
         ctx.set_materialize_grads(False)      # an unused output must not cost a zero-filled gradient the size of the prediction
         return pred, loss
@@ -738,12 +748,12 @@ class _DebedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpred, dloss):
         x, saved, pred, target, *params = ctx.saved_tensors
-        patch, cout, nst, fused = ctx.cfg
-        if fused and dpred is not None:
+        patch, cout, nst, fused, pred_grad = ctx.cfg
+        if fused and dpred is not None and not pred_grad:
             raise L.BubbleformerHipError("debed_with_loss: a gradient w.r.t. the prediction is not supported beside the fused loss; "
                                          "use debed() and a separate loss for that")
-        if (dloss if fused else dpred) is None:
-            return (None,) * (5 + len(params))
+        if dpred is None and (dloss is None or not fused):
+            return (None,) * (6 + len(params))
         B, T, h, w, E = x.shape
         d = make_dims(x.dtype, B, T, h, w, E, 1, patch=patch, cin=1, cout=cout)
         lib = L.lib()
@@ -754,30 +764,31 @@ class _DebedFn(torch.autograd.Function):
         gcw, giw, gib = _stage_arrays(gv[:nst], gv[nst:2 * nst - 1], gv[2 * nst - 1:])
         gs = L.DebedParams(gcw, giw, gib)
         dx = torch.empty_like(x)
-        if fused:
-            # loss path: d(pred) = dloss * coef[f, c] * (pred - target); an explicit dpred on top is not supported here
-            scale = dloss.contiguous().float().reshape(1)
-            L.check(lib.bf_debed_bwd(C.byref(d), C.byref(st), C.byref(gs), _p(x), None, _p(pred), _p(target), _p(scale), _p(dx),
-                                     _p(saved), _p(scratch_for(d, x.device)), _stream()), "bf_debed_bwd")
-        else:
-            dpred = dpred.contiguous().float()
-            L.check(lib.bf_debed_bwd(C.byref(d), C.byref(st), C.byref(gs), _p(x), _p(dpred), None, None, None, _p(dx), _p(saved),
-                                     _p(scratch_for(d, x.device)), _stream()), "bf_debed_bwd")
+        # the three source modes of bf_debed_bwd: the loss term dloss * coef[f, c] * (pred - target) alone, an explicit dpred alone, or
+        # (pred_grad) both, added in the registers of the last stage's kernels
+        with_loss = fused and dloss is not None
+        scale = dloss.contiguous().float().reshape(1) if with_loss else None
+        dpred = dpred.contiguous().float() if dpred is not None else None
+        L.check(lib.bf_debed_bwd(C.byref(d), C.byref(st), C.byref(gs), _p(x), _p(dpred), _p(pred) if with_loss else None,
+                                 _p(target) if with_loss else None, _p(scale), _p(dx), _p(saved), _p(scratch_for(d, x.device)), _stream()),
+                "bf_debed_bwd")
         _stage_done(params, direct)
-        return (dx, None, None, None, None, *ret)
+        return (dx, None, None, None, None, None, *ret)
 
 
 def debed(x, patch, cout, conv_w, in_w, in_b):
     """x: (B, T, h, w, E) tokens -> (B, T, Cout, H, W) fp32 prediction."""
-    pred, _ = _DebedFn.apply(x, None, patch, cout, len(conv_w), *conv_w, *in_w, *in_b)
+    pred, _ = _DebedFn.apply(x, None, patch, cout, len(conv_w), False, *conv_w, *in_w, *in_b)
     return pred
 
 
-def debed_with_loss(x, target, patch, cout, conv_w, in_w, in_b):
-    """Fused debed + relative-L2 loss (LpLoss d=2, p=2, mean B, mean T, sum C).  Returns (loss, pred); only ``loss``
-    carries gradient (pred is produced for logging)."""
-    pred, loss = _DebedFn.apply(x, target, patch, cout, len(conv_w), *conv_w, *in_w, *in_b)
-    return loss, pred.detach()
+def debed_with_loss(x, target, patch, cout, conv_w, in_w, in_b, pred_grad=False):
+    """Fused debed + relative-L2 loss (LpLoss d=2, p=2, mean B, mean T, sum C).  Returns (loss, pred).  By default only ``loss`` carries
+    gradient (pred is produced for logging).  ``pred_grad=True`` keeps the prediction in the graph as well: the backward then takes a
+    gradient w.r.t. the prediction and one w.r.t. the loss together (their sum is formed inside the last stage's backward kernels, no
+    composed gradient in memory), either one alone, or neither."""
+    pred, loss = _DebedFn.apply(x, target, patch, cout, len(conv_w), pred_grad, *conv_w, *in_w, *in_b)
+    return loss, (pred if pred_grad else pred.detach())
 
 
 # ------------------------------------------------------------------------------------------------ optimizer
@@ -915,6 +926,30 @@ def clip_gather_batch(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch.
                                          _p(oid), _p(odf), _p(odv), oid.numel(), T, _p(out), _p(fluid_tab) if fl is not None else None,
                                          _p(file_tab) if fl is not None else None, P, _p(fl) if fl is not None else None, B, H, W, Ho, Wo,
                                          _stream()), "bf_clip_gather_batch")
+    return inp, out, fl
+
+
+def clip_gather_unroll(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch.Tensor, T: int, unroll: int, in_table, out_table, Ho: int, Wo: int,
+                       fluid_tab: Optional[torch.Tensor] = None, file_tab: Optional[torch.Tensor] = None):
+    """clip_gather_batch with ``unroll`` target clips behind the input clip, still one launch: -> input clips (B, T, Cin, Ho, Wo), target
+    clips (unroll, B, T, Cout, Ho, Wo) -- targets[j] contiguous, frames first + (j + 1) T .. first + (j + 2) T - 1 -- and the fluid rows.
+    idx is clamped into the sample range and every frame number below the store's frame count on the device (a sample whose later clips
+    lie behind its own file then reads the next file's frames, and the store's last frame where the store ends, never past it); the
+    caller checks what it can on the host (DeviceClipStore.gather)."""
+    _require_gpu(frames)
+    (iid, idf, idv), (oid, odf, odv) = in_table, out_table
+    nf, total, H, W = frames.shape
+    B = idx.numel()
+    if int(unroll) != unroll or unroll < 1:
+        raise ValueError(f"clip_gather_unroll: unroll {unroll!r} must be an integer >= 1")
+    inp = torch.empty((B, T, iid.numel(), Ho, Wo), dtype=torch.float32, device=frames.device)
+    out = torch.empty((int(unroll), B, T, oid.numel(), Ho, Wo), dtype=torch.float32, device=frames.device)
+    P = int(fluid_tab.shape[1]) if fluid_tab is not None else 0
+    fl = torch.empty((B, P), dtype=torch.float32, device=frames.device) if fluid_tab is not None else None
+    L.check(L.lib().bf_clip_gather_unroll(_p(frames), total * H * W, total, _p(idx), first_tab.numel(), _p(first_tab), _p(iid), _p(idf), _p(idv), iid.numel(), T,
+                                          _p(inp), _p(oid), _p(odf), _p(odv), oid.numel(), T, int(unroll), _p(out), _p(fluid_tab) if fl is not None else None,
+                                          _p(file_tab) if fl is not None else None, P, _p(fl) if fl is not None else None, B, H, W, Ho, Wo,
+                                          _stream()), "bf_clip_gather_unroll")
     return inp, out, fl
 
 

@@ -9,13 +9,16 @@
                       blocks N-1 .. 0, then embed), overlapped with the rest of backward.  One process per GPU.
 * ``TrainStep``    -- forward (+ fused relative-L2 loss, or a caller's criterion on the prediction) -> backward -> bucket wait ->
                       [gradient norm and clip coefficient, on the device] -> fused AdamW / Adam / Lion; with
-                      ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only.
+                      ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only; with
+                      ``unroll_steps=k`` the model is run through k of its own predictions with a loss on each (``unroll_plan``).
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
 from typing import List, Optional, Sequence, Tuple
 
 import contextlib
+import inspect
+import math
 import os
 
 import torch
@@ -182,6 +185,52 @@ def accumulation_plan(per_epoch: int, k: int) -> Tuple[List[int], int]:
     return steps, len(steps)
 
 
+def unroll_weights_checked(k: int, weights=None) -> List[float]:
+    """The per-pass loss weights of a step unrolled through k passes: 1/k each by default; given ones must be k finite numbers >= 0, not all 0."""
+    if int(k) != k or k < 1:
+        raise ValueError(f"unroll_steps {k!r} must be an integer >= 1")
+    k = int(k)
+    if weights is None:
+        return [1.0 / k] * k
+    w = [float(v) for v in weights]
+    if len(w) != k:
+        raise ValueError(f"unroll_weights: {len(w)} weights for unroll_steps = {k}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in w) or not any(v > 0.0 for v in w):
+        raise ValueError(f"unroll_weights {w} must be finite and >= 0, and not all 0")
+    return w
+
+
+def unroll_plan(k: int, weights=None, backprop: bool = True, final: bool = True) -> Tuple[List[float], List[Tuple[str, int, bool]]]:
+    """The schedule of one training step unrolled through k passes, x_1 = x, x_{j+1} = pred_j, loss = sum_j w_j loss_j (passes are numbered
+    from 0 here): -> (weights, [(op, pass, flag), ...] in execution order) with
+      ("forward", j, grad)  -- pass j's forward; grad False = under no_grad, no backward follows;
+      ("backward", j, sync) -- pass j's backward; sync False = inside BucketReducer.no_sync().
+    Every pass runs forward once, in order (its loss is reported whatever its weight).
+      * backprop=True: gradients flow through the fed-back predictions.  Pass j takes gradients when some pass i >= j has w_i > 0 (it is
+        then on the path of that loss); all forwards run first, then the backwards from the last such pass down to pass 0 -- pass j's gets
+        w_j for its loss (when > 0) and the gradient its prediction collected as the input of pass j + 1.
+      * backprop=False (the pushforward form): the fed-back prediction is detached; pass j takes gradients when w_j > 0 and its backward
+        runs right after its forward, so one pass's activations are alive at a time.
+    Only the backward that runs LAST synchronises, and only when ``final`` (the micro-batch completes its accumulate_grad_batches group):
+    every bucket is then exchanged once per optimizer step, after all k passes have added to it."""
+    w = unroll_weights_checked(k, weights)
+    k = len(w)
+    if backprop:
+        last = max(j for j in range(k) if w[j] > 0.0)
+        grad = [j <= last for j in range(k)]
+        plan = [("forward", j, grad[j]) for j in range(k)] + [("backward", j, False) for j in range(last, -1, -1)]
+    else:
+        plan = []
+        for j in range(k):
+            plan.append(("forward", j, w[j] > 0.0))
+            if w[j] > 0.0:
+                plan.append(("backward", j, False))
+    if final:
+        i = max(i for i, (op, _, _) in enumerate(plan) if op == "backward")
+        plan[i] = ("backward", plan[i][1], True)
+    return w, plan
+
+
 class TrainStep:
     """optimizer: "adamw" (config/optim_cfg/adamw.yaml; modules.py:135-136), "adam" (config/optim_cfg/adam.yaml, torch.optim.Adam
     with its L2 weight decay; modules.py:137-138) or "lion" (config/optim_cfg/lion.yaml, the reference default; modules.py:139-140).
@@ -199,11 +248,23 @@ class TrainStep:
       * accumulate_grad_batches = k: a call that does not complete a group of k only adds its gradient to the flat buffer (no
         zero_grad, no collective -- BucketReducer.no_sync -- no optimizer, no scheduler step); the completing call exchanges the
         buckets, applies 1/(world*k) and steps once.  ``step_no`` counts optimizer steps.  finish_accumulation() steps on a partial
-        group with the same factor, as Lightning does on an epoch's last batch."""
+        group with the same factor, as Lightning does on an epoch's last batch.
+    unroll_steps = k > 1: the step runs the model through k of its own predictions, x_1 = x, x_{j+1} = pred_j, with a loss on each against
+    ``target[j]`` -- ``target`` is (k, B, T, C, H, W) (DeviceClipStore.gather(idx, unroll=k)) or a sequence of k clips -- and optimises
+    sum_j w_j loss_j (``unroll_weights``, default 1/k each), which is also what the call returns; ``unroll_losses`` keeps the k losses of
+    the last call on the device.  ``unroll_backprop=True`` sends gradients through the fed-back predictions: every pass has its own graph
+    (x_{j+1} = pred_j.detach().requires_grad_()), the backwards run from pass k down to pass 1, and pass j's gets its loss weight and the
+    gradient x_{j+1} collected TOGETHER -- with the fused loss that is the third source mode of the debed backward (dpred + w_j * dloss
+    formed in registers), so all k passes' activations are alive at the turn.  ``False`` is the pushforward form: predictions are fed
+    back detached and each pass's backward follows its forward (one pass's activations alive; a pass with w_j = 0 runs under no_grad).
+    Stochastic depth is drawn per pass.  Every backward but the last runs inside BucketReducer.no_sync() (unroll_plan).  The input and
+    output fields must be the same (ValueError); a model whose forward_loss cannot keep its prediction in the graph (the U-Nets) is
+    refused with NotImplementedError unless a criterion is given.  unroll_steps = 1 is the step it always was."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
-                 gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1):
+                 gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1, unroll_steps: int = 1, unroll_weights=None,
+                 unroll_backprop: bool = True):
         from . import ops
         if optimizer not in ("adamw", "adam", "lion"):
             raise ValueError(f"Optimizer {optimizer} not supported")
@@ -213,6 +274,15 @@ class TrainStep:
             raise ValueError(f"gradient_clip_val {gradient_clip_val!r} must be None or >= 0")
         if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
             raise ValueError(f"accumulate_grad_batches {accumulate_grad_batches!r} must be an integer >= 1")
+        self.unroll_weights = unroll_weights_checked(unroll_steps, unroll_weights)
+        self.unroll_steps = len(self.unroll_weights)
+        self.unroll_backprop = bool(unroll_backprop)
+        self.unroll_losses = None      # (k,) device tensor: the per-pass losses of the last call
+        if self.unroll_steps > 1:
+            fl = getattr(model, "forward_loss", None)
+            if criterion is None and (fl is None or "pred_grad" not in inspect.signature(fl).parameters):
+                raise NotImplementedError(f"unroll_steps = {self.unroll_steps}: {type(model).__name__}.forward_loss cannot feed its prediction back "
+                                          "(no pred_grad: the U-Nets' fused loss is not unrolled); pass a criterion to unroll through model(x)")
         self.ops = ops
         self.model = model
         self.flat = FlatParams(model)
@@ -236,7 +306,16 @@ class TrainStep:
             self.grad_norm = torch.zeros(2, dtype=torch.float32, device=self.flat.flat.device)
             self._coef = self.grad_norm[1:]
             self._norm_ws = None
+        self._unroll_w = None
+        if self.unroll_steps > 1:
+            self._unroll_w = torch.tensor(self.unroll_weights, dtype=torch.float32, device=self.flat.flat.device)
         self.sync_from_rank0()
+
+    @staticmethod
+    def _check_unroll_fields(cin: int, cout: int) -> None:
+        if int(cin) != int(cout):
+            raise ValueError(f"an unrolled step feeds predictions back as inputs: input fields ({int(cin)}) and output fields ({int(cout)}) "
+                             "must be the same")
 
     def sync_from_rank0(self) -> None:
         """Data parallel: every replica starts (and resumes) from rank 0's parameters, optimizer moments and step count -- what
@@ -262,7 +341,7 @@ class TrainStep:
         self.ops.set_side_defer(True)       # a stage's weight-gradient GEMMs may run into the next stage; joined below
         try:
             with contextlib.nullcontext() if final else self.reducer.no_sync():
-                loss = self._fwd_bwd(x, fluid, target)
+                loss = self._fwd_bwd(x, fluid, target) if self.unroll_steps == 1 else self._fwd_bwd_unrolled(x, fluid, target, final)
         finally:
             self.ops.set_side_defer(False)
             self.ops.set_direct_grad_slots(None)
@@ -309,3 +388,49 @@ class TrainStep:
             loss = self.criterion(self.model(x, fluid) if fluid is not None else self.model(x), target)
         loss.backward()
         return loss
+
+    def _fwd_bwd_unrolled(self, x, fluid, target, final: bool):
+        """The schedule of unroll_plan: k forward passes through the model's own predictions, their backwards in the plan's order, all but
+        the last inside no_sync().  Returns sum_j w_j loss_j; the k losses stay in ``unroll_losses``."""
+        k, w, backprop = self.unroll_steps, self.unroll_weights, self.unroll_backprop
+        if isinstance(target, torch.Tensor):
+            if target.dim() != x.dim() + 1 or target.shape[0] != k:
+                raise ValueError(f"unroll_steps = {k}: target must be (k, B, T, C, H, W) or a sequence of k clips, got {tuple(target.shape)}")
+        elif len(target) != k:
+            raise ValueError(f"unroll_steps = {k}: {len(target)} target clips")
+        self._check_unroll_fields(x.shape[2], target[0].shape[2])
+        plan = unroll_plan(k, w, backprop, final)[1]
+        takes_grad = {j: g for op, j, g in plan if op == "forward"}
+        inputs, preds, losses = [x] + [None] * (k - 1), [None] * k, [None] * k
+        for op, j, flag in plan:
+            if op == "forward":
+                feeds = backprop and j + 1 < k and takes_grad[j + 1]        # the prediction carries a gradient back from pass j + 1
+                with torch.enable_grad() if flag else torch.no_grad():
+                    if self.criterion is None:
+                        args = (inputs[j], fluid, target[j]) if fluid is not None else (inputs[j], target[j])
+                        losses[j], pred = self.model.forward_loss(*args, pred_grad=feeds)
+                    else:
+                        pred = self.model(inputs[j], fluid) if fluid is not None else self.model(inputs[j])
+                        losses[j] = self.criterion(pred, target[j])
+                preds[j] = pred if feeds else None
+                if not backprop:
+                    inputs[j] = None                                        # pushforward: a fed-back clip is done with after its pass's forward
+                if j + 1 < k:
+                    inputs[j + 1] = pred.detach().requires_grad_() if feeds else pred.detach()
+            else:
+                outs, grads = [], []
+                if w[j] > 0.0:
+                    outs.append(losses[j])
+                    grads.append(self._unroll_w[j])
+                if preds[j] is not None and inputs[j + 1].grad is not None:
+                    outs.append(preds[j])
+                    grads.append(inputs[j + 1].grad)
+                with contextlib.nullcontext() if flag else self.reducer.no_sync():
+                    torch.autograd.backward(outs, grads)
+                self.ops.release_deferred()                                 # the pass's saved activations are not held to the end of the step
+                preds[j] = None                                             # this pass's graph and what it fed are done with
+                if backprop and j + 1 < k:
+                    inputs[j + 1] = None
+                losses[j] = losses[j].detach()
+        self.unroll_losses = torch.stack([l.detach().float() for l in losses])
+        return (self.unroll_losses * self._unroll_w).sum()

@@ -258,7 +258,10 @@ int bf_pm2nchw(const float* pm, float* pred, const float* y, float* lossbuf, int
 int bf_debed_last(int dtype, const void* act, const float* sc, const float* sh, const void* wc, float* pred, const float* y,
                   float* lossbuf, int frames, int Ci, int Co, int h, int w, int Np, bf_stream_t stream);
 /* ... and its backward: dpm [frames*h*w][Np] (bf_nchw2pm's output, kept for the weight-gradient GEMM) and dact[p][ci] = sum_n dpm[p][n]*wc[ci][n]
- * in one pass.  Same declined shapes (returns 1). */
+ * in one pass.  Same declined shapes (returns 1).  Three source modes, here and in bf_debed_last_bwd_norm / bf_nchw2pm: dpred alone (pred = y =
+ * NULL), the fused loss alone (dpred = NULL; pred, y, coef given): d pred = coef[f][co] * gscale[0] * (pred - y), or BOTH (dpred, pred, y and
+ * coef all given): d pred = dpred + coef[f][co] * gscale[0] * (pred - y), formed in fp32 registers in the same pass -- the backward of one
+ * pass of a training step unrolled through its own predictions.  gscale = NULL means 1. */
 int bf_debed_last_bwd(int dtype, const float* dpred, const float* pred, const float* y, const float* coef, const float* gscale,
                       const void* wc, void* dpm, void* dact, int frames, int Ci, int Co, int h, int w, int Np, bf_stream_t stream);
 /* ... and with the InstanceNorm + GELU in front of the stage folded in (layers/patching.py:92-104 under autograd): dpm as above, and
@@ -350,6 +353,16 @@ int bf_clip_gather_batch(const float* src, int64_t field_stride, const int64_t* 
                          const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out, const int32_t* out_field,
                          const float* out_diff, const float* out_div, int Cout, int Tout, float* out_out, const float* fluid_tab,
                          const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo, bf_stream_t stream);
+/* ... with `unroll` >= 1 target clips behind the input clip, for a training step unrolled through its own predictions: out_out is
+ * (unroll, B, Tout, Cout, Ho, Wo), clip j = frames first + Tin + j*Tout .. first + Tin + (j+1)*Tout - 1, each clip contiguous; one launch.
+ * nframes = frames per field in src: idx is clamped as above, and a frame index is held below nframes, so a sample whose later clips lie
+ * behind its own file (the caller's business: DeviceClipStore.gather refuses such host indices) reads the next file's frames (the store's last frame where the store ends), never
+ * past it. */
+int bf_clip_gather_unroll(const float* src, int64_t field_stride, int64_t nframes, const int64_t* idx, int64_t nsamples, const int64_t* first_tab,
+                          const int32_t* in_field, const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out,
+                          const int32_t* out_field, const float* out_diff, const float* out_div, int Cout, int Tout, int unroll, float* out_out,
+                          const float* fluid_tab, const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo,
+                          bf_stream_t stream);
 /* Normalisation statistics of device-resident trajectories (BubbleForecast.normalize, bubbleformer/data/dataset.py:74-117: mean / std / min /
  * max of every full field of every file): segment i = seg_len[i] floats at src + seg_begin[i] (both arrays on the DEVICE);
  * out[i] = {sum, sum of squares, min, max} in fp64, summed in a fixed order (bit-reproducible).  ws: bf_field_stats_ws_doubles(nseg) doubles. */
@@ -680,7 +693,8 @@ int bf_embed_bwd(const bf_dims* d, const bf_embed_params* p, const bf_embed_para
  * configured at modules.py:50) is fused: loss[0] and the per-(frame, channel) backward coefficients are produced. */
 int bf_debed_fwd(const bf_dims* d, const bf_debed_params* p, const void* x, float* pred, const float* target, float* loss,
                  void* saved, void* scratch, bf_stream_t s);
-/* dpred: explicit (B*T, cout, H, W) fp32 gradient, or NULL to use the fused loss backward (pred, target, loss_scale[0] or 1). */
+/* dpred: explicit (B*T, cout, H, W) fp32 gradient, or NULL to use the fused loss backward (pred, target, loss_scale[0] or 1); dpred
+ * together with (pred, target): the sum of the two, d pred = dpred + loss_scale[0] * d(loss)/d(pred) (see bf_debed_last_bwd). */
 int bf_debed_bwd(const bf_dims* d, const bf_debed_params* p, const bf_debed_params* g, const void* x, const float* dpred,
                  const float* pred, const float* target, const float* loss_scale, void* dx, void* saved, void* scratch,
                  bf_stream_t s);

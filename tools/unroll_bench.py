@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""The training step unrolled through k of the model's own predictions, timed on the GPU: prints one JSON object.
+
+FiLMAViT-small (E 384, 6 heads, 12 blocks, stochastic depth 0.2) at the headline shape -- 4 fields, 16 x 192 x 192 clips, batch 8, bf16,
+AdamW -- as bench.py runs it.  Versions, each a model and a TrainStep of its own from the same seed:
+  k1                     the plain step (unroll_steps = 1)
+  k2 / k3                unroll_steps = 2 / 3, gradients through the fed-back predictions (unroll_backprop=True), fused loss
+  k2_push / k3_push      the pushforward form (unroll_backprop=False), fused loss
+  k2_composed            unroll_steps = 2 through model(x) and criterion = LpLoss(d=2, p=2, mean B, mean T, sum C): the only way to unroll
+                         before the last debed stage's backward took both gradient sources
+After a warm-up of every version they alternate in rounds of `--reps` back-to-back optimizer steps timed by device events; reported per
+version: the median over rounds of the time per step with the minimum and the maximum, and for the unrolled ones the ratio to k x the
+k1 step.  "peak_memory_GB" is the process's `max_memory_allocated`: with `--versions <one>` it is that version's (every version named
+is resident at once).  "fused_not_slower" holds when the fused k = 2 step's median is at most the composed one's.
+
+Usage: python tools/unroll_bench.py [--rounds R] [--reps K] [--batch B] [--versions k1,k3_push,...]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from bench import CFG, DROP_PATH, FIELD_STATS  # noqa: E402
+
+T, H, W = 16, 192, 192
+VERSIONS = {"k1": (1, True, False), "k2": (2, True, False), "k2_push": (2, False, False), "k3": (3, True, False), "k3_push": (3, False, False),
+            "k2_composed": (2, True, True)}
+
+
+def clip(B, seed, dev):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    x = torch.randn(B, T, 4, H, W, device=dev, generator=g)
+    for c, (mu, sd) in enumerate(FIELD_STATS):
+        x[:, :, c].mul_(sd).add_(mu)
+    return x
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=6)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--versions", default=",".join(VERSIONS))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("unroll_bench.py times the step on the GPU: no GPU here, nothing measured")
+    from bubbleformer_amd.models import get_model
+    from bubbleformer_amd.trainer import TrainStep
+    from bubbleformer_amd.utils.losses import LpLoss
+    dev = torch.device("cuda:0")
+    x = clip(a.batch, 1, dev)
+    ys = torch.stack([clip(a.batch, 2 + j, dev) for j in range(3)])
+    fluid = torch.randn(a.batch, CFG["num_fluid_params"], device=dev, generator=torch.Generator(device=dev).manual_seed(9))
+    steps = {}
+    for name in a.versions.split(","):
+        k, backprop, composed = VERSIONS[name]
+        torch.manual_seed(0)
+        model = get_model("filmavit", time_window=T, drop_path=DROP_PATH, compute_dtype=torch.bfloat16, **CFG).to(dev).train()
+        crit = LpLoss(d=2, p=2, reduce_dims=[0, 1, 2], reductions=["mean", "mean", "sum"]) if composed else None
+        step = TrainStep(model, lr=2.5e-4, weight_decay=1e-2, optimizer="adamw", criterion=crit, unroll_steps=k, unroll_backprop=backprop)
+        target = ys[0] if k == 1 else ys[:k]
+        steps[name] = (lambda s=step, t=target: s(x, fluid, t))
+    for f in steps.values():
+        for _ in range(a.warmup):
+            loss = f()
+        assert torch.isfinite(loss).all()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in steps}
+    for _ in range(a.rounds):
+        for n, f in steps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[n].append(e0.elapsed_time(e1) / a.reps)
+    out = {"shape": [a.batch, T, 4, H, W], "dtype": "bf16", "rounds": a.rounds, "reps": a.reps, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+    for n, t in ms.items():
+        out[n] = {"ms": round(statistics.median(t), 3), "ms_min": round(min(t), 3), "ms_max": round(max(t), 3)}
+    if "k1" in ms:
+        for n in ms:
+            k = VERSIONS[n][0]
+            if k > 1:
+                out[n]["ratio_to_k_plain_steps"] = round(out[n]["ms"] / (k * out["k1"]["ms"]), 4)
+    if "k2" in ms and "k2_composed" in ms:
+        out["fused_minus_composed_us"] = round(1e3 * (out["k2"]["ms"] - out["k2_composed"]["ms"]), 1)
+        out["checks"] = {"fused_not_slower": out["k2"]["ms"] <= out["k2_composed"]["ms"]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
