@@ -185,6 +185,7 @@ SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_clip_gather_unroll": (C.c_int, [fp, i64, i64, vp, i64, vp, vp, fp, fp, C.c_int, C.c_int, fp, vp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, vp, C.c_int,
                                         fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_clip_noise": (C.c_int, [fp, fp, fp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_rollout_score_ws_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_rollout_score": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

@@ -183,8 +183,6 @@ class DeviceClipStore:
         reduction launch (bf_field_stats, fp64 accumulation in a fixed order) instead of a host pass over every file, then the reference's
         rule per file and the mean over files (dataset.py:84-117).  Sets the dataset's constants and this store's tables; returns them.
         Against the host path the constants agree to fp32 rounding of the host's own float32 reductions (~1e-7 relative)."""
-        from .. import _lib as L
-        from ..ops import _p, _stream
         ds = self.ds
         if ds.norm == "none" or self.device.type != "cuda":
             out = ds.normalize()
@@ -192,6 +190,22 @@ class DeviceClipStore:
             return out
         if ds.norm not in _NORMS:
             raise ValueError(f"Unknown normalization type: {ds.norm}")
+        st, n = self._segment_stats()
+        nfile = len(ds.traj_lens)
+        mean = st[..., 0] / n
+        var = np.maximum(st[..., 1] / n - mean * mean, 0.0)
+        per_file = {name: [_NORMS[ds.norm]({"mean": mean[ci, fi], "std": float(np.sqrt(var[ci, fi])), "min": st[ci, fi, 2], "max": st[ci, fi, 3]})
+                           for fi in range(nfile)] for ci, name in enumerate(self.fields)}
+        ds.diff_terms, ds.div_terms = _combine_constants(per_file)
+        self._tables()
+        return ds.diff_terms, ds.div_terms
+
+    def _segment_stats(self) -> Tuple[np.ndarray, np.ndarray]:
+        """{sum, sum of squares, min, max} in fp64 of every (field, file) segment of the resident frames, [fields][files][4], from ONE
+        bf_field_stats launch, and the segments' element counts [fields][files]."""
+        from .. import _lib as L
+        from ..ops import _p, _stream
+        ds = self.ds
         nfile, px = len(ds.traj_lens), self.H * self.W
         total = int(self.frame0[-1])
         begin = [(ci * total + int(self.frame0[fi])) * px for ci in range(len(self.fields)) for fi in range(nfile)]
@@ -204,13 +218,23 @@ class DeviceClipStore:
         L.check(L.lib().bf_field_stats(_p(self.frames), _p(seg_b), _p(seg_n), nseg, _p(out), _p(ws), _stream()), "bf_field_stats")
         st = out.cpu().view(len(self.fields), nfile, 4).numpy()
         n = np.asarray(length, dtype=np.float64).reshape(len(self.fields), nfile)
-        mean = st[..., 0] / n
-        var = np.maximum(st[..., 1] / n - mean * mean, 0.0)
-        per_file = {name: [_NORMS[ds.norm]({"mean": mean[ci, fi], "std": float(np.sqrt(var[ci, fi])), "min": st[ci, fi, 2], "max": st[ci, fi, 3]})
-                           for fi in range(nfile)] for ci, name in enumerate(self.fields)}
-        ds.diff_terms, ds.div_terms = _combine_constants(per_file)
-        self._tables()
-        return ds.diff_terms, ds.div_terms
+        return st, n
+
+    def field_std(self) -> Dict[str, float]:
+        """Per field, the standard deviation over ALL resident frames (every file pooled), in normalised units: the deviation of the stored
+        values divided by the field's ``div`` constant (1 while the dataset has not been normalised) -- the scale ``NoiseSpec(relative=True)``
+        refers to.  On the GPU from one bf_field_stats launch (sum and sum of squares per (field, file) segment in fp64, pooled on the host,
+        as ``normalize()`` reads them); on a CPU store the same quantity from numpy in fp64."""
+        ds = self.ds
+        if self.device.type == "cuda":
+            st, n = self._segment_stats()
+            count = n.sum(axis=1)
+            mean = st[..., 0].sum(axis=1) / count
+            raw = np.sqrt(np.maximum(st[..., 1].sum(axis=1) / count - mean * mean, 0.0))
+        else:
+            raw = np.array([self.frames[ci].numpy().astype(np.float64).std() for ci in range(len(self.fields))])
+        div = [1.0 if isinstance(ds.div_terms[name], list) else float(ds.div_terms[name]) for name in self.fields]
+        return {name: float(raw[ci] / div[ci]) for ci, name in enumerate(self.fields)}
 
     def _tables(self):
         """Per-output-channel field index and normalisation constants; call again after ``ds.normalize()`` changed them."""

@@ -53,7 +53,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True) -> Dict:
+        unroll_backprop: bool = True, input_noise=None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -71,6 +71,12 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     file -- under the same seeding and rank split, the clips come from ``gather(idx, unroll=k)``, ``train_loss`` is the weighted sum and
     ``hist["unroll_loss"]`` keeps the k per-pass losses of every batch.  Validation stays the single-step criterion; checkpoints and
     resume are unchanged.  The training set's input and output fields must be the same list (ValueError, as plan_rollouts refuses it).
+    ``input_noise``: a utils.noise.NoiseSpec -- seeded Gaussian noise on the clips the model is fed while training (TrainStep): every batch's
+    dataset indices are its sample ids (staged as ``gather`` stages them: a device tensor costs no synchronisation), the draw is the
+    optimizer-step count, so a resumed run continues the sequence and the checkpoint needs no new key; ``relative=True`` is resolved once
+    from the training store (``DeviceClipStore.field_std()`` of the input fields).  Every rank uses the same seed and ranks differ by
+    their sample ids; a sample that occurs twice inside one optimizer step (DistributedSampler padding, accumulation over a tiny set)
+    gets the same noise both times.  Validation is never perturbed.  None: history and parameters are bit for bit those without it.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -87,10 +93,15 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     vstore = val_set.device_store(dev) if val_set is not None else None
     steps_per_epoch = accumulation_plan(per_epoch, accumulate_grad_batches)[1]
     sched = CosineWarmupLR(lr, warmup_iters, max_epochs * steps_per_epoch, eta_min) if warmup_iters is not None else None
+    noisy = input_noise is not None and input_noise.active
+    field_std = None
+    if noisy and input_noise.relative:
+        fs = store.field_std()
+        field_std = [fs[n] for n in train_set.input_fields]
     step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion,
                      gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
                      accumulate_grad_batches=accumulate_grad_batches, unroll_steps=unroll_steps, unroll_weights=unroll_weights,
-                     unroll_backprop=unroll_backprop)
+                     unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
     if step.grad_norm is not None:
@@ -112,7 +123,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             x, y, c = (got[0], got[1], got[2]) if conditioned else (got[0], got[1], None)
             cur_lr = sched.get_last_lr()[0] if sched is not None else step.lr      # step.lr: a reference checkpoint brings its own
             before = step.step_no
-            loss = step(x, c, y)
+            loss = step(x, c, y, sample_ids=idx) if noisy else step(x, c, y)
             if bi == len(todo) - 1:
                 step.finish_accumulation()      # an epoch's last batch completes its group, whatever the group holds
             losses.append(loss)

@@ -953,6 +953,24 @@ def clip_gather_unroll(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch
     return inp, out, fl
 
 
+def clip_noise(src: torch.Tensor, sigma: torch.Tensor, sample_ids: Optional[torch.Tensor], draw: int, pass_index: int, seed: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = src + sigma[c] * z on contiguous fp32 clips (B, T, C, H, W), z the seeded normals of bf_clip_noise (csrc/noise.hip): a pure
+    function of (seed, sample id, draw, pass, element).  sigma [C] fp32 and sample_ids [B] int64 (None: 0 .. B - 1) are device tensors;
+    draw / pass_index are taken modulo 2^32 and seed modulo 2^64.  ``out`` may be ``src`` itself (in place); None allocates.  One launch."""
+    _require_gpu(src)
+    if src.dim() != 5 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise L.BubbleformerHipError(f"clip_noise: the clip must be a contiguous fp32 (B, T, C, H, W) tensor, got {src.dtype} {tuple(src.shape)}")
+    B, T, Cn, H, W = src.shape
+    if out is None:
+        out = torch.empty_like(src)
+    want = {"sigma": (sigma, (Cn,), torch.float32), "sample_ids": (sample_ids, (B,), torch.int64), "out": (out, tuple(src.shape), torch.float32)}
+    _check_tensors("clip_noise", src.device, want, optional=("sample_ids",))
+    L.check(L.lib().bf_clip_noise(_p(src), _p(out), _p(sigma), _p(sample_ids), int(seed) & (2 ** 64 - 1), int(draw) & 0xFFFFFFFF,
+                                  int(pass_index) & 0xFFFFFFFF, B, T, Cn, H, W, _stream()), "bf_clip_noise")
+    return out
+
+
 def _check_tensors(who: str, device, want: dict, optional=()) -> None:
     """want = {name: (tensor, shape, dtype)}: every tensor contiguous, of that shape and dtype, on ``device``; the names in ``optional`` may be None."""
     for name, (t, shape, dtype) in want.items():

@@ -259,13 +259,32 @@ class TrainStep:
     back detached and each pass's backward follows its forward (one pass's activations alive; a pass with w_j = 0 runs under no_grad).
     Stochastic depth is drawn per pass.  Every backward but the last runs inside BucketReducer.no_sync() (unroll_plan).  The input and
     output fields must be the same (ValueError); a model whose forward_loss cannot keep its prediction in the graph (the U-Nets) is
-    refused with NotImplementedError unless a criterion is given.  unroll_steps = 1 is the step it always was."""
+    refused with NotImplementedError unless a criterion is given.  unroll_steps = 1 is the step it always was.
+    input_noise = utils.noise.NoiseSpec: seeded Gaussian noise on what the model is fed (one bf_clip_noise launch per perturbed pass).  The
+    gathered clip is pass 0; with unroll_steps = k the input of pass j + 1 is pred_j + noise(pass = j + 1), built from pred_j.detach() and, with
+    unroll_backprop, marked requires_grad: the gradient it collects is handed to pred_j unchanged (the addition's Jacobian is the identity).
+    The noisy clip is always a new tensor: the caller's x and the prediction a fused-loss backward has saved are never written; targets are
+    never perturbed.  The noise of element e of sample s is a pure function of (spec.seed, s, step_no at the time of the call, pass, e);
+    s comes from ``sample_ids`` of the call (the batch's dataset indices; None numbers the rows 0 .. B - 1), step_no counts optimizer steps
+    and is in every checkpoint, so a resumed run continues the sequence.  Every micro-batch of an accumulate_grad_batches group draws
+    under the same step_no: two occurrences of one sample inside one optimizer step get the same noise (NoiseSpec).  ``relative=True``
+    needs ``field_std`` (one deviation per input field, DeviceClipStore.field_std(); fit resolves it).  None, or a spec whose std is all
+    zero, is off: the step launches exactly what it launches without the argument."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1, unroll_steps: int = 1, unroll_weights=None,
-                 unroll_backprop: bool = True):
+                 unroll_backprop: bool = True, input_noise=None, field_std=None):
         from . import ops
+        from .utils.noise import NoiseSpec
+        if input_noise is not None and not isinstance(input_noise, NoiseSpec):
+            raise ValueError(f"input_noise {input_noise!r} must be None or a utils.noise.NoiseSpec")
+        if input_noise is not None and input_noise.active and input_noise.relative and field_std is None:
+            raise ValueError("input_noise: NoiseSpec(relative=True) needs the input fields' standard deviations -- train through fit(), which "
+                             "takes them from the training store, or pass field_std= (DeviceClipStore.field_std())")
+        self.input_noise = input_noise if input_noise is not None and input_noise.active else None
+        self._noise_field_std = None if field_std is None else [float(v) for v in field_std]
+        self._noise_sigma = None      # the per-channel deviations on the device, built at the first perturbed call
         if optimizer not in ("adamw", "adam", "lion"):
             raise ValueError(f"Optimizer {optimizer} not supported")
         if gradient_clip_algorithm not in ("norm", "value"):
@@ -332,8 +351,26 @@ class TrainStep:
         from . import ops
         ops._weights_changed()           # the broadcast wrote the flat buffer behind the parameters' version counters: prepared inference weights are stale
 
-    def __call__(self, x, fluid, target) -> torch.Tensor:
+    def _noise_ids(self, x, sample_ids):
+        """The sample ids of a call as the noise kernel reads them (staged once per call, no synchronisation); None when noise is off."""
+        if self.input_noise is None:
+            return None
+        from .utils.noise import stage_sample_ids
+        return stage_sample_ids(sample_ids, x.shape[0], x.device)
+
+    def _noisy(self, clip, pass_index: int, ids):
+        """``clip`` as pass ``pass_index`` is fed it: the clip itself where the spec leaves that pass alone, otherwise a NEW tensor
+        clip + sigma * z(seed, sample, step_no, pass) -- ``clip`` is never written."""
+        spec = self.input_noise
+        if spec is None or not spec.perturbs(pass_index):
+            return clip
+        if self._noise_sigma is None or self._noise_sigma.device != clip.device or self._noise_sigma.numel() != clip.shape[2]:
+            self._noise_sigma = torch.tensor(spec.sigma(clip.shape[2], self._noise_field_std), dtype=torch.float32, device=clip.device)
+        return self.ops.clip_noise(clip.detach().contiguous(), self._noise_sigma, ids, self.step_no, pass_index, spec.seed)
+
+    def __call__(self, x, fluid, target, sample_ids=None) -> torch.Tensor:
         final = self.micro + 1 >= self.accumulate_grad_batches
+        ids = self._noise_ids(x, sample_ids)
         if self.micro == 0:
             self.flat.zero_grad()
         self.reducer.begin_step()
@@ -341,7 +378,10 @@ class TrainStep:
         self.ops.set_side_defer(True)       # a stage's weight-gradient GEMMs may run into the next stage; joined below
         try:
             with contextlib.nullcontext() if final else self.reducer.no_sync():
-                loss = self._fwd_bwd(x, fluid, target) if self.unroll_steps == 1 else self._fwd_bwd_unrolled(x, fluid, target, final)
+                if self.unroll_steps == 1:
+                    loss = self._fwd_bwd(self._noisy(x, 0, ids), fluid, target)
+                else:
+                    loss = self._fwd_bwd_unrolled(x, fluid, target, final, ids)
         finally:
             self.ops.set_side_defer(False)
             self.ops.set_direct_grad_slots(None)
@@ -389,9 +429,10 @@ class TrainStep:
         loss.backward()
         return loss
 
-    def _fwd_bwd_unrolled(self, x, fluid, target, final: bool):
+    def _fwd_bwd_unrolled(self, x, fluid, target, final: bool, ids=None):
         """The schedule of unroll_plan: k forward passes through the model's own predictions, their backwards in the plan's order, all but
-        the last inside no_sync().  Returns sum_j w_j loss_j; the k losses stay in ``unroll_losses``."""
+        the last inside no_sync().  Returns sum_j w_j loss_j; the k losses stay in ``unroll_losses``.  With input noise, pass j is fed
+        _noisy(., j, ids): the gradient a noisy fed-back clip collects belongs to the prediction it was built from, unchanged."""
         k, w, backprop = self.unroll_steps, self.unroll_weights, self.unroll_backprop
         if isinstance(target, torch.Tensor):
             if target.dim() != x.dim() + 1 or target.shape[0] != k:
@@ -401,7 +442,7 @@ class TrainStep:
         self._check_unroll_fields(x.shape[2], target[0].shape[2])
         plan = unroll_plan(k, w, backprop, final)[1]
         takes_grad = {j: g for op, j, g in plan if op == "forward"}
-        inputs, preds, losses = [x] + [None] * (k - 1), [None] * k, [None] * k
+        inputs, preds, losses = [self._noisy(x, 0, ids)] + [None] * (k - 1), [None] * k, [None] * k
         for op, j, flag in plan:
             if op == "forward":
                 feeds = backprop and j + 1 < k and takes_grad[j + 1]        # the prediction carries a gradient back from pass j + 1
@@ -416,7 +457,8 @@ class TrainStep:
                 if not backprop:
                     inputs[j] = None                                        # pushforward: a fed-back clip is done with after its pass's forward
                 if j + 1 < k:
-                    inputs[j + 1] = pred.detach().requires_grad_() if feeds else pred.detach()
+                    fed = self._noisy(pred.detach(), j + 1, ids)
+                    inputs[j + 1] = fed.requires_grad_() if feeds else fed
             else:
                 outs, grads = [], []
                 if w[j] > 0.0:

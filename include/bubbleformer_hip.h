@@ -30,6 +30,7 @@
  *   bf_adamw ................. torch.optim.AdamW as configured at bubbleformer/modules.py:135-136
  *   bf_adam .................. torch.optim.Adam as configured at bubbleformer/modules.py:137-138 (config/optim_cfg/adam.yaml)
  *   bf_clip_gather ........... BubbleForecast.__getitem__ + DataLoader collate for a batch of clips: bubbleformer/data/dataset.py:120-182
+ *   bf_clip_noise ............ seeded Gaussian input noise of a training step (no reference program; Philox4x32-10 + Box-Muller)
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
@@ -363,6 +364,19 @@ int bf_clip_gather_unroll(const float* src, int64_t field_stride, int64_t nframe
                           const int32_t* out_field, const float* out_diff, const float* out_div, int Cout, int Tout, int unroll, float* out_out,
                           const float* fluid_tab, const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo,
                           bf_stream_t stream);
+/* Seeded Gaussian noise on a batch of clips (csrc/noise.hip): dst[b][t][c][y][x] = fmaf(sigma[c], z, src[b][t][c][y][x]) on contiguous fp32
+ * (B, T, C, H, W); an element of a channel with sigma[c] == 0 is handed back bit for bit.  dst == src (in place) or two buffers that do not
+ * overlap.  z is a pure function of (seed, sample id, draw, pass, element index e inside the sample's flattened (T, C, H, W) clip):
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = {e / 4, low 32 bits of sample_ids[b] (b itself when sample_ids is NULL), draw, pass},
+ *                                    key = {low, high word of seed}), Random123's constants;
+ *   Box-Muller per pair (a, b) = (w0, w1) for elements 4g, 4g + 1 and (w2, w3) for 4g + 2, 4g + 3: u1 = ((a >> 8) + 1) * 2^-24,
+ *   u2 = (b >> 8) * 2^-24, r = sqrtf(-2 * logf(u1)), the pair r * cospif(2 * u2), r * sinpif(2 * u2); |z| <= 5.77.  A sample size that is no
+ *   multiple of 4 uses the leading words of its last group.
+ * sigma [C] fp32 and sample_ids [B] int64 are DEVICE tables.  One launch, no workspace, no LDS, no atomics, capturable; two calls give the same
+ * bits, and a sample's row does not depend on B or on its position in the batch.  T * C * H * W < 2^31.  Loads and stores are 16 bytes wide when
+ * that size is a multiple of 4 and both pointers are 16-byte aligned, scalar otherwise. */
+int bf_clip_noise(const float* src, float* dst, const float* sigma, const int64_t* sample_ids, uint64_t seed, uint32_t draw, uint32_t pass,
+                  int B, int T, int C, int H, int W, bf_stream_t stream);
 /* Normalisation statistics of device-resident trajectories (BubbleForecast.normalize, bubbleformer/data/dataset.py:74-117: mean / std / min /
  * max of every full field of every file): segment i = seg_len[i] floats at src + seg_begin[i] (both arrays on the DEVICE);
  * out[i] = {sum, sum of squares, min, max} in fp64, summed in a fixed order (bit-reproducible).  ws: bf_field_stats_ws_doubles(nseg) doubles. */
