@@ -1066,8 +1066,9 @@ def test_embed_first_stage_one_pass_with_statistics(cin, h2, w2):
 def test_gather_gemm_2x2_stage(Fr, gh, gw, variant):
     """bf_gather_gemm (gather_gemm.hip): rows of 2x2 / stride-2 patches of a 96-channel map times a [384][96] weight, with GELU(x * sc + sh)
     folded into the operand (the HMLPEmbed stages, weight stored [n][k]) or plain (the HMLPDebed data gradients, weight stored [k][n]),
-    against fp64 torch on the same bf16 operands.  One tile in all, runs that cross frames (7 frames x 72 tiles over 512 x 4 waves), 16-row
-    blocks in the middle of an image row."""
+    against fp64 torch on the same bf16 operands.  One tile in all, up to 7 frames x 72 tiles (fewer than a full grid's 2 x CUs x 4 waves on
+    an MI355X: one tile per wave; tests/test_gpu_patch_edges.py runs several tiles per wave across frames), 16-row blocks in the middle of
+    an image row."""
     from bubbleformer_amd import _lib as L
     from bubbleformer_amd.ops import _p, _stream
     lib = L.lib()
