@@ -177,6 +177,11 @@ SIGNATURES = {
     "bf_adamw_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
     "bf_adam_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
     "bf_lion_dev": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, vp]),
+    "bf_adamw_avg": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
+    "bf_adam_avg": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
+    "bf_lion_avg": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
+    "bf_weight_average": (C.c_int, [fp, fp, i64, f32, vp]),
+    "bf_swap_buffers": (C.c_int, [fp, fp, i64, vp]),
     "bf_eikonal_sum": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, vp, vp]),
     "bf_eikonal_l1_frames": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, vp]),
     "bf_heatflux_rows": (C.c_int, [fp, fp, i64, i64, C.c_int, f32, f32, f32, f32, fp, vp]),

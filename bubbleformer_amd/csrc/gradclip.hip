@@ -4,6 +4,8 @@
 //   bf_adamw_dev / bf_adam_dev / bf_lion_dev -> the fused optimizers of optim_kernels.h reading that coefficient from device memory, with an
 //                                               optional clamp of the scaled gradient (gradient_clip_algorithm="value")
 //   bf_adamw / bf_adam / bf_lion             -> the same optimizers on a host gradient scale (no clipping)
+//   bf_adamw_avg / bf_adam_avg / bf_lion_avg -> any of those with an averaged copy of the weights kept in the same launch (EMA / SWA);
+//                                               bf_weight_average is that update alone, bf_swap_buffers exchanges two flat buffers
 //
 // The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
 //   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
@@ -163,4 +165,54 @@ extern "C" int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float 
     hipStream_t st = (hipStream_t)stream;
     return BF_OPT_DISPATCH(opt_launch_lion<BF_OPT_DEV>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st),
                            opt_launch_lion<BF_OPT_DEV_CLAMP>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st));
+}
+
+// ---------------------------------------------------------------------------- the optimizers with an averaged copy of the weights
+// One entry per optimizer for all three scale modes; avg moves towards the parameter value the step has just formed (avg_lerp).
+#define BF_AVG_REQUIRE(who)                                                                                         \
+    BF_REQUIRE(avg && BF_OPT_ALIGNED(avg), who ": the average buffer is required and must be 16-byte aligned");      \
+    BF_REQUIRE(avg_weight > 0.f && avg_weight <= 1.f, who ": avg_weight must be in (0, 1]")
+
+extern "C" int bf_adamw_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                            float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_avg: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_avg: buffers must be 16-byte aligned");
+    BF_AVG_REQUIRE("bf_adamw_avg");
+    return BF_OPT_AVG_DISPATCH(opt_launch_adam, true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, (hipStream_t)stream,
+                               avg, avg_weight);
+}
+
+extern "C" int bf_adam_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                           float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_avg: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_avg: buffers must be 16-byte aligned");
+    BF_AVG_REQUIRE("bf_adam_avg");
+    return BF_OPT_AVG_DISPATCH(opt_launch_adam, false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, (hipStream_t)stream,
+                               avg, avg_weight);
+}
+
+extern "C" int bf_lion_avg(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
+                           const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_avg: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_avg: buffers must be 16-byte aligned");
+    BF_AVG_REQUIRE("bf_lion_avg");
+    return BF_OPT_AVG_DISPATCH(opt_launch_lion, p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, (hipStream_t)stream, avg, avg_weight);
+}
+
+extern "C" int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream) {
+    BF_REQUIRE(avg && p && n > 0, "bf_weight_average: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(avg) && BF_OPT_ALIGNED(p), "bf_weight_average: buffers must be 16-byte aligned");
+    BF_REQUIRE(w > 0.f && w <= 1.f, "bf_weight_average: w must be in (0, 1]");
+    hipLaunchKernelGGL(avg_kernel, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, (hipStream_t)stream, avg, p, (long)n, w);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream) {
+    BF_REQUIRE(a && b && n > 0, "bf_swap_buffers: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(a) && BF_OPT_ALIGNED(b), "bf_swap_buffers: buffers must be 16-byte aligned");
+    BF_REQUIRE(a + n <= b || b + n <= a, "bf_swap_buffers: the buffers overlap");
+    hipLaunchKernelGGL(swap_kernel, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, (hipStream_t)stream, a, b, (long)n);
+    BF_CHECK_LAUNCH();
+    return 0;
 }

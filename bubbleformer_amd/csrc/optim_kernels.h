@@ -6,6 +6,10 @@
 // One body per optimizer: the variants differ in where the scale comes from (read once per thread, before the loop) and in one clamp on
 // the scaled gradient.  BF_OPT_HOST compiles to the kernel the host-scale entry points always launched; BF_OPT_DEV runs the same loop
 // body on gscale * coef_dev[0], which is gscale exactly when the coefficient is 1.0f.
+// A third family, bf_adamw_avg / bf_adam_avg / bf_lion_avg, runs the same bodies with AVG = true: the step also moves an averaged copy
+// `a` of the parameters towards the value it has just formed, a <- a + w * (p - a) (avg_lerp; an EMA or a running mean, by the caller's
+// w), for one more read and one more write of one buffer and no launch.  AVG = false has no trace of it: those are the kernels above.
+// bf_weight_average is the lerp alone and bf_swap_buffers exchanges two flat buffers; same grid rule, 16-byte body, scalar tail.
 #pragma once
 #include <algorithm>
 
@@ -30,11 +34,19 @@ __device__ __forceinline__ float opt_grad(float g, float gs, float clip) {
     return gr;
 }
 
+// the averaged copy's update, two roundings (the difference, then one fma); w == 1 copies p bit for bit.  Written once: the fused
+// bodies, their tails and avg_kernel give the same bits.  Zero padding stays zero, and a NaN in p reaches a.
+__device__ __forceinline__ float avg_lerp(float a, float p, float w) { return w == 1.f ? p : __fmaf_rn(w, p - a, a); }
+__device__ __forceinline__ float4 avg_lerp4(float4 a, const float4 p, float w) {
+    a.x = avg_lerp(a.x, p.x, w); a.y = avg_lerp(a.y, p.y, w); a.z = avg_lerp(a.z, p.z, w); a.w = avg_lerp(a.w, p.w, w);
+    return a;
+}
+
 // ---------------------------------------------------------------------------- AdamW (torch.optim.AdamW semantics)
-template <int MODE>
+template <int MODE, bool AVG>
 __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip) {
+                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
     constexpr int NT = BF_OPT_NT;
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -42,6 +54,8 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float4 aa;
+        if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_ADAM1(X)                                                        \
         { const float gr = opt_grad<MODE>(gg.X, gs, clip);                  \
           pp.X *= (1.f - lr * wd);                                          \
@@ -51,6 +65,7 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
         BF_ADAM1(x) BF_ADAM1(y) BF_ADAM1(z) BF_ADAM1(w)
 #undef BF_ADAM1
         reinterpret_cast<float4*>(p)[i] = pp;
+        if constexpr (AVG) reinterpret_cast<float4*>(a)[i] = avg_lerp4(aa, pp, w);
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
     }
@@ -62,16 +77,17 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
         const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
         pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
         p[i] = pp; m[i] = mm; v[i] = vv;
+        if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
     }
 }
 
 // ---------------------------------------------------------------------------- Adam (torch.optim.Adam semantics, single-tensor path)
 // Weight decay is an L2 term on the gradient (g += wd*p), so it passes through both moments; AdamW above decays the parameter instead.
 // Zero padding stays zero: p = g = m = v = 0 gives m / (sqrt(v) / sqrt_bc2 + eps) = 0.
-template <int MODE>
+template <int MODE, bool AVG>
 __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip) {
+                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
     constexpr int NT = BF_OPT_NT;
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -79,6 +95,8 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float4 aa;
+        if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_ADAML2(X)                                                       \
         { float gr = opt_grad<MODE>(gg.X, gs, clip);                        \
           if (wd != 0.f) gr += wd * pp.X;                                   \
@@ -88,6 +106,7 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
         BF_ADAML2(x) BF_ADAML2(y) BF_ADAML2(z) BF_ADAML2(w)
 #undef BF_ADAML2
         reinterpret_cast<float4*>(p)[i] = pp;
+        if constexpr (AVG) reinterpret_cast<float4*>(a)[i] = avg_lerp4(aa, pp, w);
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
     }
@@ -100,15 +119,16 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
         const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
         pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
         p[i] = pp; m[i] = mm; v[i] = vv;
+        if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
     }
 }
 
 // ---------------------------------------------------------------------------- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization
 // Algorithms"; the update lion_pytorch.Lion applies at bubbleformer/modules.py:139-140):
 //   p *= 1 - lr*wd;  p -= lr * sign(b1*m + (1-b1)*g);  m = b2*m + (1-b2)*g
-template <int MODE>
+template <int MODE, bool AVG>
 __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n, float lr,
-                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip) {
+                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
     constexpr int NT = BF_OPT_NT;
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -117,6 +137,8 @@ __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, 
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i];
+        float4 aa;
+        if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_LION1(X)                                                        \
         { const float gr = opt_grad<MODE>(gg.X, gs, clip);                  \
           pp.X = pp.X * (1.f - lr * wd) - lr * sgn(b1 * mm.X + (1.f - b1) * gr); \
@@ -124,37 +146,74 @@ __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, 
         BF_LION1(x) BF_LION1(y) BF_LION1(z) BF_LION1(w)
 #undef BF_LION1
         reinterpret_cast<float4*>(p)[i] = pp;
+        if constexpr (AVG) reinterpret_cast<float4*>(a)[i] = avg_lerp4(aa, pp, w);
         reinterpret_cast<float4*>(m)[i] = mm;
     }
     if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
         const long i = n4 * 4 + threadIdx.x;
         const float gr = opt_grad<MODE>(g[i], gs, clip);
-        p[i] = p[i] * (1.f - lr * wd) - lr * sgn(b1 * m[i] + (1.f - b1) * gr);
+        const float pp = p[i] * (1.f - lr * wd) - lr * sgn(b1 * m[i] + (1.f - b1) * gr);
+        p[i] = pp;
         m[i] = b2 * m[i] + (1.f - b2) * gr;
+        if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
     }
 }
 
-// launches, shared by both families of entry points (which check their own arguments)
+// ---------------------------------------------------------------------------- the averaged copy on its own, and the exchange
+// a <- avg_lerp(a, p, w): what the AVG bodies do after their step, for an average taken outside the optimizer
+__global__ void __launch_bounds__(BF_OPT_NT) avg_kernel(float* __restrict__ a, const float* __restrict__ p, long n, float w) {
+    constexpr int NT = BF_OPT_NT;
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT)
+        reinterpret_cast<float4*>(a)[i] = avg_lerp4(reinterpret_cast<float4*>(a)[i], reinterpret_cast<const float4*>(p)[i], w);
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const long i = n4 * 4 + threadIdx.x;
+        a[i] = avg_lerp(a[i], p[i], w);
+    }
+}
+// a <-> b exactly: every element is read and written by one thread (the entry point refuses overlapping buffers)
+__global__ void __launch_bounds__(BF_OPT_NT) swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    constexpr int NT = BF_OPT_NT;
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+        const float4 x = reinterpret_cast<float4*>(a)[i], y = reinterpret_cast<float4*>(b)[i];
+        reinterpret_cast<float4*>(a)[i] = y;
+        reinterpret_cast<float4*>(b)[i] = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const long i = n4 * 4 + threadIdx.x;
+        const float x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
+// launches, shared by the families of entry points (which check their own arguments); a / w: the averaged copy of the AVG kernels
 #define BF_OPT_ALIGNED(x) ((uintptr_t)(x) % 16 == 0)
-template <int MODE>
+template <int MODE, bool AVG = false>
 int opt_launch_adam(bool decoupled, float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                    float eps, float wd, float gscale, const float* coef, float clip, hipStream_t st) {
+                    float eps, float wd, float gscale, const float* coef, float clip, hipStream_t st, float* a = nullptr, float w = 0.f) {
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
     if (decoupled)
-        hipLaunchKernelGGL(adamw_kernel<MODE>, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2,
-                           gscale, coef, clip);
+        hipLaunchKernelGGL((adamw_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1,
+                           sbc2, gscale, coef, clip, a, w);
     else
-        hipLaunchKernelGGL(adam_kernel<MODE>, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1, sbc2,
-                           gscale, coef, clip);
+        hipLaunchKernelGGL((adam_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1,
+                           sbc2, gscale, coef, clip, a, w);
     BF_CHECK_LAUNCH();
     return 0;
 }
-template <int MODE>
+template <int MODE, bool AVG = false>
 int opt_launch_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale, const float* coef,
-                    float clip, hipStream_t st) {
-    hipLaunchKernelGGL(lion_kernel<MODE>, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, (long)n, lr, beta1, beta2, wd, gscale, coef, clip);
+                    float clip, hipStream_t st, float* a = nullptr, float w = 0.f) {
+    hipLaunchKernelGGL((lion_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, (long)n, lr, beta1, beta2, wd, gscale, coef,
+                       clip, a, w);
     BF_CHECK_LAUNCH();
     return 0;
 }
+// the scale mode of an _avg entry: BF_OPT_DISPATCH's choice between the device modes, and the host-scale kernel when there is neither
+#define BF_OPT_AVG_DISPATCH(LAUNCH, ...)                                                   \
+    (!isinf(clip_value) ? LAUNCH<BF_OPT_DEV_CLAMP, true>(__VA_ARGS__)                      \
+                        : (coef_dev ? LAUNCH<BF_OPT_DEV, true>(__VA_ARGS__) : LAUNCH<BF_OPT_HOST, true>(__VA_ARGS__)))
 }  // namespace

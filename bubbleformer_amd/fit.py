@@ -53,7 +53,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True, input_noise=None) -> Dict:
+        unroll_backprop: bool = True, input_noise=None, weight_average=None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -77,6 +77,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     from the training store (``DeviceClipStore.field_std()`` of the input fields).  Every rank uses the same seed and ranks differ by
     their sample ids; a sample that occurs twice inside one optimizer step (DistributedSampler padding, accumulation over a tiny set)
     gets the same noise both times.  Validation is never perturbed.  None: history and parameters are bit for bit those without it.
+    ``weight_average``: a utils.averaging.AverageSpec -- the training step keeps an EMA / SWA copy of the weights inside its optimizer kernel
+    (TrainStep).  With a validation set every epoch then validates twice: ``hist["val_loss"]`` (and the panels) stay the live weights,
+    ``hist["val_loss_avg"]`` is the same validation inside ``step.averaged_weights()``, and `log` gets ``val_loss_avg`` beside ``val_loss``.
+    Checkpoints carry the average and a resumed run continues it (utils/checkpoint.py).  None: nothing of this runs.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -101,13 +105,15 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion,
                      gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
                      accumulate_grad_batches=accumulate_grad_batches, unroll_steps=unroll_steps, unroll_weights=unroll_weights,
-                     unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std)
+                     unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std, weight_average=weight_average)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
     if step.grad_norm is not None:
         hist["grad_norm"] = []
     if k > 1:
         hist["unroll_loss"] = []
+    if step.avg is not None and vstore is not None:
+        hist["val_loss_avg"] = []
     first_epoch = 0
     if resume_from is not None:
         ck = load_checkpoint(resume_from, model, step)
@@ -148,8 +154,13 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, sample))
             if sample:
                 write_validation_strips(panel_dir, epoch, list(val_set.output_fields), *sample)
+            entry = {"epoch": epoch, "val_loss": hist["val_loss"][-1]}
+            if step.avg is not None:
+                with step.averaged_weights():
+                    hist["val_loss_avg"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion))
+                entry["val_loss_avg"] = hist["val_loss_avg"][-1]
             if log is not None:
-                log({"epoch": epoch, "val_loss": hist["val_loss"][-1]})
+                log(entry)
         if checkpoint_path is not None and rank == 0:
             save_checkpoint(checkpoint_path, model, hyper_parameters, norm, step, epoch=epoch)       # one atomic write
     return hist

@@ -1355,13 +1355,35 @@ def _coef_ptr(coef: Optional[torch.Tensor], p: torch.Tensor, who: str):
     return coef.data_ptr()
 
 
+def _avg_args(avg: Optional[torch.Tensor], avg_weight: Optional[float], p: torch.Tensor, who: str):
+    """None when the call keeps no average; otherwise (avg pointer, weight) for the _avg entry points."""
+    if avg is None and avg_weight is None:
+        return None
+    if avg is None or avg_weight is None:
+        raise L.BubbleformerHipError(f"{who}: avg and avg_weight go together (got avg={'None' if avg is None else 'a tensor'}, avg_weight={avg_weight!r})")
+    if not isinstance(avg, torch.Tensor) or avg.dtype != torch.float32 or avg.device != p.device or avg.numel() != p.numel() or not avg.is_contiguous():
+        raise L.BubbleformerHipError(f"{who}: avg must be a contiguous torch.float32 tensor of {p.numel()} elements on {p.device}")
+    return _p(avg), float(avg_weight)
+
+
+def _clip_or_inf(clip_value: Optional[float]) -> float:
+    return float("inf") if clip_value is None else float(clip_value)
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
-          grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None) -> None:
+          grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None,
+          avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
     """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140).  coef: one fp32 on the device
     that multiplies grad_scale (grad_norm_'s out[1:]); clip_value: the scaled gradient is clamped to +-clip_value first
-    (torch.nn.utils.clip_grad_value_).  Both None: the host-scale kernel."""
+    (torch.nn.utils.clip_grad_value_).  Both None: the host-scale kernel.  avg / avg_weight (together or not at all): the same launch
+    also moves the fp32 buffer ``avg`` (p's numel and device) towards the new p, avg += avg_weight * (p - avg) with 0 < avg_weight <= 1
+    (1 copies p); p and m come out bit for bit as without them (weight_average_ is that update alone)."""
     _require_gpu(p)
-    if coef is None and clip_value is None:
+    av = _avg_args(avg, avg_weight, p, "lion_")
+    if av is not None:
+        L.check(L.lib().bf_lion_avg(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
+                                    float(grad_scale), _coef_ptr(coef, p, "lion_"), _clip_or_inf(clip_value), *av, _stream()), "bf_lion_avg")
+    elif coef is None and clip_value is None:
         L.check(L.lib().bf_lion(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
                                 float(grad_scale), _stream()), "bf_lion")
     else:
@@ -1373,10 +1395,16 @@ def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0
 
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
            eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
-           clip_value: Optional[float] = None) -> None:
-    """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value: see lion_."""
+           clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
+    """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value / avg /
+    avg_weight: see lion_."""
     _require_gpu(p)
-    if coef is None and clip_value is None:
+    av = _avg_args(avg, avg_weight, p, "adamw_")
+    if av is not None:
+        L.check(L.lib().bf_adamw_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adamw_"), _clip_or_inf(clip_value), *av,
+                                     _stream()), "bf_adamw_avg")
+    elif coef is None and clip_value is None:
         L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                  float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
     else:
@@ -1388,12 +1416,17 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
 
 def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
           eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
-          clip_value: Optional[float] = None) -> None:
+          clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
     """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
     weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay.  coef / clip_value: see lion_
-    (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step())."""
+    (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step()).  avg / avg_weight: see lion_."""
     _require_gpu(p)
-    if coef is None and clip_value is None:
+    av = _avg_args(avg, avg_weight, p, "adam_")
+    if av is not None:
+        L.check(L.lib().bf_adam_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                    float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"), _clip_or_inf(clip_value), *av,
+                                    _stream()), "bf_adam_avg")
+    elif coef is None and clip_value is None:
         L.check(L.lib().bf_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                 float(weight_decay), float(grad_scale), _stream()), "bf_adam")
     else:
@@ -1401,6 +1434,31 @@ def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, st
                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"),
                                     float("inf") if clip_value is None else float(clip_value), _stream()), "bf_adam_dev")
     _weights_changed()
+
+
+def _flat_pair(a: torch.Tensor, b: torch.Tensor, who: str) -> None:
+    _require_gpu(a)
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != a.device or t.numel() != a.numel():
+            raise L.BubbleformerHipError(f"{who}: both buffers must be contiguous torch.float32 tensors of the same numel on one GPU")
+
+
+def weight_average_(avg: torch.Tensor, p: torch.Tensor, w: float) -> torch.Tensor:
+    """avg += w * (p - avg) over flat fp32 buffers, 0 < w <= 1 (1 copies p): the averaged-weights update of the optimizers' avg= on its
+    own, with the same bits (csrc/optim_kernels.h: avg_lerp)."""
+    _flat_pair(avg, p, "weight_average_")
+    L.check(L.lib().bf_weight_average(_p(avg), _p(p), avg.numel(), float(w), _stream()), "bf_weight_average")
+    return avg
+
+
+def swap_buffers_(a: torch.Tensor, b: torch.Tensor, parameters: bool = False) -> None:
+    """Exchanges the contents of two flat fp32 buffers exactly, in one launch (16-byte aligned, same numel, not overlapping).
+    parameters=True: one of them backs model parameters, which this writes behind torch's version counters -- the prepared inference
+    weights are marked stale (TrainStep.averaged_weights)."""
+    _flat_pair(a, b, "swap_buffers_")
+    L.check(L.lib().bf_swap_buffers(_p(a), _p(b), a.numel(), _stream()), "bf_swap_buffers")
+    if parameters:
+        _weights_changed()
 
 
 # ------------------------------------------------------------------------------------------------ ModernUnet (conv.hip)

@@ -10,7 +10,8 @@
 * ``TrainStep``    -- forward (+ fused relative-L2 loss, or a caller's criterion on the prediction) -> backward -> bucket wait ->
                       [gradient norm and clip coefficient, on the device] -> fused AdamW / Adam / Lion; with
                       ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only; with
-                      ``unroll_steps=k`` the model is run through k of its own predictions with a loss on each (``unroll_plan``).
+                      ``unroll_steps=k`` the model is run through k of its own predictions with a loss on each (``unroll_plan``);
+                      with ``weight_average=`` the optimizer kernel also keeps an averaged copy of the weights (EMA / SWA).
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
@@ -269,14 +270,25 @@ class TrainStep:
     and is in every checkpoint, so a resumed run continues the sequence.  Every micro-batch of an accumulate_grad_batches group draws
     under the same step_no: two occurrences of one sample inside one optimizer step get the same noise (NoiseSpec).  ``relative=True``
     needs ``field_std`` (one deviation per input field, DeviceClipStore.field_std(); fit resolves it).  None, or a spec whose std is all
-    zero, is off: the step launches exactly what it launches without the argument."""
+    zero, is off: the step launches exactly what it launches without the argument.
+    weight_average = utils.averaging.AverageSpec: an averaged copy of the flat parameter buffer, ``self.avg`` (fp32, 4 bytes per parameter),
+    kept by the optimizer kernel itself -- ``spec.weight(step_no, n_averaged)`` is handed to the fused optimizer as ``avg_weight``, so an
+    update costs one more read and write of one buffer and no launch; a step the schedule skips runs the plain kernel, and micro-batches
+    that do not step never touch the average.  ``n_averaged`` counts the updates past ``start_step``.  The copy starts as the (rank 0)
+    parameters; every rank then computes the same average from the same parameters, so the feature launches no collective.
+    ``averaged_state_dict()`` exports it, ``averaged_weights()`` puts it behind the model's parameters for a ``with`` block (validation,
+    evaluate_rollouts), checkpoints carry it (utils/checkpoint.py).  Module buffers (BatchNorm running statistics) are not averaged.
+    None: no buffer, and the optimizer calls are the ones made without the argument."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1, unroll_steps: int = 1, unroll_weights=None,
-                 unroll_backprop: bool = True, input_noise=None, field_std=None):
+                 unroll_backprop: bool = True, input_noise=None, field_std=None, weight_average=None):
         from . import ops
+        from .utils.averaging import AverageSpec
         from .utils.noise import NoiseSpec
+        if weight_average is not None and not isinstance(weight_average, AverageSpec):
+            raise ValueError(f"weight_average {weight_average!r} must be None or a utils.averaging.AverageSpec")
         if input_noise is not None and not isinstance(input_noise, NoiseSpec):
             raise ValueError(f"input_noise {input_noise!r} must be None or a utils.noise.NoiseSpec")
         if input_noise is not None and input_noise.active and input_noise.relative and field_std is None:
@@ -328,7 +340,13 @@ class TrainStep:
         self._unroll_w = None
         if self.unroll_steps > 1:
             self._unroll_w = torch.tensor(self.unroll_weights, dtype=torch.float32, device=self.flat.flat.device)
+        self.weight_average = weight_average
+        self.avg = None           # the averaged copy of flat.flat; taken below, from the parameters every rank starts with
+        self.n_averaged = 0       # updates of the average past spec.start_step
+        self._swapped = False     # inside averaged_weights(): flat.flat holds the average and avg the live weights
         self.sync_from_rank0()
+        if weight_average is not None:
+            self.avg = self.flat.flat.clone()
 
     @staticmethod
     def _check_unroll_fields(cin: int, cout: int) -> None:
@@ -342,12 +360,15 @@ class TrainStep:
         averaged afterwards, so a rank built from another seed would otherwise diverge silently."""
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
             return
-        for t in (self.flat.flat, self.m, self.v):
+        avg = getattr(self, "avg", None)      # the averaged weights and their update count travel too, once the step holds them
+        for t in (self.flat.flat, self.m, self.v, avg):
             if t is not None:
                 dist.broadcast(t, src=0)
-        n = torch.tensor([self.step_no], dtype=torch.int64, device=self.flat.flat.device)
+        n = torch.tensor([self.step_no] + ([self.n_averaged] if avg is not None else []), dtype=torch.int64, device=self.flat.flat.device)
         dist.broadcast(n, src=0)
-        self.step_no = int(n)
+        self.step_no = int(n[0])
+        if avg is not None:
+            self.n_averaged = int(n[1])
         from . import ops
         ops._weights_changed()           # the broadcast wrote the flat buffer behind the parameters' version counters: prepared inference weights are stale
 
@@ -369,6 +390,7 @@ class TrainStep:
         return self.ops.clip_noise(clip.detach().contiguous(), self._noise_sigma, ids, self.step_no, pass_index, spec.seed)
 
     def __call__(self, x, fluid, target, sample_ids=None) -> torch.Tensor:
+        self._refuse_while_swapped("a training step")
         final = self.micro + 1 >= self.accumulate_grad_batches
         ids = self._noise_ids(x, sample_ids)
         if self.micro == 0:
@@ -393,6 +415,7 @@ class TrainStep:
     def finish_accumulation(self) -> bool:
         """Step on the gradient of a partial group (an epoch's last batches), with the full group's 1/(world*k); nothing to do when no
         gradient is pending.  The pending micro-batches ran without collectives, so every bucket is exchanged here.  -> stepped or not"""
+        self._refuse_while_swapped("finish_accumulation()")
         if self.micro == 0:
             return False
         self.reducer.begin_step()
@@ -412,6 +435,12 @@ class TrainStep:
             clip = {"coef": self._coef}
         elif self.clip_val is not None:
             clip = {"clip_value": self.clip_val}
+        if self.weight_average is not None:
+            w = self.weight_average.weight(self.step_no, self.n_averaged)
+            if w is not None:
+                clip.update(avg=self.avg, avg_weight=w)
+                if self.weight_average.counts(self.step_no):
+                    self.n_averaged += 1
         if self.optimizer == "adamw":
             self.ops.adamw_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale, **clip)
         elif self.optimizer == "adam":
@@ -420,6 +449,47 @@ class TrainStep:
             self.ops.lion_(self.flat.flat, self.flat.grad, self.m, lr, self.betas, self.wd, gscale, **clip)
         if self.scheduler is not None:
             self.scheduler.step()
+
+    # ---------------------------------------------------------------------------------------- the averaged weights
+    def _refuse_while_swapped(self, what: str) -> None:
+        if self._swapped:
+            raise RuntimeError(f"{what} inside averaged_weights(): the model's parameters are the averaged weights until the block ends")
+
+    def _require_average(self, what: str) -> None:
+        if self.avg is None:
+            raise RuntimeError(f"{what}: this TrainStep keeps no average (weight_average=None)")
+
+    def averaged_state_dict(self):
+        """The averaged weights in the reference's ``state_dict`` layout ("model.<name>" keys, CPU clones; utils.checkpoint.
+        to_reference_state_dict): every trained parameter is read from ``avg`` at its flat offset, everything else -- frozen parameters,
+        module buffers such as BatchNorm running statistics -- is the live value."""
+        from .utils.checkpoint import PREFIX, to_reference_state_dict
+        self._require_average("averaged_state_dict()")
+        sd = to_reference_state_dict(self.model)
+        avg = self.flat.flat if self._swapped else self.avg
+        at = {p.data_ptr(): o for p, o in zip(self.flat.params, self.flat.offsets)}
+        for name, p in self.model.named_parameters():
+            o = at.get(p.data_ptr())
+            if o is not None and PREFIX + name in sd:
+                sd[PREFIX + name] = avg[o:o + p.numel()].view(p.shape).detach().to("cpu", copy=True)
+        return sd
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with step.averaged_weights():`` -- inside, the model's parameters (views of the flat buffer) ARE the averaged weights: one
+        exchange of ``flat`` and ``avg`` on entry (ops.swap_buffers_, which also marks the prepared inference weights stale) and one on
+        exit, also when the block raises.  For validation, evaluate_rollouts and anything else that runs the model.  A training step,
+        finish_accumulation() or a second averaged_weights() inside the block raises RuntimeError.  Module buffers are left alone: SWA of
+        a model with BatchNorm normally recomputes the running statistics for the averaged weights afterwards, which is not done here."""
+        self._require_average("averaged_weights()")
+        self._refuse_while_swapped("averaged_weights()")
+        self.ops.swap_buffers_(self.flat.flat, self.avg, parameters=True)
+        self._swapped = True
+        try:
+            yield self.model
+        finally:
+            self.ops.swap_buffers_(self.flat.flat, self.avg, parameters=True)
+            self._swapped = False
 
     def _fwd_bwd(self, x, fluid, target):
         if self.criterion is None:

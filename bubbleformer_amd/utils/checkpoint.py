@@ -6,7 +6,9 @@
   "global_step"       optimizer steps taken
 plus, for resuming the native training step, "optimizer_states" / "lr_schedulers" entries holding the flat AdamW / Adam / Lion
 moments and the scheduler position (Lightning stores its torch.optim state dicts under those keys; ours are flat buffers, so a
-checkpoint written here resumes here, while its "state_dict" loads anywhere the reference's does).
+checkpoint written here resumes here, while its "state_dict" loads anywhere the reference's does).  A training step that keeps an
+averaged copy of the weights (TrainStep(weight_average=...)) adds "weight_average": its spec, the update count and the flat average;
+`save_checkpoint(averaged=True)` instead writes the averaged weights AS the "state_dict", with no training state: the file to release.
 
 `load_checkpoint` also resumes from a file the reference's Lightning run wrote (e.g. the pre-emption `hpc_ckpt_*.ckpt` files of
 scripts/train.py): its `optimizer_states[0]` is a torch.optim state dict, which `flat_state_from_torch_optim` puts into the flat
@@ -38,18 +40,27 @@ def from_reference_state_dict(sd) -> "OrderedDict[str, torch.Tensor]":
 
 
 def save_checkpoint(path: str, model: torch.nn.Module, hyper_parameters: Optional[dict] = None, normalization_constants=None,
-                    train_step=None, global_step: Optional[int] = None, epoch: Optional[int] = None) -> None:
+                    train_step=None, global_step: Optional[int] = None, epoch: Optional[int] = None, averaged: bool = False) -> None:
     """One torch.save into `path + ".tmp"`, then os.replace: a kill between two writes (the reference's use case is SLURM pre-emption,
-    scripts/train.py:36-67) can never leave a half-written or epoch-less file behind."""
+    scripts/train.py:36-67) can never leave a half-written or epoch-less file behind.  A `train_step` that averages its weights adds
+    "weight_average" = {kind, decay, warmup, start_step, every, n_averaged, avg (the flat buffer, on the CPU)}.  averaged=True: the
+    "state_dict" is `train_step.averaged_state_dict()` and no optimizer, scheduler or average state is written -- what the reference's
+    `load_state_dict` (scripts/inference.py:205-226) should be handed."""
     hp = dict(hyper_parameters or {})
     if normalization_constants is not None:
         hp["normalization_constants"] = normalization_constants
-    ckpt = {"state_dict": to_reference_state_dict(model), "hyper_parameters": hp,
+    if averaged and (train_step is None or getattr(train_step, "avg", None) is None):
+        raise ValueError("save_checkpoint(averaged=True) needs a train_step that keeps an average (TrainStep(weight_average=...))")
+    ckpt = {"state_dict": train_step.averaged_state_dict() if averaged else to_reference_state_dict(model), "hyper_parameters": hp,
             "global_step": int(global_step if global_step is not None else (train_step.step_no if train_step is not None else 0))}
-    if train_step is not None:
+    if train_step is not None and not averaged:
         ckpt["optimizer_states"] = [{"name": train_step.optimizer, "step": train_step.step_no, "m": train_step.m.detach().cpu(),
                                      "v": None if train_step.v is None else train_step.v.detach().cpu()}]
         ckpt["lr_schedulers"] = [train_step.scheduler.state_dict()] if train_step.scheduler is not None else []
+        if getattr(train_step, "avg", None) is not None:
+            spec = train_step.weight_average
+            ckpt["weight_average"] = {"kind": spec.kind, "decay": spec.decay, "warmup": spec.warmup, "start_step": spec.start_step,
+                                      "every": spec.every, "n_averaged": int(train_step.n_averaged), "avg": train_step.avg.detach().cpu()}
     if epoch is not None:
         ckpt["epoch"] = int(epoch)
     tmp = path + ".tmp"
@@ -180,7 +191,9 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
     state dict in optimizer_states[0] (flat_state_from_torch_optim) and a CosineWarmupLR(SequentialLR) state in lr_schedulers[0].
     A reference state brings its hyperparameters along, as Optimizer.load_state_dict does under a Lightning resume: betas, eps and
     weight_decay of param_groups[0] become the training step's, and a native CosineWarmupLR takes the reference schedule's base lr,
-    warm-up, max_iters, eta_min and position.  Lightning's loop state ("loops") is not restored.  Unpickling a real Lightning file
+    warm-up, max_iters, eta_min and position.  Lightning's loop state ("loops") is not restored.  A training step that averages its weights
+    takes "weight_average" (the flat average and its update count; a numel mismatch is a ValueError) or, from a file without it, starts
+    its average from the loaded parameters with a count of 0; a step that does not average ignores the key.  Unpickling a real Lightning file
     whose hyper_parameters hold OmegaConf objects needs the `omegaconf` package (not a dependency of this project)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
     sd = from_reference_state_dict(ckpt["state_dict"])
@@ -190,6 +203,10 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
     if missing or unexpected:
         raise KeyError(f"checkpoint / model mismatch: missing {missing[:3]}..., unexpected {unexpected[:3]}...")
     reference = train_step is not None and bool(ckpt.get("optimizer_states")) and is_torch_optim_state(ckpt["optimizer_states"][0])
+    averages = train_step is not None and getattr(train_step, "avg", None) is not None
+    wa = ckpt.get("weight_average") if averages else None
+    if wa is not None and wa["avg"].numel() != train_step.avg.numel():
+        raise ValueError(f"checkpoint average holds {wa['avg'].numel()} elements, the training step's flat buffer {train_step.avg.numel()}")
     if reference:
         _load_reference_optimizer(ckpt, model, train_step)          # refuses before any weight is written
     with torch.no_grad():
@@ -205,6 +222,13 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
             train_step.v.copy_(st["v"])
         if train_step.scheduler is not None and ckpt.get("lr_schedulers"):
             train_step.scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+    if averages:
+        if wa is not None:
+            train_step.avg.copy_(wa["avg"])
+            train_step.n_averaged = int(wa["n_averaged"])
+        else:                                 # an older file, or the reference's: the average starts from the loaded weights
+            train_step.avg.copy_(train_step.flat.flat)
+            train_step.n_averaged = 0
     from .. import ops
     ops._weights_changed()                    # prepared inference weights (ops.trunk_eval) are re-made from the loaded parameters
     if train_step is not None and hasattr(train_step, "sync_from_rank0"):

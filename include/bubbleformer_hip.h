@@ -590,6 +590,20 @@ int bf_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, int ste
                 float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream);
 int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
                 const float* coef_dev, float clip_value, bf_stream_t stream);
+/* The optimizers with an averaged copy of the weights (EMA / SWA; no reference program).  bf_*_avg take the arguments of the matching
+ * _dev entry and serve all three scale modes (coef_dev NULL and clip_value +inf: the host-scale kernel body); p, m and v come out bit
+ * for bit as from the plain entry.  In the same launch avg[i] (fp32, n elements, 16-byte aligned, required) moves towards the new p[i]:
+ *   avg[i] = avg_weight == 1 ? p[i] : fma(avg_weight, p[i] - avg[i], avg[i])      two roundings; 0 < avg_weight <= 1
+ * so zero padding stays zero and a NaN in p reaches avg.  bf_weight_average is that update alone (same bits); bf_swap_buffers exchanges
+ * two non-overlapping 16-byte aligned buffers exactly, in one launch. */
+int bf_adamw_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                 float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
+int bf_adam_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
+int bf_lion_avg(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
+                const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
+int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream);
+int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream);
 
 /* ---------------------------------------------------------------- stage-level entry points (what the nn.Modules call) */
 

@@ -7,7 +7,11 @@ padded to 64 elements).  Each step reads p, g, m, v and writes p, m, v: 28 bytes
 `--reps` back-to-back launches timed by device events; the per-launch time is the median over rounds.  Reported: ms per launch, GB/s,
 and the share of the 8.0 TB/s HBM peak (MI355X_MICROARCH: about 6.3 TB/s is achievable by a float4 copy).
 
-Usage: python tools/adam_bench.py [--rounds R] [--reps K]"""
+--average times the averaged-weights step (EMA / SWA) instead, per optimizer (AdamW, Adam, Lion) under the same
+protocol: (a) the unchanged plain entry, (b) the _avg entry, which also reads and writes the average (36 bytes per element; Lion 28
+against 20), (c) the plain entry followed by bf_weight_average (40; Lion 32, and a second launch).
+
+Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average]"""
 import argparse
 import json
 import os
@@ -41,16 +45,8 @@ def flat_sizes(cfg, align=64):
     return p, n
 
 
-def time_kernels(n, rounds, reps):
-    g = torch.Generator(device="cuda").manual_seed(0)
-    p = torch.randn(n, device="cuda", generator=g) * 0.02
-    grad = torch.randn(n, device="cuda", generator=g) * 1e-3
-    m, v = torch.zeros_like(p), torch.zeros_like(p)
-    h, st = L.lib(), _stream()
-    calls = {
-        "adam": lambda: h.bf_adam(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-5, 1.0, st),
-        "adamw": lambda: h.bf_adamw(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-2, 1.0, st),
-    }
+def rounds_of(calls, rounds, reps):
+    """ms per launch of every call, one list entry per round; the calls alternate inside a round."""
     for f in calls.values():                         # warm-up: code objects loaded, buffers touched
         for _ in range(5):
             L.check(f(), "warm-up")
@@ -65,14 +61,59 @@ def time_kernels(n, rounds, reps):
             e1.record()
             e1.synchronize()
             ms[k].append(e0.elapsed_time(e1) / reps)
+    return ms
+
+
+def summary(t, n, bytes_per_element):
+    med = statistics.median(t)
+    gbs = bytes_per_element * n / (med * 1e-3) / 1e9
+    return {"ms": round(med, 4), "ms_min": round(min(t), 4), "ms_max": round(max(t), 4), "GB_s": round(gbs, 1),
+            "hbm_peak_share": round(gbs * 1e9 / HBM_PEAK, 3)}
+
+
+def time_kernels(n, rounds, reps):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    p = torch.randn(n, device="cuda", generator=g) * 0.02
+    grad = torch.randn(n, device="cuda", generator=g) * 1e-3
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    h, st = L.lib(), _stream()
+    calls = {
+        "adam": lambda: h.bf_adam(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-5, 1.0, st),
+        "adamw": lambda: h.bf_adamw(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-2, 1.0, st),
+    }
+    ms = rounds_of(calls, rounds, reps)
     assert torch.isfinite(p).all()
-    out = {}
-    for k, t in ms.items():
-        med = statistics.median(t)
-        gbs = BYTES_PER_ELEMENT * n / (med * 1e-3) / 1e9
-        out[k] = {"ms": round(med, 4), "ms_min": round(min(t), 4), "ms_max": round(max(t), 4), "GB_s": round(gbs, 1),
-                  "hbm_peak_share": round(gbs * 1e9 / HBM_PEAK, 3)}
+    out = {k: summary(t, n, BYTES_PER_ELEMENT) for k, t in ms.items()}
     out["adam_over_adamw"] = round(out["adam"]["ms"] / out["adamw"]["ms"], 3)
+    return out
+
+
+def time_average(n, rounds, reps):
+    """Per optimizer: (a) "plain", (b) "fused" = the _avg entry, (c) "separate" = plain + bf_weight_average; bytes per element are what
+    each moves (a: 28 / Lion 20; b: + 8; c: + 12)."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    p = torch.randn(n, device="cuda", generator=g) * 0.02
+    grad = torch.randn(n, device="cuda", generator=g) * 1e-3
+    m, v, a = torch.zeros_like(p), torch.zeros_like(p), p.clone()
+    h, st, inf, w = L.lib(), _stream(), float("inf"), 1e-3
+    adam_args = lambda wd: (_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, wd, 1.0)      # noqa: E731
+    lion_args = (_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, 0.1, 1.0)
+    plain = {"adamw": lambda: h.bf_adamw(*adam_args(1e-2), st), "adam": lambda: h.bf_adam(*adam_args(1e-5), st), "lion": lambda: h.bf_lion(*lion_args, st)}
+    fused = {"adamw": lambda: h.bf_adamw_avg(*adam_args(1e-2), None, inf, _p(a), w, st), "adam": lambda: h.bf_adam_avg(*adam_args(1e-5), None, inf, _p(a), w, st),
+             "lion": lambda: h.bf_lion_avg(*lion_args, None, inf, _p(a), w, st)}
+    out = {}
+    for opt in ("adamw", "adam", "lion"):
+        def separate(f=plain[opt]):
+            f()
+            return h.bf_weight_average(_p(a), _p(p), n, w, st)
+        ms = rounds_of({"plain": plain[opt], "fused": fused[opt], "separate": separate}, rounds, reps)
+        base = 20 if opt == "lion" else 28
+        res = {"plain": summary(ms["plain"], n, base), "fused": summary(ms["fused"], n, base + 8), "separate": summary(ms["separate"], n, base + 12)}
+        res["fused_over_plain"] = round(res["fused"]["ms"] / res["plain"]["ms"], 3)
+        res["separate_over_plain"] = round(res["separate"]["ms"] / res["plain"]["ms"], 3)
+        res["expected_by_bytes"] = {"fused_over_plain": round((base + 8) / base, 3), "separate_over_plain": round((base + 12) / base, 3)}
+        out[opt] = res
+    assert torch.isfinite(p).all() and torch.isfinite(a).all()
     return out
 
 
@@ -80,12 +121,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--average", action="store_true", help="time the averaged-weights step: plain, fused _avg entry, plain + bf_weight_average")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/adam_bench.py times GPU kernels: no GPU found"
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "bytes_per_element": BYTES_PER_ELEMENT}
     for name, cfg in MODELS.items():
         params, n = flat_sizes(cfg)
-        res[name] = dict(parameters=params, flat_elements=n, **time_kernels(n, args.rounds, args.reps))
+        res[name] = dict(parameters=params, flat_elements=n, **(time_average if args.average else time_kernels)(n, args.rounds, args.reps))
         torch.cuda.empty_cache()
     print(json.dumps(res))
 

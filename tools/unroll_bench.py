@@ -12,12 +12,15 @@ With ``--input-noise STD`` every version named is timed a second time as ``<vers
 ``input_noise=NoiseSpec(STD)`` (seeded Gaussian noise on the input clip and on every fed-back prediction, one bf_clip_noise launch per
 pass, sample ids resident on the device), and "clip_noise" reports the kernel alone on the input clip: microseconds per launch by
 device events over 200 back-to-back launches and the rate of its 2 x clip bytes.
+With ``--weight-average`` every version named is also timed as ``<version>_avg``: the same step with
+``weight_average=AverageSpec("ema", 0.999)`` (the averaged copy of the weights kept inside the optimizer kernel), and "avg_cost_us" is
+its median minus the plain version's.
 After a warm-up of every version they alternate in rounds of `--reps` back-to-back optimizer steps timed by device events; reported per
 version: the median over rounds of the time per step with the minimum and the maximum, and for the unrolled ones the ratio to k x the
 k1 step.  "peak_memory_GB" is the process's `max_memory_allocated`: with `--versions <one>` it is that version's (every version named
 is resident at once).  "fused_not_slower" holds when the fused k = 2 step's median is at most the composed one's.
 
-Usage: python tools/unroll_bench.py [--rounds R] [--reps K] [--batch B] [--versions k1,k3_push,...] [--input-noise STD]"""
+Usage: python tools/unroll_bench.py [--rounds R] [--reps K] [--batch B] [--versions k1,k3_push,...] [--input-noise STD] [--weight-average]"""
 import argparse
 import json
 import os
@@ -43,6 +46,13 @@ def clip(B, seed, dev):
     return x
 
 
+def base_version(name):
+    for suffix in ("_noise", "_avg"):
+        if name.endswith(suffix):
+            return name[:-len(suffix)]
+    return name
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -51,6 +61,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--versions", default=",".join(VERSIONS))
     ap.add_argument("--input-noise", type=float, default=None, metavar="STD")
+    ap.add_argument("--weight-average", action="store_true", help="also time every version with an EMA of the weights kept by the optimizer kernel")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("unroll_bench.py times the step on the GPU: no GPU here, nothing measured")
@@ -67,14 +78,18 @@ def main():
         from bubbleformer_amd.utils import NoiseSpec, add_gaussian_noise
         names = [n + suffix for n in names for suffix in ("", "_noise")]
         ids = torch.arange(a.batch, device=dev)
+    if a.weight_average:
+        from bubbleformer_amd.utils.averaging import AverageSpec
+        names = names + [n + "_avg" for n in a.versions.split(",")]
     for name in names:
-        noisy = name.endswith("_noise")
-        k, backprop, composed = VERSIONS[name[:-len("_noise")] if noisy else name]
+        noisy, averaged = name.endswith("_noise"), name.endswith("_avg")
+        k, backprop, composed = VERSIONS[base_version(name)]
         torch.manual_seed(0)
         model = get_model("filmavit", time_window=T, drop_path=DROP_PATH, compute_dtype=torch.bfloat16, **CFG).to(dev).train()
         crit = LpLoss(d=2, p=2, reduce_dims=[0, 1, 2], reductions=["mean", "mean", "sum"]) if composed else None
         step = TrainStep(model, lr=2.5e-4, weight_decay=1e-2, optimizer="adamw", criterion=crit, unroll_steps=k, unroll_backprop=backprop,
-                         input_noise=NoiseSpec(a.input_noise, seed=1) if noisy else None)
+                         input_noise=NoiseSpec(a.input_noise, seed=1) if noisy else None,
+                         weight_average=AverageSpec("ema", 0.999) if averaged else None)
         target = ys[0] if k == 1 else ys[:k]
         steps[name] = (lambda s=step, t=target: s(x, fluid, t, sample_ids=ids)) if noisy else (lambda s=step, t=target: s(x, fluid, t))
     for f in steps.values():
@@ -109,9 +124,12 @@ def main():
         e1.synchronize()
         us = 1e3 * e0.elapsed_time(e1) / launches
         out["clip_noise"] = {"us_per_launch": round(us, 2), "bytes": 2 * x.numel() * 4, "GB_per_s": round(2 * x.numel() * 4 / us / 1e3, 1)}
+    if a.weight_average:
+        for n in a.versions.split(","):
+            out[n + "_avg"]["avg_cost_us"] = round(1e3 * (out[n + "_avg"]["ms"] - out[n]["ms"]), 1)
     if "k1" in ms:
         for n in ms:
-            k = VERSIONS[n[:-len("_noise")] if n.endswith("_noise") else n][0]
+            k = VERSIONS[base_version(n)][0]
             if k > 1:
                 out[n]["ratio_to_k_plain_steps"] = round(out[n]["ms"] / (k * out["k1"]["ms"]), 4)
     if "k2" in ms and "k2_composed" in ms:
