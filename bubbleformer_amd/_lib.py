@@ -81,6 +81,25 @@ class ConvGeo(C.Structure):
 BF_CONV_PRO_NONE, BF_CONV_PRO_AFFINE_GELU, BF_CONV_PRO_GELU = 0, 1, 2
 
 
+class RolloutStep(C.Structure):
+    """bf_rollout_step: one rollout step's prediction, store, counters and field table (read during the call only)."""
+    _fields_ = [("pred", fp), ("frames", fp), ("field_stride", i64), ("total_frames", i64), ("first", vp), ("step", vp), ("field", vp), ("diff", fp),
+                ("div", fp)] + [(n, i32) for n in ("nfields", "B", "T", "C", "H", "W", "Ho", "Wo", "steps", "reserved")]
+
+
+class CensusRows(C.Structure):
+    _fields_ = [(n, vp) for n in ("count", "cells", "attached", "area")]
+
+
+class LinkRows(C.Structure):
+    _fields_ = [(n, vp) for n in ("successor", "n_successors", "predecessor", "n_predecessors", "departure_area", "events")]
+
+
+class ErrorRows(C.Structure):
+    _fields_ = [(n, vp) for n in ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error",
+                                  "spectrum_pred", "spectrum_target")]
+
+
 class RenderTile(C.Structure):
     """bf_render_tile: what one slot of an image shows (bf_render_tiles)."""
     _fields_ = [("a", fp), ("b", fp), ("mask", fp), ("frame_stride", i64), ("slot_stride", i64), ("mask_frame_stride", i64), ("mask_slot_stride", i64),
@@ -192,28 +211,22 @@ SIGNATURES = {
                                         fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_clip_noise": (C.c_int, [fp, fp, fp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_rollout_score_ws_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bf_rollout_score": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "bf_rollout_heatflux": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, fp, f32, f32, f32, f32, fp, fp, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_rollout_score": (C.c_int, [P(RolloutStep), C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, vp]),
+    "bf_rollout_heatflux": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, fp, f32, f32, f32, f32, fp, fp, vp]),
     "bf_kde_kl_ws_doubles": (i64, [C.c_int, i64, i64, C.c_int]),
     "bf_kde_kl": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, vp]),
     "bf_bubble_census_lds_cells": (i64, []),
     "bf_bubble_census_ws_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
     "bf_bubble_census": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, fp, vp, vp, vp, i64, vp]),
-    "bf_rollout_bubbles": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
-                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "bf_rollout_bubbles_labelled": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                              i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_rollout_bubbles": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, P(CensusRows), P(CensusRows), vp, vp, i64, vp]),
     "bf_bubble_links_lds_entries": (i64, []),
     "bf_bubble_links_ws_bytes": (i64, [i64, C.c_int]),
-    "bf_bubble_links": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "bf_bubble_links": (C.c_int, [vp, P(CensusRows), i64, C.c_int, C.c_int, C.c_int, C.c_int, P(LinkRows), vp, i64, vp]),
     "bf_bubble_track_ids": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp]),
-    "bf_rollout_bubble_links": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int] + [vp] * 20 + [i64] + [C.c_int] * 8 + [vp]),
+    "bf_rollout_bubble_links": (C.c_int, [P(RolloutStep), C.c_int, vp, P(CensusRows), P(CensusRows), P(LinkRows), P(LinkRows), vp, i64, vp]),
     "bf_field_errors_ws_bytes": (i64, [i64, C.c_int, C.c_int]),
-    "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp, fp, fp, vp, i64, vp]),
-    "bf_rollout_errors": (C.c_int, [fp, fp, i64, i64, C.c_int, vp, vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, vp, fp, fp,
-                                    fp, fp, vp, i64] + [C.c_int] * 8 + [vp]),
+    "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),
+    "bf_rollout_errors": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),
     "bf_render_ranges_ws_doubles": (i64, []),
     "bf_render_ranges": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "bf_render_tiles": (C.c_int, [P(RenderTile), C.c_int, P(RenderGeom), i64, vp, vp, vp, vp]),

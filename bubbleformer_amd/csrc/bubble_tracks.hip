@@ -257,6 +257,10 @@ __global__ void __launch_bounds__(NT) bubble_track_ids_kernel(TrackArgs a) {
     if (tid == 0) a.n_tracks[seq] = next;
 }
 
+// a side's link rows: all six present; as the kernels' PairOut
+bool all_rows(const bf_link_rows* r) { return r && r->successor && r->n_successors && r->predecessor && r->n_predecessors && r->departure_area && r->events; }
+PairOut pair_out(const bf_link_rows* r) { return PairOut{r->successor, r->n_successors, r->predecessor, r->n_predecessors, r->departure_area, r->events}; }
+
 long links_slot(int mb) { return (long)mb * mb > LINKS_LDS_ENTRIES ? 4L * mb * mb : 0; }
 size_t links_lds_bytes(int mb) { return (size_t)std::min((long)mb * mb, (long)LINKS_LDS_ENTRIES) * 4; }
 
@@ -278,21 +282,18 @@ extern "C" int64_t bf_bubble_links_ws_bytes(int64_t pairs, int max_bubbles) {
     return 16 + pairs * links_slot(max_bubbles);
 }
 
-extern "C" int bf_bubble_links(const int32_t* labels, const int32_t* count, const int32_t* attached, const int32_t* area, int64_t sequences, int T, int H,
-                               int W, int max_bubbles, int32_t* successor, int32_t* n_successors, int32_t* predecessor, int32_t* n_predecessors,
-                               int32_t* departure_area, int32_t* events, void* ws, int64_t ws_bytes, bf_stream_t stream) {
+extern "C" int bf_bubble_links(const int32_t* labels, const bf_census_rows* census, int64_t sequences, int T, int H, int W, int max_bubbles,
+                               const bf_link_rows* links, void* ws, int64_t ws_bytes, bf_stream_t stream) {
     BF_REQUIRE(sequences > 0 && T > 0 && H > 0 && W > 0 && max_bubbles > 0, "bf_bubble_links: bad sizes");
     BF_REQUIRE(max_bubbles <= LINKS_MAX_BUBBLES, "bf_bubble_links: at most 2^15 records per frame");
     BF_REQUIRE((int64_t)H * W <= LINKS_MAX_CELLS, "bf_bubble_links: a frame may have at most 2^24 cells");
     if (T == 1) return 0;                                                          // no pair: nothing to launch
     const int64_t pairs = sequences * (T - 1);
     BF_REQUIRE(pairs <= 0x7fffffff, "bf_bubble_links: bad sizes");
-    BF_REQUIRE(labels && count && attached && area && successor && n_successors && predecessor && n_predecessors && departure_area && events && ws,
-               "bf_bubble_links: null pointer");
+    BF_REQUIRE(labels && census && census->count && census->attached && census->area && all_rows(links) && ws, "bf_bubble_links: null pointer");
     BF_REQUIRE(ws_bytes >= bf_bubble_links_ws_bytes(pairs, max_bubbles), "bf_bubble_links: workspace smaller than bf_bubble_links_ws_bytes");
     BF_REQUIRE((uintptr_t)ws % 16 == 0, "bf_bubble_links: the workspace must be 16-byte aligned");
-    const LinksArgs a{labels, count, attached, area, T, H * W, max_bubbles, PairOut{successor, n_successors, predecessor, n_predecessors, departure_area, events},
-                      (char*)ws, links_slot(max_bubbles)};
+    const LinksArgs a{labels, census->count, census->attached, census->area, T, H * W, max_bubbles, pair_out(links), (char*)ws, links_slot(max_bubbles)};
     static BfPerDeviceOnce once;
     if (const int rc = allow_lds(bubble_links_kernel, once)) return rc;
     hipLaunchKernelGGL(bubble_links_kernel, dim3((unsigned)pairs), dim3(NT), links_lds_bytes(max_bubbles), (hipStream_t)stream, a);
@@ -311,34 +312,26 @@ extern "C" int bf_bubble_track_ids(const int32_t* count, const int32_t* successo
     return 0;
 }
 
-extern "C" int bf_rollout_bubble_links(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                       const int32_t* step, const int32_t* field, const float* diff, const float* div, int max_bubbles,
-                                       const int32_t* labels, const int32_t* count_pred, const int32_t* count_tgt, const int32_t* attached_pred,
-                                       const int32_t* attached_tgt, const int32_t* area_pred, const int32_t* area_tgt, int32_t* successor_pred,
-                                       int32_t* successor_tgt, int32_t* n_successors_pred, int32_t* n_successors_tgt, int32_t* predecessor_pred,
-                                       int32_t* predecessor_tgt, int32_t* n_predecessors_pred, int32_t* n_predecessors_tgt, int32_t* departure_area_pred,
-                                       int32_t* departure_area_tgt, int32_t* events_pred, int32_t* events_tgt, void* ws, int64_t ws_bytes, int B, int T,
-                                       int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+extern "C" int bf_rollout_bubble_links(const bf_rollout_step* s, int max_bubbles, const int32_t* labels, const bf_census_rows* census_pred,
+                                       const bf_census_rows* census_tgt, const bf_link_rows* links_pred, const bf_link_rows* links_tgt, void* ws,
+                                       int64_t ws_bytes, bf_stream_t stream) {
     RolloutStep v;
-    const bool ptrs = labels && count_pred && count_tgt && attached_pred && attached_tgt && area_pred && area_tgt && successor_pred && successor_tgt &&
-                      n_successors_pred && n_successors_tgt && predecessor_pred && predecessor_tgt && n_predecessors_pred && n_predecessors_tgt &&
-                      departure_area_pred && departure_area_tgt && events_pred && events_tgt && ws;
-    if (const int rc = rollout_step_view(v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps, ptrs,
-                                         (int64_t)B * T <= 0x3fffffff && max_bubbles > 0 && (int64_t)steps * T >= 2, "bf_rollout_bubble_links: null pointer",
-                                         "bf_rollout_bubble_links: bad sizes"))
+    const bf_census_rows *cp = census_pred, *ct = census_tgt;
+    const bool ptrs = labels && cp && ct && cp->count && ct->count && cp->attached && ct->attached && cp->area && ct->area && all_rows(links_pred) &&
+                      all_rows(links_tgt) && ws;
+    if (const int rc = rollout_step_view(v, s, ptrs, s && (int64_t)s->B * s->T <= 0x3fffffff && max_bubbles > 0 && (int64_t)s->steps * s->T >= 2,
+                                         "bf_rollout_bubble_links: null pointer", "bf_rollout_bubble_links: bad sizes"))
         return rc;
     BF_REQUIRE(max_bubbles <= LINKS_MAX_BUBBLES, "bf_rollout_bubble_links: at most 2^15 records per frame");
-    BF_REQUIRE((int64_t)Ho * Wo <= LINKS_MAX_CELLS, "bf_rollout_bubble_links: a frame may have at most 2^24 cells");
-    BF_REQUIRE(ws_bytes >= bf_bubble_links_ws_bytes(2 * (int64_t)B * T, max_bubbles),
+    BF_REQUIRE((int64_t)v.Ho * v.Wo <= LINKS_MAX_CELLS, "bf_rollout_bubble_links: a frame may have at most 2^24 cells");
+    BF_REQUIRE(ws_bytes >= bf_bubble_links_ws_bytes(2 * (int64_t)v.B * v.T, max_bubbles),
                "bf_rollout_bubble_links: workspace smaller than bf_bubble_links_ws_bytes(2 B T, max_bubbles)");
     BF_REQUIRE((uintptr_t)ws % 16 == 0, "bf_rollout_bubble_links: the workspace must be 16-byte aligned");
-    const RolloutLinksArgs a{v, labels, {count_pred, count_tgt}, {attached_pred, attached_tgt}, {area_pred, area_tgt}, max_bubbles,
-                             {PairOut{successor_pred, n_successors_pred, predecessor_pred, n_predecessors_pred, departure_area_pred, events_pred},
-                              PairOut{successor_tgt, n_successors_tgt, predecessor_tgt, n_predecessors_tgt, departure_area_tgt, events_tgt}},
-                             (char*)ws, links_slot(max_bubbles)};
+    const RolloutLinksArgs a{v, labels, {cp->count, ct->count}, {cp->attached, ct->attached}, {cp->area, ct->area}, max_bubbles,
+                             {pair_out(links_pred), pair_out(links_tgt)}, (char*)ws, links_slot(max_bubbles)};
     static BfPerDeviceOnce once;
     if (const int rc = allow_lds(rollout_links_kernel, once)) return rc;
-    hipLaunchKernelGGL(rollout_links_kernel, dim3((unsigned)(B * T), 2), dim3(NT), links_lds_bytes(max_bubbles), (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rollout_links_kernel, dim3((unsigned)(v.B * v.T), 2), dim3(NT), links_lds_bytes(max_bubbles), (hipStream_t)stream, a);
     BF_CHECK_LAUNCH();
     return 0;
 }

@@ -323,25 +323,22 @@ extern "C" int bf_bubble_census(const float* phi, int64_t frames, int H, int W, 
     return 0;
 }
 
-// bf_rollout_bubbles (ring = null) and bf_rollout_bubbles_labelled: one launch either way
-static int rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                           const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
-                           int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
-                           int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, int32_t* ring, void* ws, int64_t ws_bytes,
-                           int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+extern "C" int bf_rollout_bubbles(const bf_rollout_step* s, int sdf_channel, int connectivity, int max_bubbles, const bf_census_rows* pred,
+                                  const bf_census_rows* tgt, int32_t* labels, void* ws, int64_t ws_bytes, bf_stream_t stream) {
     RolloutStep v;
-    if (const int rc = rollout_step_view(v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
-                                         count_pred && count_tgt && cells_pred && cells_tgt && attached_pred && attached_tgt && area_pred && area_tgt && ws,
-                                         (int64_t)B * T <= 0x3fffffff && max_bubbles > 0, "bf_rollout_bubbles: null pointer", "bf_rollout_bubbles: bad sizes"))
+    if (const int rc = rollout_step_view(v, s, pred && tgt && pred->count && tgt->count && pred->cells && tgt->cells && pred->attached && tgt->attached &&
+                                         pred->area && tgt->area && ws, s && (int64_t)s->B * s->T <= 0x3fffffff && max_bubbles > 0,
+                                         "bf_rollout_bubbles: null pointer", "bf_rollout_bubbles: bad sizes"))
         return rc;
-    BF_REQUIRE(sdf_channel >= 0 && sdf_channel < C, "bf_rollout_bubbles: the signed-distance channel must be an output channel");
+    const int B = v.B, T = v.T, Ho = v.Ho, Wo = v.Wo;
+    BF_REQUIRE(sdf_channel >= 0 && sdf_channel < v.C, "bf_rollout_bubbles: the signed-distance channel must be an output channel");
     BF_REQUIRE(connectivity == 4 || connectivity == 8, "bf_rollout_bubbles: connectivity must be 4 or 8");
     BF_REQUIRE((int64_t)Ho * Wo <= BUBBLE_MAX_CELLS, "bf_rollout_bubbles: a frame may have at most 2^24 cells");
     BF_REQUIRE(ws_bytes >= bf_bubble_census_ws_bytes(2 * (int64_t)B * T, Ho, Wo, max_bubbles), "bf_rollout_bubbles: workspace smaller than bf_bubble_census_ws_bytes(2 B T, Ho, Wo, max_bubbles)");
     BF_REQUIRE((uintptr_t)ws % 16 == 0, "bf_rollout_bubbles: the workspace must be 16-byte aligned");
     const WsLayout lay(Ho, Wo, max_bubbles);
-    const RolloutBubbleArgs a{v, sdf_channel, connectivity == 8, max_bubbles, {count_pred, count_tgt}, {cells_pred, cells_tgt}, {attached_pred, attached_tgt},
-                              {area_pred, area_tgt}, (char*)ws, lay.slot, lay.parents_off, ring};
+    const RolloutBubbleArgs a{v, sdf_channel, connectivity == 8, max_bubbles, {pred->count, tgt->count}, {pred->cells, tgt->cells}, {pred->attached, tgt->attached},
+                              {pred->area, tgt->area}, (char*)ws, lay.slot, lay.parents_off, labels};
     const long n = (long)Ho * Wo;
     const dim3 grid((unsigned)(B * T), 2);
     if (n <= BUBBLE_LDS_CELLS) {
@@ -353,26 +350,4 @@ static int rollout_bubbles(const float* pred, const float* frames, int64_t field
     }
     BF_CHECK_LAUNCH();
     return 0;
-}
-
-extern "C" int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                  const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
-                                  int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt,
-                                  int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes,
-                                  int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
-    return rollout_bubbles(pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, sdf_channel, connectivity, max_bubbles, count_pred,
-                           count_tgt, cells_pred, cells_tgt, attached_pred, attached_tgt, area_pred, area_tgt, nullptr, ws, ws_bytes, B, T, C, H, W, Ho, Wo,
-                           steps, stream);
-}
-
-extern "C" int bf_rollout_bubbles_labelled(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields,
-                                           const int64_t* first, const int32_t* step, const int32_t* field, const float* diff, const float* div,
-                                           int sdf_channel, int connectivity, int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred,
-                                           int32_t* cells_tgt, int32_t* attached_pred, int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt,
-                                           int32_t* labels, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps,
-                                           bf_stream_t stream) {
-    BF_REQUIRE(labels, "bf_rollout_bubbles_labelled: null pointer");
-    return rollout_bubbles(pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, sdf_channel, connectivity, max_bubbles, count_pred,
-                           count_tgt, cells_pred, cells_tgt, attached_pred, attached_tgt, area_pred, area_tgt, labels, ws, ws_bytes, B, T, C, H, W, Ho, Wo,
-                           steps, stream);
 }

@@ -64,14 +64,13 @@ struct RolloutStep {
     __device__ __forceinline__ bool ident() const { return Ho == H && Wo == W; }
 };
 
-// The view of an entry point's arguments, after the null and size checks all three make; own_ptrs / own_sizes are the entry point's additions to them
-inline int rollout_step_view(RolloutStep& v, const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields,
-                             const int64_t* first, const int32_t* step, const int32_t* field, const float* diff, const float* div, int B, int T,
-                             int C, int H, int W, int Ho, int Wo, int steps, bool own_ptrs, bool own_sizes, const char* null_msg, const char* size_msg) {
-    BF_REQUIRE(pred && frames && first && step && field && diff && div && own_ptrs, null_msg);
-    BF_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Ho <= H && Wo <= W && steps > 0 && nfields > 0 && total_frames > 0 &&
-               field_stride >= total_frames * H * W && own_sizes, size_msg);
-    v = RolloutStep{pred, frames, (long)field_stride, (long)total_frames, nfields, (const long*)first, (const int*)step, (const int*)field, diff, div,
-                    B, T, C, H, W, Ho, Wo, steps};
+// The device view of an entry point's bf_rollout_step, after the null and size checks every per-step call makes; own_ptrs / own_sizes are the entry
+// point's additions to them (a null record fails the first, so own_sizes may be `s && ...`)
+inline int rollout_step_view(RolloutStep& v, const bf_rollout_step* s, bool own_ptrs, bool own_sizes, const char* null_msg, const char* size_msg) {
+    BF_REQUIRE(s && s->pred && s->frames && s->first && s->step && s->field && s->diff && s->div && own_ptrs, null_msg);
+    BF_REQUIRE(s->B > 0 && s->T > 0 && s->C > 0 && s->H > 0 && s->W > 0 && s->Ho > 0 && s->Wo > 0 && s->Ho <= s->H && s->Wo <= s->W && s->steps > 0 &&
+               s->nfields > 0 && s->total_frames > 0 && s->field_stride >= s->total_frames * s->H * s->W && own_sizes, size_msg);
+    v = RolloutStep{s->pred, s->frames, (long)s->field_stride, (long)s->total_frames, s->nfields, (const long*)s->first, s->step, s->field, s->diff, s->div,
+                    s->B, s->T, s->C, s->H, s->W, s->Ho, s->Wo, s->steps};
     return 0;
 }

@@ -146,19 +146,18 @@ extern "C" int64_t bf_rollout_score_ws_doubles(int B, int T, int C, int Ho, int 
     if (B <= 0 || T <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return 0;
     return (int64_t)B * T * C * (score_rows(Ho, Wo) * 4 + 1);
 }
-extern "C" int bf_rollout_score(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
-                                float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
-                                int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+extern "C" int bf_rollout_score(const bf_rollout_step* s, int sdf_channel, float dx, float* rel_l2, float* criterion, float* eik_pred, float* eik_tgt,
+                                float* next_in, float* archive, double* ws, int64_t ws_doubles, bf_stream_t stream) {
     ScoreArgs a;
-    if (const int rc = rollout_step_view(a.v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
-                                         rel_l2 && criterion && ws, (int64_t)B * T * C <= 65535, "bf_rollout_score: null pointer", "bf_rollout_score: bad sizes"))
+    if (const int rc = rollout_step_view(a.v, s, rel_l2 && criterion && ws, s && (int64_t)s->B * s->T * s->C <= 65535, "bf_rollout_score: null pointer",
+                                         "bf_rollout_score: bad sizes"))
         return rc;
+    const int B = a.v.B, T = a.v.T, C = a.v.C, Ho = a.v.Ho, Wo = a.v.Wo;
     BF_REQUIRE(sdf_channel >= -1 && sdf_channel < C, "bf_rollout_score: the signed-distance channel is -1 (none) or an output channel");
     BF_REQUIRE(sdf_channel < 0 || (eik_pred && eik_tgt && Ho >= 3 && Wo >= 3 && dx > 0.f),
                "bf_rollout_score: the Eikonal rows need their outputs, dx > 0 and >= 3 points per axis (central differences)");
-    BF_REQUIRE(pred != next_in && pred != archive, "bf_rollout_score: the copies cannot alias the prediction");
-    BF_REQUIRE(((uintptr_t)pred % 16 == 0) && ((uintptr_t)frames % 16 == 0) && ((uintptr_t)next_in % 16 == 0) && ((uintptr_t)archive % 16 == 0) &&
+    BF_REQUIRE(a.v.pred != next_in && a.v.pred != archive, "bf_rollout_score: the copies cannot alias the prediction");
+    BF_REQUIRE(((uintptr_t)a.v.pred % 16 == 0) && ((uintptr_t)a.v.src % 16 == 0) && ((uintptr_t)next_in % 16 == 0) && ((uintptr_t)archive % 16 == 0) &&
                ((uintptr_t)ws % 8 == 0), "bf_rollout_score: prediction, frames and copies must be 16-byte aligned");
     BF_REQUIRE(ws_doubles >= bf_rollout_score_ws_doubles(B, T, C, Ho, Wo), "bf_rollout_score: workspace smaller than bf_rollout_score_ws_doubles");
     const int rows = score_rows(Ho, Wo);
@@ -166,27 +165,25 @@ extern "C" int bf_rollout_score(const float* pred, const float* frames, int64_t 
     a.sdf = sdf_channel; a.inv_2dx = sdf_channel >= 0 ? 0.5f / dx : 0.f; a.next_in = next_in; a.archive = archive; a.part = ws; a.rows = rows;
     hipLaunchKernelGGL(rollout_score_kernel, dim3((unsigned)rows, (unsigned)(B * T * C)), dim3(NT), 0, (hipStream_t)stream, a);
     BF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rollout_score_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)ws, ratio, (int*)step, rel_l2, criterion,
-                       eik_pred, eik_tgt, B, T, C, steps, rows, sdf_channel, (double)Ho * (double)Wo);
+    hipLaunchKernelGGL(rollout_score_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)ws, ratio, (int*)s->step, rel_l2, criterion,
+                       eik_pred, eik_tgt, B, T, C, a.v.steps, rows, sdf_channel, (double)Ho * (double)Wo);
     BF_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                   const int32_t* step, const int32_t* field, const float* diff, const float* div, int dfun_channel, int temp_channel,
-                                   const float* heater_temp, float x_min, float dx, float lc, float conductivity, float* flux_pred, float* flux_tgt,
-                                   int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+extern "C" int bf_rollout_heatflux(const bf_rollout_step* s, int dfun_channel, int temp_channel, const float* heater_temp, float x_min, float dx, float lc,
+                                   float conductivity, float* flux_pred, float* flux_tgt, bf_stream_t stream) {
     HeatfluxArgs a;
-    if (const int rc = rollout_step_view(a.v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
-                                         heater_temp && flux_pred && flux_tgt, (int64_t)B * T <= 0x7fffffff, "bf_rollout_heatflux: null pointer",
-                                         "bf_rollout_heatflux: bad sizes"))
+    if (const int rc = rollout_step_view(a.v, s, heater_temp && flux_pred && flux_tgt, s && (int64_t)s->B * s->T <= 0x7fffffff,
+                                         "bf_rollout_heatflux: null pointer", "bf_rollout_heatflux: bad sizes"))
         return rc;
+    const int C = a.v.C;
     BF_REQUIRE(dfun_channel >= 0 && dfun_channel < C && temp_channel >= 0 && temp_channel < C,
                "bf_rollout_heatflux: the signed-distance and the temperature channel must be output channels");
     BF_REQUIRE(dx > 0.f && lc > 0.f, "bf_rollout_heatflux: dx and lc must be positive");
     a.dfun_c = dfun_channel; a.temp_c = temp_channel; a.heater_temp = heater_temp; a.x_min = x_min; a.dx = dx; a.coef = conductivity / (dx * lc);
     a.flux_pred = flux_pred; a.flux_tgt = flux_tgt;
-    hipLaunchKernelGGL(rollout_heatflux_kernel, dim3((unsigned)(B * T), 2), dim3(64), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rollout_heatflux_kernel, dim3((unsigned)(a.v.B * a.v.T), 2), dim3(64), 0, (hipStream_t)stream, a);
     BF_CHECK_LAUNCH();
     return 0;
 }

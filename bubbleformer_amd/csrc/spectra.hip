@@ -369,6 +369,11 @@ __global__ void __launch_bounds__(NT) errors_finish_kernel(ErrArgs a) {
     }
 }
 
+void set_rows(ErrArgs& a, const bf_error_rows& r) {                         // the nine optional outputs under the kernels' names
+    a.rmse = r.rmse; a.max_error = r.max_error; a.boundary_rmse = r.boundary_rmse; a.interface_rmse = r.interface_rmse; a.interface_cells = r.interface_cells;
+    a.bands = r.spectral_error; a.spec[0] = r.spectrum_error; a.spec[1] = r.spectrum_pred; a.spec[2] = r.spectrum_target;
+}
+
 int launch_errors(ErrArgs& a, long F, long mframes, bool have_sdf, int want_spectra, void* ws, int64_t ws_bytes, hipStream_t st) {
     const int H = a.H, W = a.W;
     BF_REQUIRE(H <= MAX_SIDE && W <= MAX_SIDE, "field errors: a side may be at most 1024");
@@ -417,31 +422,24 @@ extern "C" int64_t bf_field_errors_ws_bytes(int64_t frames, int H, int W) {
 }
 
 extern "C" int bf_field_errors(const float* pred, const float* target, const float* sdf, int64_t frames, int H, int W, int interface_radius, int lo,
-                               int hi, int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse,
-                               int32_t* interface_cells, float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target,
-                               void* ws, int64_t ws_bytes, bf_stream_t stream) {
-    BF_REQUIRE(pred && target, "bf_field_errors: null pointer");
+                               int hi, int want_spectra, const bf_error_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream) {
+    BF_REQUIRE(pred && target && rows, "bf_field_errors: null pointer");
     BF_REQUIRE(frames > 0 && H > 0 && W > 0 && bf_field_errors_ws_bytes(frames, H, W) > 0, "bf_field_errors: bad sizes");
     ErrArgs a{};
     a.rollout = 0; a.pred = pred; a.tgt = target; a.sdf = sdf; a.H = H; a.W = W; a.radius = interface_radius; a.lo = lo; a.hi = hi;
-    a.rmse = rmse; a.max_error = max_error; a.boundary_rmse = boundary_rmse; a.interface_rmse = interface_rmse; a.interface_cells = interface_cells;
-    a.bands = spectral_error; a.spec[0] = spectrum_error; a.spec[1] = spectrum_pred; a.spec[2] = spectrum_target;
+    set_rows(a, *rows);
     return launch_errors(a, frames, frames, sdf != nullptr, want_spectra, ws, ws_bytes, (hipStream_t)stream);
 }
 
-extern "C" int bf_rollout_errors(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                 const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int interface_radius,
-                                 int lo, int hi, int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse,
-                                 int32_t* interface_cells, float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target,
-                                 void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream) {
+extern "C" int bf_rollout_errors(const bf_rollout_step* s, int sdf_channel, int interface_radius, int lo, int hi, int want_spectra,
+                                 const bf_error_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream) {
     ErrArgs a{};
-    if (const int rc = rollout_step_view(a.v, pred, frames, field_stride, total_frames, nfields, first, step, field, diff, div, B, T, C, H, W, Ho, Wo, steps,
-                                         true, bf_field_errors_ws_bytes((int64_t)B * T * C, Ho, Wo) > 0, "bf_rollout_errors: null pointer",
-                                         "bf_rollout_errors: bad sizes"))
+    if (const int rc = rollout_step_view(a.v, s, rows != nullptr, s && bf_field_errors_ws_bytes((int64_t)s->B * s->T * s->C, s->Ho, s->Wo) > 0,
+                                         "bf_rollout_errors: null pointer", "bf_rollout_errors: bad sizes"))
         return rc;
-    BF_REQUIRE(sdf_channel >= -1 && sdf_channel < C, "bf_rollout_errors: the signed-distance channel is -1 (none) or an output channel");
-    a.rollout = 1; a.sdf_c = sdf_channel; a.H = Ho; a.W = Wo; a.radius = interface_radius; a.lo = lo; a.hi = hi;
-    a.rmse = rmse; a.max_error = max_error; a.boundary_rmse = boundary_rmse; a.interface_rmse = interface_rmse; a.interface_cells = interface_cells;
-    a.bands = spectral_error; a.spec[0] = spectrum_error; a.spec[1] = spectrum_pred; a.spec[2] = spectrum_target;
-    return launch_errors(a, (long)B * T * C, (long)B * T, sdf_channel >= 0, want_spectra, ws, ws_bytes, (hipStream_t)stream);
+    const RolloutStep& v = a.v;
+    BF_REQUIRE(sdf_channel >= -1 && sdf_channel < v.C, "bf_rollout_errors: the signed-distance channel is -1 (none) or an output channel");
+    a.rollout = 1; a.sdf_c = sdf_channel; a.H = v.Ho; a.W = v.Wo; a.radius = interface_radius; a.lo = lo; a.hi = hi;
+    set_rows(a, *rows);
+    return launch_errors(a, (long)v.B * v.T * v.C, (long)v.B * v.T, sdf_channel >= 0, want_spectra, ws, ws_bytes, (hipStream_t)stream);
 }

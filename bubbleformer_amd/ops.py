@@ -981,7 +981,7 @@ def _check_tensors(who: str, device, want: dict, optional=()) -> None:
 
 
 def _rollout_step_args(who: str, pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int):
-    """The three per-step rollout bindings' checks of prediction, store, first / step and field table -> their entry points' leading and trailing arguments."""
+    """The per-step rollout bindings' checks of prediction, store, first / step and field table -> their entry points' bf_rollout_step and the stream."""
     _require_gpu(pred)
     if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous():
         raise L.BubbleformerHipError(f"{who}: the prediction must be a contiguous fp32 (B, T, C, H, W) tensor")
@@ -993,7 +993,8 @@ def _rollout_step_args(who: str, pred: torch.Tensor, frames: torch.Tensor, first
         raise L.BubbleformerHipError(f"{who}: the frames must be a contiguous fp32 (fields, frames, H, W) tensor on {pred.device}")
     if ids.numel() != Cn:
         raise L.BubbleformerHipError(f"{who}: the field table has {ids.numel()} channels, the prediction {Cn}")
-    return (_p(pred), _p(frames), total * H * W, total, nf, _p(first), _p(step), _p(ids), _p(diff), _p(div)), (B, T, Cn, H, W, Ho, Wo, int(steps), _stream())
+    return L.RolloutStep(pred=_p(pred), frames=_p(frames), field_stride=total * H * W, total_frames=total, first=_p(first), step=_p(step), field=_p(ids),
+                         diff=_p(diff), div=_p(div), nfields=nf, B=B, T=T, C=Cn, H=H, W=W, Ho=Ho, Wo=Wo, steps=int(steps)), _stream()
 
 
 def rollout_score_workspace(pred: torch.Tensor) -> torch.Tensor:
@@ -1010,14 +1011,14 @@ def rollout_score(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor,
     frames ``first[b] + (s + 1) * T + t`` of the store, s = the int32 ``step`` tensor ON THE DEVICE, which the call increments.  Writes row
     s * T + t of rel_l2 (B, steps*T, C), criterion (B, steps), eik_pred / eik_tgt (B, steps*T) (sdf_channel >= 0), and the optional copies
     next_in (like pred) and archive (B, steps*T, C, Ho, Wo).  Allocates nothing: capturable in a HIP graph."""
-    lead, tail = _rollout_step_args("rollout_score", pred, frames, first, step, table, steps)
+    rec, stream = _rollout_step_args("rollout_score", pred, frames, first, step, table, steps)
     B, T, Cn, Ho, Wo = pred.shape
     f32 = torch.float32
     _check_tensors("rollout_score", pred.device, {"rel_l2": (rel_l2, (B, steps * T, Cn), f32), "criterion": (criterion, (B, steps), f32),
                    "eik_pred": (eik_pred, (B, steps * T), f32), "eik_tgt": (eik_tgt, (B, steps * T), f32), "next_in": (next_in, (B, T, Cn, Ho, Wo), f32),
                    "archive": (archive, (B, steps * T, Cn, Ho, Wo), f32), "ws": (ws, (ws.numel(),), torch.float64)}, ("eik_pred", "eik_tgt", "next_in", "archive"))
-    L.check(L.lib().bf_rollout_score(*lead, int(sdf_channel), float(dx), _p(rel_l2), _p(criterion), _p(eik_pred), _p(eik_tgt), _p(next_in), _p(archive),
-                                     _p(ws), ws.numel(), *tail), "bf_rollout_score")
+    L.check(L.lib().bf_rollout_score(C.byref(rec), int(sdf_channel), float(dx), _p(rel_l2), _p(criterion), _p(eik_pred), _p(eik_tgt), _p(next_in),
+                                     _p(archive), _p(ws), ws.numel(), stream), "bf_rollout_score")
 
 
 def rollout_heatflux(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, dfun_channel: int, temp_channel: int,
@@ -1027,14 +1028,14 @@ def rollout_heatflux(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tens
     flux_tgt (B, steps*T) from row 0 of the de-normalised prediction and of the stored frame ``first[b] + (s + 1) * T + t``, s = the int32
     ``step`` tensor ON THE DEVICE, which this call only reads -- issue it BEFORE the step's ``rollout_score``.  heater_temp (B,) fp32 on the
     device.  Allocates nothing: capturable in a HIP graph."""
-    lead, tail = _rollout_step_args("rollout_heatflux", pred, frames, first, step, table, steps)
+    rec, stream = _rollout_step_args("rollout_heatflux", pred, frames, first, step, table, steps)
     B, T, Cn = pred.shape[:3]
     _check_tensors("rollout_heatflux", pred.device, {"flux_pred": (flux_pred, (B, steps * T), torch.float32), "flux_tgt": (flux_tgt, (B, steps * T), torch.float32),
                                                      "heater_temp": (heater_temp, (B,), torch.float32)})
     if not (0 <= int(dfun_channel) < Cn and 0 <= int(temp_channel) < Cn):
         raise L.BubbleformerHipError(f"rollout_heatflux: channels {dfun_channel} / {temp_channel} are not among the prediction's {Cn}")
-    L.check(L.lib().bf_rollout_heatflux(*lead, int(dfun_channel), int(temp_channel), _p(heater_temp), float(x_min), float(dx), float(lc),
-                                        float(conductivity), _p(flux_pred), _p(flux_tgt), *tail), "bf_rollout_heatflux")
+    L.check(L.lib().bf_rollout_heatflux(C.byref(rec), int(dfun_channel), int(temp_channel), _p(heater_temp), float(x_min), float(dx), float(lc),
+                                        float(conductivity), _p(flux_pred), _p(flux_tgt), stream), "bf_rollout_heatflux")
 
 
 def kde_kl_workspace(rows: int, n: int, m: int, points: int, device) -> torch.Tensor:
@@ -1103,25 +1104,42 @@ def bubble_census(phi: torch.Tensor, connectivity: int, max_bubbles: int, ws: to
 def rollout_bubbles(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
                     connectivity: int, max_bubbles: int, ws: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor, cells_pred: torch.Tensor,
                     cells_tgt: torch.Tensor, attached_pred: torch.Tensor, attached_tgt: torch.Tensor, area_pred: torch.Tensor,
-                    area_tgt: torch.Tensor) -> None:
+                    area_tgt: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
     """The bubble census of one rollout step (bf_rollout_bubbles; include/bubbleformer_hip.h has the contract): row s * T + t of the int32 outputs
     count / cells / attached (B, steps*T) and area (B, steps*T, max_bubbles), for the de-normalised signed-distance channel of the prediction
     (_pred) and for the stored frame ``first[b] + (s + 1) * T + t`` (_tgt), s = the int32 ``step`` tensor ON THE DEVICE, which this call only
-    reads -- issue it BEFORE the step's ``rollout_score``.  ws: ``bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)``.  Allocates nothing."""
-    lead, tail = _rollout_step_args("rollout_bubbles", pred, frames, first, step, table, steps)
+    reads -- issue it BEFORE the step's ``rollout_score``.  labels: None, or the ring of ``rollout_bubbles_labelled``.  ws:
+    ``bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)``.  Allocates nothing."""
+    _rollout_census("rollout_bubbles", (pred, frames, first, step, table, steps), sdf_channel, connectivity, max_bubbles, ws,
+                    (count_pred, cells_pred, attached_pred, area_pred), (count_tgt, cells_tgt, attached_tgt, area_tgt), labels)
+
+
+def _census_rows(who: str, device, side: str, lead: tuple, mb: int, count, cells, attached, area, need_cells: bool = True):
+    """One side's census tensors, checked -> bf_census_rows; the link calls do not read cells, where need_cells = False lets it be None."""
+    i32 = torch.int32
+    want = {f"count{side}": (count, lead, i32), f"cells{side}": (cells, lead, i32), f"attached{side}": (attached, lead, i32), f"area{side}": (area, lead + (mb,), i32)}
+    _check_tensors(who, device, want, () if need_cells else (f"cells{side}",))
+    return L.CensusRows(count=_p(count), cells=_p(cells), attached=_p(attached), area=_p(area))
+
+
+def _rollout_census(who: str, step_args: tuple, sdf_channel: int, connectivity: int, max_bubbles: int, ws: torch.Tensor, side_pred: tuple, side_tgt: tuple,
+                    labels: Optional[torch.Tensor], need_labels: bool = False) -> None:
+    """``rollout_bubbles`` and ``rollout_bubbles_labelled``: one entry point, with or without the ring."""
+    rec, stream = _rollout_step_args(who, *step_args)
+    pred, steps = step_args[0], step_args[-1]
     B, T, Cn, Ho, Wo = pred.shape
     mb = int(max_bubbles)
-    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
-    _check_tensors("rollout_bubbles", pred.device, {"count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32), "cells_pred": (cells_pred, rows, i32),
-                   "cells_tgt": (cells_tgt, rows, i32), "attached_pred": (attached_pred, rows, i32), "attached_tgt": (attached_tgt, rows, i32),
-                   "area_pred": (area_pred, recs, i32), "area_tgt": (area_tgt, recs, i32), "ws": (ws, (ws.numel(),), torch.uint8)})
+    census_pred = _census_rows(who, pred.device, "_pred", (B, steps * T), mb, *side_pred)
+    census_tgt = _census_rows(who, pred.device, "_tgt", (B, steps * T), mb, *side_tgt)
+    _check_tensors(who, pred.device, {"labels": (labels, (2, 2, B, T, Ho, Wo), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)},
+                   () if need_labels else ("labels",))
     if not 0 <= int(sdf_channel) < Cn:
-        raise L.BubbleformerHipError(f"rollout_bubbles: channel {sdf_channel} is not among the prediction's {Cn}")
+        raise L.BubbleformerHipError(f"{who}: channel {sdf_channel} is not among the prediction's {Cn}")
     need = L.lib().bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, mb)
     if need <= 0 or ws.numel() < need:
-        raise L.BubbleformerHipError("rollout_bubbles: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
-    L.check(L.lib().bf_rollout_bubbles(*lead, int(sdf_channel), int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt),
-                                       _p(attached_pred), _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(ws), ws.numel(), *tail), "bf_rollout_bubbles")
+        raise L.BubbleformerHipError(f"{who}: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
+    L.check(L.lib().bf_rollout_bubbles(C.byref(rec), int(sdf_channel), int(connectivity), mb, C.byref(census_pred), C.byref(census_tgt), _p(labels), _p(ws),
+                                       ws.numel(), stream), "bf_rollout_bubbles")
 
 
 def bubble_links_workspace(pairs: int, max_bubbles: int, device) -> torch.Tensor:
@@ -1146,6 +1164,15 @@ def _link_rows(lead: tuple, mb: int) -> dict:
             "departure_area": lead + (mb,), "events": lead + (5,)}
 
 
+def _link_record(who: str, device, side: str, lead: tuple, mb: int, given: dict):
+    """One side's six link tensors (``_link_rows(lead, mb)``), checked -> bf_link_rows."""
+    shapes = _link_rows(lead, mb)
+    if given.keys() != shapes.keys():
+        raise L.BubbleformerHipError(f"{who}: links{side} must hold exactly {sorted(shapes)}")
+    _check_tensors(who, device, {f"{k}{side}": (given[k], shape, torch.int32) for k, shape in shapes.items()})
+    return L.LinkRows(**{k: _p(given[k]) for k in shapes})
+
+
 def bubble_links(labels: torch.Tensor, count: torch.Tensor, attached: torch.Tensor, area: torch.Tensor, ws: torch.Tensor, successor: torch.Tensor,
                  n_successors: torch.Tensor, predecessor: torch.Tensor, n_predecessors: torch.Tensor, departure_area: torch.Tensor,
                  events: torch.Tensor) -> None:
@@ -1161,11 +1188,10 @@ def bubble_links(labels: torch.Tensor, count: torch.Tensor, attached: torch.Tens
         raise L.BubbleformerHipError("bubble_links: area must be a (sequences, T, max_bubbles) tensor")
     N, T, H, W = labels.shape
     mb = int(area.shape[-1])
-    outs = dict(successor=successor, n_successors=n_successors, predecessor=predecessor, n_predecessors=n_predecessors, departure_area=departure_area,
-                events=events)
-    want = {"count": (count, (N, T), i32), "attached": (attached, (N, T), i32), "area": (area, (N, T, mb), i32), "ws": (ws, (ws.numel(),), torch.uint8)}
-    want.update({k: (outs[k], shape, i32) for k, shape in _link_rows((N, T - 1), mb).items()})
-    _check_tensors("bubble_links", labels.device, want)
+    census = _census_rows("bubble_links", labels.device, "", (N, T), mb, count, None, attached, area, need_cells=False)
+    _check_tensors("bubble_links", labels.device, {"ws": (ws, (ws.numel(),), torch.uint8)})
+    links = _link_record("bubble_links", labels.device, "", (N, T - 1), mb, dict(successor=successor, n_successors=n_successors, predecessor=predecessor,
+                         n_predecessors=n_predecessors, departure_area=departure_area, events=events))
     if N < 1 or T < 1 or H < 1 or W < 1 or mb < 1:
         raise L.BubbleformerHipError(f"bubble_links: needs at least one sequence of at least one frame of at least one cell, got {tuple(labels.shape)}")
     if T == 1:
@@ -1173,8 +1199,7 @@ def bubble_links(labels: torch.Tensor, count: torch.Tensor, attached: torch.Tens
     need = L.lib().bf_bubble_links_ws_bytes(N * (T - 1), mb)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("bubble_links: the workspace is smaller than bubble_links_workspace(sequences * (T - 1), max_bubbles)")
-    L.check(L.lib().bf_bubble_links(_p(labels), _p(count), _p(attached), _p(area), N, T, H, W, mb, _p(successor), _p(n_successors), _p(predecessor),
-                                    _p(n_predecessors), _p(departure_area), _p(events), _p(ws), ws.numel(), _stream()), "bf_bubble_links")
+    L.check(L.lib().bf_bubble_links(_p(labels), C.byref(census), N, T, H, W, mb, C.byref(links), _p(ws), ws.numel(), _stream()), "bf_bubble_links")
 
 
 def bubble_track_ids(count: torch.Tensor, successor: torch.Tensor, predecessor: torch.Tensor, track_id: torch.Tensor, n_tracks: torch.Tensor) -> None:
@@ -1198,25 +1223,11 @@ def rollout_bubbles_labelled(pred: torch.Tensor, frames: torch.Tensor, first: to
                              connectivity: int, max_bubbles: int, ws: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor,
                              cells_pred: torch.Tensor, cells_tgt: torch.Tensor, attached_pred: torch.Tensor, attached_tgt: torch.Tensor,
                              area_pred: torch.Tensor, area_tgt: torch.Tensor, labels: torch.Tensor) -> None:
-    """``rollout_bubbles`` that also leaves its label images (bf_rollout_bubbles_labelled): labels (2, 2, B, T, Ho, Wo) int32 is a ring of two
+    """``rollout_bubbles`` that also leaves its label images (bf_rollout_bubbles with the ring): labels (2, 2, B, T, Ho, Wo) int32 is a ring of two
     steps, [0] the prediction and [1] the simulation; step s writes half ``s & 1`` and leaves the other, which ``rollout_bubble_links`` still needs.
     Everything else as ``rollout_bubbles``.  Allocates nothing."""
-    lead, tail = _rollout_step_args("rollout_bubbles_labelled", pred, frames, first, step, table, steps)
-    B, T, Cn, Ho, Wo = pred.shape
-    mb = int(max_bubbles)
-    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
-    _check_tensors("rollout_bubbles_labelled", pred.device, {"count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32),
-                   "cells_pred": (cells_pred, rows, i32), "cells_tgt": (cells_tgt, rows, i32), "attached_pred": (attached_pred, rows, i32),
-                   "attached_tgt": (attached_tgt, rows, i32), "area_pred": (area_pred, recs, i32), "area_tgt": (area_tgt, recs, i32),
-                   "labels": (labels, (2, 2, B, T, Ho, Wo), i32), "ws": (ws, (ws.numel(),), torch.uint8)})
-    if not 0 <= int(sdf_channel) < Cn:
-        raise L.BubbleformerHipError(f"rollout_bubbles_labelled: channel {sdf_channel} is not among the prediction's {Cn}")
-    need = L.lib().bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, mb)
-    if need <= 0 or ws.numel() < need:
-        raise L.BubbleformerHipError("rollout_bubbles_labelled: the workspace is smaller than bubble_census_workspace(2 * B * T, Ho, Wo, max_bubbles)")
-    L.check(L.lib().bf_rollout_bubbles_labelled(*lead, int(sdf_channel), int(connectivity), mb, _p(count_pred), _p(count_tgt), _p(cells_pred), _p(cells_tgt),
-                                                _p(attached_pred), _p(attached_tgt), _p(area_pred), _p(area_tgt), _p(labels), _p(ws), ws.numel(), *tail),
-            "bf_rollout_bubbles_labelled")
+    _rollout_census("rollout_bubbles_labelled", (pred, frames, first, step, table, steps), sdf_channel, connectivity, max_bubbles, ws,
+                    (count_pred, cells_pred, attached_pred, area_pred), (count_tgt, cells_tgt, attached_tgt, area_tgt), labels, need_labels=True)
 
 
 def rollout_bubble_links(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int, max_bubbles: int,
@@ -1228,27 +1239,21 @@ def rollout_bubble_links(pred: torch.Tensor, frames: torch.Tensor, first: torch.
     links_tgt: dicts of successor, n_successors, predecessor, n_predecessors, departure_area (B, steps*T - 1, max_bubbles) and events
     (B, steps*T - 1, 5) int32; the pair that ends in frame t of step s is row s * T + t - 1.  ws: ``bubble_links_workspace(2 * B * T, max_bubbles)``.
     A rollout of one frame (steps * T = 1) has no pair and launches nothing.  Allocates nothing."""
-    lead, tail = _rollout_step_args("rollout_bubble_links", pred, frames, first, step, table, steps)
+    rec, stream = _rollout_step_args("rollout_bubble_links", pred, frames, first, step, table, steps)
     B, T, Cn, Ho, Wo = pred.shape
-    mb = int(max_bubbles)
-    rows, recs, i32 = (B, steps * T), (B, steps * T, mb), torch.int32
-    want = {"labels": (labels, (2, 2, B, T, Ho, Wo), i32), "count_pred": (count_pred, rows, i32), "count_tgt": (count_tgt, rows, i32),
-            "attached_pred": (attached_pred, rows, i32), "attached_tgt": (attached_tgt, rows, i32), "area_pred": (area_pred, recs, i32),
-            "area_tgt": (area_tgt, recs, i32), "ws": (ws, (ws.numel(),), torch.uint8)}
-    shapes = _link_rows((B, steps * T - 1), mb)
-    for side, given in (("pred", links_pred), ("tgt", links_tgt)):
-        if sorted(given) != sorted(shapes):
-            raise L.BubbleformerHipError(f"rollout_bubble_links: links_{side} must hold exactly {sorted(shapes)}")
-        want.update({f"{k}_{side}": (given[k], shape, i32) for k, shape in shapes.items()})
-    _check_tensors("rollout_bubble_links", pred.device, want)
+    mb, dev = int(max_bubbles), pred.device
+    _check_tensors("rollout_bubble_links", dev, {"labels": (labels, (2, 2, B, T, Ho, Wo), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)})
+    census_pred = _census_rows("rollout_bubble_links", dev, "_pred", (B, steps * T), mb, count_pred, None, attached_pred, area_pred, need_cells=False)
+    census_tgt = _census_rows("rollout_bubble_links", dev, "_tgt", (B, steps * T), mb, count_tgt, None, attached_tgt, area_tgt, need_cells=False)
+    rows_pred = _link_record("rollout_bubble_links", dev, "_pred", (B, steps * T - 1), mb, links_pred)
+    rows_tgt = _link_record("rollout_bubble_links", dev, "_tgt", (B, steps * T - 1), mb, links_tgt)
     need = L.lib().bf_bubble_links_ws_bytes(2 * B * T, mb)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("rollout_bubble_links: the workspace is smaller than bubble_links_workspace(2 * B * T, max_bubbles)")
     if steps * T < 2:
         return
-    both = [_p(side[k]) for k in ("successor", "n_successors", "predecessor", "n_predecessors", "departure_area", "events") for side in (links_pred, links_tgt)]
-    L.check(L.lib().bf_rollout_bubble_links(*lead, mb, _p(labels), _p(count_pred), _p(count_tgt), _p(attached_pred), _p(attached_tgt), _p(area_pred),
-                                            _p(area_tgt), *both, _p(ws), ws.numel(), *tail), "bf_rollout_bubble_links")
+    L.check(L.lib().bf_rollout_bubble_links(C.byref(rec), mb, _p(labels), C.byref(census_pred), C.byref(census_tgt), C.byref(rows_pred), C.byref(rows_tgt),
+                                            _p(ws), ws.numel(), stream), "bf_rollout_bubble_links")
 
 
 _ERROR_ROWS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
@@ -1265,7 +1270,7 @@ def field_errors_workspace(frames: int, H: int, W: int, device) -> torch.Tensor:
 
 
 def _error_rows(who: str, device, lead: tuple, K: int, rows: dict, ws: torch.Tensor):
-    """The nine optional outputs of the error calls, checked -> their pointers in the entry points' order."""
+    """The nine optional outputs of the error calls, checked -> bf_error_rows."""
     unknown = set(rows) - set(_ERROR_ROWS)
     if unknown:
         raise L.BubbleformerHipError(f"{who}: unknown outputs {sorted(unknown)}")
@@ -1276,7 +1281,7 @@ def _error_rows(who: str, device, lead: tuple, K: int, rows: dict, ws: torch.Ten
     want = {k: (rows.get(k), shape, dtype) for k, (shape, dtype) in shapes.items()}
     want["ws"] = (ws, (ws.numel(),), torch.uint8)
     _check_tensors(who, device, want, _ERROR_ROWS)
-    return [_p(rows.get(k)) for k in _ERROR_ROWS]
+    return L.ErrorRows(**{k: _p(rows.get(k)) for k in _ERROR_ROWS})
 
 
 def shell_count(H: int, W: int) -> int:
@@ -1297,12 +1302,12 @@ def field_errors(pred: torch.Tensor, target: torch.Tensor, sdf: Optional[torch.T
         raise L.BubbleformerHipError("field_errors: pred must be a contiguous fp32 (frames, H, W) tensor")
     F, H, W = pred.shape
     _check_tensors("field_errors", pred.device, {"target": (target, (F, H, W), torch.float32), "sdf": (sdf, (F, H, W), torch.float32)}, ("sdf",))
-    ptrs = _error_rows("field_errors", pred.device, (F,), shell_count(H, W), rows, ws)
+    rec = _error_rows("field_errors", pred.device, (F,), shell_count(H, W), rows, ws)
     need = L.lib().bf_field_errors_ws_bytes(F, H, W)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("field_errors: the workspace is smaller than field_errors_workspace(frames, H, W)")
-    L.check(L.lib().bf_field_errors(_p(pred), _p(target), _p(sdf), F, H, W, int(interface_radius), int(lo), int(hi), int(bool(want_spectra)), *ptrs,
-                                    _p(ws), ws.numel(), _stream()), "bf_field_errors")
+    L.check(L.lib().bf_field_errors(_p(pred), _p(target), _p(sdf), F, H, W, int(interface_radius), int(lo), int(hi), int(bool(want_spectra)),
+                                    C.byref(rec), _p(ws), ws.numel(), _stream()), "bf_field_errors")
 
 
 def rollout_errors(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
@@ -1312,16 +1317,16 @@ def rollout_errors(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor
     ``field_errors`` names, here (B, steps*T, C) with the same tails, for the prediction against the stored frame ``first[b] + (s + 1) * T + t``,
     s = the int32 ``step`` tensor ON THE DEVICE, which this call only reads -- issue it BEFORE the step's ``rollout_score``.  The interface mask
     comes from the raw stored frame of ``sdf_channel`` (-1: none).  ws: ``field_errors_workspace(B * T * C, Ho, Wo)``.  Allocates nothing."""
-    lead, tail = _rollout_step_args("rollout_errors", pred, frames, first, step, table, steps)
+    rec, stream = _rollout_step_args("rollout_errors", pred, frames, first, step, table, steps)
     B, T, Cn, Ho, Wo = pred.shape
-    ptrs = _error_rows("rollout_errors", pred.device, (B, steps * T, Cn), shell_count(Ho, Wo), rows, ws)
+    out = _error_rows("rollout_errors", pred.device, (B, steps * T, Cn), shell_count(Ho, Wo), rows, ws)
     if not -1 <= int(sdf_channel) < Cn:
         raise L.BubbleformerHipError(f"rollout_errors: channel {sdf_channel} is not among the prediction's {Cn}")
     need = L.lib().bf_field_errors_ws_bytes(B * T * Cn, Ho, Wo)
     if need <= 0 or ws.numel() < need:
         raise L.BubbleformerHipError("rollout_errors: the workspace is smaller than field_errors_workspace(B * T * C, Ho, Wo)")
-    L.check(L.lib().bf_rollout_errors(*lead, int(sdf_channel), int(interface_radius), int(lo), int(hi), int(bool(want_spectra)), *ptrs, _p(ws),
-                                      ws.numel(), *tail), "bf_rollout_errors")
+    L.check(L.lib().bf_rollout_errors(C.byref(rec), int(sdf_channel), int(interface_radius), int(lo), int(hi), int(bool(want_spectra)), C.byref(out), _p(ws),
+                                      ws.numel(), stream), "bf_rollout_errors")
 
 
 def grad_norm_workspace(n: int, device) -> torch.Tensor:

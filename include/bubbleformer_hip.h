@@ -392,12 +392,35 @@ int bf_eikonal_sum(const float* phi, int64_t frames, int H, int W, float dx, dou
 int bf_eikonal_l1_frames(const float* phi, int64_t frames, int H, int W, float dx, float* out, bf_stream_t stream);
 int bf_heatflux_rows(const float* dfun, const float* temp, int64_t frames, int64_t frame_stride, int W, float x_min, float dx,
                      float heater_temp, float lc, float* flux, bf_stream_t stream);
+/* The records of the rollout-evaluation calls.  The library reads a record DURING the call only and keeps no pointer to it; what a kernel needs
+ * of it is copied by value into the kernel's arguments, so the calls stay capturable and a record may live on the caller's stack.
+ * bf_rollout_step (the calls' parameter `s`): ONE autoregressive rollout step, the prediction and where its targets lie.  pred (B, T, C, Ho, Wo)
+ * fp32; frames [nfields][total_frames][H][W] fp32 with field_stride floats per field (DeviceClipStore.frames); first [B] int64 (device) = absolute
+ * first INPUT frame of step 0 per trajectory; step = one int32 in DEVICE memory, the step NUMBER s = *step: READ by every call and written by
+ * bf_rollout_score alone (its last launch increments it, hence not const), so a step's other calls are issued BEFORE its bf_rollout_score;
+ * field / diff / div [C] = the store's output-field table.  Target of (b, t, c): y = (frames[field[c]][first[b] + (s + 1) * T + t][ys][xs] - diff[c]) /
+ * div[c], the expression and nearest-neighbour map of bf_clip_gather (the same device functions), frame index clamped into the store.  steps = the
+ * steps a report has rows for: with s outside [0, steps) a call writes nothing.  reserved is unread: it spells out the padding that ends the record. */
+typedef struct bf_rollout_step {
+    const float *pred, *frames;
+    int64_t field_stride, total_frames;
+    const int64_t* first; int32_t* step; const int32_t* field;
+    const float *diff, *div;
+    int32_t nfields, B, T, C, H, W, Ho, Wo, steps, reserved;
+} bf_rollout_step;
+/* One side's census rows: bf_bubble_census' count / vapour_cells / attached [rows] and area [rows][max_bubbles] */
+typedef struct bf_census_rows { int32_t *count, *cells, *attached, *area; } bf_census_rows;
+/* One side's link rows: bf_bubble_links' five [pairs][max_bubbles] outputs and events [pairs][5] */
+typedef struct bf_link_rows { int32_t *successor, *n_successors, *predecessor, *n_predecessors, *departure_area, *events; } bf_link_rows;
+/* bf_field_errors' outputs; each may be NULL and is then not computed */
+typedef struct bf_error_rows {
+    float *rmse, *max_error, *boundary_rmse, *interface_rmse;
+    int32_t* interface_cells;
+    float *spectral_error, *spectrum_error, *spectrum_pred, *spectrum_target;
+} bf_error_rows;
 /* All scores of ONE autoregressive rollout step from one pass over the prediction (scripts/inference.py:230-266, utils/plot_utils.py:30-33, the
  * rollout notebook's get_eikonal_loss); allocation-free, capturable, no atomics (two calls on the same inputs give the same bits).
- * pred (B, T, C, Ho, Wo) fp32; frames [nfields][total_frames][H][W] fp32 with field_stride floats per field (DeviceClipStore.frames); first [B]
- * int64 (device) = absolute first INPUT frame of step 0 per trajectory; step = one int32 in DEVICE memory, s = *step; field / diff / div [C] = the
- * store's output-field table.  Target of (b, t, c): y = (frames[field[c]][first[b] + (s + 1) * T + t][ys][xs] - diff[c]) / div[c], the expression
- * and nearest-neighbour map of bf_clip_gather (the same device functions), frame index clamped into the store.  Written at row s * T + t:
+ * s: see bf_rollout_step.  Written at row s * T + t:
  *   rel_l2 [B][steps*T][C]  = sqrt(sum (pred - y)^2 / sum y^2) over (Ho, Wo): differences, squares, sums, quotient and root in fp64, rounded once
  *                             (a target frame of zeros gives inf or NaN, as the reference's quotient of norms does);
  *   criterion [B][steps]    = mean over t, then over c, of those fp64 quotients (LpLoss(d=2, p=2, reduce_dims=[0, 1], reductions=["mean", "mean"]));
@@ -408,15 +431,12 @@ int bf_heatflux_rows(const float* dfun, const float* temp, int64_t frames, int64
  * ws: bf_rollout_score_ws_doubles(B, T, C, Ho, Wo) doubles (fp64 partials per workgroup, added in a fixed order).  pred, frames and the copies
  * 16-byte aligned; B * T * C <= 65535. */
 int64_t bf_rollout_score_ws_doubles(int B, int T, int C, int Ho, int Wo);
-int bf_rollout_score(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                     int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, float dx, float* rel_l2,
-                     float* criterion, float* eik_pred, float* eik_tgt, float* next_in, float* archive, double* ws, int64_t ws_doubles,
-                     int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+int bf_rollout_score(const bf_rollout_step* s, int sdf_channel, float dx, float* rel_l2, float* criterion, float* eik_pred, float* eik_tgt,
+                     float* next_in, float* archive, double* ws, int64_t ws_doubles, bf_stream_t stream);
 /* The heat-flux rows of ONE rollout step (utils/heatflux.py:3-38 per step of scripts/inference.py:239-252; csrc/rollout.hip), for the prediction
- * and for the simulation; allocation-free, capturable, no atomics (the same bits on every call), never makes the host wait.  pred, frames,
- * field_stride, total_frames, nfields, first, field / diff / div and the sizes are bf_rollout_score's.  step = one int32 in DEVICE memory, READ and
- * never written: the call must be issued BEFORE the step's bf_rollout_score, which increments that counter.  With s = *step, row s * T + t of
- * trajectory b of flux_pred / flux_tgt [B][steps*T] is bf_heatflux_rows' expression on row 0 (the heater row) of frame t:
+ * and for the simulation; allocation-free, capturable, no atomics (the same bits on every call), never makes the host wait.  s: see
+ * bf_rollout_step.  With the step number s = *s->step, row s * T + t of trajectory b of flux_pred / flux_tgt [B][steps*T] is
+ * bf_heatflux_rows' expression on row 0 (the heater row) of frame t:
  *   mean over ALL Wo cells of [-5 <= x_c <= 5 and dfun < 0] * (heater_temp[b] - temp) * conductivity / (dx * lc),  x_c = x_min + (i + 0.5) * dx in fp64,
  * the difference in fp32, the sum in fp64 in a fixed order, one rounding; heater_temp [B] fp32 on the DEVICE.
  *   flux_pred: dfun = pred * div + diff of channel dfun_channel, temp likewise of temp_channel (fp32 multiply, then add, unfused: the physical
@@ -424,10 +444,8 @@ int bf_rollout_score(const float* pred, const float* frames, int64_t field_strid
  *   flux_tgt:  the stored raw frame first[b] + (s + 1) * T + t (clamped into the store) of fields field[dfun_channel] / field[temp_channel],
  *              through bf_clip_gather's nearest-neighbour map when Ho x Wo < H x W.
  * With s outside [0, steps) nothing is written. */
-int bf_rollout_heatflux(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                        const int32_t* step, const int32_t* field, const float* diff, const float* div, int dfun_channel, int temp_channel,
-                        const float* heater_temp, float x_min, float dx, float lc, float conductivity, float* flux_pred, float* flux_tgt,
-                        int B, int T, int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+int bf_rollout_heatflux(const bf_rollout_step* s, int dfun_channel, int temp_channel, const float* heater_temp, float x_min, float dx, float lc,
+                        float conductivity, float* flux_pred, float* flux_tgt, bf_stream_t stream);
 /* KL(p || q) of the Gaussian kernel density estimates of two sample sets, for R independent rows (examples/data_visualization.ipynb cell 4:
  * scipy.stats.gaussian_kde of each set, np.linspace grid, scipy.integrate.simpson; csrc/physics.hip).  Everything fp64 on the device, allocation-free,
  * capturable, no atomics (the same bits on every call, and a row has the same bits alone and in a batch).  p [R][n] (the simulation), q [R][m]
@@ -461,30 +479,21 @@ int64_t bf_bubble_census_ws_bytes(int64_t frames, int H, int W, int max_bubbles)
 int bf_bubble_census(const float* phi, int64_t frames, int H, int W, int connectivity, int max_bubbles, int32_t* count, int32_t* vapour_cells,
                      int32_t* attached, int32_t* area, float* centroid, unsigned char* on_heater, int32_t* labels, void* ws, int64_t ws_bytes,
                      bf_stream_t stream);
-/* The bubble census of ONE rollout step, of the prediction and of the simulation in one call.  pred, frames, field_stride, total_frames, nfields,
- * first, field / diff / div and the sizes are bf_rollout_score's.  step = one int32 in DEVICE memory, READ and never written: issue the call BEFORE
- * the step's bf_rollout_score.  With s = *step, row s * T + t of trajectory b of count_* / cells_* / attached_* [B][steps*T] and of
- * area_* [B][steps*T][max_bubbles] is bf_bubble_census' count / vapour_cells / attached / area of
- *   *_pred: pred * div + diff of channel sdf_channel (fp32 multiply, then add, unfused), frame t of trajectory b;
- *   *_tgt:  the stored raw frame first[b] + (s + 1) * T + t (clamped into the store) of field field[sdf_channel] (clamped likewise), through
- *           bf_clip_gather's nearest-neighbour map when Ho x Wo < H x W: the grid the model sees.
+/* The bubble census of ONE rollout step, of the prediction and of the simulation in one call.  s: see bf_rollout_step.  With the step number s = *s->step, row
+ * s * T + t of trajectory b of a side's count / cells / attached [B][steps*T] and area [B][steps*T][max_bubbles] is bf_bubble_census' count /
+ * vapour_cells / attached / area of
+ *   pred: pred * div + diff of channel sdf_channel (fp32 multiply, then add, unfused), frame t of trajectory b;
+ *   tgt:  the stored raw frame first[b] + (s + 1) * T + t (clamped into the store) of field field[sdf_channel] (clamped likewise), through
+ *         bf_clip_gather's nearest-neighbour map when Ho x Wo < H x W: the grid the model sees.
+ * labels may be NULL; otherwise the call also leaves its label images: labels [2 sides][2 halves][B][T][Ho][Wo] int32 is a ring of two steps, side 0
+ * the prediction, side 1 the simulation; the call for step s writes bf_bubble_census' label image of frame (b, t) into half s & 1 and touches nothing
+ * of the other half, which still holds step s - 1 for bf_rollout_bubble_links.
  * With s outside [0, steps) nothing is written.  ws: bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, max_bubbles) bytes, 16-byte aligned. */
-int bf_rollout_bubbles(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                       const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
-                       int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt, int32_t* attached_pred,
-                       int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W,
-                       int Ho, int Wo, int steps, bf_stream_t stream);
-/* bf_rollout_bubbles that also leaves its label images: labels [2 sides][2 halves][B][T][Ho][Wo] int32 is a ring of two steps, side 0 the prediction,
- * side 1 the simulation; the call for step s = *step writes bf_bubble_census' label image of frame (b, t) into half s & 1 and touches nothing of the
- * other half, which still holds step s - 1 for bf_rollout_bubble_links.  Everything else, the step counter included, is bf_rollout_bubbles'. */
-int bf_rollout_bubbles_labelled(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                                const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int connectivity,
-                                int max_bubbles, int32_t* count_pred, int32_t* count_tgt, int32_t* cells_pred, int32_t* cells_tgt, int32_t* attached_pred,
-                                int32_t* attached_tgt, int32_t* area_pred, int32_t* area_tgt, int32_t* labels, void* ws, int64_t ws_bytes, int B, int T,
-                                int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
-/* Bubbles followed from frame to frame (csrc/bubble_tracks.hip; the reference has no program for it).  labels [sequences][T][H][W], count / attached
- * [sequences][T] and area [sequences][T][max_bubbles] are what bf_bubble_census left for sequences * T frames; a pair is two consecutive frames a, b
- * of one sequence, pair row q = sequence * (T - 1) + t for frames t, t + 1.  With ka = min(count_a, max_bubbles), kb likewise (labels above them count
+int bf_rollout_bubbles(const bf_rollout_step* s, int sdf_channel, int connectivity, int max_bubbles, const bf_census_rows* pred,
+                       const bf_census_rows* tgt, int32_t* labels, void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* Bubbles followed from frame to frame (csrc/bubble_tracks.hip; the reference has no program for it).  labels [sequences][T][H][W] and census' count / attached
+ * [sequences][T] and area [sequences][T][max_bubbles] (cells is unread and may be NULL) are what bf_bubble_census left for sequences * T frames; a pair is two consecutive frames a, b
+ * of one sequence, pair row q = sequence * (T - 1) + t of the link rows for frames t, t + 1.  With ka = min(count_a, max_bubbles), kb likewise (labels above them count
  * as liquid) and overlap[i][j] = the number of cells with La == i and Lb == j, per pair:
  *   successor [pairs][max_bubbles] int32       slot i - 1: the j of the largest overlap[i][j] > 0, ties to the smallest j, 0 if none;
  *   n_successors                               the number of j with overlap[i][j] > 0;
@@ -499,32 +508,26 @@ int bf_rollout_bubbles_labelled(const float* pred, const float* frames, int64_t 
  * irrelevant before and after (0 from the query: sizes out of range). */
 int64_t bf_bubble_links_lds_entries(void);
 int64_t bf_bubble_links_ws_bytes(int64_t pairs, int max_bubbles);
-int bf_bubble_links(const int32_t* labels, const int32_t* count, const int32_t* attached, const int32_t* area, int64_t sequences, int T, int H, int W,
-                    int max_bubbles, int32_t* successor, int32_t* n_successors, int32_t* predecessor, int32_t* n_predecessors, int32_t* departure_area,
-                    int32_t* events, void* ws, int64_t ws_bytes, bf_stream_t stream);
+int bf_bubble_links(const int32_t* labels, const bf_census_rows* census, int64_t sequences, int T, int H, int W, int max_bubbles,
+                    const bf_link_rows* links, void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* Track ids from the links: bubble j of frame t + 1 continues bubble i of frame t iff predecessor[j] == i and successor[i] == j; every other bubble
  * (every bubble of frame 0, and of the later frame of a pair that holds -1) starts a new track.  Tracks are numbered 1, 2, ... per sequence in order of
  * (frame, bubble number) of their first member.  count [sequences][T]; successor, predecessor [sequences][T - 1][max_bubbles] (unread when T == 1);
  * track_id [sequences][T][max_bubbles] int32, 0 in unused slots; n_tracks [sequences] int32.  One workgroup per sequence walks the frames in order. */
 int bf_bubble_track_ids(const int32_t* count, const int32_t* successor, const int32_t* predecessor, int64_t sequences, int T, int max_bubbles,
                         int32_t* track_id, int32_t* n_tracks, bf_stream_t stream);
-/* bf_bubble_links for ONE rollout step, both sides in one call, on the ring bf_rollout_bubbles_labelled filled and the census rows it wrote.  step is
- * READ and never written: issue the call after the step's bf_rollout_bubbles_labelled and BEFORE its bf_rollout_score.  With s = *step, per side and
- * trajectory b the pairs that end in a frame of step s: (t - 1, t) for t = 1 .. T - 1 from half s & 1, and for s > 0 the pair (frame T - 1 of half
- * (s - 1) & 1, frame 0 of half s & 1).  The pair that ends in frame t goes to row s * T + t - 1 of [B][steps*T - 1][max_bubbles] (events:
- * [B][steps*T - 1][5]); no other row is touched, and with s outside [0, steps) nothing is written.  count_* / attached_* [B][steps*T] and
- * area_* [B][steps*T][max_bubbles] are the census rows.  pred, frames, ..., div and the sizes are bf_rollout_score's (checked, the fields unread);
- * steps * T >= 2.  ws: bf_bubble_links_ws_bytes(2 * B * T, max_bubbles) bytes, 16-byte aligned. */
-int bf_rollout_bubble_links(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                            const int32_t* step, const int32_t* field, const float* diff, const float* div, int max_bubbles, const int32_t* labels,
-                            const int32_t* count_pred, const int32_t* count_tgt, const int32_t* attached_pred, const int32_t* attached_tgt,
-                            const int32_t* area_pred, const int32_t* area_tgt, int32_t* successor_pred, int32_t* successor_tgt, int32_t* n_successors_pred,
-                            int32_t* n_successors_tgt, int32_t* predecessor_pred, int32_t* predecessor_tgt, int32_t* n_predecessors_pred,
-                            int32_t* n_predecessors_tgt, int32_t* departure_area_pred, int32_t* departure_area_tgt, int32_t* events_pred,
-                            int32_t* events_tgt, void* ws, int64_t ws_bytes, int B, int T, int C, int H, int W, int Ho, int Wo, int steps,
-                            bf_stream_t stream);
+/* bf_bubble_links for ONE rollout step, both sides in one call, on the ring `labels` the step's bf_rollout_bubbles filled and the census rows it
+ * wrote: issue the call after it.  s: see bf_rollout_step (checked, the fields unread).  With the step number s = *s->step, per side and trajectory b the pairs that
+ * end in a frame of step s: (t - 1, t) for t = 1 .. T - 1 from half s & 1, and for s > 0 the pair (frame T - 1 of half (s - 1) & 1, frame 0 of
+ * half s & 1).  The pair that ends in frame t goes to row s * T + t - 1 of a side's link rows [B][steps*T - 1][max_bubbles] (events:
+ * [B][steps*T - 1][5]); no other row is touched, and with s outside [0, steps) nothing is written.  census_*: count / attached [B][steps*T] and area
+ * [B][steps*T][max_bubbles]; cells is unread and may be NULL.  steps * T >= 2.  ws: bf_bubble_links_ws_bytes(2 * B * T, max_bubbles) bytes,
+ * 16-byte aligned. */
+int bf_rollout_bubble_links(const bf_rollout_step* s, int max_bubbles, const int32_t* labels, const bf_census_rows* census_pred,
+                            const bf_census_rows* census_tgt, const bf_link_rows* links_pred, const bf_link_rows* links_tgt, void* ws,
+                            int64_t ws_bytes, bf_stream_t stream);
 /* Where a prediction is wrong and at which scales (csrc/spectra.hip; the reference has no program for it).  pred, target
- * [frames][H][W] fp32, e = pred - target in fp64; sdf (optional) [frames][H][W] fp32 in physical units.  Any output may be NULL and is then not computed:
+ * [frames][H][W] fp32, e = pred - target in fp64; sdf (optional) [frames][H][W] fp32 in physical units.  Any member of rows may be NULL and is then not computed:
  *   rmse, max_error, boundary_rmse [frames] fp32   sqrt(mean e^2); max |e| (NaN if any e is NaN); the root mean square over the outer ring of cells;
  *   interface_rmse [frames] fp32, interface_cells [frames] int32   the same over the cells whose (2 r + 1)^2 window (r = interface_radius >= 1, clipped to
  *     the frame) holds both vapour (sdf > 0) and liquid (anything else: zero and NaN too), and their number; NaN where there is none.  Both need sdf;
@@ -537,19 +540,13 @@ int bf_rollout_bubble_links(const float* pred, const float* frames, int64_t fiel
  * makes the host wait.  ws: bf_field_errors_ws_bytes(frames, H, W) bytes, 16-byte aligned (0 from the query: sizes out of range). */
 int64_t bf_field_errors_ws_bytes(int64_t frames, int H, int W);
 int bf_field_errors(const float* pred, const float* target, const float* sdf, int64_t frames, int H, int W, int interface_radius, int lo, int hi,
-                    int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse, int32_t* interface_cells,
-                    float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target, void* ws, int64_t ws_bytes,
-                    bf_stream_t stream);
+                    int want_spectra, const bf_error_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* bf_field_errors of ONE rollout step: frame (b, t, c) of the prediction against the stored frame first[b] + (s + 1) * T + t of field[c], read where it
  * lies with the bits bf_clip_gather returns; the interface mask from the raw stored frame of channel sdf_channel (-1: none, the interface rows must be
- * NULL), one mask for all C channels of (b, t).  Rows (b, s * T + t, c) of [B][steps*T][C]([K] or [3]) are written and no other; with s = *step outside
- * [0, steps) nothing is written.  step is READ and never written: issue the call BEFORE the step's bf_rollout_score.  pred, frames, ..., div and the
- * sizes are bf_rollout_score's.  ws: bf_field_errors_ws_bytes(B * T * C, Ho, Wo) bytes, 16-byte aligned. */
-int bf_rollout_errors(const float* pred, const float* frames, int64_t field_stride, int64_t total_frames, int nfields, const int64_t* first,
-                      const int32_t* step, const int32_t* field, const float* diff, const float* div, int sdf_channel, int interface_radius, int lo,
-                      int hi, int want_spectra, float* rmse, float* max_error, float* boundary_rmse, float* interface_rmse, int32_t* interface_cells,
-                      float* spectral_error, float* spectrum_error, float* spectrum_pred, float* spectrum_target, void* ws, int64_t ws_bytes, int B, int T,
-                      int C, int H, int W, int Ho, int Wo, int steps, bf_stream_t stream);
+ * NULL), one mask for all C channels of (b, t).  Rows (b, s * T + t, c) of [B][steps*T][C]([K] or [3]) are written and no other; with the step number s = *s->step outside
+ * [0, steps) nothing is written.  s: see bf_rollout_step.  ws: bf_field_errors_ws_bytes(B * T * C, Ho, Wo) bytes, 16-byte aligned. */
+int bf_rollout_errors(const bf_rollout_step* s, int sdf_channel, int interface_radius, int lo, int hi, int want_spectra, const bf_error_rows* rows,
+                      void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
@@ -841,6 +838,8 @@ void bf_prof_enable(int on);
 int bf_prof_report(char* buf, int n);   /* JSON {kernel: {calls, ms, flops, bytes}}; bytes written or -1 */
 
 const char* bf_last_error(void);
+/* 2.  The number changes when a declaration of this header changes or is removed (a caller built against the older header would pass garbage without
+ * any error); a declaration that is only added leaves it as it is. */
 int bf_abi_version(void);
 
 #ifdef __cplusplus

@@ -25,7 +25,82 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(h, n), n
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
-    assert h.bf_abi_version() == 1
+    assert h.bf_abi_version() == 2
+
+
+RECORDS = {"bf_rollout_step": "RolloutStep", "bf_census_rows": "CensusRows", "bf_link_rows": "LinkRows", "bf_error_rows": "ErrorRows"}
+
+
+def _record_fields(name):
+    """[(field, ctypes type)] of `typedef struct name { ... } name;` as the header declares it: any pointer is a c_void_p, int64_t a c_int64,
+    int32_t / int a c_int32; a declaration may name several fields (`float *a, *b;`, the star belongs to the declarator)."""
+    import ctypes as C
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "bubbleformer_hip.h")).read(), flags=re.S)
+    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), txt, flags=re.S)
+    assert m, name
+    scalars = {"int64_t": C.c_int64, "int32_t": C.c_int32, "int": C.c_int32}
+    fields = []
+    for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+        base, rest = re.match(r"(?:const\s+)?(\w+)\s*(.*)$", decl, flags=re.S).groups()
+        for d in rest.split(","):
+            fields.append((d.replace("*", "").strip(), C.c_void_p if "*" in d else scalars[base]))
+    return fields
+
+
+@pytest.mark.parametrize("name", sorted(RECORDS))
+def test_record_mirrors_the_header(name):
+    """A ctypes record has the header's fields under the header's names, in its order and of its types, and neither has padding: two fields
+    of one type in the wrong order are a different list of names, which the positional argument lists could not show."""
+    import ctypes as C
+    from bubbleformer_amd import _lib
+    rec = getattr(_lib, RECORDS[name])
+    declared = _record_fields(name)
+    assert [(n, t) for n, t in rec._fields_] == declared
+    assert C.sizeof(rec) == sum(C.sizeof(t) for _, t in declared)
+
+
+def _null_pointer_calls():
+    """name -> (call with every record NULL, call with full records whose first required pointer alone is NULL); every other pointer is the
+    address of a host buffer nothing reads, every size valid.  bf_field_errors' record has no required member: there it is `pred`."""
+    import ctypes as C
+    from bubbleformer_amd import _lib as L
+    buf = (C.c_char * 64)()
+    p = C.addressof(buf)
+
+    def step(**kw):
+        return L.RolloutStep(**{**dict(pred=p, frames=p, field_stride=64, total_frames=4, first=p, step=p, field=p, diff=p, div=p, nfields=1, B=1, T=2,
+                                       C=1, H=4, W=4, Ho=4, Wo=4, steps=1), **kw})
+
+    def census(**kw):
+        return L.CensusRows(**{**dict(count=p, cells=p, attached=p, area=p), **kw})
+
+    links = L.LinkRows(*[p] * 6)
+    errs, ref = L.ErrorRows(), C.byref
+    return {
+        "bf_rollout_score": lambda h, s: h.bf_rollout_score(s and ref(step(pred=None)), -1, 1.0, p, p, None, None, None, None, p, 1 << 20, None),
+        "bf_rollout_heatflux": lambda h, s: h.bf_rollout_heatflux(s and ref(step(pred=None)), 0, 0, p, 0.0, 1.0, 1.0, 1.0, p, p, None),
+        "bf_rollout_bubbles": lambda h, s: h.bf_rollout_bubbles(s and ref(step(pred=None)), 0, 4, 1, s and ref(census()), s and ref(census()), None, p, 1 << 20, None),
+        "bf_rollout_bubble_links": lambda h, s: h.bf_rollout_bubble_links(s and ref(step(pred=None)), 1, p, s and ref(census()), s and ref(census()),
+                                                                          s and ref(links), s and ref(links), p, 1 << 20, None),
+        "bf_rollout_errors": lambda h, s: h.bf_rollout_errors(s and ref(step(pred=None)), -1, 1, 0, 0, 0, s and ref(errs), p, 1 << 20, None),
+        "bf_bubble_links": lambda h, s: h.bf_bubble_links(p, s and ref(census(count=None)), 1, 2, 4, 4, 1, s and ref(links), p, 1 << 20, None),
+        "bf_field_errors": lambda h, s: h.bf_field_errors(p if not s else None, p, None, 1, 4, 4, 1, 0, 0, 0, s and ref(errs), p, 1 << 20, None),
+    }
+
+
+@pytest.mark.parametrize("name", ["bf_rollout_score", "bf_rollout_heatflux", "bf_rollout_bubbles", "bf_rollout_bubble_links", "bf_rollout_errors",
+                                  "bf_bubble_links", "bf_field_errors"])
+def test_null_record_and_null_member_are_refused(name):
+    """Each re-signed entry point refuses a NULL record, and a record whose first required pointer is NULL, as its null pointer: both return at
+    the first check, before any HIP call, so no GPU is needed."""
+    from bubbleformer_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    h = _lib.lib()
+    call = _null_pointer_calls()[name]
+    for with_records in (None, True):
+        assert call(h, with_records) != 0
+        assert h.bf_last_error().decode().endswith(name + ": null pointer"), (with_records, h.bf_last_error())
 
 
 def test_register_audit_no_spills_beside_counted_waits():

@@ -153,8 +153,8 @@ def test_report_helpers_and_saved_keys(tmp_path):
 def test_entry_points_are_declared_and_bound():
     from bubbleformer_amd import _lib, ops
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "bubbleformer_hip.h")).read(), flags=re.S)
-    for name in ("bf_bubble_links", "bf_bubble_links_ws_bytes", "bf_bubble_links_lds_entries", "bf_bubble_track_ids", "bf_rollout_bubbles_labelled",
-                 "bf_rollout_bubble_links"):
+    assert not re.search(r"\bbf_rollout_bubbles_labelled\b", txt)                     # bf_rollout_bubbles takes the ring itself
+    for name in ("bf_bubble_links", "bf_bubble_links_ws_bytes", "bf_bubble_links_lds_entries", "bf_bubble_track_ids", "bf_rollout_bubble_links"):
         assert name in _lib.SIGNATURES, name
         m = re.search(r"\b(?:int|int64_t)\s+%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S)
         assert m, name

@@ -142,6 +142,6 @@ def test_abi_declares_the_clip_entry_points():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     h = _lib.lib()
-    assert all(hasattr(h, n) for n in new) and h.bf_abi_version() == 1
+    assert all(hasattr(h, n) for n in new) and h.bf_abi_version() == 2
     # the slab rule depends on n alone: at most 1024 partials, one for a short buffer
     assert h.bf_grad_norm_ws_doubles(64) == 1 and h.bf_grad_norm_ws_doubles(4160) == 2 and 1 <= h.bf_grad_norm_ws_doubles(1 << 34) <= 1024
