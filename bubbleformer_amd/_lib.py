@@ -100,6 +100,11 @@ class ErrorRows(C.Structure):
                                   "spectrum_pred", "spectrum_target")]
 
 
+class EnsembleRows(C.Structure):
+    """bf_ensemble_rows: mean_rmse, spread and crps are required together; rank_hist and mean may be NULL."""
+    _fields_ = [(n, vp) for n in ("mean_rmse", "spread", "crps", "rank_hist", "mean")]
+
+
 class RenderTile(C.Structure):
     """bf_render_tile: what one slot of an image shows (bf_render_tiles)."""
     _fields_ = [("a", fp), ("b", fp), ("mask", fp), ("frame_stride", i64), ("slot_stride", i64), ("mask_frame_stride", i64), ("mask_slot_stride", i64),
@@ -227,6 +232,9 @@ SIGNATURES = {
     "bf_field_errors_ws_bytes": (i64, [i64, C.c_int, C.c_int]),
     "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),
     "bf_rollout_errors": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),
+    "bf_ensemble_scores_ws_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_ensemble_scores": (C.c_int, [fp, i64, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(EnsembleRows), vp, i64, vp]),
+    "bf_rollout_ensemble": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, P(EnsembleRows), vp, i64, vp]),
     "bf_render_ranges_ws_doubles": (i64, []),
     "bf_render_ranges": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "bf_render_tiles": (C.c_int, [P(RenderTile), C.c_int, P(RenderGeom), i64, vp, vp, vp, vp]),

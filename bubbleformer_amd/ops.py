@@ -1329,6 +1329,70 @@ def rollout_errors(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor
                                       ws.numel(), stream), "bf_rollout_errors")
 
 
+_ENSEMBLE_ROWS = ("mean_rmse", "spread", "crps", "rank_hist", "mean")
+
+
+def ensemble_workspace(frames: int, members: int, H: int, W: int, device) -> torch.Tensor:
+    """The workspace ``ensemble_scores`` (and, with frames = Bt * T * C, ``rollout_ensemble``) needs: allocate once, outside a graph capture.  It
+    holds the fp64 and int32 partials of every workgroup; a member count outside 2 .. 32 is refused here, before any launch."""
+    nbytes = L.lib().bf_ensemble_scores_ws_bytes(int(frames), int(members), int(H), int(W))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"ensemble_workspace: {frames} frames of {H} x {W} with {members} members are not supported (2 to 32 members, at "
+                                     "least one frame of at least one pixel)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _ensemble_rows(who: str, device, lead: tuple, members: int, H: int, W: int, rows: dict, ws: torch.Tensor):
+    """The outputs of the ensemble calls by name, checked -> bf_ensemble_rows: mean_rmse, spread and crps are required, rank_hist and mean optional."""
+    unknown = set(rows) - set(_ENSEMBLE_ROWS)
+    if unknown:
+        raise L.BubbleformerHipError(f"{who}: unknown outputs {sorted(unknown)}")
+    f32 = torch.float32
+    shapes = {"mean_rmse": (lead, f32), "spread": (lead, f32), "crps": (lead, f32), "rank_hist": (lead + (members + 1,), torch.int32),
+              "mean": (lead + (H, W), f32)}
+    want = {k: (rows.get(k), shape, dtype) for k, (shape, dtype) in shapes.items()}
+    want["ws"] = (ws, (ws.numel(),), torch.uint8)
+    _check_tensors(who, device, want, ("rank_hist", "mean"))
+    return L.EnsembleRows(**{k: _p(rows.get(k)) for k in _ENSEMBLE_ROWS})
+
+
+def ensemble_scores(members: torch.Tensor, target: torch.Tensor, ws: torch.Tensor, fair: bool = False, **rows: Optional[torch.Tensor]) -> None:
+    """The statistics across the members of an ensemble, per frame (bf_ensemble_scores; include/bubbleformer_hip.h has the contract): members
+    (M, F, H, W) fp32 whose member blocks are contiguous (``members.stride(0)`` may exceed F * H * W: it is the call's member_stride) against target
+    (F, H, W) fp32.  rows: mean_rmse, spread, crps (F,) fp32, and optionally rank_hist (F, M + 1) int32 and mean (F, H, W) fp32.  ws:
+    ``ensemble_workspace(F, M, H, W)``.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(members)
+    if members.dim() != 4 or members.dtype != torch.float32 or not members[0].is_contiguous() or (members.shape[0] > 1 and members.stride(0) < members[0].numel()):
+        raise L.BubbleformerHipError("ensemble_scores: members must be an fp32 (M, frames, H, W) tensor of contiguous member blocks")
+    M, F, H, W = members.shape
+    _check_tensors("ensemble_scores", members.device, {"target": (target, (F, H, W), torch.float32)})
+    rec = _ensemble_rows("ensemble_scores", members.device, (F,), M, H, W, rows, ws)
+    need = L.lib().bf_ensemble_scores_ws_bytes(F, M, H, W)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("ensemble_scores: 2 to 32 members, and a workspace of ensemble_workspace(frames, members, H, W)")
+    L.check(L.lib().bf_ensemble_scores(_p(members), members.stride(0), _p(target), F, M, H, W, int(bool(fair)), C.byref(rec), _p(ws), ws.numel(),
+                                       _stream()), "bf_ensemble_scores")
+
+
+def rollout_ensemble(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int, members: int,
+                     ws: torch.Tensor, fair: bool = False, **rows: Optional[torch.Tensor]) -> None:
+    """The ensemble rows of one rollout step (bf_rollout_ensemble; include/bubbleformer_hip.h has the contract): pred (M * Bt, T, C, Ho, Wo) holds the
+    members as row blocks, member-major; rows (b, s * T + t, c) of mean_rmse / spread / crps (Bt, steps*T, C), rank_hist (.., M + 1) and mean
+    (.., Ho, Wo) are written against the stored frame ``first[b] + (s + 1) * T + t``, s = the int32 ``step`` tensor ON THE DEVICE, which this call
+    only reads -- issue it BEFORE the step's ``rollout_score``.  ws: ``ensemble_workspace(Bt * T * C, M, Ho, Wo)``.  Allocates nothing."""
+    rec, stream = _rollout_step_args("rollout_ensemble", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    M = int(members)
+    if not 2 <= M <= 32 or B % M:
+        raise L.BubbleformerHipError(f"rollout_ensemble: {M} members (2 to 32) must divide the prediction's {B} rows")
+    Bt = B // M
+    out = _ensemble_rows("rollout_ensemble", pred.device, (Bt, steps * T, Cn), M, Ho, Wo, rows, ws)
+    need = L.lib().bf_ensemble_scores_ws_bytes(Bt * T * Cn, M, Ho, Wo)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_ensemble: the workspace is smaller than ensemble_workspace(Bt * T * C, members, Ho, Wo)")
+    L.check(L.lib().bf_rollout_ensemble(C.byref(rec), M, int(bool(fair)), C.byref(out), _p(ws), ws.numel(), stream), "bf_rollout_ensemble")
+
+
 def grad_norm_workspace(n: int, device) -> torch.Tensor:
     """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
     return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)

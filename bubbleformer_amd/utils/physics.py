@@ -370,3 +370,98 @@ def field_errors(pred: torch.Tensor, target: torch.Tensor, sdf: Optional[torch.T
     ops.field_errors(p, y, phi, ops.field_errors_workspace(F, H, W, p.device), int(spec.interface_radius), int(spec.bands[0]), int(spec.bands[1]),
                      spec.spectra, **rows)
     return FieldErrors(**{k: (rows[k].reshape(lead + tuple(rows[k].shape[1:])) if k in rows else None) for k in ops._ERROR_ROWS})
+
+
+MAX_ENSEMBLE_MEMBERS = 32              # bf_ensemble_scores' limit: the members of a pixel are held in registers
+
+
+@dataclasses.dataclass(frozen=True)
+class EnsembleSpec:
+    """An ensemble rollout (``evaluate_rollouts(..., ensemble=EnsembleSpec(members, std))``): every trajectory is rolled out ``members`` times
+    from perturbed copies of its first input clip, and every predicted frame is scored across the members.
+
+    members         2 .. 32 rollouts per trajectory.
+    std             a float >= 0, or one per input field, in the units the model sees (after normalisation): the standard deviation of the
+                    Gaussian noise added to the first input clip (``add_gaussian_noise``); later steps feed the predictions back unperturbed.
+    relative        multiply ``std`` by each input field's standard deviation over the store (``DeviceClipStore.field_std()``).
+    seed            the generator's key: the noise of member m of the trajectory from sample s is a pure function of (seed, s, m, element).
+    control         member 0 is the unperturbed rollout (its rows are those of the plain call).
+    fair            the CRPS' pair term is weighted 1 / (2 M (M - 1)) instead of 1 / (2 M^2): unbiased for the CRPS of the underlying distribution.
+    rank_histogram  keep the rank histogram of the truth among the members.
+    keep_mean       keep the ensemble mean of every predicted frame (as large as one member's archive)."""
+    members: int
+    std: Union[float, tuple]
+    relative: bool = False
+    seed: int = 0
+    control: bool = True
+    fair: bool = False
+    rank_histogram: bool = True
+    keep_mean: bool = False
+
+    def __post_init__(self):
+        from .noise import NoiseSpec
+        m = self.members
+        if isinstance(m, bool) or not isinstance(m, int) or not 2 <= m <= MAX_ENSEMBLE_MEMBERS:
+            raise ValueError(f"EnsembleSpec: members {m!r} must be an integer from 2 to {MAX_ENSEMBLE_MEMBERS}")
+        for name in ("control", "fair", "rank_histogram", "keep_mean"):
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"EnsembleSpec: {name} {getattr(self, name)!r} must be a bool")
+        try:
+            noise = NoiseSpec(self.std, self.relative, self.seed)       # std, relative and seed are a NoiseSpec's: one set of rules
+        except ValueError as e:
+            raise ValueError(str(e).replace("NoiseSpec", "EnsembleSpec")) from None
+        object.__setattr__(self, "std", noise.std)
+
+    def sigma(self, channels: int, field_std: Optional[Sequence[float]] = None) -> list:
+        """The per-channel standard deviations for a clip of ``channels`` input fields; ``relative`` needs ``field_std`` (one per field)."""
+        from .noise import NoiseSpec
+        return NoiseSpec(self.std, self.relative, self.seed).sigma(channels, field_std)
+
+
+@dataclasses.dataclass
+class EnsembleScores:
+    """What ``ensemble_scores`` returns; every tensor is on the device and keeps the leading dims of the target."""
+    mean_rmse: torch.Tensor                         # (...)            fp32  RMSE of the ensemble mean
+    spread: torch.Tensor                            # (...)            fp32  sqrt(mean over pixels of the unbiased member variance)
+    crps: torch.Tensor                              # (...)            fp32  mean over pixels of the continuous ranked probability score
+    rank_hist: Optional[torch.Tensor]               # (..., M + 1)     int32 pixels whose truth has exactly r members strictly below it, or None
+    mean: Optional[torch.Tensor]                    # (..., H, W)      fp32  the ensemble mean, or None
+    members: int
+
+    def spread_skill(self) -> torch.Tensor:
+        """spread * sqrt((M + 1) / M) / mean_rmse: 1 for a reliable ensemble, below 1 for an under-dispersive one.  Never synchronises."""
+        return self.spread * math.sqrt((self.members + 1) / self.members) / self.mean_rmse
+
+
+def ensemble_scores(members: torch.Tensor, target: torch.Tensor, *, fair: bool = False, rank_histogram: bool = True,
+                    return_mean: bool = False) -> EnsembleScores:
+    """How well the spread of an ensemble matches its error, per frame, on the device (``ops.ensemble_scores``): members
+    (..., M, H, W) against target (..., H, W), contiguous fp32 device tensors, 2 <= M <= 32.  Per frame: the RMSE of the member mean, the spread
+    (root of the mean unbiased member variance), the CRPS in its pairwise form (``fair``: the pair term over M (M - 1) instead of M^2) and the rank
+    histogram of the truth (strictly-below counts).  More than one frame costs one transposing copy of the members: the kernel reads member-major
+    blocks.  fp64 arithmetic, one rounding, the same bits on every call and for a frame alone or in a batch; never synchronises.  There is no
+    CPU path."""
+    from .. import ops
+    if not isinstance(members, torch.Tensor) or not isinstance(target, torch.Tensor) or not members.is_cuda or not target.is_cuda:
+        raise L.BubbleformerHipError("ensemble_scores runs only on a ROCm GPU (gfx950): got a CPU tensor; there is no CPU fallback")
+    if members.dim() < 3 or target.dim() != members.dim() - 1 or tuple(members.shape[:-3]) + tuple(members.shape[-2:]) != tuple(target.shape):
+        raise ValueError(f"ensemble_scores expects members (..., M, H, W) and target (..., H, W), got {tuple(members.shape)} and {tuple(target.shape)}")
+    if members.dtype != torch.float32 or target.dtype != torch.float32 or not members.is_contiguous() or not target.is_contiguous():
+        raise ValueError("ensemble_scores expects contiguous fp32 tensors")
+    lead, (M, H, W) = tuple(target.shape[:-2]), members.shape[-3:]
+    if not 2 <= M <= MAX_ENSEMBLE_MEMBERS:
+        raise ValueError(f"ensemble_scores: {M} members, 2 to {MAX_ENSEMBLE_MEMBERS} are supported")
+    F = target.numel() // (H * W) if H * W else 0
+    if F < 1:
+        raise ValueError(f"ensemble_scores needs at least one frame of at least one pixel, got {tuple(target.shape)}")
+    x = members.reshape(F, M, H, W).transpose(0, 1)
+    x = x.contiguous() if F > 1 else x.reshape(M, 1, H, W)
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=x.device)
+    rows = {k: new(torch.float32, F) for k in ("mean_rmse", "spread", "crps")}
+    if rank_histogram:
+        rows["rank_hist"] = new(torch.int32, F, M + 1)
+    if return_mean:
+        rows["mean"] = new(torch.float32, F, H, W)
+    ops.ensemble_scores(x, target.reshape(F, H, W), ops.ensemble_workspace(F, M, H, W, x.device), fair, **rows)
+    shaped = {k: (rows[k].reshape(lead + tuple(rows[k].shape[1:])) if k in rows else None) for k in ops._ENSEMBLE_ROWS}
+    return EnsembleScores(members=int(M), **shaped)

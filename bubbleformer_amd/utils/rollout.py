@@ -158,6 +158,38 @@ class RolloutReport:
     spectrum_error = None                               # (B, steps*T, C, K)  fp32 shell power of e
     spectrum_pred = None                                # (B, steps*T, C, K)  fp32 shell power of the prediction
     spectrum_target = None                              # (B, steps*T, C, K)  fp32 shell power of the target
+    # with ensemble=EnsembleSpec(M, ...): B = M * Bt rows above, member-major (row m * Bt + b is member m of trajectory b), and the statistics across
+    # the members (physics.ensemble_scores) per trajectory, else None.  Attributes as the error rows are, for the same reason
+    ensemble_members = None                             # M
+    ensemble_mean_rmse = None                           # (Bt, steps*T, C)         fp32 RMSE of the member mean
+    ensemble_spread = None                              # (Bt, steps*T, C)         fp32 sqrt(mean unbiased member variance)
+    ensemble_crps = None                                # (Bt, steps*T, C)         fp32 mean CRPS over the pixels
+    ensemble_rank_hist = None                           # (Bt, steps*T, C, M + 1)  int32 pixels whose truth has r members strictly below it
+    ensemble_mean = None                                # (Bt, steps*T, C, Ho, Wo) fp32 the member mean (EnsembleSpec(keep_mean=True))
+
+    def _ensemble(self):
+        if self.ensemble_members is None:
+            raise ValueError("this report has no ensemble rows: call evaluate_rollouts(..., ensemble=EnsembleSpec(members, std))")
+        return int(self.ensemble_members)
+
+    def by_member(self, t: torch.Tensor) -> torch.Tensor:
+        """A per-member tensor of the report (M * Bt, ...) as a view (M, Bt, ...)."""
+        M = self._ensemble()
+        return t.view(M, t.shape[0] // M, *t.shape[1:])
+
+    def spread_skill(self) -> torch.Tensor:
+        """(Bt, steps*T, C) fp32: ensemble_spread * sqrt((M + 1) / M) / ensemble_mean_rmse, 1 for a reliable ensemble (below 1: the members
+        agree more than their mean is right).  On the device; never synchronises."""
+        M = self._ensemble()
+        return self.ensemble_spread * float(np.sqrt((M + 1) / M)) / self.ensemble_mean_rmse
+
+    def rank_histogram(self) -> torch.Tensor:
+        """(Bt, C, M + 1) int64: the rank histogram summed over the frames (flat for a reliable ensemble, U-shaped for an under-dispersive
+        one).  On the device; never synchronises."""
+        self._ensemble()
+        if self.ensemble_rank_hist is None:
+            raise ValueError("this report kept no rank histogram: use EnsembleSpec(rank_histogram=True)")
+        return self.ensemble_rank_hist.sum(dim=1, dtype=torch.int64)
 
     def save(self, path) -> None:
         """``torch.save`` of the report's tensors, in the spirit of scripts/inference.py:265."""
@@ -174,7 +206,7 @@ class RolloutReport:
         if self.bubble_events_pred is not None:
             for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
-        for key in _ERROR_KEYS:
+        for key in _ERROR_KEYS + _ENSEMBLE_KEYS:
             if getattr(self, key) is not None:
                 out[key] = getattr(self, key)
         torch.save(out, path)
@@ -280,6 +312,7 @@ _TRACK_KEYS = ("bubble_events_pred", "bubble_events_target", "bubble_successor_p
                "bubble_predecessor_target", "bubble_departure_area_pred", "bubble_departure_area_target")
 _ERROR_KEYS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
                "spectrum_target")
+_ENSEMBLE_KEYS = ("ensemble_members", "ensemble_mean_rmse", "ensemble_spread", "ensemble_crps", "ensemble_rank_hist", "ensemble_mean")
 _BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
                 "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
 
@@ -292,7 +325,8 @@ def _to_device(values, dtype, device) -> torch.Tensor:
 def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
                       keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None,  # noqa: F821 (physics.HeaterSpec)
                       bubbles: "Optional[BubbleSpec]" = None,  # noqa: F821 (physics.BubbleSpec)
-                      errors: "Optional[ErrorSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.ErrorSpec)
+                      errors: "Optional[ErrorSpec]" = None,  # noqa: F821 (physics.ErrorSpec)
+                      ensemble: "Optional[EnsembleSpec]" = None) -> RolloutReport:  # noqa: F821 (physics.EnsembleSpec)
     """Roll ``model`` out over ``B = len(starts)`` test trajectories at once and score every predicted frame against the simulation.
 
     data: a ``BubbleForecast`` (its device store is made on the model's device) or a ``DeviceClipStore``; starts: dataset sample indices.
@@ -309,12 +343,27 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows.  With ``errors`` (a ``physics.ErrorSpec``) one more call before the scoring
     call (``ops.rollout_errors``) leaves ``physics.field_errors``' rows of every predicted frame and field against the stored target: ``rmse``,
     ``max_error``, ``boundary_rmse``, the interface rows when the signed-distance field is among the outputs, and with ``spectra`` the shell
-    spectra and the band-limited errors; ``None`` leaves the launches and the report as they are without it.  Never synchronises."""
+    spectra and the band-limited errors; ``None`` leaves the launches and the report as they are without it.  Never synchronises.
+
+    With ``ensemble`` (a ``physics.EnsembleSpec`` of M members) the call is the plain call on ``list(starts) * M`` -- every row of the report,
+    the heat-flux, bubble and error rows included, is then per member, (M * Bt, ...) member-major, ``report.by_member(t)`` views it as
+    (M, Bt, ...), and ``render_rollouts(report, data, list(starts) * M, ...)`` draws it -- plus two things.  After the input gather, member m's
+    block of the first input clips is perturbed in place by one ``add_gaussian_noise`` launch with ``draw=m`` and the trajectories' sample
+    numbers as ids (member 0 stays as gathered with ``control``): the noise of member m of the trajectory from sample s is a pure function of
+    (seed, s, m, element), whatever the other trajectories, Bt or M of the call.  And one more call before the scoring call
+    (``ops.rollout_ensemble``, captured with it) leaves the statistics across the members of every predicted frame and field:
+    ``ensemble_mean_rmse``, ``ensemble_spread``, ``ensemble_crps`` (Bt, steps*T, C), ``ensemble_rank_hist`` and, if kept, ``ensemble_mean``;
+    ``report.spread_skill()`` and ``report.rank_histogram()`` read them.  ``EnsembleSpec(relative=True)`` takes ``store.field_std()`` first,
+    which is ONE host synchronisation before the loop; nothing else of the call waits for the device."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
     store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
     ds = store.ds
+    members = None
+    if ensemble is not None:
+        members, trajectories = int(ensemble.members), [int(i) for i in starts]
+        starts = trajectories * members                 # member-major: row m * Bt + b is member m of trajectory b
     plan = plan_rollouts(ds, starts, steps, getattr(model, "time_window", None))
     if store.frames.device != device:
         raise ValueError(f"the store is on {store.frames.device}, the model on {device}")
@@ -331,6 +380,20 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     x = ops.clip_gather(store.frames, first, 0, T, store.in_tab, Ho, Wo)          # the input clips of data[starts[b]], as gather() builds them
     C = len(fields)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    if members is not None:
+        from .noise import add_gaussian_noise, stage_sample_ids
+        Bt = len(trajectories)
+        field_std = None
+        if ensemble.relative:                           # the one host synchronisation of an ensemble call
+            by_name = store.field_std()
+            field_std = [by_name[name] for name in ds.input_fields]
+        sigma = ensemble.sigma(x.shape[2], field_std)
+        if any(v > 0.0 for v in sigma):
+            sigma = torch.tensor(sigma, dtype=torch.float32).pin_memory().to(device, non_blocking=True)
+            ids = stage_sample_ids(trajectories, Bt, device)
+            for m in range(1 if ensemble.control else 0, members):
+                block = x[m * Bt:(m + 1) * Bt]
+                add_gaussian_noise(block, sigma, sample_ids=ids, draw=m, pass_index=0, seed=ensemble.seed, out=block)
     rel_l2, criterion = new(B, steps * T, C), new(B, steps)
     eik_p, eik_t = (new(B, steps * T), new(B, steps * T)) if sdf >= 0 else (None, None)
     archive = new(B, steps * T, C, Ho, Wo) if keep_predictions else None
@@ -379,6 +442,17 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
                                                                   int(errors.interface_radius), int(errors.bands[0]), int(errors.bands[1]),
                                                                   errors.spectra, **err_rows))
 
+    ens_rows = None
+    if members is not None:
+        ens_rows = {key: new(Bt, steps * T, C) for key in ("mean_rmse", "spread", "crps")}
+        if ensemble.rank_histogram:
+            ens_rows["rank_hist"] = torch.empty((Bt, steps * T, C, members + 1), dtype=torch.int32, device=device)
+        if ensemble.keep_mean:
+            ens_rows["mean"] = new(Bt, steps * T, C, Ho, Wo)
+        ens_ws = ops.ensemble_workspace(Bt * T * C, members, Ho, Wo, device)
+        before_score.append(lambda pred, step: ops.rollout_ensemble(pred, store.frames, first, step, store.out_tab, steps, members, ens_ws,
+                                                                    ensemble.fair, **ens_rows))
+
     def score(pred, step, next_in, arch):
         if pred.dtype != torch.float32 or not pred.is_contiguous():
             pred = pred.float().contiguous()
@@ -424,6 +498,10 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     if err_rows is not None:
         for key, rows in err_rows.items():
             setattr(report, key, rows)
+    if ens_rows is not None:
+        report.ensemble_members = members
+        for key, rows in ens_rows.items():
+            setattr(report, "ensemble_" + key, rows)
     return report
 
 

@@ -38,6 +38,7 @@
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
  *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
  *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
+ *   bf_ensemble_scores ....... ensemble-mean RMSE, spread, CRPS and rank histogram across members (no reference program); bf_rollout_ensemble: per step
  *   bf_render_ranges / bf_render_tiles .. plot_bubbleml and the wandb_*_plotter strips: utils/plot_utils.py:12-228 (no matplotlib, no cv2)
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
@@ -547,6 +548,32 @@ int bf_field_errors(const float* pred, const float* target, const float* sdf, in
  * [0, steps) nothing is written.  s: see bf_rollout_step.  ws: bf_field_errors_ws_bytes(B * T * C, Ho, Wo) bytes, 16-byte aligned. */
 int bf_rollout_errors(const bf_rollout_step* s, int sdf_channel, int interface_radius, int lo, int hi, int want_spectra, const bf_error_rows* rows,
                       void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* bf_ensemble_scores' outputs: mean_rmse, spread, crps [rows] are required together; rank_hist [rows][members + 1] and mean [rows][H][W] may be NULL
+ * and are then not computed */
+typedef struct bf_ensemble_rows { float *mean_rmse, *spread, *crps; int32_t* rank_hist; float* mean; } bf_ensemble_rows;
+/* The statistics across the M = members members of an ensemble forecast, per frame (csrc/ensemble.hip; the reference has no program for it; DESIGN.md
+ * section 23).  members_ptr[m * member_stride + f * H * W + p] fp32 is member m of frame f, target[f * H * W + p] fp32 the truth; 2 <= M <= 32,
+ * n = H * W, member_stride >= frames * H * W.  Differences, squares, sums, quotients and roots in fp64 from the fp32 inputs, one rounding to fp32:
+ *   mean_rmse [frames]           sqrt(1/n sum_p (xbar_p - y_p)^2), xbar_p the member mean;
+ *   spread [frames]              sqrt(1/n sum_p s2_p), s2_p the unbiased member variance, from centred squares (a second pass over the values in registers);
+ *   crps [frames]                1/n sum_p [ 1/M sum_m |x_m - y| - w sum_m sum_n |x_m - x_n| ], w = 1 / (2 M^2), or 1 / (2 M (M - 1)) with fair != 0: the
+ *                                pairwise form, the two non-negative sums kept apart in fp64 until the last line (a shared offset of the members cancels
+ *                                in every difference, not in the sum);
+ *   rank_hist [frames][M + 1]    int32: the number of pixels whose truth has exactly r members STRICTLY below it (a member equal to the truth is not below);
+ *   mean [frames][H][W]          fp32: xbar_p rounded once.
+ * fp64 partials per workgroup added in a fixed order, the counts through integer atomics: the same bits on every call, and for a frame alone or in a
+ * batch.  16-byte loads where W % 4 == 0, member_stride % 4 == 0 and the pointers are 16-byte aligned, 4-byte loads otherwise (any alignment of
+ * fp32 data works).  Allocation-free, capturable, never makes the host wait.  ws: bf_ensemble_scores_ws_bytes(frames, members, H, W) bytes, 8-byte
+ * aligned (0 from the query: sizes out of range). */
+int64_t bf_ensemble_scores_ws_bytes(int frames, int members, int H, int W);
+int bf_ensemble_scores(const float* members_ptr, int64_t member_stride, const float* target, int frames, int members, int H, int W, int fair,
+                       const bf_ensemble_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* bf_ensemble_scores of ONE rollout step.  s: see bf_rollout_step; its B = members * Bt rows are member-major: row m * Bt + b is member m of trajectory
+ * b (B % members != 0 is a size error), and first[b] == first[m * Bt + b] (row b's is read).  Frame (b, t, c) is scored against the stored frame
+ * first[b] + (s + 1) * T + t of field[c], read where it lies with the bits bf_clip_gather returns.  Rows (b, s * T + t, c) of [Bt][steps*T][C]([M + 1] or
+ * [Ho][Wo]) are written and no other; with the step number s = *s->step outside [0, steps) nothing is written.  The counter is read, not advanced: issue the
+ * call before the step's bf_rollout_score.  ws: bf_ensemble_scores_ws_bytes(Bt * T * C, members, Ho, Wo) bytes. */
+int bf_rollout_ensemble(const bf_rollout_step* s, int members, int fair, const bf_ensemble_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),

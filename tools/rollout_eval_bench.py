@@ -15,7 +15,9 @@ spread.  `scoring` times the scoring call alone with device events: bytes (predi
 share of 8 TB/s.
 
 Usage: python tools/rollout_eval_bench.py [--rounds R] [--only today|batched|scoring] [--batches 1,2,4,8] [--graph-only] [--tree CHECKOUT]
-(--tree imports bubbleformer_amd from another checkout of this repository, to time `today` on another commit in the same run)."""
+(--tree imports bubbleformer_amd from another checkout of this repository, to time `today` on another commit in the same run).
+--ensemble 4,16 runs the ensemble measurement instead: per member count M, the step on M * 2 rows with and without EnsembleSpec(M), and the
+bf_rollout_ensemble call alone beside bf_rollout_score on the same prediction (device events, bytes over time)."""
 import argparse
 import json
 import os
@@ -93,8 +95,74 @@ def scoring(store, B, reps=20):
     return out
 
 
+def device_time(call, reps=20):
+    """Median seconds of `call` over three runs of `reps` back-to-back calls between two device events, after one untimed call."""
+    times = []
+    for _ in range(3):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        call()
+        ev[0].record()
+        for _ in range(reps):
+            call()
+        ev[1].record()
+        torch.cuda.synchronize()
+        times.append(ev[0].elapsed_time(ev[1]) / reps * 1e-3)
+    return statistics.median(times)
+
+
+def ensemble(model, store, M, rounds, Bt=2):
+    """The step at M * Bt rows with and without EnsembleSpec(M) (marginal ms per step, as `summary`), and the bf_rollout_ensemble call alone
+    beside bf_rollout_score on the same prediction, both with device events: bytes read ((M + 1) * Bt * T * C * H * W * 4: every member once, the
+    truth once; the rows written are noise beside them) over time."""
+    from bubbleformer_amd import ops
+    from bubbleformer_amd.utils import EnsembleSpec
+    from bubbleformer_amd.utils import rollout as R
+    starts = [i * len(store.ds) // NTRAJ for i in range(Bt)]
+    spec = EnsembleSpec(M, 0.05, seed=1)
+    variants = {"plain": lambda steps: R.evaluate_rollouts(model, store, starts * M, steps),
+                "ensemble": lambda steps: R.evaluate_rollouts(model, store, starts, steps, ensemble=spec)}
+    times = {k: [] for k in variants}
+    for r in range(rounds + 1):                                         # round 0 is the warm-up and is dropped
+        for name, fn in variants.items():
+            pair = (clock(lambda: fn(STEPS)), clock(lambda: fn(SHORT)))
+            if r:
+                times[name].append(pair)
+    out = {}
+    for name in variants:
+        ms = [(a - b) / (STEPS - SHORT) * 1e3 for a, b in times[name]]
+        out[name + "_ms_per_step"] = round(statistics.median(ms), 4)
+        out[name + "_ms_per_step_min_max"] = [round(min(ms), 4), round(max(ms), 4)]
+    B = M * Bt
+    first = torch.tensor(plan_rollouts_first(store, starts * M), dtype=torch.int64, device="cuda")
+    pred = store.gather(starts * M)[1] + 0.01 * torch.randn(B, T, 4, H, W, device="cuda")
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")
+    rows = {"mean_rmse": new(Bt, STEPS * T, 4), "spread": new(Bt, STEPS * T, 4), "crps": new(Bt, STEPS * T, 4),
+            "rank_hist": torch.empty((Bt, STEPS * T, 4, M + 1), dtype=torch.int32, device="cuda")}
+    ws = ops.ensemble_workspace(Bt * T * 4, M, H, W, "cuda")
+    counter = torch.zeros(1, dtype=torch.int32, device="cuda")            # never advanced: the call only reads it
+    t = device_time(lambda: ops.rollout_ensemble(pred, store.frames, first, counter, store.out_tab, STEPS, M, ws, **rows))
+    nbytes = (M + 1) * Bt * T * 4 * H * W * 4
+    out["rollout_ensemble"] = {"us": round(t * 1e6, 1), "bytes_read": nbytes, "TB_per_s": round(nbytes / t / 1e12, 3)}
+    rel, crit, ep, et, nxt = new(B, STEPS * T, 4), new(B, STEPS), new(B, STEPS * T), new(B, STEPS * T), torch.empty_like(pred)
+    sws = ops.rollout_score_workspace(pred)
+
+    def score():
+        counter.zero_()
+        ops.rollout_score(pred, store.frames, first, counter, store.out_tab, 0, STEPS, rel, crit, sws, ep, et, nxt, None)
+    t = device_time(score)
+    nbytes = pred.numel() * 4 * 3                                         # prediction read, target frames read, next input written
+    out["rollout_score_same_run"] = {"us": round(t * 1e6, 1), "bytes": nbytes, "TB_per_s": round(nbytes / t / 1e12, 3), "B": B}
+    return out
+
+
+def plan_rollouts_first(store, starts):
+    from bubbleformer_amd.utils.rollout import plan_rollouts
+    return plan_rollouts(store.ds, starts, STEPS).first
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ensemble", default=None, help="member counts, e.g. 4,16: time the step with and without EnsembleSpec and the ensemble call alone (nothing else runs)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", choices=("today", "batched", "scoring"), default=None)
     ap.add_argument("--batches", default="1,2,4,8", help="trajectories per forward of the batched variants")
@@ -113,6 +181,12 @@ def main():
     model.load_state_dict(Wt.generate(Wt.param_shapes(**CFG), seed=42))
     model = model.cuda().eval()
     store = study()
+    if a.ensemble:
+        out = {"tree": tree, "geometry": f"{T}x{H}x{W}x4 bf16 FiLMAViT-small, Bt = 2 trajectories x M members, {STEPS} steps", "rounds": a.rounds}
+        for M in [int(m) for m in a.ensemble.split(",")]:
+            out[f"M{M}"] = ensemble(model, store, M, a.rounds)
+        print(json.dumps(out))
+        return 0
     starts = [i * len(store.ds) // NTRAJ for i in range(NTRAJ)]            # the first sample of every trajectory
     variants = {}
 
