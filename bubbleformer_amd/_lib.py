@@ -19,6 +19,7 @@ BF_AUX_NONE, BF_AUX_ADD, BF_AUX_DGELU = 0, 1, 2
 BF_OUT_STORE, BF_OUT_STORE_F32, BF_OUT_ATOMIC_F32 = 0, 1, 2
 BF_MAX_STAGES = 5
 BF_LOSS_LIMBS = 5          # int64 limbs per relative-L2 partial sum (include/bubbleformer_hip.h)
+BF_OPT_CHUNK, BF_OPT_MAX_GROUPS = 64, 64      # elements per parameter-group chunk, groups per step (include/bubbleformer_hip.h)
 
 vp, fp, i32, i64, f32 = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -206,6 +207,12 @@ SIGNATURES = {
     "bf_lion_avg": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
     "bf_weight_average": (C.c_int, [fp, fp, i64, f32, vp]),
     "bf_swap_buffers": (C.c_int, [fp, fp, i64, vp]),
+    "bf_adamw_groups": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
+    "bf_adam_groups": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
+    "bf_lion_groups": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
+    "bf_group_sumsq_ws_doubles": (i64, [i64]),
+    "bf_group_sumsq": (C.c_int, [fp, i64, vp, C.c_int, vp, vp, i64, vp]),
+    "bf_group_clip_coef": (C.c_int, [vp, vp, C.c_int, f32, f32, fp, fp, vp]),
     "bf_eikonal_sum": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, vp, vp]),
     "bf_eikonal_l1_frames": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, vp]),
     "bf_heatflux_rows": (C.c_int, [fp, fp, i64, i64, C.c_int, f32, f32, f32, f32, fp, vp]),

@@ -6,6 +6,9 @@
 //   bf_adamw / bf_adam / bf_lion             -> the same optimizers on a host gradient scale (no clipping)
 //   bf_adamw_avg / bf_adam_avg / bf_lion_avg -> any of those with an averaged copy of the weights kept in the same launch (EMA / SWA);
 //                                               bf_weight_average is that update alone, bf_swap_buffers exchanges two flat buffers
+//   bf_adamw_groups / bf_adam_groups / bf_lion_groups -> those bodies again with a group id per 64-element chunk that selects the learning-rate
+//                                               scale, the weight decay and a frozen flag (parameter groups); bf_group_sumsq and
+//                                               bf_group_clip_coef are the norm above per group, and over the groups that are not frozen
 //
 // The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
 //   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
@@ -87,6 +90,96 @@ __global__ void __launch_bounds__(GN_NT) grad_norm_finish_kernel(const double* _
     }
     const double sum = gn_block_sum(a, red);
     if (threadIdx.x == 0) {
+        const float norm = (float)((double)gscale * sqrt(sum));
+        const float c = __fdiv_rn(max_norm, norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.f ? 1.f : c;                      // a NaN norm stays a NaN coefficient (torch.clamp)
+    }
+}
+
+// ---------------------------------------------------------------------------- sums of squares per parameter group
+// bf_group_sumsq keeps bf_grad_norm's slabs (gn_slab_groups: a function of n alone, a whole number of chunks) and its fp64 squares, but a
+// slab yields one partial per group.  A wave sweeps 64 consecutive 16-byte groups = 4 chunks per load; the 16 lanes of a chunk share its
+// group id.  A lane adds its squares into `a` while its chunk's group stays the same (parameters are long runs of chunks); when a run of
+// lanes meets another group, the wave reduces `a` over each 16-lane run (xor 1, 2, 4, 8) and the runs that changed add theirs to the wave's
+// own LDS row, run 0 first: every order here is fixed by the chunk map alone.  The 4 wave rows are added in wave order, the slab partials
+// by group_sumsq_finish_kernel in a fixed order.  A map byte can take 256 values, so the LDS rows have 256 columns: an id the caller did
+// not mean writes inside the row and is never read back.
+constexpr int GS_IDS = 256;
+constexpr int GS_RUN = BF_OPT_CHUNK / 4;      // 16 lanes share a chunk
+static_assert(GN_NT % GS_RUN == 0 && 64 % GS_RUN == 0, "a slab starts on a chunk boundary and a chunk does not straddle two waves");
+
+__device__ __forceinline__ void gs_flush(double (*acc)[GS_IDS], int wave, int lane, double a, int cur, bool flush) {
+    double r = a;
+#pragma unroll
+    for (int o = 1; o < GS_RUN; o <<= 1) r += __shfl_xor(r, o, 64);
+#pragma unroll
+    for (int q = 0; q < 64 / GS_RUN; ++q)          // one run at a time: two runs of the wave may hold the same group
+        if (lane == q * GS_RUN && flush && cur >= 0) acc[wave][cur] += r;
+}
+
+__global__ void __launch_bounds__(GN_NT) group_sumsq_kernel(const float* __restrict__ x, long n, long slab_groups, const uint8_t* __restrict__ chunk,
+                                                           double* __restrict__ part) {
+    __shared__ double acc[GN_NT / 64][GS_IDS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = lane; k < GS_IDS; k += 64) acc[wave][k] = 0.0;      // a wave clears, fills and flushes its own row: no barrier before the end
+    const long G = n / 4;
+    const long g0 = (long)blockIdx.x * slab_groups, g1 = min(G, g0 + slab_groups);
+    const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+    double a = 0.0;
+    int cur = -1;
+    for (long base = g0 + wave * 64; base < g1; base += GN_NT) {     // wave-uniform trip count: shuffles and votes see all 64 lanes
+        const long i = base + lane;
+        const bool run_in = (i & ~(long)(GS_RUN - 1)) < g1;           // the lane's chunk has elements below g1 (whole runs, so uniform per run)
+        const int k = run_in ? (int)chunk[i / GS_RUN] : cur;
+        double s = 0.0;
+        if (i < g1) {
+            const float4 q = x4[i];
+            s = ((double)q.x * (double)q.x + (double)q.y * (double)q.y) + ((double)q.z * (double)q.z + (double)q.w * (double)q.w);
+        }
+        const bool changed = k != cur;
+        if (__any(changed)) {
+            gs_flush(acc, wave, lane, a, cur, changed);
+            if (changed) { a = 0.0; cur = k; }
+        }
+        a += s;
+    }
+    gs_flush(acc, wave, lane, a, cur, true);
+    __syncthreads();
+    if (threadIdx.x < BF_OPT_MAX_GROUPS) {
+        const int k = threadIdx.x;
+        double s = acc[0][k];
+#pragma unroll
+        for (int w = 1; w < GN_NT / 64; ++w) s += acc[w][k];
+        if (blockIdx.x == gridDim.x - 1)
+            for (long e = G * 4; e < n; ++e)
+                if (chunk[e / BF_OPT_CHUNK] == k) s += (double)x[e] * (double)x[e];
+        part[(long)blockIdx.x * BF_OPT_MAX_GROUPS + k] = s;
+    }
+}
+
+// sums[k] = the slab partials of group k: thread t adds slabs t / 64, t / 64 + 4, ... of group t % 64 in order, the four quarters in order
+__global__ void __launch_bounds__(GN_NT) group_sumsq_finish_kernel(const double* __restrict__ part, int nslabs, int n_groups, double* __restrict__ sums) {
+    static_assert(BF_OPT_MAX_GROUPS == 64 && GN_NT == 256, "four threads per group");
+    __shared__ double red[GN_NT / BF_OPT_MAX_GROUPS][BF_OPT_MAX_GROUPS];
+    const int k = threadIdx.x % BF_OPT_MAX_GROUPS, q = threadIdx.x / BF_OPT_MAX_GROUPS;
+    double a = 0.0;
+    for (int s = q; s < nslabs; s += GN_NT / BF_OPT_MAX_GROUPS) a += part[(long)s * BF_OPT_MAX_GROUPS + k];
+    red[q][k] = a;
+    __syncthreads();
+    if (threadIdx.x < n_groups) sums[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+// {norm, coef} over the groups that are not frozen, as grad_norm_finish_kernel forms them; one workgroup of BF_OPT_MAX_GROUPS threads
+__global__ void __launch_bounds__(BF_OPT_MAX_GROUPS) group_clip_coef_kernel(const double* __restrict__ sums, const uint8_t* __restrict__ frozen, int n_groups,
+                                                                           float gscale, float max_norm, float* __restrict__ out,
+                                                                           float* __restrict__ group_norm) {
+    const int t = threadIdx.x;
+    if (group_norm && t < n_groups) group_norm[t] = (float)((double)gscale * sqrt(sums[t]));
+    if (t == 0) {
+        double sum = 0.0;
+        for (int k = 0; k < n_groups; ++k)
+            if (!frozen[k]) sum += sums[k];
         const float norm = (float)((double)gscale * sqrt(sum));
         const float c = __fdiv_rn(max_norm, norm + 1e-6f);
         out[0] = norm;
@@ -213,6 +306,78 @@ extern "C" int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream
     BF_REQUIRE(BF_OPT_ALIGNED(a) && BF_OPT_ALIGNED(b), "bf_swap_buffers: buffers must be 16-byte aligned");
     BF_REQUIRE(a + n <= b || b + n <= a, "bf_swap_buffers: the buffers overlap");
     hipLaunchKernelGGL(swap_kernel, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, (hipStream_t)stream, a, b, (long)n);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- the optimizers with parameter groups
+// One entry per optimizer for all three scale modes, with or without the averaged copy.  There is no wd argument: every group has its own.
+#define BF_GROUPS_REQUIRE(who)                                                                                                    \
+    BF_REQUIRE(chunk_group && lr_scale && weight_decay && frozen, who ": the chunk map and the three group tables are required");   \
+    BF_REQUIRE(n_groups >= 1 && n_groups <= BF_OPT_MAX_GROUPS, who ": n_groups must be 1 .. 64");                                  \
+    BF_REQUIRE((uintptr_t)lr_scale % 4 == 0 && (uintptr_t)weight_decay % 4 == 0, who ": the group tables must be 4-byte aligned");  \
+    BF_REQUIRE(!avg || (BF_OPT_ALIGNED(avg) && avg_weight > 0.f && avg_weight <= 1.f),                                             \
+               who ": the average buffer must be 16-byte aligned and avg_weight in (0, 1]")
+#define BF_GROUPS_RECORD() opt_groups<true>{chunk_group, lr_scale, weight_decay, frozen, n_groups}
+
+extern "C" int bf_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                               float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
+                               const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_groups: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_groups: buffers must be 16-byte aligned");
+    BF_GROUPS_REQUIRE("bf_adamw_groups");
+    return BF_OPT_GROUPS_DISPATCH(opt_launch_adam, true, p, g, m, v, n, step, lr, beta1, beta2, eps, 0.f, gscale, coef_dev, clip_value,
+                                  (hipStream_t)stream, avg, avg_weight, BF_GROUPS_RECORD());
+}
+
+extern "C" int bf_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                              float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
+                              const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_groups: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_groups: buffers must be 16-byte aligned");
+    BF_GROUPS_REQUIRE("bf_adam_groups");
+    return BF_OPT_GROUPS_DISPATCH(opt_launch_adam, false, p, g, m, v, n, step, lr, beta1, beta2, eps, 0.f, gscale, coef_dev, clip_value,
+                                  (hipStream_t)stream, avg, avg_weight, BF_GROUPS_RECORD());
+}
+
+extern "C" int bf_lion_groups(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float gscale, const float* coef_dev,
+                              float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group, const float* lr_scale,
+                              const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
+    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_groups: bad arguments");
+    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_groups: buffers must be 16-byte aligned");
+    BF_GROUPS_REQUIRE("bf_lion_groups");
+    return BF_OPT_GROUPS_DISPATCH(opt_launch_lion, p, g, m, n, lr, beta1, beta2, 0.f, gscale, coef_dev, clip_value, (hipStream_t)stream, avg,
+                                  avg_weight, BF_GROUPS_RECORD());
+}
+
+extern "C" int64_t bf_group_sumsq_ws_doubles(int64_t n) { return n > 0 ? (int64_t)gn_slabs((long)(n / 4)) * BF_OPT_MAX_GROUPS : 0; }
+
+extern "C" int bf_group_sumsq(const float* x, int64_t n, const uint8_t* chunk_group, int n_groups, double* sums, double* ws, int64_t ws_doubles,
+                              bf_stream_t stream) {
+    BF_REQUIRE(x && n > 0, "bf_group_sumsq: bad arguments");
+    BF_REQUIRE(chunk_group && sums && (uintptr_t)sums % 8 == 0, "bf_group_sumsq: the chunk map and the output sums are required");
+    BF_REQUIRE(n_groups >= 1 && n_groups <= BF_OPT_MAX_GROUPS, "bf_group_sumsq: n_groups must be 1 .. 64");
+    BF_REQUIRE(BF_OPT_ALIGNED(x), "bf_group_sumsq: the buffer must be 16-byte aligned");
+    const long G = (long)(n / 4);
+    const int nslabs = gn_slabs(G);
+    BF_REQUIRE(ws && ws_doubles >= (int64_t)nslabs * BF_OPT_MAX_GROUPS && (uintptr_t)ws % 8 == 0,
+               "bf_group_sumsq: the workspace is smaller than bf_group_sumsq_ws_doubles(n)");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(group_sumsq_kernel, dim3(nslabs), dim3(GN_NT), 0, st, x, (long)n, gn_slab_groups(G), chunk_group, ws);
+    BF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(group_sumsq_finish_kernel, dim3(1), dim3(GN_NT), 0, st, (const double*)ws, nslabs, n_groups, sums);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bf_group_clip_coef(const double* sums, const uint8_t* frozen, int n_groups, float gscale, float max_norm, float* out,
+                                  float* group_norm, bf_stream_t stream) {
+    BF_REQUIRE(sums && frozen && (uintptr_t)sums % 8 == 0, "bf_group_clip_coef: the sums and the frozen table are required");
+    BF_REQUIRE(out, "bf_group_clip_coef: the output {norm, coef} is null");
+    BF_REQUIRE(n_groups >= 1 && n_groups <= BF_OPT_MAX_GROUPS, "bf_group_clip_coef: n_groups must be 1 .. 64");
+    BF_REQUIRE(max_norm > 0.f, "bf_group_clip_coef: max_norm must be positive");
+    hipLaunchKernelGGL(group_clip_coef_kernel, dim3(1), dim3(BF_OPT_MAX_GROUPS), 0, (hipStream_t)stream, sums, frozen, n_groups, gscale, max_norm, out,
+                       group_norm);
     BF_CHECK_LAUNCH();
     return 0;
 }

@@ -10,6 +10,11 @@
 // `a` of the parameters towards the value it has just formed, a <- a + w * (p - a) (avg_lerp; an EMA or a running mean, by the caller's
 // w), for one more read and one more write of one buffer and no launch.  AVG = false has no trace of it: those are the kernels above.
 // bf_weight_average is the lerp alone and bf_swap_buffers exchanges two flat buffers; same grid rule, 16-byte body, scalar tail.
+// A fourth family, bf_adamw_groups / bf_adam_groups / bf_lion_groups, runs the same bodies with GRP = true: every chunk of BF_OPT_CHUNK
+// elements carries a group id (one byte per chunk), and the group's learning-rate scale, weight decay and frozen flag replace the launch's
+// lr and wd for that chunk (opt_group_table / opt_group_of).  A 16-byte access never straddles a chunk, the 16 lanes that share a chunk
+// share the lookup, and a frozen chunk is skipped by those 16 lanes together: the live chunks keep their 256-byte runs.  GRP = false has no
+// trace of it either.
 #pragma once
 #include <algorithm>
 
@@ -42,15 +47,70 @@ __device__ __forceinline__ float4 avg_lerp4(float4 a, const float4 p, float w) {
     return a;
 }
 
+// ---------------------------------------------------------------------------- parameter groups
+// BF_OPT_CHUNK consecutive elements are one chunk (trainer.FlatParams starts every parameter on such a boundary, so a chunk belongs to
+// one parameter); chunk[] names each chunk's group.  GRP = false: an empty record, nothing is passed or read.
+static_assert(BF_OPT_CHUNK % 4 == 0 && BF_OPT_MAX_GROUPS <= 256, "a 16-byte access stays inside one chunk; a group id is one byte");
+constexpr int BF_OPT_CHUNK4 = BF_OPT_CHUNK / 4;      // 16-byte accesses per chunk
+constexpr int BF_OPT_IDS = 256;                       // every value a map byte can take has a table row: an id past n_groups is frozen
+template <bool GRP> struct opt_groups {};
+template <> struct opt_groups<true> {
+    const uint8_t* chunk;
+    const float *lr_scale, *wd;
+    const uint8_t* frozen;
+    int n;
+};
+// the workgroup's copy of the group tables in LDS, one row per possible id: {lr * lr_scale[k], weight_decay[k]}, x < 0 = frozen (a
+// scale is >= 0).  Built once per workgroup, so the loop's dependent lookup is one byte from the map and one LDS read.
+__device__ __forceinline__ void opt_group_table(float2* tab, const opt_groups<true>& G, float lr) {
+    static_assert(BF_OPT_NT == BF_OPT_IDS, "one table row per thread");
+    const int k = threadIdx.x;
+    const bool live = k < G.n && !G.frozen[k];
+    tab[k] = live ? make_float2(lr * G.lr_scale[k], G.wd[k]) : make_float2(-1.f, 0.f);
+    __syncthreads();
+}
+#define BF_OPT_GROUP_TABLE()                                   \
+    float2* tab = nullptr;                                     \
+    if constexpr (GRP) {                                       \
+        __shared__ float2 tab_lds[BF_OPT_IDS];                 \
+        tab = tab_lds;                                         \
+        opt_group_table(tab, G, lr);                           \
+    }
+// lr_k and wd_k of 16-byte access I (for element e pass e / 4); a frozen chunk takes SKIP and touches nothing
+#define BF_OPT_GROUP_OF(ID, SKIP)                              \
+    float lr_k = lr, wd_k = wd;                                \
+    if constexpr (GRP) {                                       \
+        const float2 t = tab[ID];                              \
+        if (t.x < 0.f) SKIP;                                   \
+        lr_k = t.x; wd_k = t.y;                                \
+    }
+// the grid-stride loop's id, read one trip ahead: the map byte of the next access is in flight while this one's buffers are
+#define BF_OPT_GROUP_FIRST()                                   \
+    int id = 0, id_next = 0;                                   \
+    if constexpr (GRP) {                                       \
+        const long i0 = (long)blockIdx.x * NT + threadIdx.x;   \
+        if (i0 < n4) id_next = G.chunk[i0 / BF_OPT_CHUNK4];    \
+    }
+#define BF_OPT_GROUP_NEXT(I)                                   \
+    if constexpr (GRP) {                                       \
+        id = id_next;                                          \
+        const long i1 = (I) + (long)gridDim.x * NT;            \
+        if (i1 < n4) id_next = G.chunk[i1 / BF_OPT_CHUNK4];    \
+    }
+
 // ---------------------------------------------------------------------------- AdamW (torch.optim.AdamW semantics)
-template <int MODE, bool AVG>
+template <int MODE, bool AVG, bool GRP>
 __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
+                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
+    BF_OPT_GROUP_FIRST()
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+        BF_OPT_GROUP_NEXT(i)
+        BF_OPT_GROUP_OF(id, continue)
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
@@ -58,10 +118,10 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
         if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_ADAM1(X)                                                        \
         { const float gr = opt_grad<MODE>(gg.X, gs, clip);                  \
-          pp.X *= (1.f - lr * wd);                                          \
+          pp.X *= (1.f - lr_k * wd_k);                                       \
           mm.X = b1 * mm.X + (1.f - b1) * gr;                               \
           vv.X = b2 * vv.X + (1.f - b2) * gr * gr;                          \
-          pp.X -= (lr / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
+          pp.X -= (lr_k / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
         BF_ADAM1(x) BF_ADAM1(y) BF_ADAM1(z) BF_ADAM1(w)
 #undef BF_ADAM1
         reinterpret_cast<float4*>(p)[i] = pp;
@@ -71,11 +131,13 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
     }
     if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
         const long i = n4 * 4 + threadIdx.x;
+        if constexpr (GRP) id = G.chunk[i / BF_OPT_CHUNK];
+        BF_OPT_GROUP_OF(id, return)
         const float gr = opt_grad<MODE>(g[i], gs, clip);
-        float pp = p[i] * (1.f - lr * wd);
+        float pp = p[i] * (1.f - lr_k * wd_k);
         const float mm = b1 * m[i] + (1.f - b1) * gr;
         const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
+        pp -= (lr_k / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
         p[i] = pp; m[i] = mm; v[i] = vv;
         if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
     }
@@ -84,14 +146,18 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
 // ---------------------------------------------------------------------------- Adam (torch.optim.Adam semantics, single-tensor path)
 // Weight decay is an L2 term on the gradient (g += wd*p), so it passes through both moments; AdamW above decays the parameter instead.
 // Zero padding stays zero: p = g = m = v = 0 gives m / (sqrt(v) / sqrt_bc2 + eps) = 0.
-template <int MODE, bool AVG>
+template <int MODE, bool AVG, bool GRP>
 __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
+                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
+    BF_OPT_GROUP_FIRST()
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+        BF_OPT_GROUP_NEXT(i)
+        BF_OPT_GROUP_OF(id, continue)
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
@@ -99,10 +165,10 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
         if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_ADAML2(X)                                                       \
         { float gr = opt_grad<MODE>(gg.X, gs, clip);                        \
-          if (wd != 0.f) gr += wd * pp.X;                                   \
+          if (wd_k != 0.f) gr += wd_k * pp.X;                                \
           mm.X = b1 * mm.X + (1.f - b1) * gr;                               \
           vv.X = b2 * vv.X + (1.f - b2) * gr * gr;                          \
-          pp.X -= (lr / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
+          pp.X -= (lr_k / bc1) * mm.X / (sqrtf(vv.X) / sqrt_bc2 + eps); }
         BF_ADAML2(x) BF_ADAML2(y) BF_ADAML2(z) BF_ADAML2(w)
 #undef BF_ADAML2
         reinterpret_cast<float4*>(p)[i] = pp;
@@ -112,12 +178,14 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
     }
     if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
         const long i = n4 * 4 + threadIdx.x;
+        if constexpr (GRP) id = G.chunk[i / BF_OPT_CHUNK];
+        BF_OPT_GROUP_OF(id, return)
         float pp = p[i];
         float gr = opt_grad<MODE>(g[i], gs, clip);
-        if (wd != 0.f) gr += wd * pp;
+        if (wd_k != 0.f) gr += wd_k * pp;
         const float mm = b1 * m[i] + (1.f - b1) * gr;
         const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        pp -= (lr / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
+        pp -= (lr_k / bc1) * mm / (sqrtf(vv) / sqrt_bc2 + eps);
         p[i] = pp; m[i] = mm; v[i] = vv;
         if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
     }
@@ -126,14 +194,18 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
 // ---------------------------------------------------------------------------- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization
 // Algorithms"; the update lion_pytorch.Lion applies at bubbleformer/modules.py:139-140):
 //   p *= 1 - lr*wd;  p -= lr * sign(b1*m + (1-b1)*g);  m = b2*m + (1-b2)*g
-template <int MODE, bool AVG>
+template <int MODE, bool AVG, bool GRP>
 __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n, float lr,
-                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w) {
+                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
     auto sgn = [](float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); };
+    BF_OPT_GROUP_FIRST()
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+        BF_OPT_GROUP_NEXT(i)
+        BF_OPT_GROUP_OF(id, continue)
         float4 pp = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i];
@@ -141,7 +213,7 @@ __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, 
         if constexpr (AVG) aa = reinterpret_cast<float4*>(a)[i];
 #define BF_LION1(X)                                                        \
         { const float gr = opt_grad<MODE>(gg.X, gs, clip);                  \
-          pp.X = pp.X * (1.f - lr * wd) - lr * sgn(b1 * mm.X + (1.f - b1) * gr); \
+          pp.X = pp.X * (1.f - lr_k * wd_k) - lr_k * sgn(b1 * mm.X + (1.f - b1) * gr); \
           mm.X = b2 * mm.X + (1.f - b2) * gr; }
         BF_LION1(x) BF_LION1(y) BF_LION1(z) BF_LION1(w)
 #undef BF_LION1
@@ -151,8 +223,10 @@ __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, 
     }
     if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
         const long i = n4 * 4 + threadIdx.x;
+        if constexpr (GRP) id = G.chunk[i / BF_OPT_CHUNK];
+        BF_OPT_GROUP_OF(id, return)
         const float gr = opt_grad<MODE>(g[i], gs, clip);
-        const float pp = p[i] * (1.f - lr * wd) - lr * sgn(b1 * m[i] + (1.f - b1) * gr);
+        const float pp = p[i] * (1.f - lr_k * wd_k) - lr_k * sgn(b1 * m[i] + (1.f - b1) * gr);
         p[i] = pp;
         m[i] = b2 * m[i] + (1.f - b2) * gr;
         if constexpr (AVG) a[i] = avg_lerp(a[i], pp, w);
@@ -190,25 +264,26 @@ __global__ void __launch_bounds__(BF_OPT_NT) swap_kernel(float* __restrict__ a, 
 
 // launches, shared by the families of entry points (which check their own arguments); a / w: the averaged copy of the AVG kernels
 #define BF_OPT_ALIGNED(x) ((uintptr_t)(x) % 16 == 0)
-template <int MODE, bool AVG = false>
+template <int MODE, bool AVG = false, bool GRP = false>
 int opt_launch_adam(bool decoupled, float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                    float eps, float wd, float gscale, const float* coef, float clip, hipStream_t st, float* a = nullptr, float w = 0.f) {
+                    float eps, float wd, float gscale, const float* coef, float clip, hipStream_t st, float* a = nullptr, float w = 0.f,
+                    opt_groups<GRP> G = {}) {
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
     if (decoupled)
-        hipLaunchKernelGGL((adamw_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1,
-                           sbc2, gscale, coef, clip, a, w);
+        hipLaunchKernelGGL((adamw_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd,
+                           bc1, sbc2, gscale, coef, clip, a, w, G);
     else
-        hipLaunchKernelGGL((adam_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd, bc1,
-                           sbc2, gscale, coef, clip, a, w);
+        hipLaunchKernelGGL((adam_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd,
+                           bc1, sbc2, gscale, coef, clip, a, w, G);
     BF_CHECK_LAUNCH();
     return 0;
 }
-template <int MODE, bool AVG = false>
+template <int MODE, bool AVG = false, bool GRP = false>
 int opt_launch_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale, const float* coef,
-                    float clip, hipStream_t st, float* a = nullptr, float w = 0.f) {
-    hipLaunchKernelGGL((lion_kernel<MODE, AVG>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, (long)n, lr, beta1, beta2, wd, gscale, coef,
-                       clip, a, w);
+                    float clip, hipStream_t st, float* a = nullptr, float w = 0.f, opt_groups<GRP> G = {}) {
+    hipLaunchKernelGGL((lion_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, (long)n, lr, beta1, beta2, wd, gscale, coef,
+                       clip, a, w, G);
     BF_CHECK_LAUNCH();
     return 0;
 }
@@ -216,4 +291,9 @@ int opt_launch_lion(float* p, const float* g, float* m, int64_t n, float lr, flo
 #define BF_OPT_AVG_DISPATCH(LAUNCH, ...)                                                   \
     (!isinf(clip_value) ? LAUNCH<BF_OPT_DEV_CLAMP, true>(__VA_ARGS__)                      \
                         : (coef_dev ? LAUNCH<BF_OPT_DEV, true>(__VA_ARGS__) : LAUNCH<BF_OPT_HOST, true>(__VA_ARGS__)))
+// the same choice for a _groups entry, with or without the averaged copy (AVG is a template argument: written out for both)
+#define BF_OPT_GROUPS_MODE(LAUNCH, AVG, ...)                                               \
+    (!isinf(clip_value) ? LAUNCH<BF_OPT_DEV_CLAMP, AVG, true>(__VA_ARGS__)                 \
+                        : (coef_dev ? LAUNCH<BF_OPT_DEV, AVG, true>(__VA_ARGS__) : LAUNCH<BF_OPT_HOST, AVG, true>(__VA_ARGS__)))
+#define BF_OPT_GROUPS_DISPATCH(LAUNCH, ...) (avg ? BF_OPT_GROUPS_MODE(LAUNCH, true, __VA_ARGS__) : BF_OPT_GROUPS_MODE(LAUNCH, false, __VA_ARGS__))
 }  // namespace

@@ -53,7 +53,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True, input_noise=None, weight_average=None) -> Dict:
+        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -81,6 +81,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     (TrainStep).  With a validation set every epoch then validates twice: ``hist["val_loss"]`` (and the panels) stay the live weights,
     ``hist["val_loss_avg"]`` is the same validation inside ``step.averaged_weights()``, and `log` gets ``val_loss_avg`` beside ``val_loss``.
     Checkpoints carry the average and a resumed run continues it (utils/checkpoint.py).  None: nothing of this runs.
+    ``param_groups``: a list of utils.param_groups.GroupSpec -- frozen parameters, per-group learning-rate scale and weight decay inside the
+    one optimizer launch (TrainStep; the scale multiplies the scheduled learning rate).  With clipping by norm ``hist["group_grad_norm"]``
+    holds one row per optimizer step with the scaled gradient norm of every group, recorded as ``grad_norm`` is, and the `log` dict of a
+    batch that stepped carries the row as a device tensor.  Checkpoints record the partition, and resuming into another one is refused.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -105,11 +109,14 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     step = TrainStep(model, lr=lr, weight_decay=weight_decay, optimizer=optimizer, scheduler=sched, criterion=criterion,
                      gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
                      accumulate_grad_batches=accumulate_grad_batches, unroll_steps=unroll_steps, unroll_weights=unroll_weights,
-                     unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std, weight_average=weight_average)
+                     unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std, weight_average=weight_average,
+                     param_groups=param_groups)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
     if step.grad_norm is not None:
         hist["grad_norm"] = []
+    if step.group_grad_norm is not None:
+        hist["group_grad_norm"] = []
     if k > 1:
         hist["unroll_loss"] = []
     if step.avg is not None and vstore is not None:
@@ -121,7 +128,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(steps_per_epoch, 1)
     for epoch in range(first_epoch, max_epochs):
         model.train()
-        losses, norms, per_pass = [], [], []
+        losses, norms, gnorms, per_pass = [], [], [], []
         order = epoch_indices(n_pool, epoch, seed, True, rank, world)
         todo = batches(order if pool is None else [pool[i] for i in order], batch_size, limit_train_batches)
         for bi, idx in enumerate(todo):
@@ -140,12 +147,17 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             if step.grad_norm is not None and step.step_no != before:
                 norms.append(step.grad_norm[0].clone())      # the next step overwrites the pair
                 entry["grad_norm"] = norms[-1]
+                if step.group_grad_norm is not None:
+                    gnorms.append(step.group_grad_norm.clone())
+                    entry["group_grad_norm"] = gnorms[-1]
             if log is not None:
                 log(entry)
         ep = torch.stack(losses).float()
         hist["train_loss"].extend(ep.tolist())
         if norms:
             hist["grad_norm"].extend(torch.stack(norms).tolist())
+        if gnorms:
+            hist["group_grad_norm"].extend(torch.stack(gnorms).tolist())
         if per_pass:
             hist["unroll_loss"].extend(torch.stack(per_pass).tolist())
         hist["epoch_train_loss"].append(float(ep.mean()))

@@ -1439,17 +1439,113 @@ def _clip_or_inf(clip_value: Optional[float]) -> float:
     return float("inf") if clip_value is None else float(clip_value)
 
 
+class ParamGroupTables:
+    """The device side of a step's parameter groups, built once (``param_group_tables``): ``chunk`` (uint8, one group id per 64-element
+    chunk of the flat buffer), ``lr_scale`` / ``weight_decay`` (fp32) and ``frozen`` (uint8), one row per group, ``n_groups`` of them, for
+    a flat buffer of ``numel`` elements.  What adamw_ / adam_ / lion_ take as ``groups=``, and group_sumsq / group_clip_coef_."""
+
+    def __init__(self, chunk, lr_scale, weight_decay, frozen, n_groups: int, numel: int):
+        self.chunk, self.lr_scale, self.weight_decay, self.frozen, self.n_groups, self.numel = chunk, lr_scale, weight_decay, frozen, n_groups, numel
+
+
+def param_group_tables(chunk_map: torch.Tensor, lr_scale, weight_decay, frozen, numel: int, device) -> ParamGroupTables:
+    """Checks a chunk map (uint8, ceil(numel / 64) ids, e.g. utils.param_groups.ResolvedGroups.chunk_map) and the three per-group lists
+    against each other on the host -- every id below the number of groups, 1 to 64 groups, scales and decays >= 0: the kernels cannot
+    check ids without reading the map -- and puts them on ``device``."""
+    if chunk_map is None or lr_scale is None or weight_decay is None or frozen is None:
+        raise L.BubbleformerHipError("param_group_tables: the chunk map and the three group tables are required")
+    G = len(lr_scale)
+    if not 1 <= G <= L.BF_OPT_MAX_GROUPS or len(weight_decay) != G or len(frozen) != G:
+        raise L.BubbleformerHipError(f"param_group_tables: {G} / {len(weight_decay)} / {len(frozen)} table rows; there must be 1 to "
+                                     f"{L.BF_OPT_MAX_GROUPS} groups, the same number in every table")
+    if not all(float(v) >= 0 for v in list(lr_scale) + list(weight_decay)):
+        raise L.BubbleformerHipError("param_group_tables: lr_scale and weight_decay must be >= 0")
+    cm = torch.as_tensor(chunk_map)
+    chunks = (int(numel) + L.BF_OPT_CHUNK - 1) // L.BF_OPT_CHUNK
+    if cm.dtype != torch.uint8 or cm.dim() != 1 or cm.numel() != chunks:
+        raise L.BubbleformerHipError(f"param_group_tables: the chunk map must be {chunks} uint8 ids (one per {L.BF_OPT_CHUNK} of {int(numel)} elements), "
+                                     f"got {tuple(cm.shape)} {cm.dtype}")
+    if int(cm.max()) >= G:
+        raise L.BubbleformerHipError(f"param_group_tables: the chunk map names group {int(cm.max())}, there are {G}")
+    return ParamGroupTables(cm.to(device).contiguous(), torch.tensor([float(v) for v in lr_scale], dtype=torch.float32, device=device),
+                            torch.tensor([float(v) for v in weight_decay], dtype=torch.float32, device=device),
+                            torch.tensor([int(bool(v)) for v in frozen], dtype=torch.uint8, device=device), G, int(numel))
+
+
+def _group_args(groups: ParamGroupTables, p: torch.Tensor, who: str):
+    """(chunk map, lr_scale, weight_decay, frozen, n_groups) for the _groups entry points; the map must be the one of p's length."""
+    if not isinstance(groups, ParamGroupTables):
+        raise L.BubbleformerHipError(f"{who}: groups must be an ops.ParamGroupTables (param_group_tables), got {type(groups).__name__}")
+    chunks = (p.numel() + L.BF_OPT_CHUNK - 1) // L.BF_OPT_CHUNK
+    if groups.chunk is None or groups.chunk.numel() != chunks or groups.chunk.device != p.device:
+        raise L.BubbleformerHipError(f"{who}: the chunk map must hold {chunks} ids on {p.device} for a buffer of {p.numel()} elements"
+                                     + ("" if groups.chunk is None else f", it holds {groups.chunk.numel()} on {groups.chunk.device}"))
+    tabs = [None if t is None else _p(t) for t in (groups.lr_scale, groups.weight_decay, groups.frozen)]
+    return _p(groups.chunk), tabs[0], tabs[1], tabs[2], int(groups.n_groups)
+
+
+def group_sumsq_workspace(n: int, device) -> torch.Tensor:
+    """The fp64 slab partials of group_sumsq for a buffer of n elements (64 per slab, at most 1024 slabs)."""
+    return torch.empty(int(L.lib().bf_group_sumsq_ws_doubles(int(n))), dtype=torch.float64, device=device)
+
+
+def group_sumsq(buf: torch.Tensor, groups: ParamGroupTables, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[k] = the sum of buf[i]^2 over the elements whose chunk belongs to group k (fp64, n_groups elements on the device; allocated when
+    None).  fp64 squares added in a fixed order, no float atomics (csrc/gradclip.hip): the same bits on every call.  ws:
+    group_sumsq_workspace(buf.numel(), device), allocated per call when None."""
+    _require_gpu(buf)
+    if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.dim() != 1:
+        raise L.BubbleformerHipError("group_sumsq: buf must be a contiguous 1-D torch.float32 tensor")
+    chunk, _, _, _, G = _group_args(groups, buf, "group_sumsq")
+    if out is None:
+        out = torch.empty(G, dtype=torch.float64, device=buf.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != G or out.device != buf.device:
+        raise L.BubbleformerHipError(f"group_sumsq: out must be a contiguous torch.float64 tensor of {G} elements on {buf.device}")
+    if ws is None:
+        ws = group_sumsq_workspace(buf.numel(), buf.device)
+    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.device != buf.device:
+        raise L.BubbleformerHipError(f"group_sumsq: ws must be a contiguous torch.float64 tensor on {buf.device}")
+    L.check(L.lib().bf_group_sumsq(_p(buf), buf.numel(), chunk, G, _p(out), _p(ws), ws.numel(), _stream()), "bf_group_sumsq")
+    return out
+
+
+def group_clip_coef_(sums: torch.Tensor, groups: ParamGroupTables, out: torch.Tensor, max_norm: float, grad_scale: float = 1.0,
+                     group_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_norm_'s {norm, coef} from group_sumsq's sums, over the groups that are not frozen -- torch.nn.utils.clip_grad_norm_ over the
+    parameters a torch optimizer would hold: out[0] = grad_scale * sqrt(sum of the live groups' sums), out[1] = min(max_norm / (out[0] +
+    1e-6), 1).  group_norm (fp32, n_groups elements on the device, optional) receives grad_scale * sqrt(sums[k]) of every group."""
+    _require_gpu(sums)
+    G = int(groups.n_groups)
+    if sums.dtype != torch.float64 or not sums.is_contiguous() or sums.numel() != G:
+        raise L.BubbleformerHipError(f"group_clip_coef_: sums must be a contiguous torch.float64 tensor of {G} elements (group_sumsq's)")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 2 or out.device != sums.device:
+        raise L.BubbleformerHipError(f"group_clip_coef_: out must be a contiguous torch.float32 tensor of 2 elements on {sums.device}")
+    if group_norm is not None and (group_norm.dtype != torch.float32 or not group_norm.is_contiguous() or group_norm.numel() != G
+                                   or group_norm.device != sums.device):
+        raise L.BubbleformerHipError(f"group_clip_coef_: group_norm must be a contiguous torch.float32 tensor of {G} elements on {sums.device}")
+    L.check(L.lib().bf_group_clip_coef(_p(sums), None if groups.frozen is None else _p(groups.frozen), G, float(grad_scale), float(max_norm), _p(out),
+                                       None if group_norm is None else _p(group_norm), _stream()), "bf_group_clip_coef")
+    return out
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
           grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None,
-          avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
+          avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None, groups: Optional[ParamGroupTables] = None) -> None:
     """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140).  coef: one fp32 on the device
     that multiplies grad_scale (grad_norm_'s out[1:]); clip_value: the scaled gradient is clamped to +-clip_value first
     (torch.nn.utils.clip_grad_value_).  Both None: the host-scale kernel.  avg / avg_weight (together or not at all): the same launch
     also moves the fp32 buffer ``avg`` (p's numel and device) towards the new p, avg += avg_weight * (p - avg) with 0 < avg_weight <= 1
-    (1 copies p); p and m come out bit for bit as without them (weight_average_ is that update alone)."""
+    (1 copies p); p and m come out bit for bit as without them (weight_average_ is that update alone).  groups (param_group_tables):
+    parameter groups -- an element whose chunk belongs to group k is stepped with lr * lr_scale[k] and weight_decay[k], a frozen group's
+    chunks are neither read nor written (p, m, avg keep their bits); the ``weight_decay`` argument is then ignored, every group has its
+    own.  One launch (bf_lion_groups) for every combination of coef / clip_value / avg.  None: exactly the calls made without it."""
     _require_gpu(p)
     av = _avg_args(avg, avg_weight, p, "lion_")
-    if av is not None:
+    if groups is not None:
+        L.check(L.lib().bf_lion_groups(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(grad_scale),
+                                       _coef_ptr(coef, p, "lion_"), _clip_or_inf(clip_value), *(av or (None, 0.0)), *_group_args(groups, p, "lion_"),
+                                       _stream()), "bf_lion_groups")
+    elif av is not None:
         L.check(L.lib().bf_lion_avg(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
                                     float(grad_scale), _coef_ptr(coef, p, "lion_"), _clip_or_inf(clip_value), *av, _stream()), "bf_lion_avg")
     elif coef is None and clip_value is None:
@@ -1464,12 +1560,17 @@ def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0
 
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
            eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
-           clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
+           clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None,
+           groups: Optional[ParamGroupTables] = None) -> None:
     """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value / avg /
-    avg_weight: see lion_."""
+    avg_weight / groups: see lion_ (bf_adamw_groups; m and v of a frozen chunk keep their bits too)."""
     _require_gpu(p)
     av = _avg_args(avg, avg_weight, p, "adamw_")
-    if av is not None:
+    if groups is not None:
+        L.check(L.lib().bf_adamw_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                        float(grad_scale), _coef_ptr(coef, p, "adamw_"), _clip_or_inf(clip_value), *(av or (None, 0.0)),
+                                        *_group_args(groups, p, "adamw_"), _stream()), "bf_adamw_groups")
+    elif av is not None:
         L.check(L.lib().bf_adamw_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                      float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adamw_"), _clip_or_inf(clip_value), *av,
                                      _stream()), "bf_adamw_avg")
@@ -1485,13 +1586,19 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
 
 def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
           eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
-          clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None) -> None:
+          clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None,
+          groups: Optional[ParamGroupTables] = None) -> None:
     """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
     weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay.  coef / clip_value: see lion_
-    (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step()).  avg / avg_weight: see lion_."""
+    (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step()).  avg / avg_weight / groups: see lion_
+    (bf_adam_groups: a group's weight decay is its L2 term)."""
     _require_gpu(p)
     av = _avg_args(avg, avg_weight, p, "adam_")
-    if av is not None:
+    if groups is not None:
+        L.check(L.lib().bf_adam_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                       float(grad_scale), _coef_ptr(coef, p, "adam_"), _clip_or_inf(clip_value), *(av or (None, 0.0)),
+                                       *_group_args(groups, p, "adam_"), _stream()), "bf_adam_groups")
+    elif av is not None:
         L.check(L.lib().bf_adam_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"), _clip_or_inf(clip_value), *av,
                                     _stream()), "bf_adam_avg")

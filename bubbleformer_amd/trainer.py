@@ -11,7 +11,8 @@
                       [gradient norm and clip coefficient, on the device] -> fused AdamW / Adam / Lion; with
                       ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only; with
                       ``unroll_steps=k`` the model is run through k of its own predictions with a loss on each (``unroll_plan``);
-                      with ``weight_average=`` the optimizer kernel also keeps an averaged copy of the weights (EMA / SWA).
+                      with ``weight_average=`` the optimizer kernel also keeps an averaged copy of the weights (EMA / SWA);
+                      with ``param_groups=`` it freezes parameters and gives groups their own learning-rate scale and weight decay.
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
@@ -26,9 +27,13 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ._lib import BF_OPT_CHUNK
+
 
 class FlatParams:
-    def __init__(self, module: nn.Module, align: int = 64):
+    def __init__(self, module: nn.Module, align: int = BF_OPT_CHUNK):
+        """align: every parameter starts on a multiple of it.  The default is the optimizers' chunk (one parameter-group id per chunk,
+        utils/param_groups.py); a step with param_groups needs a multiple of it."""
         params = [p for p in module.parameters() if p.requires_grad]
         self.params = params
         offs, n = [], 0
@@ -278,12 +283,26 @@ class TrainStep:
     parameters; every rank then computes the same average from the same parameters, so the feature launches no collective.
     ``averaged_state_dict()`` exports it, ``averaged_weights()`` puts it behind the model's parameters for a ``with`` block (validation,
     evaluate_rollouts), checkpoints carry it (utils/checkpoint.py).  Module buffers (BatchNorm running statistics) are not averaged.
-    None: no buffer, and the optimizer calls are the ones made without the argument."""
+    None: no buffer, and the optimizer calls are the ones made without the argument.
+    param_groups = a list of utils.param_groups.GroupSpec (its helpers no_weight_decay / layer_decay / freeze return such lists and compose by
+    ``+``): the parameters are sorted into at most 64 groups of one (lr_scale, weight_decay, frozen) each (``resolved_groups``; group 0 is the
+    default: scale 1, this step's weight_decay), and a one-byte group id per 64-element chunk of the flat buffer (``groups``: the map and the
+    tables on the device, built once) selects them inside the same single optimizer launch.  The SCHEDULED learning rate is multiplied by the
+    group's scale -- timm's ``lr_scale`` convention.  That is not torch's per-group CosineAnnealingLR, whose ``eta_min`` is absolute: here the
+    floor of a group is eta_min * lr_scale.  A frozen parameter, its moments and its average are never read or written by the optimizer (the
+    average stays bit-equal to the parameter); its gradient is still computed and, data parallel, exchanged.  Clipping by norm takes the norm
+    over the parameters that are not frozen -- what clip_grad_norm_ sees of a torch optimizer's parameters -- from ops.group_sumsq +
+    ops.group_clip_coef_ in place of ops.grad_norm_; ``grad_norm`` keeps its meaning ({norm, coef} of the last optimizer step), and
+    ``group_grad_norm`` (fp32 [groups], on the device; clipping by norm only, None otherwise) holds the scaled gradient norm of every group,
+    frozen ones included, of the last optimizer step.  Clipping by value, the averaged weights, accumulation, unrolling and input noise work
+    as without groups; every rank builds the same tables from the same specs.  ``requires_grad=False`` is not a way to freeze here: such a
+    parameter has no home in the flat buffers.  None: nothing is built and the optimizer calls are the ones made without the argument.
+    utils.param_groups.group_norms(step) gives every group's parameter and gradient norm on demand."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1, unroll_steps: int = 1, unroll_weights=None,
-                 unroll_backprop: bool = True, input_noise=None, field_std=None, weight_average=None):
+                 unroll_backprop: bool = True, input_noise=None, field_std=None, weight_average=None, param_groups=None):
         from . import ops
         from .utils.averaging import AverageSpec
         from .utils.noise import NoiseSpec
@@ -340,6 +359,11 @@ class TrainStep:
         self._unroll_w = None
         if self.unroll_steps > 1:
             self._unroll_w = torch.tensor(self.unroll_weights, dtype=torch.float32, device=self.flat.flat.device)
+        self.resolved_groups = None    # utils.param_groups.ResolvedGroups of param_groups
+        self.groups = None             # ops.ParamGroupTables: the chunk map and the group tables on the device
+        self.group_grad_norm = None    # param_groups and "norm" clipping: the scaled gradient norm of every group, last optimizer step
+        if param_groups is not None:
+            self._build_groups(param_groups)
         self.weight_average = weight_average
         self.avg = None           # the averaged copy of flat.flat; taken below, from the parameters every rank starts with
         self.n_averaged = 0       # updates of the average past spec.start_step
@@ -347,6 +371,20 @@ class TrainStep:
         self.sync_from_rank0()
         if weight_average is not None:
             self.avg = self.flat.flat.clone()
+
+    def _build_groups(self, specs) -> None:
+        from .utils.param_groups import CHUNK, resolve
+        flat = self.flat
+        if any(o % CHUNK for o in flat.offsets) or flat.numel % CHUNK:
+            raise ValueError(f"param_groups: the flat buffer must start every parameter on a multiple of {CHUNK} elements")
+        self.resolved_groups = res = resolve(self.model, list(specs), self.wd)
+        name_of = {id(p): n for n, p in self.model.named_parameters()}
+        cmap = res.chunk_map([name_of[id(p)] for p in flat.params], flat.offsets, flat.numel)
+        self.groups = self.ops.param_group_tables(cmap, [t[0] for t in res.table], [t[1] for t in res.table], [t[2] for t in res.table],
+                                                  flat.numel, flat.flat.device)
+        if self.grad_norm is not None:
+            self.group_grad_norm = torch.zeros(len(res), dtype=torch.float32, device=flat.flat.device)
+            self._group_sums = torch.zeros(len(res), dtype=torch.float64, device=flat.flat.device)
 
     @staticmethod
     def _check_unroll_fields(cin: int, cout: int) -> None:
@@ -428,7 +466,13 @@ class TrainStep:
         self.step_no += 1
         lr = self.scheduler.get_last_lr()[0] if self.scheduler is not None else self.lr
         clip = {}
-        if self.grad_norm is not None:
+        if self.grad_norm is not None and self.groups is not None:      # the norm over the groups that are not frozen
+            if self._norm_ws is None:
+                self._norm_ws = self.ops.group_sumsq_workspace(self.flat.numel, self.flat.grad.device)
+            self.ops.group_sumsq(self.flat.grad, self.groups, self._group_sums, self._norm_ws)
+            self.ops.group_clip_coef_(self._group_sums, self.groups, self.grad_norm, self.clip_val, gscale, self.group_grad_norm)
+            clip = {"coef": self._coef}
+        elif self.grad_norm is not None:
             if self._norm_ws is None:
                 self._norm_ws = self.ops.grad_norm_workspace(self.flat.numel, self.flat.grad.device)
             self.ops.grad_norm_(self.flat.grad, self.grad_norm, self.clip_val, gscale, self._norm_ws)
@@ -441,6 +485,8 @@ class TrainStep:
                 clip.update(avg=self.avg, avg_weight=w)
                 if self.weight_average.counts(self.step_no):
                     self.n_averaged += 1
+        if self.groups is not None:
+            clip["groups"] = self.groups
         if self.optimizer == "adamw":
             self.ops.adamw_(self.flat.flat, self.flat.grad, self.m, self.v, self.step_no, lr, self.betas, self.eps, self.wd, gscale, **clip)
         elif self.optimizer == "adam":

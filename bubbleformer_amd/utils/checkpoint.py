@@ -8,6 +8,8 @@ plus, for resuming the native training step, "optimizer_states" / "lr_schedulers
 moments and the scheduler position (Lightning stores its torch.optim state dicts under those keys; ours are flat buffers, so a
 checkpoint written here resumes here, while its "state_dict" loads anywhere the reference's does).  A training step that keeps an
 averaged copy of the weights (TrainStep(weight_average=...)) adds "weight_average": its spec, the update count and the flat average;
+a step with parameter groups (TrainStep(param_groups=...)) adds "param_groups": its partition, a list of {name, lr_scale, weight_decay,
+frozen, params: [names]} (utils.param_groups.ResolvedGroups.partition), which a grouped step checks on loading;
 `save_checkpoint(averaged=True)` instead writes the averaged weights AS the "state_dict", with no training state: the file to release.
 
 `load_checkpoint` also resumes from a file the reference's Lightning run wrote (e.g. the pre-emption `hpc_ckpt_*.ckpt` files of
@@ -61,6 +63,8 @@ def save_checkpoint(path: str, model: torch.nn.Module, hyper_parameters: Optiona
             spec = train_step.weight_average
             ckpt["weight_average"] = {"kind": spec.kind, "decay": spec.decay, "warmup": spec.warmup, "start_step": spec.start_step,
                                       "every": spec.every, "n_averaged": int(train_step.n_averaged), "avg": train_step.avg.detach().cpu()}
+        if getattr(train_step, "resolved_groups", None) is not None:
+            ckpt["param_groups"] = train_step.resolved_groups.partition()
     if epoch is not None:
         ckpt["epoch"] = int(epoch)
     tmp = path + ".tmp"
@@ -171,6 +175,9 @@ def _load_reference_optimizer(ckpt: dict, model: torch.nn.Module, train_step) ->
         raise ValueError("the reference's optimizer holds every model parameter; this training step's flat buffer does not")
     got = flat_state_from_torch_optim(ckpt["optimizer_states"][0], [p.shape for p in flat.params], flat.offsets, flat.numel,
                                       train_step.optimizer)
+    if getattr(train_step, "resolved_groups", None) is not None and got["weight_decay"] != train_step.wd:
+        raise ValueError(f"the checkpoint's weight_decay {got['weight_decay']} would replace the training step's {train_step.wd}, from which its "
+                         f"parameter-group tables were built: construct the TrainStep with weight_decay={got['weight_decay']}")
     if train_step.scheduler is None:
         train_step.lr = got["lr"]             # what Optimizer.load_state_dict leaves in the group when nothing schedules it
     elif ckpt.get("lr_schedulers"):
@@ -193,7 +200,11 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
     weight_decay of param_groups[0] become the training step's, and a native CosineWarmupLR takes the reference schedule's base lr,
     warm-up, max_iters, eta_min and position.  Lightning's loop state ("loops") is not restored.  A training step that averages its weights
     takes "weight_average" (the flat average and its update count; a numel mismatch is a ValueError) or, from a file without it, starts
-    its average from the loaded parameters with a count of 0; a step that does not average ignores the key.  Unpickling a real Lightning file
+    its average from the loaded parameters with a count of 0; a step that does not average ignores the key.  A training step with parameter
+    groups refuses (ValueError, before any weight is written) a file whose "param_groups" partition differs from its own -- the moments of a
+    parameter that was frozen there are not the moments of one that trained; a file without the key loads as always, and a step without
+    groups ignores it.  The reference's multi-group torch.optim state stays refused (flat_state_from_torch_optim), and a grouped step refuses a
+    reference state whose weight_decay is not its own (its default group's row was built from that).  Unpickling a real Lightning file
     whose hyper_parameters hold OmegaConf objects needs the `omegaconf` package (not a dependency of this project)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
     sd = from_reference_state_dict(ckpt["state_dict"])
@@ -207,6 +218,13 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
     wa = ckpt.get("weight_average") if averages else None
     if wa is not None and wa["avg"].numel() != train_step.avg.numel():
         raise ValueError(f"checkpoint average holds {wa['avg'].numel()} elements, the training step's flat buffer {train_step.avg.numel()}")
+    own_groups = getattr(train_step, "resolved_groups", None) if train_step is not None else None
+    if own_groups is not None and ckpt.get("param_groups") is not None:
+        from .param_groups import same_partition
+        if not same_partition(ckpt["param_groups"], own_groups.partition()):
+            raise ValueError("checkpoint was written with other parameter groups than the training step's: its (lr_scale, weight_decay, frozen) "
+                             f"partition {[(g['name'], len(g['params'])) for g in ckpt['param_groups']]} differs from "
+                             f"{[(n, len(m)) for n, m in zip(own_groups.names, own_groups.members)]}")
     if reference:
         _load_reference_optimizer(ckpt, model, train_step)          # refuses before any weight is written
     with torch.no_grad():

@@ -628,6 +628,39 @@ int bf_lion_avg(float* p, const float* g, float* m, int64_t n, float lr, float b
                 const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
 int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream);
 int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream);
+/* Parameter groups for the flat optimizers (freeze, per-group learning-rate scale and weight decay).  The flat
+ * buffer is cut into chunks of BF_OPT_CHUNK consecutive elements; trainer.FlatParams starts every parameter on a chunk boundary, so a
+ * chunk belongs to one parameter.  chunk_group[ceil(n / BF_OPT_CHUNK)] (uint8, DEVICE memory) names each chunk's group, and three tables
+ * in DEVICE memory describe the n_groups groups (1 <= n_groups <= BF_OPT_MAX_GROUPS): lr_scale[k] (fp32, >= 0), weight_decay[k] (fp32,
+ * >= 0, absolute) and frozen[k] (uint8).
+ * bf_adamw_groups / bf_adam_groups / bf_lion_groups take the arguments of the matching _avg entry WITHOUT its wd (every group brings its
+ * own), then the chunk map, the tables and n_groups; avg may be NULL (no average kept; avg_weight is then ignored).  The scale mode is
+ * chosen as in the _avg entries.  An element of group k is stepped with lr * lr_scale[k] and weight_decay[k] by the same kernel body as the
+ * ungrouped entries: one group of scale 1 gives their bits.  lr_scale[k] == 0 with frozen[k] == 0 is torch's lr = 0: the moments move,
+ * the parameter does not.  A chunk of a frozen group is neither read nor written: p, m, v and avg keep their bits and nothing in its
+ * gradient (a NaN included) reaches anything.  The entry points cannot check the map's ids without reading it; the kernels treat an id
+ * >= n_groups as frozen.
+ * bf_group_sumsq: sums[k] = sum of x[i]^2 over the elements whose chunk has group k (fp64, n_groups doubles in DEVICE memory), in a fixed
+ *   order with no float atomics: the same bits on every call.  ws: at least bf_group_sumsq_ws_doubles(n) doubles, 8-byte aligned.
+ * bf_group_clip_coef: from those sums, out = {norm, coef} (two fp32 in DEVICE memory) as bf_grad_norm writes them, with
+ *   norm = gscale * sqrt(sum over the groups with frozen[k] == 0 of sums[k]), added in group order -- clip_grad_norm_ over the parameters a
+ *   torch optimizer would hold -- and, when group_norm is not NULL, group_norm[k] = gscale * sqrt(sums[k]) for every group (fp32). */
+#define BF_OPT_CHUNK 64
+#define BF_OPT_MAX_GROUPS 64
+int bf_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                    float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
+                    const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
+int bf_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
+                   float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
+                   const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
+int bf_lion_groups(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float gscale, const float* coef_dev,
+                   float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group, const float* lr_scale,
+                   const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
+int64_t bf_group_sumsq_ws_doubles(int64_t n);
+int bf_group_sumsq(const float* x, int64_t n, const uint8_t* chunk_group, int n_groups, double* sums, double* ws, int64_t ws_doubles,
+                   bf_stream_t stream);
+int bf_group_clip_coef(const double* sums, const uint8_t* frozen, int n_groups, float gscale, float max_norm, float* out,
+                       float* group_norm, bf_stream_t stream);
 
 /* ---------------------------------------------------------------- stage-level entry points (what the nn.Modules call) */
 

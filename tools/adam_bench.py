@@ -11,7 +11,12 @@ and the share of the 8.0 TB/s HBM peak (MI355X_MICROARCH: about 6.3 TB/s is achi
 protocol: (a) the unchanged plain entry, (b) the _avg entry, which also reads and writes the average (36 bytes per element; Lion 28
 against 20), (c) the plain entry followed by bf_weight_average (40; Lion 32, and a second launch).
 
-Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average]"""
+--groups times the parameter-group launch per optimizer (AdamW, Lion) under the same protocol: (a) the unchanged
+ungrouped entry, (b) the _groups entry with every group live -- the table utils.param_groups gives no_weight_decay + layer_decay(0.75) on
+the model's parameter names and shapes, (c) the _groups entry with the trunk (blocks.*) frozen.  The grouped launches also read one map
+byte per 64 elements; a frozen chunk moves no other byte, so (c) is reported beside the live share of the buffer.
+
+Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average | --groups]"""
 import argparse
 import json
 import os
@@ -117,17 +122,70 @@ def time_average(n, rounds, reps):
     return out
 
 
+def group_tables(cfg, specs_of, weight_decay):
+    """ops.ParamGroupTables for the model's flat layout from its parameter names and shapes alone (meta tensors), and the live share."""
+    from bubbleformer_amd import ops
+    from bubbleformer_amd.utils import param_groups as PG
+    named = [(k, torch.empty(shape, device="meta")) for k, shape in W.param_shapes(**cfg).items()]
+    offs, n = [], 0
+    for _, t in named:
+        offs.append(n)
+        n += (t.numel() + PG.CHUNK - 1) // PG.CHUNK * PG.CHUNK
+    res = PG.resolve(named, specs_of(named), weight_decay)
+    cmap = res.chunk_map([k for k, _ in named], offs, n)
+    frozen = torch.tensor([t[2] for t in res.table])
+    live = 1.0 - float(frozen[cmap.long()].float().mean())
+    return ops.param_group_tables(cmap, [t[0] for t in res.table], [t[1] for t in res.table], [t[2] for t in res.table], n, "cuda"), len(res), live
+
+
+def time_groups(cfg, n, rounds, reps):
+    """Per optimizer: "ungrouped" (bf_adamw / bf_lion), "all_live" and "trunk_frozen" (the _groups entry); ms per launch, and each grouped
+    launch over the ungrouped one of the same run."""
+    from bubbleformer_amd.utils import param_groups as PG
+    g = torch.Generator(device="cuda").manual_seed(0)
+    p = torch.randn(n, device="cuda", generator=g) * 0.02
+    grad = torch.randn(n, device="cuda", generator=g) * 1e-3
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    h, st, inf = L.lib(), _stream(), float("inf")
+    out = {}
+    for opt, wd, base in (("adamw", 1e-2, 28), ("lion", 0.1, 20)):
+        live_t, G_live, _ = group_tables(cfg, lambda named: PG.no_weight_decay() + PG.layer_decay(named, 0.75), wd)
+        froz_t, G_froz, share = group_tables(cfg, lambda named: PG.freeze(r"^blocks\."), wd)
+
+        def grouped(t):
+            tabs = (_p(t.chunk), _p(t.lr_scale), _p(t.weight_decay), _p(t.frozen), t.n_groups)
+            if opt == "adamw":
+                return lambda: h.bf_adamw_groups(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1.0, None, inf, None, 0.0, *tabs, st)
+            return lambda: h.bf_lion_groups(_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, 1.0, None, inf, None, 0.0, *tabs, st)
+        plain = (lambda: h.bf_adamw(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, wd, 1.0, st)) if opt == "adamw" else \
+            (lambda: h.bf_lion(_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, wd, 1.0, st))
+        ms = rounds_of({"ungrouped": plain, "all_live": grouped(live_t), "trunk_frozen": grouped(froz_t)}, rounds, reps)
+        res = {"ungrouped": summary(ms["ungrouped"], n, base), "all_live": summary(ms["all_live"], n, base),
+               "trunk_frozen": summary(ms["trunk_frozen"], int(n * share), base)}
+        res["groups_all_live"], res["groups_trunk_frozen"], res["live_share_trunk_frozen"] = G_live, G_froz, round(share, 4)
+        res["all_live_over_ungrouped"] = round(res["all_live"]["ms"] / res["ungrouped"]["ms"], 3)
+        res["trunk_frozen_over_ungrouped"] = round(res["trunk_frozen"]["ms"] / res["ungrouped"]["ms"], 3)
+        out[opt] = res
+    assert torch.isfinite(p).all()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--average", action="store_true", help="time the averaged-weights step: plain, fused _avg entry, plain + bf_weight_average")
+    ap.add_argument("--groups", action="store_true", help="time the parameter-group launch: ungrouped, every group live, trunk frozen")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/adam_bench.py times GPU kernels: no GPU found"
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "bytes_per_element": BYTES_PER_ELEMENT}
     for name, cfg in MODELS.items():
         params, n = flat_sizes(cfg)
-        res[name] = dict(parameters=params, flat_elements=n, **(time_average if args.average else time_kernels)(n, args.rounds, args.reps))
+        if args.groups:
+            timed = time_groups(cfg, n, args.rounds, args.reps)
+        else:
+            timed = (time_average if args.average else time_kernels)(n, args.rounds, args.reps)
+        res[name] = dict(parameters=params, flat_elements=n, **timed)
         torch.cuda.empty_cache()
     print(json.dumps(res))
 
