@@ -231,6 +231,10 @@ SIGNATURES = {
     "bf_bubble_census_ws_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
     "bf_bubble_census": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, fp, vp, vp, vp, i64, vp]),
     "bf_rollout_bubbles": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, P(CensusRows), P(CensusRows), vp, vp, i64, vp]),
+    "bf_redistance_lds_cells": (i64, []),
+    "bf_redistance_ws_bytes": (i64, [i64, C.c_int, C.c_int]),
+    "bf_redistance": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, f32, C.c_int, fp, vp, fp, vp, i64, vp]),
+    "bf_rollout_redistance": (C.c_int, [P(RolloutStep), C.c_int, f32, f32, C.c_int, C.c_int, fp, vp, fp, vp, i64, vp]),
     "bf_bubble_links_lds_entries": (i64, []),
     "bf_bubble_links_ws_bytes": (i64, [i64, C.c_int]),
     "bf_bubble_links": (C.c_int, [vp, P(CensusRows), i64, C.c_int, C.c_int, C.c_int, C.c_int, P(LinkRows), vp, i64, vp]),

@@ -1142,6 +1142,59 @@ def _rollout_census(who: str, step_args: tuple, sdf_channel: int, connectivity: 
                                        ws.numel(), stream), "bf_rollout_bubbles")
 
 
+def redistance_workspace(frames: int, H: int, W: int, device) -> torch.Tensor:
+    """The workspace ``redistance`` (and, with frames = B * T, ``rollout_redistance``) needs: allocate once, outside a graph capture.  It holds the
+    distances of frames that do not fit ``redistance_lds_cells()``; a frame larger than the library supports is refused here, before any launch."""
+    nbytes = L.lib().bf_redistance_ws_bytes(int(frames), int(H), int(W))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"redistance_workspace: {frames} frames of {H} x {W} are not supported (every size at least 1, at most 2^24 cells per frame)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def redistance_lds_cells() -> int:
+    """Frames of at most this many cells are redistanced in LDS, larger ones in the workspace (bf_redistance_lds_cells)."""
+    return int(L.lib().bf_redistance_lds_cells())
+
+
+def redistance(phi: torch.Tensor, dx: float, band: Optional[float], max_rounds: Optional[int], ws: torch.Tensor, out: torch.Tensor,
+               rounds: Optional[torch.Tensor] = None, change_rms: Optional[torch.Tensor] = None) -> None:
+    """out = the signed distance to the zero level set of every frame of phi (F, H, W) fp32 at spacing dx (bf_redistance;
+    include/bubbleformer_hip.h has the contract); out may be phi.  band None: no cap; max_rounds None: H + W.  rounds (F,) int32 and
+    change_rms (F,) fp32 are optional.  ws: ``redistance_workspace(F, H, W)``.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(phi)
+    if phi.dim() != 3 or phi.dtype != torch.float32 or not phi.is_contiguous():
+        raise L.BubbleformerHipError("redistance: phi must be a contiguous fp32 (frames, H, W) tensor")
+    F, H, W = (int(v) for v in phi.shape)
+    _check_tensors("redistance", phi.device, {"out": (out, (F, H, W), torch.float32), "rounds": (rounds, (F,), torch.int32),
+                   "change_rms": (change_rms, (F,), torch.float32), "ws": (ws, (ws.numel(),), torch.uint8)}, ("rounds", "change_rms"))
+    need = L.lib().bf_redistance_ws_bytes(F, H, W)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("redistance: the workspace is smaller than redistance_workspace(frames, H, W)")
+    L.check(L.lib().bf_redistance(_p(phi), F, H, W, float(dx), 0.0 if band is None else float(band), 0 if max_rounds is None else int(max_rounds),
+                                  _p(out), _p(rounds), _p(change_rms), _p(ws), ws.numel(), _stream()), "bf_redistance")
+
+
+def rollout_redistance(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, sdf_channel: int, steps: int,
+                       dx: float, band: Optional[float], max_rounds: Optional[int], every: int, ws: torch.Tensor,
+                       rounds: Optional[torch.Tensor] = None, change_rms: Optional[torch.Tensor] = None) -> None:
+    """``redistance`` of the de-normalised signed-distance channel of one rollout step's prediction, written back IN PLACE and renormalised
+    (bf_rollout_redistance; include/bubbleformer_hip.h has the contract), on the steps s with (s + 1) % every == 0, s = the int32 ``step`` tensor
+    ON THE DEVICE, which this call only reads -- issue it BEFORE every other call of the step.  Row s * T + t of rounds (B, steps*T) int32 and
+    change_rms (B, steps*T) fp32 (each optional).  ws: ``redistance_workspace(B * T, Ho, Wo)``.  Allocates nothing."""
+    rec, stream = _rollout_step_args("rollout_redistance", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    _check_tensors("rollout_redistance", pred.device, {"rounds": (rounds, (B, steps * T), torch.int32), "change_rms": (change_rms, (B, steps * T), torch.float32),
+                   "ws": (ws, (ws.numel(),), torch.uint8)}, ("rounds", "change_rms"))
+    if not 0 <= int(sdf_channel) < Cn:
+        raise L.BubbleformerHipError(f"rollout_redistance: channel {sdf_channel} is not among the prediction's {Cn}")
+    need = L.lib().bf_redistance_ws_bytes(B * T, Ho, Wo)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_redistance: the workspace is smaller than redistance_workspace(B * T, Ho, Wo)")
+    L.check(L.lib().bf_rollout_redistance(C.byref(rec), int(sdf_channel), float(dx), 0.0 if band is None else float(band),
+                                          0 if max_rounds is None else int(max_rounds), int(every), _p(pred), _p(rounds), _p(change_rms), _p(ws),
+                                          ws.numel(), stream), "bf_rollout_redistance")
+
+
 def bubble_links_workspace(pairs: int, max_bubbles: int, device) -> torch.Tensor:
     """The workspace ``bubble_links`` (and, with pairs = 2 * B * T, ``rollout_bubble_links``) needs: allocate once, outside a graph capture.  It holds
     the overlap tables that do not fit ``bubble_links_lds_entries()``; more records than the library supports are refused here, before any launch."""

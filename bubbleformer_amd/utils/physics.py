@@ -221,6 +221,74 @@ def bubble_census(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int 
                         on_heater.reshape(lead + (mb,)), (int(H), int(W)), labels.reshape(lead + (int(H), int(W))) if labels is not None else None)
 
 
+def _check_redistance_arguments(dx, band, max_rounds) -> None:
+    if not dx > 0:
+        raise ValueError(f"dx must be positive, got {dx}")
+    if band is not None and not band > 0:
+        raise ValueError(f"band must be None or positive, got {band}")
+    if max_rounds is not None and (int(max_rounds) != max_rounds or int(max_rounds) < 1):
+        raise ValueError(f"max_rounds must be None or an integer of at least 1, got {max_rounds!r}")
+
+
+@dataclasses.dataclass(frozen=True)
+class RedistanceSpec:
+    """Redistancing of the predicted signed-distance field during a rollout (``evaluate_rollouts_redistanced(..., RedistanceSpec())``): the cell
+    size, the distance cap (None: none), the pass limit (None: H + W), and ``every``: the correction runs on the steps s with (s + 1) % every == 0.
+    The scheme is first order and moves the interpolated zero crossings by a few hundredths of a cell per application, so on a long rollout a
+    larger ``every`` keeps the interface from creeping."""
+    dx: float = 1.0 / 32
+    band: Optional[float] = None
+    max_rounds: Optional[int] = None
+    every: int = 1
+    sdf_field: str = "dfun"
+
+    def __post_init__(self):
+        _check_redistance_arguments(self.dx, self.band, self.max_rounds)
+        if int(self.every) != self.every or int(self.every) < 1:
+            raise ValueError(f"every must be an integer of at least 1, got {self.every!r}")
+
+    def channel(self, fields: Sequence[str]) -> int:
+        """The signed-distance channel among the output fields."""
+        fields = list(fields)
+        if self.sdf_field not in fields:
+            raise ValueError(f"redistancing needs the field {self.sdf_field!r} among the output fields {fields}")
+        return fields.index(self.sdf_field)
+
+
+def redistance(phi: torch.Tensor, dx: float = 1.0 / 32, band: Optional[float] = None, max_rounds: Optional[int] = None,
+               out: Optional[torch.Tensor] = None, return_status: bool = False):
+    """The signed distance to the zero level set of every frame of phi (..., H, W), an fp32 field in physical units on the device, by
+    first-order redistancing at spacing ``dx`` (``ops.redistance``): interface cells take the distance to the linearly
+    interpolated crossings and are frozen, the others the Godunov upwind solution of |grad d| = 1, capped at ``band`` if given.  The signs and
+    the interface cells are those of phi exactly.  ``out`` (like phi, contiguous; may be phi) receives the result.  With ``return_status``
+    -> (result, rounds, change_rms), both of phi's leading dims: rounds int32 >= 1 passes run, 0 a one-sign frame (unchanged), -1 a non-finite
+    frame (unchanged), -2 ``max_rounds`` (default H + W) ran out; change_rms fp32 the root mean square change.  One launch, a workgroup per
+    frame; never synchronises; the same bits on every call, and for a frame alone or in a batch."""
+    _check_redistance_arguments(dx, band, max_rounds)
+    if phi.dim() < 2:
+        raise ValueError(f"redistance expects (..., H, W), got {tuple(phi.shape)}")
+    if phi.numel() < 1:                               # before any reshape: a zero-sized axis has no frame to name
+        raise ValueError(f"redistance needs at least one frame of at least one cell, got {tuple(phi.shape)}")
+    from .. import ops
+    _require_gpu(phi)
+    if phi.dtype != torch.float32:
+        raise L.BubbleformerHipError(f"redistance: phi must be fp32, got {phi.dtype}")
+    lead, (H, W) = tuple(phi.shape[:-2]), (int(phi.shape[-2]), int(phi.shape[-1]))
+    flat = phi.reshape(-1, H, W).contiguous()
+    F = flat.shape[0]
+    if out is None:
+        result = torch.empty_like(flat)
+    else:
+        if out.shape != phi.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != phi.device:
+            raise L.BubbleformerHipError(f"redistance: out must be a contiguous fp32 tensor of shape {tuple(phi.shape)} on {phi.device}")
+        result = out.view(-1, H, W)
+    rounds = torch.empty(F, dtype=torch.int32, device=flat.device) if return_status else None
+    change = torch.empty(F, dtype=torch.float32, device=flat.device) if return_status else None
+    ops.redistance(flat, float(dx), band, max_rounds, ops.redistance_workspace(F, H, W, flat.device), result, rounds, change)
+    result = out if out is not None else result.reshape(phi.shape)
+    return (result, rounds.reshape(lead), change.reshape(lead)) if return_status else result
+
+
 def departure_diameters(departure_area: torch.Tensor, dx: float = 1.0 / 32) -> torch.Tensor:
     """The equivalent diameters of the bubbles that leave the heater, a 1-D fp32 device tensor in row order, from ``departure_area`` rows (area at
     the departing bubble's slot, 0 elsewhere, -1 in an invalid pair).  SYNCHRONISES: dropping the empty slots makes the host wait for their number."""

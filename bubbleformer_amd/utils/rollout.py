@@ -166,6 +166,9 @@ class RolloutReport:
     ensemble_crps = None                                # (Bt, steps*T, C)         fp32 mean CRPS over the pixels
     ensemble_rank_hist = None                           # (Bt, steps*T, C, M + 1)  int32 pixels whose truth has r members strictly below it
     ensemble_mean = None                                # (Bt, steps*T, C, Ho, Wo) fp32 the member mean (EnsembleSpec(keep_mean=True))
+    # from evaluate_rollouts_redistanced: the status and the change of the correction of every predicted frame (physics.redistance), else None
+    redistance_rounds = None                            # (B, steps*T)        int32 passes run; 0 one sign or a skipped step, -1 non-finite, -2 ran out
+    redistance_change = None                            # (B, steps*T)        fp32 root mean square change of the physical field
 
     def _ensemble(self):
         if self.ensemble_members is None:
@@ -206,7 +209,7 @@ class RolloutReport:
         if self.bubble_events_pred is not None:
             for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
-        for key in _ERROR_KEYS + _ENSEMBLE_KEYS:
+        for key in _ERROR_KEYS + _ENSEMBLE_KEYS + _REDISTANCE_KEYS:
             if getattr(self, key) is not None:
                 out[key] = getattr(self, key)
         torch.save(out, path)
@@ -313,6 +316,7 @@ _TRACK_KEYS = ("bubble_events_pred", "bubble_events_target", "bubble_successor_p
 _ERROR_KEYS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
                "spectrum_target")
 _ENSEMBLE_KEYS = ("ensemble_members", "ensemble_mean_rmse", "ensemble_spread", "ensemble_crps", "ensemble_rank_hist", "ensemble_mean")
+_REDISTANCE_KEYS = ("redistance_rounds", "redistance_change")
 _BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
                 "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
 
@@ -354,7 +358,31 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     (``ops.rollout_ensemble``, captured with it) leaves the statistics across the members of every predicted frame and field:
     ``ensemble_mean_rmse``, ``ensemble_spread``, ``ensemble_crps`` (Bt, steps*T, C), ``ensemble_rank_hist`` and, if kept, ``ensemble_mean``;
     ``report.spread_skill()`` and ``report.rank_histogram()`` read them.  ``EnsembleSpec(relative=True)`` takes ``store.field_std()`` first,
-    which is ONE host synchronisation before the loop; nothing else of the call waits for the device."""
+    which is ONE host synchronisation before the loop; nothing else of the call waits for the device.
+
+    ``evaluate_rollouts_redistanced`` is this call with the predicted signed-distance field redistanced in place at the head of every step."""
+    return _evaluate_rollouts(model, data, starts, steps, None, use_graph=use_graph, sdf_field=sdf_field, keep_predictions=keep_predictions,
+                              heatflux=heatflux, bubbles=bubbles, errors=errors, ensemble=ensemble)
+
+
+def evaluate_rollouts_redistanced(model, data, starts: Sequence[int], steps: int, redistance: "Optional[RedistanceSpec]",  # noqa: F821 (physics.RedistanceSpec)
+                                  **options) -> RolloutReport:
+    """``evaluate_rollouts(model, data, starts, steps, **options)`` with the predicted signed-distance field repaired as the rollout goes.
+
+    With ``redistance`` (a ``physics.RedistanceSpec``) the FIRST call of a step, before every other call of it, replaces the signed-distance channel of the
+    prediction in place by its redistanced field (``ops.rollout_redistance``: de-normalised, ``physics.redistance``, renormalised), on the steps s
+    with (s + 1) % every == 0: the heat flux, the census, the errors, the ensemble statistics and the scores all see the corrected prediction, and the
+    scoring call feeds it back and archives it.  The report gains ``redistance_rounds`` and ``redistance_change`` (B, steps*T), per member with
+    ``ensemble``.  ``redistance=None`` is ``evaluate_rollouts`` itself: the same launches, the same bits.  The operation is first order and not differentiable: it
+    belongs to evaluation, not to ``autoregressive_rollout`` or the training step.
+
+    A function of its own rather than one more keyword of ``evaluate_rollouts``: that function's parameter list is held as it is."""
+    return _evaluate_rollouts(model, data, starts, steps, redistance, **options)
+
+
+def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True, sdf_field="dfun", keep_predictions=False, heatflux=None, bubbles=None,
+                       errors=None, ensemble=None) -> RolloutReport:
+    """The one implementation behind ``evaluate_rollouts`` (redistance = None) and ``evaluate_rollouts_redistanced``."""
     from .. import ops
     from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
@@ -400,6 +428,12 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     counter = torch.zeros(1, dtype=torch.int32, device=device)
     ws = ops.rollout_score_workspace(x)
     before_score = []                               # (pred, step) calls that read the step counter the scoring call then advances, in launch order
+    red_rows = None
+    if redistance is not None:                      # first: every later call of the step reads the corrected prediction
+        red_args = (redistance.channel(fields), steps, float(redistance.dx), redistance.band, redistance.max_rounds, int(redistance.every),
+                    ops.redistance_workspace(B * T, Ho, Wo, device))
+        red_rows = (torch.empty((B, steps * T), dtype=torch.int32, device=device), new(B, steps * T))
+        before_score.append(lambda pred, step: ops.rollout_redistance(pred, store.frames, first, step, store.out_tab, *red_args, *red_rows))
     hf_p = hf_t = None
     if heatflux is not None:
         hf_channels = heatflux.channels(fields)
@@ -498,6 +532,8 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     if err_rows is not None:
         for key, rows in err_rows.items():
             setattr(report, key, rows)
+    if red_rows is not None:
+        report.redistance_rounds, report.redistance_change = red_rows
     if ens_rows is not None:
         report.ensemble_members = members
         for key, rows in ens_rows.items():

@@ -36,6 +36,7 @@
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
+ *   bf_redistance ............ first-order redistancing of a signed-distance field (no reference program); bf_rollout_redistance: per step, in place
  *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
  *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
  *   bf_ensemble_scores ....... ensemble-mean RMSE, spread, CRPS and rank histogram across members (no reference program); bf_rollout_ensemble: per step
@@ -492,6 +493,40 @@ int bf_bubble_census(const float* phi, int64_t frames, int H, int W, int connect
  * With s outside [0, steps) nothing is written.  ws: bf_bubble_census_ws_bytes(2 * B * T, Ho, Wo, max_bubbles) bytes, 16-byte aligned. */
 int bf_rollout_bubbles(const bf_rollout_step* s, int sdf_channel, int connectivity, int max_bubbles, const bf_census_rows* pred,
                        const bf_census_rows* tgt, int32_t* labels, void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* Redistancing (reinitialisation) of `frames` signed-distance fields phi [frames][H][W] fp32 in physical units with square cells of size dx
+ * (csrc/redistance.hip; the reference has no program for it): out = the signed distance to phi's own zero level set, first order.
+ *   sign       a cell is vapour (+) iff phi > 0; an exact zero is liquid (-), bf_bubble_census' convention;
+ *   interface  a cell with a 4-neighbour inside the frame of the other sign.  Per such neighbour n the crossing distance is t = dx |phi_c| / (|phi_c| + |phi_n|);
+ *              tx = the smaller t over left / right, ty over up / down; d = t with one axis present, 1 / sqrt(1 / tx^2 + 1 / ty^2) with both, 0 if a present
+ *              t is 0.  Interface cells are frozen;
+ *   the rest   start at +inf and take the fixed point of the Godunov upwind update of |grad d| = 1: a = min(left, right), b = min(up, down) (neighbours
+ *              outside the frame are absent), lo = min(a, b), hi = max(a, b); u = lo + dx if hi is absent, infinite or hi - lo >= dx, else
+ *              (lo + hi + sqrt(2 dx^2 - (hi - lo)^2)) / 2; with band > 0, u = min(u, band); a value is replaced only by a strictly smaller u.  A pass is two
+ *              checkerboard half-passes in place, cells with even x + y first; passes run until one changes no cell;
+ *   out        +d on vapour, -d on liquid cells: the signs and the interface cells of phi exactly.  out may be phi.
+ *   rounds [frames] int32 (may be NULL)      >= 1: passes executed, the quiet last one included; 0: the frame has one sign throughout and is returned unchanged;
+ *              -1: the frame holds a NaN or an inf and is returned unchanged; -2: max_rounds passes ran without a quiet one: the frame holds the values
+ *              reached, cells no pass reached hold sign * (band if given, else (H + W) dx).  max_rounds <= 0 means H + W;
+ *   change_rms [frames] fp32 (may be NULL)   sqrt(mean (out - phi)^2): differences and the sum in fp64 in a fixed order, one rounding; 0 for an unchanged frame.
+ * One workgroup owns a frame; fp32 distances without fused contraction, no float atomics, no race between the cells of a half-pass: the same bits on every
+ * call, and a frame has the same bits alone and in a batch.  Allocation-free, capturable, never makes the host wait.  Any H, W >= 1 with H * W <= 2^24
+ * (refused beyond, before any launch).  Frames of at most bf_redistance_lds_cells() cells keep the distances in LDS, larger ones in the workspace.
+ * ws: bf_redistance_ws_bytes(frames, H, W) bytes (at least 16), 16-byte aligned (0 from the query: sizes out of range). */
+int64_t bf_redistance_lds_cells(void);
+int64_t bf_redistance_ws_bytes(int64_t frames, int H, int W);
+int bf_redistance(const float* phi, int64_t frames, int H, int W, float dx, float band, int max_rounds, float* out, int32_t* rounds, float* change_rms,
+                  void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* bf_redistance of the signed-distance channel of ONE rollout step's prediction, IN PLACE: issue it before every other call of the step, which then all see the
+ * corrected prediction.  s: see bf_rollout_step; pred is the tensor s->pred names, here written.  With the step number s = *s->step in [0, steps) and
+ * (s + 1) % every == 0, frame (b, t) of channel sdf_channel is read as pred * div + diff (fp32 multiply, then add, unfused: the physical field the other
+ * rollout calls see), redistanced, and written back as (d - diff) / div (bf_clip_gather's expression); row s * T + t of trajectory b of rounds / change_rms
+ * [B][steps*T] (each may be NULL) is bf_redistance's status and change of that frame (in physical units).  A frame with status 0 or -1 is not written.
+ * One exception to "the signs of the input exactly": the write-back rounds, so a cell whose distance is 0 or within the rounding of diff comes back as a
+ * physical value of 0 (liquid to every later call) or, rarely, of the other sign, whichever its sign was; bf_redistance itself has no such case.  On a
+ * step in [0, steps) that `every` skips, the call writes rounds = 0 and change_rms = 0 in the step's rows and nothing else; with s outside [0, steps) nothing.
+ * ws: bf_redistance_ws_bytes(B * T, Ho, Wo) bytes, 16-byte aligned. */
+int bf_rollout_redistance(const bf_rollout_step* s, int sdf_channel, float dx, float band, int max_rounds, int every, float* pred, int32_t* rounds,
+                          float* change_rms, void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* Bubbles followed from frame to frame (csrc/bubble_tracks.hip; the reference has no program for it).  labels [sequences][T][H][W] and census' count / attached
  * [sequences][T] and area [sequences][T][max_bubbles] (cells is unread and may be NULL) are what bf_bubble_census left for sequences * T frames; a pair is two consecutive frames a, b
  * of one sequence, pair row q = sequence * (T - 1) + t of the link rows for frames t, t + 1.  With ka = min(count_a, max_bubbles), kb likewise (labels above them count

@@ -14,10 +14,13 @@ those fixed costs out, and `traj_steps_per_s` is its inverse times the trajector
 spread.  `scoring` times the scoring call alone with device events: bytes (prediction once + target frames once + copies) over time as a
 share of 8 TB/s.
 
-Usage: python tools/rollout_eval_bench.py [--rounds R] [--only today|batched|scoring] [--batches 1,2,4,8] [--graph-only] [--tree CHECKOUT]
+Usage: python tools/rollout_eval_bench.py [--rounds R] [--only today|batched|scoring] [--batches 1,2,4,8] [--graph-only] [--tree CHECKOUT] [--redistance]
 (--tree imports bubbleformer_amd from another checkout of this repository, to time `today` on another commit in the same run).
 --ensemble 4,16 runs the ensemble measurement instead: per member count M, the step on M * 2 rows with and without EnsembleSpec(M), and the
-bf_rollout_ensemble call alone beside bf_rollout_score on the same prediction (device events, bytes over time)."""
+bf_rollout_ensemble call alone beside bf_rollout_score on the same prediction (device events, bytes over time).
+--redistance runs the redistancing measurement instead: the batched graph variant at 8 trajectories per forward with and without
+RedistanceSpec(), alternated inside every round, and the passes the correction took (the synthetic study's dfun is noise, nearly all
+interface cells: few passes; tools/redistance_bench.py times the kernel on bubble-like frames)."""
 import argparse
 import json
 import os
@@ -155,6 +158,34 @@ def ensemble(model, store, M, rounds, Bt=2):
     return out
 
 
+def redistance(model, store, rounds, B=NTRAJ):
+    """evaluate_rollouts(use_graph=True) and evaluate_rollouts_redistanced(RedistanceSpec(), use_graph=True) at B trajectories per forward: marginal ms per step and
+    trajectory-steps per second as `summary` gives them, alternated inside every round, and the pass counts of the last corrected run."""
+    from bubbleformer_amd.utils import RedistanceSpec
+    from bubbleformer_amd.utils import rollout as R
+    starts = [i * len(store.ds) // NTRAJ for i in range(NTRAJ)]
+    last = {}
+
+    def run(steps, spec):
+        for k in range(0, NTRAJ, B):
+            if spec is None:
+                last["report"] = R.evaluate_rollouts(model, store, starts[k:k + B], steps, use_graph=True)
+            else:
+                last["report"] = R.evaluate_rollouts_redistanced(model, store, starts[k:k + B], steps, spec, use_graph=True)
+    variants = {"without": lambda steps: run(steps, None), "with_redistance": lambda steps: run(steps, RedistanceSpec())}
+    times = {k: [] for k in variants}
+    for r in range(rounds + 1):                                         # round 0 is the warm-up and is dropped
+        for name, fn in variants.items():
+            pair = (clock(lambda: fn(STEPS)), clock(lambda: fn(SHORT)))
+            if r:
+                times[name].append(pair)
+    out = {name: summary(times[name], B) for name in variants}
+    passes = last["report"].redistance_rounds.float()
+    out["passes_mean_max"] = [round(float(passes.mean()), 2), int(passes.max())]
+    out["rms_change_mean"] = float(last["report"].redistance_change.mean())
+    return out
+
+
 def plan_rollouts_first(store, starts):
     from bubbleformer_amd.utils.rollout import plan_rollouts
     return plan_rollouts(store.ds, starts, STEPS).first
@@ -163,6 +194,7 @@ def plan_rollouts_first(store, starts):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ensemble", default=None, help="member counts, e.g. 4,16: time the step with and without EnsembleSpec and the ensemble call alone (nothing else runs)")
+    ap.add_argument("--redistance", action="store_true", help="time the batched graph variant at 8 trajectories per forward with and without RedistanceSpec() (nothing else runs)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", choices=("today", "batched", "scoring"), default=None)
     ap.add_argument("--batches", default="1,2,4,8", help="trajectories per forward of the batched variants")
@@ -185,6 +217,11 @@ def main():
         out = {"tree": tree, "geometry": f"{T}x{H}x{W}x4 bf16 FiLMAViT-small, Bt = 2 trajectories x M members, {STEPS} steps", "rounds": a.rounds}
         for M in [int(m) for m in a.ensemble.split(",")]:
             out[f"M{M}"] = ensemble(model, store, M, a.rounds)
+        print(json.dumps(out))
+        return 0
+    if a.redistance:
+        out = {"tree": tree, "geometry": f"{T}x{H}x{W}x4 bf16 FiLMAViT-small, {NTRAJ} trajectories per forward, {STEPS} steps", "rounds": a.rounds}
+        out.update(redistance(model, store, a.rounds))
         print(json.dumps(out))
         return 0
     starts = [i * len(store.ds) // NTRAJ for i in range(NTRAJ)]            # the first sample of every trajectory
