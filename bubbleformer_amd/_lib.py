@@ -106,6 +106,13 @@ class EnsembleRows(C.Structure):
     _fields_ = [(n, vp) for n in ("mean_rmse", "spread", "crps", "rank_hist", "mean")]
 
 
+class OptStep(C.Structure):
+    """bf_opt_step: one fused optimizer step -- buffers, clip coefficient, average, parameter groups, sizes, scalars (read during the call only)."""
+    _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("coef_dev", fp), ("avg", fp), ("chunk_group", vp), ("group_lr_scale", fp),
+                ("group_weight_decay", fp), ("group_frozen", vp), ("n", i64), ("step", i32), ("n_groups", i32)] + [
+        (n, f32) for n in ("lr", "beta1", "beta2", "eps", "wd", "gscale", "clip_value", "avg_weight")]
+
+
 class RenderTile(C.Structure):
     """bf_render_tile: what one slot of an image shows (bf_render_tiles)."""
     _fields_ = [("a", fp), ("b", fp), ("mask", fp), ("frame_stride", i64), ("slot_stride", i64), ("mask_frame_stride", i64), ("mask_slot_stride", i64),
@@ -194,22 +201,13 @@ SIGNATURES = {
     "bf_wgrad_unprep": (C.c_int, [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_film_net_fwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]),
     "bf_film_net_bwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]),
-    "bf_adamw": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
-    "bf_adam": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]),
-    "bf_lion": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, vp]),
+    "bf_adamw": (C.c_int, [P(OptStep), vp]),
+    "bf_adam": (C.c_int, [P(OptStep), vp]),
+    "bf_lion": (C.c_int, [P(OptStep), vp]),
     "bf_grad_norm_ws_doubles": (i64, [i64]),
     "bf_grad_norm": (C.c_int, [fp, i64, f32, f32, fp, vp, i64, vp]),
-    "bf_adamw_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
-    "bf_adam_dev": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, vp]),
-    "bf_lion_dev": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, vp]),
-    "bf_adamw_avg": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
-    "bf_adam_avg": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
-    "bf_lion_avg": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp]),
     "bf_weight_average": (C.c_int, [fp, fp, i64, f32, vp]),
     "bf_swap_buffers": (C.c_int, [fp, fp, i64, vp]),
-    "bf_adamw_groups": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
-    "bf_adam_groups": (C.c_int, [fp, fp, fp, fp, i64, C.c_int, f32, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
-    "bf_lion_groups": (C.c_int, [fp, fp, fp, i64, f32, f32, f32, f32, fp, f32, fp, f32, vp, fp, fp, vp, C.c_int, vp]),
     "bf_group_sumsq_ws_doubles": (i64, [i64]),
     "bf_group_sumsq": (C.c_int, [fp, i64, vp, C.c_int, vp, vp, i64, vp]),
     "bf_group_clip_coef": (C.c_int, [vp, vp, C.c_int, f32, f32, fp, fp, vp]),

@@ -20,7 +20,7 @@ int bf_decline(const char* msg) {
     return 1;
 }
 extern "C" const char* bf_last_error(void) { return g_err; }
-extern "C" int bf_abi_version(void) { return 2; }
+extern "C" int bf_abi_version(void) { return 3; }
 
 // ------------------------------------------------------------------------------------------------ launch profiler
 #include <map>

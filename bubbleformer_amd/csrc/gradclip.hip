@@ -1,14 +1,13 @@
 // Gradient clipping for the training step, without a host round trip:
 //   bf_grad_norm                             -> {norm, coef} of the flat gradient buffer in device memory (torch.nn.utils.clip_grad_norm_,
 //                                               norm_type 2: what Lightning's Trainer(gradient_clip_val=...) calls)
-//   bf_adamw_dev / bf_adam_dev / bf_lion_dev -> the fused optimizers of optim_kernels.h reading that coefficient from device memory, with an
-//                                               optional clamp of the scaled gradient (gradient_clip_algorithm="value")
-//   bf_adamw / bf_adam / bf_lion             -> the same optimizers on a host gradient scale (no clipping)
-//   bf_adamw_avg / bf_adam_avg / bf_lion_avg -> any of those with an averaged copy of the weights kept in the same launch (EMA / SWA);
-//                                               bf_weight_average is that update alone, bf_swap_buffers exchanges two flat buffers
-//   bf_adamw_groups / bf_adam_groups / bf_lion_groups -> those bodies again with a group id per 64-element chunk that selects the learning-rate
-//                                               scale, the weight decay and a frozen flag (parameter groups); bf_group_sumsq and
-//                                               bf_group_clip_coef are the norm above per group, and over the groups that are not frozen
+//   bf_adamw / bf_adam / bf_lion             -> the fused optimizers of optim_kernels.h, one entry each: a bf_opt_step record says whether the
+//                                               gradient scale is a host float or completed by that coefficient in device memory, whether the
+//                                               scaled gradient is clamped (gradient_clip_algorithm="value"), whether an averaged copy of the
+//                                               weights is kept in the same launch (EMA / SWA) and whether a group id per 64-element chunk
+//                                               selects the learning-rate scale, the weight decay and a frozen flag (parameter groups)
+//   bf_weight_average / bf_swap_buffers      -> the average's update alone; two flat buffers exchanged
+//   bf_group_sumsq / bf_group_clip_coef      -> the norm above per group, and over the groups that are not frozen
 //
 // The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
 //   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
@@ -207,90 +206,45 @@ extern "C" int bf_grad_norm(const float* g, int64_t n, float gscale, float max_n
     return 0;
 }
 
-// ---------------------------------------------------------------------------- the optimizers on a host gradient scale
-extern "C" int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                       bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && n > 0, "bf_lion: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0), "bf_lion: buffers must be 16-byte aligned");
-    return opt_launch_lion<BF_OPT_HOST>(p, g, m, n, lr, beta1, beta2, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
+// ---------------------------------------------------------------------------- the optimizers
+// The one checked path of bf_adamw / bf_adam / bf_lion: every check of the record, each under the calling entry's name and before any HIP
+// call, then the instantiation by one rule -- GRP when there is a chunk map, AVG when there is an average, and MODE = the clamp when
+// clip_value is finite (+inf = no clamp: the other two have no clamp code at all), else the device coefficient when there is one, else the
+// host scale (whose bits a coefficient of 1 would give).
+#define BF_OPT_REQUIRE(who, cond, what)                                  \
+    do {                                                             \
+        if (!(cond)) {                                               \
+            char msg[128];                                           \
+            snprintf(msg, sizeof(msg), "%s: %s", who, what);         \
+            return bf_fail_msg(msg, __FILE__, __LINE__);             \
+        }                                                            \
+    } while (0)
+
+static int opt_step(int rule, const char* who, const bf_opt_step* s, bf_stream_t stream) {
+    const bool adam = rule != BF_OPT_LION;
+    BF_OPT_REQUIRE(who, s && s->p && s->g && s->m && (s->v || !adam), "null pointer");
+    BF_OPT_REQUIRE(who, s->n > 0, "n must be positive");
+    BF_OPT_REQUIRE(who, !adam || s->step >= 1, "step must be >= 1");
+    BF_OPT_REQUIRE(who, BF_OPT_ALIGNED(s->p) && BF_OPT_ALIGNED(s->g) && BF_OPT_ALIGNED(s->m) && (!adam || BF_OPT_ALIGNED(s->v)),
+                   "buffers must be 16-byte aligned");
+    BF_OPT_REQUIRE(who, s->clip_value > 0.f, "clip_value must be positive (+inf: no clamp)");      // refuses a NaN too
+    if (s->avg) {
+        BF_OPT_REQUIRE(who, BF_OPT_ALIGNED(s->avg), "the average buffer must be 16-byte aligned");
+        BF_OPT_REQUIRE(who, s->avg_weight > 0.f && s->avg_weight <= 1.f, "avg_weight must be in (0, 1]");
+    }
+    if (s->chunk_group) {
+        BF_OPT_REQUIRE(who, s->group_lr_scale && s->group_weight_decay && s->group_frozen, "a chunk map needs the three group tables");
+        BF_OPT_REQUIRE(who, s->n_groups >= 1 && s->n_groups <= BF_OPT_MAX_GROUPS, "n_groups must be 1 .. 64");
+        BF_OPT_REQUIRE(who, (uintptr_t)s->group_lr_scale % 4 == 0 && (uintptr_t)s->group_weight_decay % 4 == 0, "the group tables must be 4-byte aligned");
+    }
+    const int mode = !isinf(s->clip_value) ? BF_OPT_DEV_CLAMP : (s->coef_dev ? BF_OPT_DEV : BF_OPT_HOST);
+    return opt_launch_table[mode][s->avg != nullptr][s->chunk_group != nullptr](rule, *s, (hipStream_t)stream);
 }
+#undef BF_OPT_REQUIRE
 
-extern "C" int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                        float eps, float wd, float gscale, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adamw: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adamw: buffers must be 16-byte aligned");
-    return opt_launch_adam<BF_OPT_HOST>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
-}
-
-extern "C" int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                       float eps, float wd, float gscale, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bf_adam: bad arguments");
-    BF_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "bf_adam: buffers must be 16-byte aligned");
-    return opt_launch_adam<BF_OPT_HOST>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, nullptr, 0.f, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------- the optimizers on a device-resident coefficient
-// clip_value = +inf = no clamp: that variant has no clamp code at all, so its loop body is the host-scale kernel's
-#define BF_OPT_DISPATCH(CALL_DEV, CALL_CLAMP) (isinf(clip_value) ? (CALL_DEV) : (CALL_CLAMP))
-
-extern "C" int bf_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                            float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_dev: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_dev: buffers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    return BF_OPT_DISPATCH(opt_launch_adam<BF_OPT_DEV>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st),
-                           opt_launch_adam<BF_OPT_DEV_CLAMP>(true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st));
-}
-
-extern "C" int bf_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                           float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_dev: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_dev: buffers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    return BF_OPT_DISPATCH(opt_launch_adam<BF_OPT_DEV>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st),
-                           opt_launch_adam<BF_OPT_DEV_CLAMP>(false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, st));
-}
-
-extern "C" int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                           const float* coef_dev, float clip_value, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_dev: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_dev: buffers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    return BF_OPT_DISPATCH(opt_launch_lion<BF_OPT_DEV>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st),
-                           opt_launch_lion<BF_OPT_DEV_CLAMP>(p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, st));
-}
-
-// ---------------------------------------------------------------------------- the optimizers with an averaged copy of the weights
-// One entry per optimizer for all three scale modes; avg moves towards the parameter value the step has just formed (avg_lerp).
-#define BF_AVG_REQUIRE(who)                                                                                         \
-    BF_REQUIRE(avg && BF_OPT_ALIGNED(avg), who ": the average buffer is required and must be 16-byte aligned");      \
-    BF_REQUIRE(avg_weight > 0.f && avg_weight <= 1.f, who ": avg_weight must be in (0, 1]")
-
-extern "C" int bf_adamw_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                            float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_avg: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_avg: buffers must be 16-byte aligned");
-    BF_AVG_REQUIRE("bf_adamw_avg");
-    return BF_OPT_AVG_DISPATCH(opt_launch_adam, true, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, (hipStream_t)stream,
-                               avg, avg_weight);
-}
-
-extern "C" int bf_adam_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                           float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_avg: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_avg: buffers must be 16-byte aligned");
-    BF_AVG_REQUIRE("bf_adam_avg");
-    return BF_OPT_AVG_DISPATCH(opt_launch_adam, false, p, g, m, v, n, step, lr, beta1, beta2, eps, wd, gscale, coef_dev, clip_value, (hipStream_t)stream,
-                               avg, avg_weight);
-}
-
-extern "C" int bf_lion_avg(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                           const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_avg: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_avg: buffers must be 16-byte aligned");
-    BF_AVG_REQUIRE("bf_lion_avg");
-    return BF_OPT_AVG_DISPATCH(opt_launch_lion, p, g, m, n, lr, beta1, beta2, wd, gscale, coef_dev, clip_value, (hipStream_t)stream, avg, avg_weight);
-}
+extern "C" int bf_adamw(const bf_opt_step* s, bf_stream_t stream) { return opt_step(BF_OPT_ADAMW, "bf_adamw", s, stream); }
+extern "C" int bf_adam(const bf_opt_step* s, bf_stream_t stream) { return opt_step(BF_OPT_ADAM, "bf_adam", s, stream); }
+extern "C" int bf_lion(const bf_opt_step* s, bf_stream_t stream) { return opt_step(BF_OPT_LION, "bf_lion", s, stream); }
 
 extern "C" int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream) {
     BF_REQUIRE(avg && p && n > 0, "bf_weight_average: bad arguments");
@@ -308,46 +262,6 @@ extern "C" int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream
     hipLaunchKernelGGL(swap_kernel, dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, (hipStream_t)stream, a, b, (long)n);
     BF_CHECK_LAUNCH();
     return 0;
-}
-
-// ---------------------------------------------------------------------------- the optimizers with parameter groups
-// One entry per optimizer for all three scale modes, with or without the averaged copy.  There is no wd argument: every group has its own.
-#define BF_GROUPS_REQUIRE(who)                                                                                                    \
-    BF_REQUIRE(chunk_group && lr_scale && weight_decay && frozen, who ": the chunk map and the three group tables are required");   \
-    BF_REQUIRE(n_groups >= 1 && n_groups <= BF_OPT_MAX_GROUPS, who ": n_groups must be 1 .. 64");                                  \
-    BF_REQUIRE((uintptr_t)lr_scale % 4 == 0 && (uintptr_t)weight_decay % 4 == 0, who ": the group tables must be 4-byte aligned");  \
-    BF_REQUIRE(!avg || (BF_OPT_ALIGNED(avg) && avg_weight > 0.f && avg_weight <= 1.f),                                             \
-               who ": the average buffer must be 16-byte aligned and avg_weight in (0, 1]")
-#define BF_GROUPS_RECORD() opt_groups<true>{chunk_group, lr_scale, weight_decay, frozen, n_groups}
-
-extern "C" int bf_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                               float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
-                               const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adamw_groups: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adamw_groups: buffers must be 16-byte aligned");
-    BF_GROUPS_REQUIRE("bf_adamw_groups");
-    return BF_OPT_GROUPS_DISPATCH(opt_launch_adam, true, p, g, m, v, n, step, lr, beta1, beta2, eps, 0.f, gscale, coef_dev, clip_value,
-                                  (hipStream_t)stream, avg, avg_weight, BF_GROUPS_RECORD());
-}
-
-extern "C" int bf_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                              float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
-                              const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value > 0.f, "bf_adam_groups: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m) && BF_OPT_ALIGNED(v), "bf_adam_groups: buffers must be 16-byte aligned");
-    BF_GROUPS_REQUIRE("bf_adam_groups");
-    return BF_OPT_GROUPS_DISPATCH(opt_launch_adam, false, p, g, m, v, n, step, lr, beta1, beta2, eps, 0.f, gscale, coef_dev, clip_value,
-                                  (hipStream_t)stream, avg, avg_weight, BF_GROUPS_RECORD());
-}
-
-extern "C" int bf_lion_groups(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float gscale, const float* coef_dev,
-                              float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group, const float* lr_scale,
-                              const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream) {
-    BF_REQUIRE(p && g && m && n > 0 && clip_value > 0.f, "bf_lion_groups: bad arguments");
-    BF_REQUIRE(BF_OPT_ALIGNED(p) && BF_OPT_ALIGNED(g) && BF_OPT_ALIGNED(m), "bf_lion_groups: buffers must be 16-byte aligned");
-    BF_GROUPS_REQUIRE("bf_lion_groups");
-    return BF_OPT_GROUPS_DISPATCH(opt_launch_lion, p, g, m, n, lr, beta1, beta2, 0.f, gscale, coef_dev, clip_value, (hipStream_t)stream, avg,
-                                  avg_weight, BF_GROUPS_RECORD());
 }
 
 extern "C" int64_t bf_group_sumsq_ws_doubles(int64_t n) { return n > 0 ? (int64_t)gn_slabs((long)(n / 4)) * BF_OPT_MAX_GROUPS : 0; }

@@ -1,20 +1,18 @@
-// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates, shared by their two families of entry points,
-// both in gradclip.hip:
-//   bf_adamw / bf_adam / bf_lion              gradient scale = a host float                       (BF_OPT_HOST)
-//   bf_adamw_dev / bf_adam_dev / bf_lion_dev  gradient scale = gscale * coef_dev[0] (device)      (BF_OPT_DEV)
-//                                             ... and the scaled gradient clamped to +-clip       (BF_OPT_DEV_CLAMP)
-// One body per optimizer: the variants differ in where the scale comes from (read once per thread, before the loop) and in one clamp on
-// the scaled gradient.  BF_OPT_HOST compiles to the kernel the host-scale entry points always launched; BF_OPT_DEV runs the same loop
-// body on gscale * coef_dev[0], which is gscale exactly when the coefficient is 1.0f.
-// A third family, bf_adamw_avg / bf_adam_avg / bf_lion_avg, runs the same bodies with AVG = true: the step also moves an averaged copy
-// `a` of the parameters towards the value it has just formed, a <- a + w * (p - a) (avg_lerp; an EMA or a running mean, by the caller's
-// w), for one more read and one more write of one buffer and no launch.  AVG = false has no trace of it: those are the kernels above.
-// bf_weight_average is the lerp alone and bf_swap_buffers exchanges two flat buffers; same grid rule, 16-byte body, scalar tail.
-// A fourth family, bf_adamw_groups / bf_adam_groups / bf_lion_groups, runs the same bodies with GRP = true: every chunk of BF_OPT_CHUNK
-// elements carries a group id (one byte per chunk), and the group's learning-rate scale, weight decay and frozen flag replace the launch's
-// lr and wd for that chunk (opt_group_table / opt_group_of).  A 16-byte access never straddles a chunk, the 16 lanes that share a chunk
-// share the lookup, and a frozen chunk is skipped by those 16 lanes together: the live chunks keep their 256-byte runs.  GRP = false has no
-// trace of it either.
+// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates <MODE, AVG, GRP>, behind one entry point each in gradclip.hip
+// (bf_adamw / bf_adam / bf_lion, which take a bf_opt_step record and choose the instantiation by one rule: opt_step there).
+//   MODE  where the gradient scale comes from (read once per thread, before the loop), and one clamp on the scaled gradient:
+//           BF_OPT_HOST       a host float, gscale
+//           BF_OPT_DEV        gscale * coef_dev[0] (device), which is gscale exactly when the coefficient is 1.0f: the same loop body
+//           BF_OPT_DEV_CLAMP  ... and the scaled gradient clamped to +-clip
+//   AVG   the step also moves an averaged copy `a` of the parameters towards the value it has just formed, a <- a + w * (p - a) (avg_lerp; an
+//         EMA or a running mean, by the caller's w), for one more read and one more write of one buffer and no launch.  AVG = false has no
+//         trace of it.  bf_weight_average is the lerp alone and bf_swap_buffers exchanges two flat buffers; same grid rule, 16-byte body,
+//         scalar tail.
+//   GRP   every chunk of BF_OPT_CHUNK elements carries a group id (one byte per chunk), and the group's learning-rate scale, weight decay and
+//         frozen flag replace the launch's lr and wd for that chunk (opt_group_table / opt_group_of).  A 16-byte access never straddles a
+//         chunk, the 16 lanes that share a chunk share the lookup, and a frozen chunk is skipped by those 16 lanes together: the live chunks
+//         keep their 256-byte runs.  GRP = false has no trace of it either.
+// One body per optimizer; all 3 x 3 x 2 x 2 instantiations exist (opt_launch_table).
 #pragma once
 #include <algorithm>
 
@@ -262,38 +260,37 @@ __global__ void __launch_bounds__(BF_OPT_NT) swap_kernel(float* __restrict__ a, 
     }
 }
 
-// launches, shared by the families of entry points (which check their own arguments); a / w: the averaged copy of the AVG kernels
 #define BF_OPT_ALIGNED(x) ((uintptr_t)(x) % 16 == 0)
-template <int MODE, bool AVG = false, bool GRP = false>
-int opt_launch_adam(bool decoupled, float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2,
-                    float eps, float wd, float gscale, const float* coef, float clip, hipStream_t st, float* a = nullptr, float w = 0.f,
-                    opt_groups<GRP> G = {}) {
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    if (decoupled)
-        hipLaunchKernelGGL((adamw_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd,
-                           bc1, sbc2, gscale, coef, clip, a, w, G);
-    else
-        hipLaunchKernelGGL((adam_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, v, (long)n, lr, beta1, beta2, eps, wd,
-                           bc1, sbc2, gscale, coef, clip, a, w, G);
+enum { BF_OPT_ADAMW = 0, BF_OPT_ADAM = 1, BF_OPT_LION = 2 };      // the update rule of a launch
+
+// the launch of one checked step (gradclip.hip: opt_step).  Without groups the kernel gets the record's wd, with them 0 (every group brings
+// its own); without an average it gets a = nullptr, w = 0.
+template <int MODE, bool AVG, bool GRP>
+int opt_launch(int rule, const bf_opt_step& s, hipStream_t st) {
+    opt_groups<GRP> G;
+    if constexpr (GRP) G = {s.chunk_group, s.group_lr_scale, s.group_weight_decay, s.group_frozen, s.n_groups};
+    const float wd = GRP ? 0.f : s.wd, w = AVG ? s.avg_weight : 0.f;
+    float* a = AVG ? s.avg : nullptr;
+    const dim3 grid(opt_grid_for(s.n)), block(BF_OPT_NT);
+    if (rule == BF_OPT_LION) {
+        hipLaunchKernelGGL((lion_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, (long)s.n, s.lr, s.beta1, s.beta2, wd, s.gscale, s.coef_dev,
+                           s.clip_value, a, w, G);
+    } else {
+        const float bc1 = 1.f - powf(s.beta1, (float)s.step);
+        const float sbc2 = sqrtf(1.f - powf(s.beta2, (float)s.step));
+        if (rule == BF_OPT_ADAMW)
+            hipLaunchKernelGGL((adamw_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
+                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G);
+        else
+            hipLaunchKernelGGL((adam_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
+                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G);
+    }
     BF_CHECK_LAUNCH();
     return 0;
 }
-template <int MODE, bool AVG = false, bool GRP = false>
-int opt_launch_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale, const float* coef,
-                    float clip, hipStream_t st, float* a = nullptr, float w = 0.f, opt_groups<GRP> G = {}) {
-    hipLaunchKernelGGL((lion_kernel<MODE, AVG, GRP>), dim3(opt_grid_for(n)), dim3(BF_OPT_NT), 0, st, p, g, m, (long)n, lr, beta1, beta2, wd, gscale, coef,
-                       clip, a, w, G);
-    BF_CHECK_LAUNCH();
-    return 0;
-}
-// the scale mode of an _avg entry: BF_OPT_DISPATCH's choice between the device modes, and the host-scale kernel when there is neither
-#define BF_OPT_AVG_DISPATCH(LAUNCH, ...)                                                   \
-    (!isinf(clip_value) ? LAUNCH<BF_OPT_DEV_CLAMP, true>(__VA_ARGS__)                      \
-                        : (coef_dev ? LAUNCH<BF_OPT_DEV, true>(__VA_ARGS__) : LAUNCH<BF_OPT_HOST, true>(__VA_ARGS__)))
-// the same choice for a _groups entry, with or without the averaged copy (AVG is a template argument: written out for both)
-#define BF_OPT_GROUPS_MODE(LAUNCH, AVG, ...)                                               \
-    (!isinf(clip_value) ? LAUNCH<BF_OPT_DEV_CLAMP, AVG, true>(__VA_ARGS__)                 \
-                        : (coef_dev ? LAUNCH<BF_OPT_DEV, AVG, true>(__VA_ARGS__) : LAUNCH<BF_OPT_HOST, AVG, true>(__VA_ARGS__)))
-#define BF_OPT_GROUPS_DISPATCH(LAUNCH, ...) (avg ? BF_OPT_GROUPS_MODE(LAUNCH, true, __VA_ARGS__) : BF_OPT_GROUPS_MODE(LAUNCH, false, __VA_ARGS__))
+// [MODE][AVG][GRP]: every instantiation, named once
+#define BF_OPT_ROW(MODE) {{opt_launch<MODE, false, false>, opt_launch<MODE, false, true>}, {opt_launch<MODE, true, false>, opt_launch<MODE, true, true>}}
+constexpr int (*opt_launch_table[3][2][2])(int, const bf_opt_step&, hipStream_t) = {BF_OPT_ROW(BF_OPT_HOST), BF_OPT_ROW(BF_OPT_DEV),
+                                                                                    BF_OPT_ROW(BF_OPT_DEV_CLAMP)};
+#undef BF_OPT_ROW
 }  // namespace

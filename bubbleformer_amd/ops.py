@@ -1478,7 +1478,7 @@ def _coef_ptr(coef: Optional[torch.Tensor], p: torch.Tensor, who: str):
 
 
 def _avg_args(avg: Optional[torch.Tensor], avg_weight: Optional[float], p: torch.Tensor, who: str):
-    """None when the call keeps no average; otherwise (avg pointer, weight) for the _avg entry points."""
+    """None when the call keeps no average; otherwise (avg pointer, weight) for the step record."""
     if avg is None and avg_weight is None:
         return None
     if avg is None or avg_weight is None:
@@ -1486,10 +1486,6 @@ def _avg_args(avg: Optional[torch.Tensor], avg_weight: Optional[float], p: torch
     if not isinstance(avg, torch.Tensor) or avg.dtype != torch.float32 or avg.device != p.device or avg.numel() != p.numel() or not avg.is_contiguous():
         raise L.BubbleformerHipError(f"{who}: avg must be a contiguous torch.float32 tensor of {p.numel()} elements on {p.device}")
     return _p(avg), float(avg_weight)
-
-
-def _clip_or_inf(clip_value: Optional[float]) -> float:
-    return float("inf") if clip_value is None else float(clip_value)
 
 
 class ParamGroupTables:
@@ -1526,7 +1522,7 @@ def param_group_tables(chunk_map: torch.Tensor, lr_scale, weight_decay, frozen, 
 
 
 def _group_args(groups: ParamGroupTables, p: torch.Tensor, who: str):
-    """(chunk map, lr_scale, weight_decay, frozen, n_groups) for the _groups entry points; the map must be the one of p's length."""
+    """(chunk map, lr_scale, weight_decay, frozen, n_groups) for the step record and the group norms; the map must be the one of p's length."""
     if not isinstance(groups, ParamGroupTables):
         raise L.BubbleformerHipError(f"{who}: groups must be an ops.ParamGroupTables (param_group_tables), got {type(groups).__name__}")
     chunks = (p.numel() + L.BF_OPT_CHUNK - 1) // L.BF_OPT_CHUNK
@@ -1581,6 +1577,19 @@ def group_clip_coef_(sums: torch.Tensor, groups: ParamGroupTables, out: torch.Te
     return out
 
 
+def _opt_step(who: str, p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups) -> "L.OptStep":
+    """The bf_opt_step record of one adamw_ / adam_ / lion_ call, built by field name (lion_: v None, step 0, eps 0)."""
+    av = _avg_args(avg, avg_weight, p, who)
+    rec = L.OptStep(p=_p(p), g=_p(g), m=_p(m), v=None if v is None else _p(v), coef_dev=_coef_ptr(coef, p, who), n=p.numel(), step=int(step),
+                    lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), wd=float(weight_decay), gscale=float(grad_scale),
+                    clip_value=float("inf") if clip_value is None else float(clip_value))
+    if av is not None:
+        rec.avg, rec.avg_weight = av
+    if groups is not None:
+        rec.chunk_group, rec.group_lr_scale, rec.group_weight_decay, rec.group_frozen, rec.n_groups = _group_args(groups, p, who)
+    return rec
+
+
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
           grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None,
           avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None, groups: Optional[ParamGroupTables] = None) -> None:
@@ -1591,23 +1600,10 @@ def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0
     (1 copies p); p and m come out bit for bit as without them (weight_average_ is that update alone).  groups (param_group_tables):
     parameter groups -- an element whose chunk belongs to group k is stepped with lr * lr_scale[k] and weight_decay[k], a frozen group's
     chunks are neither read nor written (p, m, avg keep their bits); the ``weight_decay`` argument is then ignored, every group has its
-    own.  One launch (bf_lion_groups) for every combination of coef / clip_value / avg.  None: exactly the calls made without it."""
+    own.  One launch (bf_lion) for every combination of coef / clip_value / avg / groups.  None: exactly the kernels launched without it."""
     _require_gpu(p)
-    av = _avg_args(avg, avg_weight, p, "lion_")
-    if groups is not None:
-        L.check(L.lib().bf_lion_groups(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(grad_scale),
-                                       _coef_ptr(coef, p, "lion_"), _clip_or_inf(clip_value), *(av or (None, 0.0)), *_group_args(groups, p, "lion_"),
-                                       _stream()), "bf_lion_groups")
-    elif av is not None:
-        L.check(L.lib().bf_lion_avg(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
-                                    float(grad_scale), _coef_ptr(coef, p, "lion_"), _clip_or_inf(clip_value), *av, _stream()), "bf_lion_avg")
-    elif coef is None and clip_value is None:
-        L.check(L.lib().bf_lion(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
-                                float(grad_scale), _stream()), "bf_lion")
-    else:
-        L.check(L.lib().bf_lion_dev(_p(p), _p(g), _p(m), p.numel(), float(lr), float(betas[0]), float(betas[1]), float(weight_decay),
-                                    float(grad_scale), _coef_ptr(coef, p, "lion_"), float("inf") if clip_value is None else float(clip_value),
-                                    _stream()), "bf_lion_dev")
+    rec = _opt_step("lion_", p, g, m, None, 0, lr, betas, 0.0, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    L.check(L.lib().bf_lion(C.byref(rec), _stream()), "bf_lion")
     _weights_changed()
 
 
@@ -1616,24 +1612,10 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
            clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None,
            groups: Optional[ParamGroupTables] = None) -> None:
     """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value / avg /
-    avg_weight / groups: see lion_ (bf_adamw_groups; m and v of a frozen chunk keep their bits too)."""
+    avg_weight / groups: see lion_ (bf_adamw; m and v of a frozen chunk keep their bits too)."""
     _require_gpu(p)
-    av = _avg_args(avg, avg_weight, p, "adamw_")
-    if groups is not None:
-        L.check(L.lib().bf_adamw_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                        float(grad_scale), _coef_ptr(coef, p, "adamw_"), _clip_or_inf(clip_value), *(av or (None, 0.0)),
-                                        *_group_args(groups, p, "adamw_"), _stream()), "bf_adamw_groups")
-    elif av is not None:
-        L.check(L.lib().bf_adamw_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adamw_"), _clip_or_inf(clip_value), *av,
-                                     _stream()), "bf_adamw_avg")
-    elif coef is None and clip_value is None:
-        L.check(L.lib().bf_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                 float(weight_decay), float(grad_scale), _stream()), "bf_adamw")
-    else:
-        L.check(L.lib().bf_adamw_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                     float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adamw_"),
-                                     float("inf") if clip_value is None else float(clip_value), _stream()), "bf_adamw_dev")
+    rec = _opt_step("adamw_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    L.check(L.lib().bf_adamw(C.byref(rec), _stream()), "bf_adamw")
     _weights_changed()
 
 
@@ -1644,24 +1626,10 @@ def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, st
     """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
     weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay.  coef / clip_value: see lion_
     (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step()).  avg / avg_weight / groups: see lion_
-    (bf_adam_groups: a group's weight decay is its L2 term)."""
+    (bf_adam: a group's weight decay is its L2 term)."""
     _require_gpu(p)
-    av = _avg_args(avg, avg_weight, p, "adam_")
-    if groups is not None:
-        L.check(L.lib().bf_adam_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                       float(grad_scale), _coef_ptr(coef, p, "adam_"), _clip_or_inf(clip_value), *(av or (None, 0.0)),
-                                       *_group_args(groups, p, "adam_"), _stream()), "bf_adam_groups")
-    elif av is not None:
-        L.check(L.lib().bf_adam_avg(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                    float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"), _clip_or_inf(clip_value), *av,
-                                    _stream()), "bf_adam_avg")
-    elif coef is None and clip_value is None:
-        L.check(L.lib().bf_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                float(weight_decay), float(grad_scale), _stream()), "bf_adam")
-    else:
-        L.check(L.lib().bf_adam_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                    float(weight_decay), float(grad_scale), _coef_ptr(coef, p, "adam_"),
-                                    float("inf") if clip_value is None else float(clip_value), _stream()), "bf_adam_dev")
+    rec = _opt_step("adam_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    L.check(L.lib().bf_adam(C.byref(rec), _stream()), "bf_adam")
     _weights_changed()
 
 

@@ -42,7 +42,7 @@
  *   bf_ensemble_scores ....... ensemble-mean RMSE, spread, CRPS and rank histogram across members (no reference program); bf_rollout_ensemble: per step
  *   bf_render_ranges / bf_render_tiles .. plot_bubbleml and the wandb_*_plotter strips: utils/plot_utils.py:12-228 (no matplotlib, no cv2)
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
- *   bf_grad_norm / bf_*_dev .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
+ *   bf_grad_norm, bf_opt_step's coef_dev / clip_value .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
  */
 #ifndef BUBBLEFORMER_HIP_H
 #define BUBBLEFORMER_HIP_H
@@ -336,12 +336,6 @@ int bf_film_net_fwd(const float* cond, const float* lnw, const float* lnb, const
                     float* chat, float* crstd, int B, int P, int E2, bf_stream_t stream);
 int bf_film_net_bwd(const float* dgb, const float* chat, const float* lnw, const float* lnb, const float* W, float* dW,
                     float* dbias, float* dlnw, float* dlnb, int B, int P, int E2, bf_stream_t stream);
-int bf_adamw(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-             float wd, float gscale, bf_stream_t stream);
-/* Adam (torch.optim.Adam, amsgrad = maximize = False), same buffers and checks as bf_adamw; weight decay is an L2 term on the gradient:
- * g = gscale*grad; g += wd*p (wd != 0); m = beta1*m + (1-beta1)*g; v = beta2*v + (1-beta2)*g^2; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps) */
-int bf_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-            float wd, float gscale, bf_stream_t stream);
 /* Batch of normalised clips from device-resident trajectories src [fields][frames][H][W] (fp32):
  * out[b][t][c][yo][xo] = (src[field[c]][first[b] + t0 + t][ys][xs] - diff[c]) / div[c], (ys, xs) = nearest-neighbour source pixel of
  * (yo, xo) when Ho x Wo < H x W (F.interpolate(mode="nearest") index rule), identity otherwise.  out is (B, T, C, Ho, Wo) fp32. */
@@ -626,9 +620,6 @@ int bf_lp_rows_bwd(const float* pred, const float* y, const float* g, const doub
  * in DEVICE memory.  Gather form (no atomics), fp64 arithmetic, one rounding.  A cell with |grad phi| = 0 contributes 0 (autograd of the reference's
  * expression gives 0 * inf = NaN there).  A 1-wide axis has a zero derivative. */
 int bf_eikonal_bwd(const float* phi, int64_t frames, int H, int W, float dx, const float* g, float* dphi, bf_stream_t stream);
-/* Lion: p *= 1 - lr*wd; p -= lr*sign(beta1*m + (1-beta1)*g); m = beta2*m + (1-beta2)*g   (g is multiplied by gscale first) */
-int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-            bf_stream_t stream);
 /* Gradient clipping without a host round trip (csrc/gradclip.hip).
  * bf_grad_norm: out = {norm, coef} (two fp32 in DEVICE memory) of the flat gradient buffer g[n] (fp32, 16-byte aligned, n > 0):
  *   norm = gscale * sqrt(sum g^2)   squares and sums in fp64, rounded once to fp32; gscale = the factor the optimizer applies to g
@@ -639,58 +630,56 @@ int bf_lion(float* p, const float* g, float* m, int64_t n, float lr, float beta1
  * any device.  max_norm <= 0 or a null out is an error. */
 int64_t bf_grad_norm_ws_doubles(int64_t n);
 int bf_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* out, double* ws, int64_t ws_doubles, bf_stream_t stream);
-/* bf_adamw / bf_adam / bf_lion with the gradient scale completed on the device: the effective gradient is (gscale * coef_dev[0]) * g[i]
- * (coef_dev = one fp32 in DEVICE memory, e.g. bf_grad_norm's out + 1; NULL = 1), clamped to [-clip_value, clip_value] before any use
- * (clip_value > 0; +inf = off; a NaN stays a NaN).  Same kernel bodies as the host-scale entry points: with coef_dev[0] == 1.0f and
- * clip_value = +inf they produce the same bits. */
-int bf_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                 float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream);
-int bf_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                float wd, float gscale, const float* coef_dev, float clip_value, bf_stream_t stream);
-int bf_lion_dev(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                const float* coef_dev, float clip_value, bf_stream_t stream);
-/* The optimizers with an averaged copy of the weights (EMA / SWA; no reference program).  bf_*_avg take the arguments of the matching
- * _dev entry and serve all three scale modes (coef_dev NULL and clip_value +inf: the host-scale kernel body); p, m and v come out bit
- * for bit as from the plain entry.  In the same launch avg[i] (fp32, n elements, 16-byte aligned, required) moves towards the new p[i]:
- *   avg[i] = avg_weight == 1 ? p[i] : fma(avg_weight, p[i] - avg[i], avg[i])      two roundings; 0 < avg_weight <= 1
- * so zero padding stays zero and a NaN in p reaches avg.  bf_weight_average is that update alone (same bits); bf_swap_buffers exchanges
- * two non-overlapping 16-byte aligned buffers exactly, in one launch. */
-int bf_adamw_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                 float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
-int bf_adam_avg(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                float wd, float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
-int bf_lion_avg(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float wd, float gscale,
-                const float* coef_dev, float clip_value, float* avg, float avg_weight, bf_stream_t stream);
+/* The fused flat-buffer optimizers (csrc/optim_kernels.h, csrc/gradclip.hip; DESIGN.md sections 22 and 24): ONE entry point per optimizer, which
+ * takes one step as a record.  The library reads the record DURING the call only and keeps no pointer to it; what the kernel needs is copied by
+ * value into its arguments, so the calls stay capturable and a record may live on the caller's stack.  One launch per call.
+ * Buffers: p, g, m, v [n] fp32 in DEVICE memory, 16-byte aligned, n > 0; bf_lion has no second moment and ignores v, step and eps; step >= 1 for
+ * the Adams (bc1 = 1 - beta1^step, bc2 = 1 - beta2^step).  With G[i] the effective gradient (below):
+ *   bf_adamw (torch.optim.AdamW)  p *= 1 - lr*wd; m = beta1*m + (1-beta1)*G; v = beta2*v + (1-beta2)*G^2; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+ *   bf_adam  (torch.optim.Adam, amsgrad = maximize = False)  weight decay is an L2 term on the gradient: G += wd*p (wd != 0), then m, v and p as above
+ *   bf_lion  (lion_pytorch.Lion)  p *= 1 - lr*wd; p -= lr*sign(beta1*m + (1-beta1)*G); m = beta2*m + (1-beta2)*G
+ * Effective gradient: G[i] = (gscale * coef_dev[0]) * g[i], clamped to [-clip_value, clip_value] before any use (before Adam's L2 term too).
+ *   coef_dev = one fp32 in DEVICE memory, e.g. bf_grad_norm's out + 1; NULL = 1.  clip_value > 0; +inf = no clamp; a NaN gradient stays a NaN.
+ *   The kernel is chosen by one rule: the clamping body when clip_value is finite, else the body that reads coef_dev when it is not NULL, else the
+ *   host-scale body (G = gscale * g[i]).  The three run the same loop: coef_dev[0] == 1.0f and clip_value = +inf give the host-scale body's bits,
+ *   which is why coef_dev == NULL with clip_value = +inf launches that body and reads no coefficient.
+ * Average (EMA / SWA; no reference program): avg = NULL keeps none and avg_weight is unread.  Otherwise avg [n] fp32, 16-byte aligned,
+ *   0 < avg_weight <= 1, and the same launch moves it towards the p[i] it has just formed, whatever the scale mode and the groups:
+ *     avg[i] = avg_weight == 1 ? p[i] : fma(avg_weight, p[i] - avg[i], avg[i])      two roundings
+ *   so zero padding stays zero and a NaN in p reaches avg; p, m and v come out bit for bit as without it.
+ * Parameter groups (freeze, per-group learning-rate scale and weight decay): chunk_group = NULL means none; n_groups and the three tables are then
+ *   unread and wd is every element's weight decay.  Otherwise the flat buffer is cut into chunks of BF_OPT_CHUNK consecutive elements
+ *   (trainer.FlatParams starts every parameter on a chunk boundary, so a chunk belongs to one parameter); chunk_group[ceil(n / BF_OPT_CHUNK)] (uint8,
+ *   DEVICE memory) names each chunk's group, and three tables in DEVICE memory describe the n_groups groups (1 <= n_groups <= BF_OPT_MAX_GROUPS):
+ *   group_lr_scale[k] (fp32, >= 0), group_weight_decay[k] (fp32, >= 0, absolute) and group_frozen[k] (uint8).  wd is then unread: every group
+ *   brings its own.  An element of group k is stepped with lr * group_lr_scale[k] and group_weight_decay[k] by the same kernel body as without
+ *   groups: one group of scale 1 gives those bits.  group_lr_scale[k] == 0 with group_frozen[k] == 0 is torch's lr = 0: the moments move, the
+ *   parameter does not.  A chunk of a frozen group is neither read nor written: p, m, v and avg keep their bits and nothing in its gradient (a NaN
+ *   included) reaches anything.  The entry points cannot check the map's ids without reading it; the kernels treat an id >= n_groups as frozen.
+ * A null record or a null required pointer is refused as "<entry>: null pointer", and every other check is made, before any HIP call. */
+#define BF_OPT_CHUNK 64
+#define BF_OPT_MAX_GROUPS 64
+typedef struct bf_opt_step {
+    float* p; const float* g; float *m, *v;
+    const float* coef_dev; float* avg;
+    const uint8_t* chunk_group; const float *group_lr_scale, *group_weight_decay; const uint8_t* group_frozen;
+    int64_t n;
+    int32_t step, n_groups;
+    float lr, beta1, beta2, eps, wd, gscale, clip_value, avg_weight;
+} bf_opt_step;
+int bf_adamw(const bf_opt_step* s, bf_stream_t stream);
+int bf_adam(const bf_opt_step* s, bf_stream_t stream);
+int bf_lion(const bf_opt_step* s, bf_stream_t stream);
+/* bf_weight_average is the optimizers' avg update alone (same bits; w as avg_weight); bf_swap_buffers exchanges two non-overlapping 16-byte
+ * aligned buffers exactly, in one launch. */
 int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream);
 int bf_swap_buffers(float* a, float* b, int64_t n, bf_stream_t stream);
-/* Parameter groups for the flat optimizers (freeze, per-group learning-rate scale and weight decay).  The flat
- * buffer is cut into chunks of BF_OPT_CHUNK consecutive elements; trainer.FlatParams starts every parameter on a chunk boundary, so a
- * chunk belongs to one parameter.  chunk_group[ceil(n / BF_OPT_CHUNK)] (uint8, DEVICE memory) names each chunk's group, and three tables
- * in DEVICE memory describe the n_groups groups (1 <= n_groups <= BF_OPT_MAX_GROUPS): lr_scale[k] (fp32, >= 0), weight_decay[k] (fp32,
- * >= 0, absolute) and frozen[k] (uint8).
- * bf_adamw_groups / bf_adam_groups / bf_lion_groups take the arguments of the matching _avg entry WITHOUT its wd (every group brings its
- * own), then the chunk map, the tables and n_groups; avg may be NULL (no average kept; avg_weight is then ignored).  The scale mode is
- * chosen as in the _avg entries.  An element of group k is stepped with lr * lr_scale[k] and weight_decay[k] by the same kernel body as the
- * ungrouped entries: one group of scale 1 gives their bits.  lr_scale[k] == 0 with frozen[k] == 0 is torch's lr = 0: the moments move,
- * the parameter does not.  A chunk of a frozen group is neither read nor written: p, m, v and avg keep their bits and nothing in its
- * gradient (a NaN included) reaches anything.  The entry points cannot check the map's ids without reading it; the kernels treat an id
- * >= n_groups as frozen.
+/* The gradient norm per parameter group (chunk_group and group tables as in bf_opt_step).
  * bf_group_sumsq: sums[k] = sum of x[i]^2 over the elements whose chunk has group k (fp64, n_groups doubles in DEVICE memory), in a fixed
  *   order with no float atomics: the same bits on every call.  ws: at least bf_group_sumsq_ws_doubles(n) doubles, 8-byte aligned.
  * bf_group_clip_coef: from those sums, out = {norm, coef} (two fp32 in DEVICE memory) as bf_grad_norm writes them, with
  *   norm = gscale * sqrt(sum over the groups with frozen[k] == 0 of sums[k]), added in group order -- clip_grad_norm_ over the parameters a
  *   torch optimizer would hold -- and, when group_norm is not NULL, group_norm[k] = gscale * sqrt(sums[k]) for every group (fp32). */
-#define BF_OPT_CHUNK 64
-#define BF_OPT_MAX_GROUPS 64
-int bf_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                    float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
-                    const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
-int bf_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1, float beta2, float eps,
-                   float gscale, const float* coef_dev, float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group,
-                   const float* lr_scale, const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
-int bf_lion_groups(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float gscale, const float* coef_dev,
-                   float clip_value, float* avg, float avg_weight, const uint8_t* chunk_group, const float* lr_scale,
-                   const float* weight_decay, const uint8_t* frozen, int n_groups, bf_stream_t stream);
 int64_t bf_group_sumsq_ws_doubles(int64_t n);
 int bf_group_sumsq(const float* x, int64_t n, const uint8_t* chunk_group, int n_groups, double* sums, double* ws, int64_t ws_doubles,
                    bf_stream_t stream);
@@ -933,7 +922,7 @@ void bf_prof_enable(int on);
 int bf_prof_report(char* buf, int n);   /* JSON {kernel: {calls, ms, flops, bytes}}; bytes written or -1 */
 
 const char* bf_last_error(void);
-/* 2.  The number changes when a declaration of this header changes or is removed (a caller built against the older header would pass garbage without
+/* 3.  The number changes when a declaration of this header changes or is removed (a caller built against the older header would pass garbage without
  * any error); a declaration that is only added leaves it as it is. */
 int bf_abi_version(void);
 

@@ -25,20 +25,21 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(h, n), n
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
-    assert h.bf_abi_version() == 2
+    assert h.bf_abi_version() == 3
 
 
-RECORDS = {"bf_rollout_step": "RolloutStep", "bf_census_rows": "CensusRows", "bf_link_rows": "LinkRows", "bf_error_rows": "ErrorRows"}
+RECORDS = {"bf_rollout_step": "RolloutStep", "bf_census_rows": "CensusRows", "bf_link_rows": "LinkRows", "bf_error_rows": "ErrorRows",
+           "bf_ensemble_rows": "EnsembleRows", "bf_opt_step": "OptStep"}
 
 
 def _record_fields(name):
     """[(field, ctypes type)] of `typedef struct name { ... } name;` as the header declares it: any pointer is a c_void_p, int64_t a c_int64,
-    int32_t / int a c_int32; a declaration may name several fields (`float *a, *b;`, the star belongs to the declarator)."""
+    int32_t / int a c_int32, float a c_float; a declaration may name several fields (`float *a, *b;`, the star belongs to the declarator)."""
     import ctypes as C
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "bubbleformer_hip.h")).read(), flags=re.S)
     m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), txt, flags=re.S)
     assert m, name
-    scalars = {"int64_t": C.c_int64, "int32_t": C.c_int32, "int": C.c_int32}
+    scalars = {"int64_t": C.c_int64, "int32_t": C.c_int32, "int": C.c_int32, "float": C.c_float}
     fields = []
     for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
         base, rest = re.match(r"(?:const\s+)?(\w+)\s*(.*)$", decl, flags=re.S).groups()
@@ -59,6 +60,57 @@ def test_record_mirrors_the_header(name):
     assert C.sizeof(rec) == sum(C.sizeof(t) for _, t in declared)
 
 
+_OPT_BUF = []
+
+
+def _opt_step(**kw):
+    """A bf_opt_step every check accepts -- 16-byte aligned host buffers nothing reads, a coefficient, an average and one parameter group --
+    with `kw` over it; the value "+4" (or "+2") puts a pointer 4 (2) bytes past its valid place."""
+    import ctypes as C
+    from bubbleformer_amd import _lib as L
+    if not _OPT_BUF:
+        _OPT_BUF.append((C.c_char * 144)())
+    p = (C.addressof(_OPT_BUF[0]) + 15) // 16 * 16
+    good = dict(p=p, g=p + 16, m=p + 32, v=p + 48, coef_dev=p + 64, avg=p + 80, chunk_group=p + 96, group_lr_scale=p + 100, group_weight_decay=p + 104,
+                group_frozen=p + 108, n=4, step=1, n_groups=1, lr=1e-3, beta1=0.9, beta2=0.99, eps=1e-8, wd=0.0, gscale=1.0, clip_value=float("inf"),
+                avg_weight=0.5)
+    return L.OptStep(**{**good, **{k: good[k] + int(v) if v in ("+4", "+2") else v for k, v in kw.items()}})
+
+
+# defect -> (the fields it sets, what the refusal says); bf_lion reads neither step nor v, so those three are the Adams' alone
+_OPT_DEFECTS = {
+    "n_zero": (dict(n=0), "n must be positive"), "step_zero": (dict(step=0), "step must be >= 1"), "v_null": (dict(v=None), "null pointer"),
+    "p_off_by_4": (dict(p="+4"), "buffers must be 16-byte aligned"), "g_off_by_4": (dict(g="+4"), "buffers must be 16-byte aligned"),
+    "m_off_by_4": (dict(m="+4"), "buffers must be 16-byte aligned"), "v_off_by_4": (dict(v="+4"), "buffers must be 16-byte aligned"),
+    "clip_zero": (dict(clip_value=0.0), "clip_value must be positive"), "clip_negative": (dict(clip_value=-1.0), "clip_value must be positive"),
+    "clip_nan": (dict(clip_value=float("nan")), "clip_value must be positive"),
+    "avg_weight_zero": (dict(avg_weight=0.0), "avg_weight must be in (0, 1]"), "avg_weight_1.5": (dict(avg_weight=1.5), "avg_weight must be in (0, 1]"),
+    "avg_weight_nan": (dict(avg_weight=float("nan")), "avg_weight must be in (0, 1]"),
+    "avg_off_by_4": (dict(avg="+4"), "the average buffer must be 16-byte aligned"),
+    "lr_scale_null": (dict(group_lr_scale=None), "a chunk map needs the three group tables"), "weight_decay_null": (dict(group_weight_decay=None), "a chunk map needs the three group tables"),
+    "frozen_null": (dict(group_frozen=None), "a chunk map needs the three group tables"),
+    "lr_scale_off_by_2": (dict(group_lr_scale="+2"), "the group tables must be 4-byte aligned"),
+    "weight_decay_off_by_2": (dict(group_weight_decay="+2"), "the group tables must be 4-byte aligned"),
+    "n_groups_zero": (dict(n_groups=0), "n_groups must be 1 .. 64"), "n_groups_65": (dict(n_groups=65), "n_groups must be 1 .. 64"),
+}
+_OPT_CASES = [(name, d) for name in ("bf_adamw", "bf_adam", "bf_lion") for d in sorted(_OPT_DEFECTS)
+              if not (name == "bf_lion" and d in ("step_zero", "v_null", "v_off_by_4"))]
+
+
+@pytest.mark.parametrize("name,defect", _OPT_CASES)
+def test_optimizer_record_with_one_defect_is_refused(name, defect):
+    """bf_adamw / bf_adam / bf_lion run every check of their record before any HIP call: no GPU needed.  An otherwise valid record (host
+    buffers nobody reads) with exactly one defect is refused under the entry's name and for that defect; no valid call is made here."""
+    import ctypes as C
+    from bubbleformer_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    h = _lib.lib()
+    fields, reason = _OPT_DEFECTS[defect]
+    assert getattr(h, name)(C.byref(_opt_step(**fields)), None) != 0
+    assert (name + ": " + reason) in h.bf_last_error().decode(), h.bf_last_error()
+
+
 def _null_pointer_calls():
     """name -> (call with every record NULL, call with full records whose first required pointer alone is NULL); every other pointer is the
     address of a host buffer nothing reads, every size valid.  bf_field_errors' record has no required member: there it is `pred`."""
@@ -76,7 +128,9 @@ def _null_pointer_calls():
 
     links = L.LinkRows(*[p] * 6)
     errs, ref = L.ErrorRows(), C.byref
+    opt = lambda name: lambda h, s: getattr(h, name)(s and ref(_opt_step(p=None)), None)      # noqa: E731
     return {
+        "bf_adamw": opt("bf_adamw"), "bf_adam": opt("bf_adam"), "bf_lion": opt("bf_lion"),
         "bf_rollout_score": lambda h, s: h.bf_rollout_score(s and ref(step(pred=None)), -1, 1.0, p, p, None, None, None, None, p, 1 << 20, None),
         "bf_rollout_heatflux": lambda h, s: h.bf_rollout_heatflux(s and ref(step(pred=None)), 0, 0, p, 0.0, 1.0, 1.0, 1.0, p, p, None),
         "bf_rollout_bubbles": lambda h, s: h.bf_rollout_bubbles(s and ref(step(pred=None)), 0, 4, 1, s and ref(census()), s and ref(census()), None, p, 1 << 20, None),
@@ -89,7 +143,7 @@ def _null_pointer_calls():
 
 
 @pytest.mark.parametrize("name", ["bf_rollout_score", "bf_rollout_heatflux", "bf_rollout_bubbles", "bf_rollout_bubble_links", "bf_rollout_errors",
-                                  "bf_bubble_links", "bf_field_errors"])
+                                  "bf_bubble_links", "bf_field_errors", "bf_adamw", "bf_adam", "bf_lion"])
 def test_null_record_and_null_member_are_refused(name):
     """Each re-signed entry point refuses a NULL record, and a record whose first required pointer is NULL, as its null pointer: both return at
     the first check, before any HIP call, so no GPU is needed."""

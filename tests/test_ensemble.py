@@ -156,7 +156,7 @@ def test_size_errors_name_the_function():
         assert "bf_rollout_ensemble: bad sizes" in h.bf_last_error().decode()
     assert h.bf_ensemble_scores_ws_bytes(1, 1, 4, 4) == 0 and h.bf_ensemble_scores_ws_bytes(1, 33, 4, 4) == 0 and h.bf_ensemble_scores_ws_bytes(0, 2, 4, 4) == 0
     assert h.bf_ensemble_scores_ws_bytes(3, 5, 4, 4) == (3 * (32 + 6 * 4) + 15) // 16 * 16 and h.bf_ensemble_scores_ws_bytes(1, 2, 2, 2) % 16 == 0
-    assert h.bf_abi_version() == 2
+    assert h.bf_abi_version() == 3
 
 
 def test_ensemble_scores_has_no_cpu_path():

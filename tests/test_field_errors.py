@@ -63,7 +63,7 @@ def test_new_symbols_are_declared_and_bound():
     h = _lib.lib()
     for name in ("bf_field_errors_ws_bytes", "bf_field_errors", "bf_rollout_errors"):
         assert name in _lib.SIGNATURES and hasattr(h, name)
-    assert h.bf_abi_version() == 2
+    assert h.bf_abi_version() == 3
     assert h.bf_field_errors_ws_bytes(0, 8, 8) == 0 and h.bf_field_errors_ws_bytes(1, 8, 1025) == 0 and h.bf_field_errors_ws_bytes(1, 0, 8) == 0
     one, two = h.bf_field_errors_ws_bytes(1, 1024, 1024), h.bf_field_errors_ws_bytes(2, 1024, 1024)
     assert 0 < one < two and one % 16 == 0

@@ -1,6 +1,6 @@
 """GPU: gradient clipping and gradient accumulation in the training step.
 
-csrc/gradclip.hip (bf_grad_norm, bf_adamw_dev / bf_adam_dev / bf_lion_dev) against fp64 torch and against torch.nn.utils.clip_grad_norm_ /
+csrc/gradclip.hip (bf_grad_norm, bf_adamw / bf_adam / bf_lion with coef_dev / clip_value) against fp64 torch and against torch.nn.utils.clip_grad_norm_ /
 clip_grad_value_; TrainStep(gradient_clip_val, gradient_clip_algorithm, accumulate_grad_batches) and fit() with the same arguments.
 Every test runs under a watchdog of its own (STEP_LIMIT_S): a test that hangs ends the process instead of starting the next one."""
 import faulthandler

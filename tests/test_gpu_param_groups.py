@@ -1,4 +1,4 @@
-"""GPU: parameter groups in the fused optimizers (csrc/optim_kernels.h GRP = true: bf_adamw_groups / bf_adam_groups / bf_lion_groups;
+"""GPU: parameter groups in the fused optimizers (csrc/optim_kernels.h GRP = true: bf_adamw / bf_adam / bf_lion with chunk_group;
 csrc/gradclip.hip: bf_group_sumsq, bf_group_clip_coef) against torch optimizers built with one torch param group per live group, and
 TrainStep(param_groups=...) / fit(param_groups=...) on the tiny FiLMAViT in fp32."""
 import os

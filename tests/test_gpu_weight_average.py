@@ -1,5 +1,5 @@
 """GPU: the averaged copy of the weights (EMA / SWA) kept inside the fused optimizer kernels (csrc/optim_kernels.h: the AVG bodies,
-bf_adamw_avg / bf_adam_avg / bf_lion_avg, bf_weight_average, bf_swap_buffers), TrainStep(weight_average=...), its averaged_weights()
+bf_adamw / bf_adam / bf_lion with avg, bf_weight_average, bf_swap_buffers), TrainStep(weight_average=...), its averaged_weights()
 context, fit and checkpoints, and two data-parallel ranks.
 
 The bound on the average is per element and comes from the arithmetic alone (tests/averaging_restatement.py): the kernel's update is a

@@ -137,11 +137,16 @@ def test_abi_declares_the_clip_entry_points():
     txt = open(os.path.join(REPO, "include", "bubbleformer_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     declared = set(re.findall(r"\b(bf_[a-z0-9_]+)\s*\(", txt))
-    new = {"bf_grad_norm", "bf_grad_norm_ws_doubles", "bf_adamw_dev", "bf_adam_dev", "bf_lion_dev"}
+    new = {"bf_grad_norm", "bf_grad_norm_ws_doubles", "bf_adamw", "bf_adam", "bf_lion"}
     assert new <= declared and new <= set(_lib.SIGNATURES)
+    # the device coefficient and the clamp are fields of the optimizers' bf_opt_step record: the _dev entries are gone, one entry of two parameters each
+    gone = {"bf_adamw_dev", "bf_adam_dev", "bf_lion_dev"}
+    assert not any(n in txt for n in gone) and not gone & set(_lib.SIGNATURES)
+    assert all(len(_lib.SIGNATURES[n][1]) == 2 and len(re.search(r"\b%s\s*\(([^)]*)\)" % n, txt).group(1).split(",")) == 2 for n in ("bf_adamw", "bf_adam", "bf_lion"))
+    assert {"coef_dev", "clip_value"} <= {n for n, _ in _lib.OptStep._fields_}
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     h = _lib.lib()
-    assert all(hasattr(h, n) for n in new) and h.bf_abi_version() == 2
+    assert all(hasattr(h, n) for n in new) and h.bf_abi_version() == 3
     # the slab rule depends on n alone: at most 1024 partials, one for a short buffer
     assert h.bf_grad_norm_ws_doubles(64) == 1 and h.bf_grad_norm_ws_doubles(4160) == 2 and 1 <= h.bf_grad_norm_ws_doubles(1 << 34) <= 1024

@@ -8,16 +8,17 @@ padded to 64 elements).  Each step reads p, g, m, v and writes p, m, v: 28 bytes
 and the share of the 8.0 TB/s HBM peak (MI355X_MICROARCH: about 6.3 TB/s is achievable by a float4 copy).
 
 --average times the averaged-weights step (EMA / SWA) instead, per optimizer (AdamW, Adam, Lion) under the same
-protocol: (a) the unchanged plain entry, (b) the _avg entry, which also reads and writes the average (36 bytes per element; Lion 28
-against 20), (c) the plain entry followed by bf_weight_average (40; Lion 32, and a second launch).
+protocol: (a) the plain step, (b) the step with its record's avg set, which also reads and writes the average (36 bytes per element;
+Lion 28 against 20), (c) the plain step followed by bf_weight_average (40; Lion 32, and a second launch).
 
 --groups times the parameter-group launch per optimizer (AdamW, Lion) under the same protocol: (a) the unchanged
-ungrouped entry, (b) the _groups entry with every group live -- the table utils.param_groups gives no_weight_decay + layer_decay(0.75) on
-the model's parameter names and shapes, (c) the _groups entry with the trunk (blocks.*) frozen.  The grouped launches also read one map
+ungrouped step, (b) the step with its record's groups set and every group live -- the table utils.param_groups gives no_weight_decay +
+layer_decay(0.75) on the model's parameter names and shapes, (c) the grouped step with the trunk (blocks.*) frozen.  The grouped launches also read one map
 byte per 64 elements; a frozen chunk moves no other byte, so (c) is reported beside the live share of the buffer.
 
 Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average | --groups]"""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -48,6 +49,21 @@ def flat_sizes(cfg, align=64):
         p += k
         n += (k + align - 1) // align * align
     return p, n
+
+
+ADAM = dict(step=10, lr=2.5e-4, beta1=0.9, beta2=0.999, eps=1e-8)
+LION = dict(lr=5e-5, beta1=0.9, beta2=0.99, wd=0.1)
+
+
+def opt_call(entry, p, g, m, v=None, **fields):
+    """A call of bf_adamw / bf_adam / bf_lion on one bf_opt_step record, built once by field name (gscale 1, no clamp unless `fields` says so)."""
+    rec = L.OptStep(**{**dict(p=_p(p), g=_p(g), m=_p(m), v=None if v is None else _p(v), n=p.numel(), gscale=1.0, clip_value=float("inf")), **fields})
+    fn, ref, st = getattr(L.lib(), entry), C.byref(rec), _stream()
+    return lambda: fn(ref, st)
+
+
+def group_fields(t):
+    return dict(chunk_group=_p(t.chunk), group_lr_scale=_p(t.lr_scale), group_weight_decay=_p(t.weight_decay), group_frozen=_p(t.frozen), n_groups=t.n_groups)
 
 
 def rounds_of(calls, rounds, reps):
@@ -81,11 +97,7 @@ def time_kernels(n, rounds, reps):
     p = torch.randn(n, device="cuda", generator=g) * 0.02
     grad = torch.randn(n, device="cuda", generator=g) * 1e-3
     m, v = torch.zeros_like(p), torch.zeros_like(p)
-    h, st = L.lib(), _stream()
-    calls = {
-        "adam": lambda: h.bf_adam(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-5, 1.0, st),
-        "adamw": lambda: h.bf_adamw(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1e-2, 1.0, st),
-    }
+    calls = {"adam": opt_call("bf_adam", p, grad, m, v, wd=1e-5, **ADAM), "adamw": opt_call("bf_adamw", p, grad, m, v, wd=1e-2, **ADAM)}
     ms = rounds_of(calls, rounds, reps)
     assert torch.isfinite(p).all()
     out = {k: summary(t, n, BYTES_PER_ELEMENT) for k, t in ms.items()}
@@ -94,18 +106,17 @@ def time_kernels(n, rounds, reps):
 
 
 def time_average(n, rounds, reps):
-    """Per optimizer: (a) "plain", (b) "fused" = the _avg entry, (c) "separate" = plain + bf_weight_average; bytes per element are what
+    """Per optimizer: (a) "plain", (b) "fused" = the step with avg set, (c) "separate" = plain + bf_weight_average; bytes per element are what
     each moves (a: 28 / Lion 20; b: + 8; c: + 12)."""
     g = torch.Generator(device="cuda").manual_seed(0)
     p = torch.randn(n, device="cuda", generator=g) * 0.02
     grad = torch.randn(n, device="cuda", generator=g) * 1e-3
     m, v, a = torch.zeros_like(p), torch.zeros_like(p), p.clone()
-    h, st, inf, w = L.lib(), _stream(), float("inf"), 1e-3
-    adam_args = lambda wd: (_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, wd, 1.0)      # noqa: E731
-    lion_args = (_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, 0.1, 1.0)
-    plain = {"adamw": lambda: h.bf_adamw(*adam_args(1e-2), st), "adam": lambda: h.bf_adam(*adam_args(1e-5), st), "lion": lambda: h.bf_lion(*lion_args, st)}
-    fused = {"adamw": lambda: h.bf_adamw_avg(*adam_args(1e-2), None, inf, _p(a), w, st), "adam": lambda: h.bf_adam_avg(*adam_args(1e-5), None, inf, _p(a), w, st),
-             "lion": lambda: h.bf_lion_avg(*lion_args, None, inf, _p(a), w, st)}
+    h, st, w = L.lib(), _stream(), 1e-3
+    steps = {"adamw": lambda **kw: opt_call("bf_adamw", p, grad, m, v, wd=1e-2, **ADAM, **kw), "adam": lambda **kw: opt_call("bf_adam", p, grad, m, v, wd=1e-5, **ADAM, **kw),
+             "lion": lambda **kw: opt_call("bf_lion", p, grad, m, **LION, **kw)}
+    plain = {opt: step() for opt, step in steps.items()}
+    fused = {opt: step(avg=_p(a), avg_weight=w) for opt, step in steps.items()}
     out = {}
     for opt in ("adamw", "adam", "lion"):
         def separate(f=plain[opt]):
@@ -139,27 +150,23 @@ def group_tables(cfg, specs_of, weight_decay):
 
 
 def time_groups(cfg, n, rounds, reps):
-    """Per optimizer: "ungrouped" (bf_adamw / bf_lion), "all_live" and "trunk_frozen" (the _groups entry); ms per launch, and each grouped
+    """Per optimizer: "ungrouped" (bf_adamw / bf_lion), "all_live" and "trunk_frozen" (the same entry with groups); ms per launch, and each grouped
     launch over the ungrouped one of the same run."""
     from bubbleformer_amd.utils import param_groups as PG
     g = torch.Generator(device="cuda").manual_seed(0)
     p = torch.randn(n, device="cuda", generator=g) * 0.02
     grad = torch.randn(n, device="cuda", generator=g) * 1e-3
     m, v = torch.zeros_like(p), torch.zeros_like(p)
-    h, st, inf = L.lib(), _stream(), float("inf")
     out = {}
     for opt, wd, base in (("adamw", 1e-2, 28), ("lion", 0.1, 20)):
         live_t, G_live, _ = group_tables(cfg, lambda named: PG.no_weight_decay() + PG.layer_decay(named, 0.75), wd)
         froz_t, G_froz, share = group_tables(cfg, lambda named: PG.freeze(r"^blocks\."), wd)
 
-        def grouped(t):
-            tabs = (_p(t.chunk), _p(t.lr_scale), _p(t.weight_decay), _p(t.frozen), t.n_groups)
+        def step(**kw):
             if opt == "adamw":
-                return lambda: h.bf_adamw_groups(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, 1.0, None, inf, None, 0.0, *tabs, st)
-            return lambda: h.bf_lion_groups(_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, 1.0, None, inf, None, 0.0, *tabs, st)
-        plain = (lambda: h.bf_adamw(_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8, wd, 1.0, st)) if opt == "adamw" else \
-            (lambda: h.bf_lion(_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, wd, 1.0, st))
-        ms = rounds_of({"ungrouped": plain, "all_live": grouped(live_t), "trunk_frozen": grouped(froz_t)}, rounds, reps)
+                return opt_call("bf_adamw", p, grad, m, v, **{**ADAM, "wd": wd, **kw})
+            return opt_call("bf_lion", p, grad, m, **{**LION, "wd": wd, **kw})
+        ms = rounds_of({"ungrouped": step(), "all_live": step(**group_fields(live_t)), "trunk_frozen": step(**group_fields(froz_t))}, rounds, reps)
         res = {"ungrouped": summary(ms["ungrouped"], n, base), "all_live": summary(ms["all_live"], n, base),
                "trunk_frozen": summary(ms["trunk_frozen"], int(n * share), base)}
         res["groups_all_live"], res["groups_trunk_frozen"], res["live_share_trunk_frozen"] = G_live, G_froz, round(share, 4)
@@ -174,7 +181,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--average", action="store_true", help="time the averaged-weights step: plain, fused _avg entry, plain + bf_weight_average")
+    ap.add_argument("--average", action="store_true", help="time the averaged-weights step: plain, fused (avg set), plain + bf_weight_average")
     ap.add_argument("--groups", action="store_true", help="time the parameter-group launch: ungrouped, every group live, trunk frozen")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/adam_bench.py times GPU kernels: no GPU found"

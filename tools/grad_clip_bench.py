@@ -2,8 +2,8 @@
 """Gradient-clipping kernels, timed on the GPU: prints one JSON object.
 
 bf_grad_norm (csrc/gradclip.hip: the fp64 fixed-order 2-norm of the flat gradient buffer and the clip coefficient, two launches) and the
-three fused optimizers reading that coefficient from device memory (bf_adamw_dev / bf_adam_dev / bf_lion_dev, with and without the value
-clamp) beside their host-scale twins (bf_adamw / bf_adam / bf_lion), all in one run on the flat fp32 buffers TrainStep keeps for
+three fused optimizers reading that coefficient from device memory (bf_adamw / bf_adam / bf_lion with their record's coef_dev set, with and
+without the value clamp: the rows *_dev and *_dev_clamp) beside their host-scale twins (no coefficient, no clamp), all in one run on the flat fp32 buffers TrainStep keeps for
 FiLMAViT-small (E 384, 6 heads, 12 blocks; every parameter padded to 64 elements as trainer.FlatParams lays them out).  The kernels
 alternate in rounds of `--reps` back-to-back calls timed by device events; reported per kernel: the median over rounds of the time per
 call, with the minimum and the maximum, and the bytes it moves per second (the norm reads 4 B per element, AdamW / Adam 28 B, Lion 20 B).
@@ -25,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from bubbleformer_amd import _lib as L  # noqa: E402
 from bubbleformer_amd.ops import _p, _stream  # noqa: E402
-from tools.adam_bench import MODELS, flat_sizes  # noqa: E402
+from tools.adam_bench import ADAM, LION, MODELS, flat_sizes, opt_call  # noqa: E402
 
 INF = float("inf")
 BYTES = {"grad_norm": 4, "adamw": 28, "adam": 28, "lion": 20}
@@ -40,20 +40,11 @@ def time_kernels(n, rounds, reps):
     h, st = L.lib(), _stream()
     ws = torch.empty(int(h.bf_grad_norm_ws_doubles(n)), dtype=torch.float64, device="cuda")
     coef = pair[1:].data_ptr()
-    adam_args = (_p(p), _p(grad), _p(m), _p(v), n, 10, 2.5e-4, 0.9, 0.999, 1e-8)
-    lion_args = (_p(p), _p(grad), _p(m), n, 5e-5, 0.9, 0.99, 0.1, 1.0)
-    calls = {
-        "grad_norm": lambda: h.bf_grad_norm(_p(grad), n, 1.0, 1.0, _p(pair), _p(ws), ws.numel(), st),
-        "adamw": lambda: h.bf_adamw(*adam_args, 1e-2, 1.0, st),
-        "adamw_dev": lambda: h.bf_adamw_dev(*adam_args, 1e-2, 1.0, coef, INF, st),
-        "adamw_dev_clamp": lambda: h.bf_adamw_dev(*adam_args, 1e-2, 1.0, coef, 1e-3, st),
-        "adam": lambda: h.bf_adam(*adam_args, 1e-5, 1.0, st),
-        "adam_dev": lambda: h.bf_adam_dev(*adam_args, 1e-5, 1.0, coef, INF, st),
-        "adam_dev_clamp": lambda: h.bf_adam_dev(*adam_args, 1e-5, 1.0, coef, 1e-3, st),
-        "lion": lambda: h.bf_lion(*lion_args, st),
-        "lion_dev": lambda: h.bf_lion_dev(*lion_args, coef, INF, st),
-        "lion_dev_clamp": lambda: h.bf_lion_dev(*lion_args, coef, 1e-3, st),
-    }
+    steps = {"adamw": lambda **kw: opt_call("bf_adamw", p, grad, m, v, wd=1e-2, **ADAM, **kw), "adam": lambda **kw: opt_call("bf_adam", p, grad, m, v, wd=1e-5, **ADAM, **kw),
+             "lion": lambda **kw: opt_call("bf_lion", p, grad, m, **LION, **kw)}
+    calls = {"grad_norm": lambda: h.bf_grad_norm(_p(grad), n, 1.0, 1.0, _p(pair), _p(ws), ws.numel(), st)}
+    for opt, step in steps.items():          # the _dev rows keep a coefficient that is not null: they time the BF_OPT_DEV kernels
+        calls.update({opt: step(), opt + "_dev": step(coef_dev=coef, clip_value=INF), opt + "_dev_clamp": step(coef_dev=coef, clip_value=1e-3)})
     for f in calls.values():                         # warm-up: code objects loaded, buffers touched (the first call leaves a coefficient behind)
         for _ in range(5):
             L.check(f(), "warm-up")
