@@ -1,6 +1,7 @@
 // The device clip store, trajectories resident in HBM as [fields][total_frames][H][W] fp32: the clip gather of a batch and the dataset's
 // field statistics.  The index map and the normalisation are clip_store.h's: the rollout kernels build their targets through the same two.
 #include "clip_store.h"
+#include "philox.h"
 #include <algorithm>
 
 namespace {
@@ -133,6 +134,90 @@ __global__ void __launch_bounds__(NT) clip_gather_unroll_kernel(const float* __r
         gather_quad(row, dst, xq, d, q, sx, W, Wo, ident);
     }
 }
+// The unroll kernel's batch with a seeded mirror in x and a seeded Hc x Wc window per SAMPLE (unroll >= 1, the unroll
+// kernel's output layout and frame clamp).  Everything is defined on the output grid, after the nearest-neighbour map:
+//   out[c][t][y][x] = clip_norm(s_c * raw(c, t, y0 + y, xs), diff_c, div_c),  xs = x0 + x, or x0 + Wc - 1 - x when the sample is mirrored
+//   s_c = -1 iff the sample is mirrored and odd[c] != 0 (a field that changes sign under x -> -x, velx): the sign goes on the STORED value
+// One Philox4x32-10 block per sample (philox.h), key = the seed, counter {0xFFFFFFFF, low 32 bits of the clamped idx[b], draw, 0} -- word 0 of
+// bf_clip_noise's counter is a group number < 2^29, so under one seed the two never share a block:
+//   mirrored iff w0 < thr (thr = round(flip_p 2^32), 0 .. 2^32);  x0 = (w1 (Wo - Wc + 1)) >> 32;  y0 = (w2 (Ho - Hc + 1)) >> 32 or 0 (crop_y)
+// eval_view: no block is drawn -- never mirrored, x0 = (Wo - Wc) / 2, y0 = 0.  The input clip, every target clip and all their frames share
+// the sample's decision; the fluid row is the plain one.
+// Samples lie on the grid's y axis: the block is computed ONCE per thread and sample, in front of that sample's pixel loop (it depends on
+// nothing a lane owns, so the compiler may hold it in scalar registers), never per pixel, and no second launch or buffer is involved.
+// A thread serves 4 output pixels of a row.  16-byte loads and stores when the map is the identity and W, Wc and x0 are multiples of 4
+// (a mirrored quad is then one aligned quad read back to front); scalar loads otherwise (an odd origin, a ragged window, a downsampled
+// store), still with one 16-byte store per quad when Wc is a multiple of 4.  A kernel of its own, as clip_gather_unroll_kernel is and for its reason.
+struct ClipAugment { const int* odd_a; const int* odd_b; uint32_t k0, k1, draw; unsigned long long thr; int Hc, Wc, random_y, eval_view; };
+__global__ void __launch_bounds__(NT) clip_gather_augment_kernel(const float* __restrict__ src, long field_stride, const long* __restrict__ idx, long nsamples,
+                                                                const long* __restrict__ first_tab, ClipSeg a, ClipSeg b,
+                                                                const float* __restrict__ fluid_tab, const long* __restrict__ file_tab, int P,
+                                                                float* __restrict__ fluid_out, int B, int H, int W, int Ho, int Wo, int unroll, long nframes,
+                                                                ClipAugment g) {
+    const int Hc = g.Hc, Wc = g.Wc;
+    const int wq = (Wc + 3) / 4;
+    const long per_a = (long)a.T * a.C * Hc * wq, per_b = (long)b.T * b.C * Hc * wq, per = per_a + per_b;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const bool ident = Ho == H && Wo == W;
+    const int Tc = b.T / unroll;
+    if (fluid_out && blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < B * P; i += NT) fluid_out[i] = fluid_tab[file_tab[min(max(idx[i / P], 0L), nsamples - 1)] * P + i % P];
+    for (int bb = blockIdx.y; bb < B; bb += gridDim.y) {
+        const long smp = min(max(idx[bb], 0L), nsamples - 1);
+        bool flip = false;
+        int x0 = (Wo - Wc) / 2, y0 = 0;
+        if (!g.eval_view) {
+            const Quad q = philox4x32_10(0xFFFFFFFFu, (uint32_t)(unsigned long)smp, g.draw, 0u, g.k0, g.k1);
+            flip = (unsigned long long)q.w[0] < g.thr;
+            x0 = (int)(((unsigned long long)q.w[1] * (unsigned long long)(Wo - Wc + 1)) >> 32);
+            y0 = g.random_y ? (int)(((unsigned long long)q.w[2] * (unsigned long long)(Ho - Hc + 1)) >> 32) : 0;
+        }
+        const long first = first_tab[smp];
+        const bool vec = ident && ((W | Wc | x0) & 3) == 0;
+        for (long r0 = (long)blockIdx.x * NT + threadIdx.x; r0 < per; r0 += (long)gridDim.x * NT) {
+            long r = r0;
+            const bool second = r >= per_a;
+            if (second) r -= per_a;
+            const ClipSeg& sg = second ? b : a;
+            const int xq = (int)(r % wq); r /= wq;
+            const int y = (int)(r % Hc); r /= Hc;
+            const int c = (int)(r % sg.C);
+            const int t = (int)(r / sg.C);
+            const int ys = nearest_src(y0 + y, sy, H, ident);
+            const long frame = min(first + sg.t0 + t, nframes - 1);
+            const int j = second ? t / Tc : 0;
+            const long orow = second ? ((long)j * B + bb) * Tc + (t - j * Tc) : (long)bb * sg.T + t;      // as the unroll kernel lays its rows out
+            const float* row = src + (long)sg.field[c] * field_stride + (frame * H + ys) * (long)W;
+            float* dst = sg.out + ((orow * sg.C + c) * Hc + y) * (long)Wc + 4 * xq;
+            const float d = sg.diff[c], q = sg.dv[c];
+            const bool neg = flip && (second ? g.odd_b : g.odd_a)[c] != 0;
+            if (vec) {                                                  // 4 xq + 3 < Wc: the window is whole quads
+                const float4 v = *reinterpret_cast<const float4*>(row + (flip ? x0 + Wc - 4 - 4 * xq : x0 + 4 * xq));
+                const float e0 = flip ? v.w : v.x, e1 = flip ? v.z : v.y, e2 = flip ? v.y : v.z, e3 = flip ? v.x : v.w;
+                *reinterpret_cast<float4*>(dst) = make_float4(clip_norm(neg ? -e0 : e0, d, q), clip_norm(neg ? -e1 : e1, d, q),
+                                                              clip_norm(neg ? -e2 : e2, d, q), clip_norm(neg ? -e3 : e3, d, q));
+            } else if ((Wc & 3) == 0) {                                 // whole quads at an origin or through a map that is not aligned: scalar loads, one 16-byte store
+                float o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x = 4 * xq + k;
+                    const float v = row[nearest_src(flip ? x0 + Wc - 1 - x : x0 + x, sx, W, ident)];
+                    o[k] = clip_norm(neg ? -v : v, d, q);
+                }
+                *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x = 4 * xq + k;
+                    if (x < Wc) {
+                        const float v = row[nearest_src(flip ? x0 + Wc - 1 - x : x0 + x, sx, W, ident)];
+                        dst[k] = clip_norm(neg ? -v : v, d, q);
+                    }
+                }
+            }
+        }
+    }
+}
 extern "C" int bf_clip_gather_batch(const float* src, int64_t field_stride, const int64_t* idx, int64_t nsamples, const int64_t* first_tab, const int32_t* in_field,
                                     const float* in_diff, const float* in_div, int Cin, int Tin, float* in_out, const int32_t* out_field,
                                     const float* out_diff, const float* out_div, int Cout, int Tout, float* out_out, const float* fluid_tab,
@@ -166,6 +251,34 @@ extern "C" int bf_clip_gather_unroll(const float* src, int64_t field_stride, int
     const long total = (long)B * ((long)Tin * Cin + (long)unroll * Tout * Cout) * Ho * ((Wo + 3) / 4);
     hipLaunchKernelGGL(clip_gather_unroll_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, src, (long)field_stride, (const long*)idx, (long)nsamples,
                        (const long*)first_tab, a, b, fluid_tab, (const long*)file_tab, P, fluid_out, B, H, W, Ho, Wo, unroll, (long)nframes);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ... and with the seeded mirror and window of clip_gather_augment_kernel: bf_clip_gather_unroll's job as a record, and the draw as another
+extern "C" int bf_clip_gather_augment(const bf_clip_gather_job* j, const bf_clip_augment* g, bf_stream_t stream) {
+    BF_REQUIRE(j && g && j->src && j->idx && j->first_tab && j->in_field && j->in_diff && j->in_div && j->in_out && j->out_field && j->out_diff && j->out_div &&
+               j->out_out && g->in_odd && g->out_odd, "bf_clip_gather_augment: null pointer");
+    BF_REQUIRE(j->nsamples > 0 && j->B > 0 && j->Tin > 0 && j->Tout > 0 && j->Cin > 0 && j->Cout > 0 && j->H > 0 && j->W > 0 && j->Ho > 0 && j->Wo > 0 &&
+               j->Ho <= j->H && j->Wo <= j->W, "bf_clip_gather_augment: bad sizes");
+    BF_REQUIRE(j->unroll >= 1 && j->unroll <= 1024 && j->nframes > 0 && j->field_stride >= j->nframes * (int64_t)j->H * j->W,
+               "bf_clip_gather_augment: bad unroll count or frame count");
+    BF_REQUIRE(!j->fluid_out || (j->fluid_tab && j->file_tab && j->P > 0), "bf_clip_gather_augment: the fluid rows need their table, the file table and P > 0");
+    BF_REQUIRE(((uintptr_t)j->src % 16 == 0) && ((uintptr_t)j->in_out % 16 == 0) && ((uintptr_t)j->out_out % 16 == 0),
+               "bf_clip_gather_augment: buffers must be 16-byte aligned");
+    BF_REQUIRE(g->Hc >= 1 && g->Hc <= j->Ho && g->Wc >= 1 && g->Wc <= j->Wo, "bf_clip_gather_augment: the window must be 1 .. Ho by 1 .. Wo");
+    BF_REQUIRE(g->flip_thr >= 0 && g->flip_thr <= (1LL << 32) && (g->crop_y == 0 || g->crop_y == 1) && (g->eval_view == 0 || g->eval_view == 1),
+               "bf_clip_gather_augment: bad flip threshold, crop_y or eval_view");
+    const ClipSeg a{(const int*)j->in_field, j->in_diff, j->in_div, j->in_out, j->Tin, j->Cin, 0};
+    const ClipSeg b{(const int*)j->out_field, j->out_diff, j->out_div, j->out_out, j->unroll * j->Tout, j->Cout, j->Tin};
+    const ClipAugment aug{(const int*)g->in_odd, (const int*)g->out_odd, (uint32_t)(uint64_t)g->seed, (uint32_t)((uint64_t)g->seed >> 32), (uint32_t)g->draw,
+                          (unsigned long long)g->flip_thr, g->Hc, g->Wc, g->crop_y, g->eval_view};
+    const long per = ((long)j->Tin * j->Cin + (long)j->unroll * j->Tout * j->Cout) * g->Hc * ((g->Wc + 3) / 4);
+    const int gy = std::min(j->B, 65535);
+    const int gx = (int)std::max<long>(1, std::min<long>((per + NT - 1) / NT, std::max(1, 256 * 16 / gy)));
+    hipLaunchKernelGGL(clip_gather_augment_kernel, dim3(gx, gy), dim3(NT), 0, (hipStream_t)stream, j->src, (long)j->field_stride, (const long*)j->idx,
+                       (long)j->nsamples, (const long*)j->first_tab, a, b, j->fluid_tab, (const long*)j->file_tab, j->P, j->fluid_out, j->B, j->H, j->W, j->Ho,
+                       j->Wo, j->unroll, (long)j->nframes, aug);
     BF_CHECK_LAUNCH();
     return 0;
 }

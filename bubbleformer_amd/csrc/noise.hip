@@ -9,24 +9,11 @@
 // A streaming kernel: one thread per group of four elements, grid-stride over a sample's groups, samples on the grid's y axis; 16-byte loads
 // and stores when the per-sample size is a multiple of 4 and both pointers are 16-byte aligned, scalar ones otherwise (clip_store.hip's
 // split).  No LDS, no atomics; dst == src (in place) is allowed, a partial overlap is not.
-#include "bf_common.h"
+#include "philox.h"
 #include <algorithm>
 
 namespace {
 constexpr int NT = 256;
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-struct Quad { uint32_t w[4]; };
-__device__ __forceinline__ Quad philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    return Quad{{c0, c1, c2, c3}};
-}
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
     const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f;      // (0, 1]: the integer is <= 2^24, exact in fp32
     const float two_u2 = (float)(b >> 8) * 0x1p-23f;         // 2 u2 in [0, 2), exact

@@ -173,6 +173,7 @@ class DeviceClipStore:
                 host[ci, self.frame0[fi]:self.frame0[fi + 1]] = torch.from_numpy(np.array(f[name][...], dtype=np.float32))
         self.frames = host.to(self.device)
         self._unroll_masks = {}       # per (dataset geometry, k): which samples are in ds.unrollable(k)
+        self._odd_tabs = {}           # per (odd fields, input fields, output fields): the sign-eligibility tables of gather(augment=...)
         self.fluid = None
         if ds.return_fluid_params:
             self.fluid = torch.tensor([_fluid_vector(fp) for fp in ds.fluid_params], dtype=torch.float32, device=self.device)
@@ -269,7 +270,16 @@ class DeviceClipStore:
             cache[key] = mask
         return cache[key]
 
-    def gather(self, indices, unroll: Optional[int] = None):
+    def _odd_tables(self, odd_fields) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per input / output channel, 1 where the channel's field is in ``odd_fields`` (int32 device tables; names the dataset lacks match nothing)."""
+        ds = self.ds
+        key = (tuple(odd_fields), tuple(ds.input_fields), tuple(ds.output_fields))
+        cache = self._odd_tabs
+        if key not in cache:
+            cache[key] = tuple(torch.tensor([int(n in key[0]) for n in names], dtype=torch.int32, device=self.device) for names in key[1:])
+        return cache[key]
+
+    def gather(self, indices, unroll: Optional[int] = None, augment=None, draw: int = 0):
         """indices: sample indices as a sequence of ints or an integer tensor -- a DEVICE tensor (e.g. a slice of
         ``torch.randperm(len(ds), device=...)``) keeps the whole step free of host-device synchronisation; host indices are staged
         through pinned memory.
@@ -279,11 +289,27 @@ class DeviceClipStore:
         synchronisation: they are clamped into the sample range, as without ``unroll``, and with ``unroll`` every frame number is also
         held below the store's frame count (bf_clip_gather_unroll; the single-clip launch needs no such clamp) -- a sample whose later
         clips lie behind its own file then yields the frames that follow on the store's frame axis, those of the next file, and the
-        store's last frame where the store ends; so draw device indices from ``ds.unrollable(k)``.  ``unroll=None`` is the call it always was."""
+        store's last frame where the store ends; so draw device indices from ``ds.unrollable(k)``.  ``unroll=None`` is the call it always was.
+        ``augment``: a utils.augment.AugmentSpec -- per sample a seeded mirror in x (the odd fields change sign) and a seeded window of
+        the output grid, decided on the device as a pure function of (spec.seed, sample index, ``draw``) and applied by the ONE launch
+        that gathers (bf_clip_gather_augment): the clips come out ``(B, T, C, Hc, Wc)`` / ``(k, B, T, C, Hc, Wc)``, the fluid rows
+        unchanged; ``utils.augment.augment_plan`` states the same decisions on the host.  A crop larger than the output grid and a CPU
+        store raise ValueError.  None or an inactive spec: exactly the calls made without the argument, and ``draw`` is unread."""
         from .. import ops
         ds = self.ds
         if unroll is not None and (int(unroll) != unroll or unroll < 1):
             raise ValueError(f"gather: unroll {unroll!r} must be None or an integer >= 1")
+        if augment is not None:
+            from ..utils.augment import AugmentSpec, flip_threshold
+            if not isinstance(augment, AugmentSpec):
+                raise ValueError(f"gather: augment {augment!r} must be None or a utils.augment.AugmentSpec")
+            if not augment.active:
+                augment = None
+        if augment is not None:
+            f = ds.downsample_factor
+            window = augment.window(*((self.H // f, self.W // f) if f > 1 else (self.H, self.W)))
+            if self.device.type != "cuda":
+                raise ValueError("gather: augmentation runs inside the device gather (bf_clip_gather_augment); a CPU store has none")
         first_all, file_all = self._index_tables()
         if isinstance(indices, torch.Tensor) and indices.device == self.device:
             idx = indices.to(torch.int64)
@@ -296,6 +322,15 @@ class DeviceClipStore:
             idx = host.pin_memory().to(self.device, non_blocking=True) if self.device.type == "cuda" else host.to(self.device)
         tw, f = ds.time_window, ds.downsample_factor
         ho, wo = (self.H // f, self.W // f) if f > 1 else (self.H, self.W)
+        if augment is not None:              # one launch: the mirrored / windowed input clip, target clips and the plain fluid rows
+            in_odd, out_odd = self._odd_tables(augment.odd_fields)
+            inp, out, fl = ops.clip_gather_augment(self.frames, idx.contiguous(), first_all, tw, 1 if unroll is None else int(unroll), self.in_tab,
+                                                   self.out_tab, ho, wo, in_odd, out_odd, augment.seed, int(draw), flip_threshold(augment.flip_p),
+                                                   window[0], window[1], augment.crop_y == "random", augment.eval, self.fluid,
+                                                   file_all if self.fluid is not None else None)
+            if unroll is None:
+                out = out[0]
+            return (inp, out, fl) if self.fluid is not None else (inp, out)
         if unroll is not None:               # one launch: the input clip, all `unroll` target clips and the fluid rows
             inp, out, fl = ops.clip_gather_unroll(self.frames, idx.contiguous(), first_all, tw, int(unroll), self.in_tab, self.out_tab, ho, wo,
                                                   self.fluid, file_all if self.fluid is not None else None)

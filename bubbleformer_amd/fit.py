@@ -53,7 +53,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None) -> Dict:
+        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None, augment=None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -85,6 +85,13 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     one optimizer launch (TrainStep; the scale multiplies the scheduled learning rate).  With clipping by norm ``hist["group_grad_norm"]``
     holds one row per optimizer step with the scaled gradient norm of every group, recorded as ``grad_norm`` is, and the `log` dict of a
     batch that stepped carries the row as a device tensor.  Checkpoints record the partition, and resuming into another one is refused.
+    ``augment``: a utils.augment.AugmentSpec -- every training batch is gathered with a seeded mirror in x and / or a seeded window per sample,
+    inside the gather's one launch (``DeviceClipStore.gather(idx, augment=..., draw=step.step_no)``): the decision of a sample is a pure
+    function of (seed, dataset index, optimizer-step count), so a resumed run continues the sequence and the checkpoint needs no new key;
+    every rank uses the same seed and ranks differ by their sample ids.  With a crop the model trains on ``Hc x Wc`` windows and validation
+    sees ``augment.eval_view()`` -- never mirrored, the window centred in x on the heater row -- so its clips have the training shape;
+    without a crop validation is gathered plainly.  Panels show what validation saw.  Composes with ``unroll_steps``, ``input_noise``,
+    accumulation and conditioning; None or an inactive spec: every call, history and parameter bit for bit as without it.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -102,6 +109,13 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     steps_per_epoch = accumulation_plan(per_epoch, accumulate_grad_batches)[1]
     sched = CosineWarmupLR(lr, warmup_iters, max_epochs * steps_per_epoch, eta_min) if warmup_iters is not None else None
     noisy = input_noise is not None and input_noise.active
+    if augment is not None:
+        from .utils.augment import AugmentSpec
+        if not isinstance(augment, AugmentSpec):
+            raise ValueError(f"augment {augment!r} must be None or a utils.augment.AugmentSpec")
+        if not augment.active:
+            augment = None
+    val_view = augment.eval_view() if augment is not None and augment.crop is not None else None
     field_std = None
     if noisy and input_noise.relative:
         fs = store.field_std()
@@ -132,7 +146,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         order = epoch_indices(n_pool, epoch, seed, True, rank, world)
         todo = batches(order if pool is None else [pool[i] for i in order], batch_size, limit_train_batches)
         for bi, idx in enumerate(todo):
-            got = store.gather(idx) if k == 1 else store.gather(idx, unroll=k)
+            if augment is None:
+                got = store.gather(idx) if k == 1 else store.gather(idx, unroll=k)
+            else:
+                got = store.gather(idx, unroll=k if k > 1 else None, augment=augment, draw=step.step_no)
             x, y, c = (got[0], got[1], got[2]) if conditioned else (got[0], got[1], None)
             cur_lr = sched.get_last_lr()[0] if sched is not None else step.lr      # step.lr: a reference checkpoint brings its own
             before = step.step_no
@@ -163,13 +180,13 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         hist["epoch_train_loss"].append(float(ep.mean()))
         if vstore is not None:
             sample = [] if panel_dir is not None and rank == 0 else None
-            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, sample))
+            hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, sample, val_view))
             if sample:
                 write_validation_strips(panel_dir, epoch, list(val_set.output_fields), *sample)
             entry = {"epoch": epoch, "val_loss": hist["val_loss"][-1]}
             if step.avg is not None:
                 with step.averaged_weights():
-                    hist["val_loss_avg"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion))
+                    hist["val_loss_avg"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, augment=val_view))
                 entry["val_loss_avg"] = hist["val_loss_avg"][-1]
             if log is not None:
                 log(entry)
@@ -180,15 +197,16 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
 
 @torch.no_grad()
 def validate(model, val_set, vstore, batch_size: int, limit_val_batches: Optional[int], rank: int = 0, world: int = 1, criterion=None,
-             sample: Optional[list] = None) -> float:
+             sample: Optional[list] = None, augment=None) -> float:
     """Mean over the (limited) validation batches of the training criterion, as `validation_step` logs it on epoch end.  A list passed as
-    ``sample`` receives (target, prediction) of sample 0 of batch 0, (T, C, H, W) each (`validation_sample` of modules.py:185-189)."""
+    ``sample`` receives (target, prediction) of sample 0 of batch 0, (T, C, H, W) each (`validation_sample` of modules.py:185-189).
+    ``augment``: the view the clips are gathered in (fit passes ``AugmentSpec.eval_view()`` of a spec with a crop); None gathers plainly."""
     was_training = model.training
     model.eval()
     conditioned = getattr(val_set, "return_fluid_params", False)
     tot, n = 0.0, 0
     for idx in batches(epoch_indices(len(val_set), 0, 0, False, rank, world), batch_size, limit_val_batches):
-        got = vstore.gather(idx)
+        got = vstore.gather(idx) if augment is None else vstore.gather(idx, augment=augment)
         if criterion is None:
             loss, pred = model.forward_loss(got[0], got[2], got[1]) if conditioned else model.forward_loss(got[0], got[1])
         else:

@@ -953,6 +953,39 @@ def clip_gather_unroll(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch
     return inp, out, fl
 
 
+def clip_gather_augment(frames: torch.Tensor, idx: torch.Tensor, first_tab: torch.Tensor, T: int, unroll: int, in_table, out_table, Ho: int, Wo: int,
+                        in_odd: torch.Tensor, out_odd: torch.Tensor, seed: int, draw: int, flip_thr: int, Hc: int, Wc: int, random_y: bool = False,
+                        eval_view: bool = False, fluid_tab: Optional[torch.Tensor] = None, file_tab: Optional[torch.Tensor] = None):
+    """clip_gather_unroll with a seeded mirror in x and a seeded ``Hc x Wc`` window of the ``Ho x Wo`` output grid per sample, one launch
+    (bf_clip_gather_augment; utils/augment.py states the draw): -> input clips (B, T, Cin, Hc, Wc), target clips (unroll, B, T, Cout, Hc, Wc)
+    and the plain fluid rows.  in_odd [Cin] / out_odd [Cout]: int32 device tables, 1 where the channel's field changes sign when mirrored.
+    ``seed`` counts modulo 2^64 and ``draw`` modulo 2^32; ``flip_thr`` = min(round(flip_p 2^32), 2^32); ``eval_view`` draws nothing (never
+    mirrored, the window centred in x at y0 = 0)."""
+    _require_gpu(frames)
+    (iid, idf, idv), (oid, odf, odv) = in_table, out_table
+    nf, total, H, W = frames.shape
+    B = idx.numel()
+    if int(unroll) != unroll or unroll < 1:
+        raise ValueError(f"clip_gather_augment: unroll {unroll!r} must be an integer >= 1")
+    if not (1 <= int(Hc) <= Ho and 1 <= int(Wc) <= Wo):
+        raise ValueError(f"clip_gather_augment: the window {(Hc, Wc)} must lie inside the output grid {(Ho, Wo)}")
+    _check_tensors("clip_gather_augment", frames.device, {"in_odd": (in_odd, (iid.numel(),), torch.int32), "out_odd": (out_odd, (oid.numel(),), torch.int32)})
+    inp = torch.empty((B, T, iid.numel(), Hc, Wc), dtype=torch.float32, device=frames.device)
+    out = torch.empty((int(unroll), B, T, oid.numel(), Hc, Wc), dtype=torch.float32, device=frames.device)
+    P = int(fluid_tab.shape[1]) if fluid_tab is not None else 0
+    fl = torch.empty((B, P), dtype=torch.float32, device=frames.device) if fluid_tab is not None else None
+    signed = lambda v, bits: (v & (2 ** bits - 1)) - (2 ** bits if v & 2 ** (bits - 1) else 0)      # noqa: E731  (the record's signed bit patterns)
+    job = L.ClipGatherJob(src=_p(frames), idx=_p(idx), first_tab=_p(first_tab), in_field=_p(iid), in_diff=_p(idf), in_div=_p(idv), in_out=_p(inp),
+                          out_field=_p(oid), out_diff=_p(odf), out_div=_p(odv), out_out=_p(out), fluid_tab=_p(fluid_tab) if fl is not None else None,
+                          file_tab=_p(file_tab) if fl is not None else None, fluid_out=_p(fl) if fl is not None else None, field_stride=total * H * W,
+                          nframes=total, nsamples=first_tab.numel(), Cin=iid.numel(), Tin=T, Cout=oid.numel(), Tout=T, unroll=int(unroll), P=P, B=B, H=H, W=W,
+                          Ho=Ho, Wo=Wo)
+    aug = L.ClipAugment(in_odd=_p(in_odd), out_odd=_p(out_odd), seed=signed(int(seed), 64), flip_thr=int(flip_thr), draw=signed(int(draw), 32), Hc=int(Hc),
+                        Wc=int(Wc), crop_y=int(bool(random_y)), eval_view=int(bool(eval_view)))
+    L.check(L.lib().bf_clip_gather_augment(C.byref(job), C.byref(aug), _stream()), "bf_clip_gather_augment")
+    return inp, out, fl
+
+
 def clip_noise(src: torch.Tensor, sigma: torch.Tensor, sample_ids: Optional[torch.Tensor], draw: int, pass_index: int, seed: int,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = src + sigma[c] * z on contiguous fp32 clips (B, T, C, H, W), z the seeded normals of bf_clip_noise (csrc/noise.hip): a pure

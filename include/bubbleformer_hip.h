@@ -30,6 +30,7 @@
  *   bf_adamw ................. torch.optim.AdamW as configured at bubbleformer/modules.py:135-136
  *   bf_adam .................. torch.optim.Adam as configured at bubbleformer/modules.py:137-138 (config/optim_cfg/adam.yaml)
  *   bf_clip_gather ........... BubbleForecast.__getitem__ + DataLoader collate for a batch of clips: bubbleformer/data/dataset.py:120-182
+ *   bf_clip_gather_augment ... the unrolled batch gather with a seeded mirror in x and a seeded window per sample (no reference program)
  *   bf_clip_noise ............ seeded Gaussian input noise of a training step (no reference program; Philox4x32-10 + Box-Muller)
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
@@ -360,6 +361,38 @@ int bf_clip_gather_unroll(const float* src, int64_t field_stride, int64_t nframe
                           const int32_t* out_field, const float* out_diff, const float* out_div, int Cout, int Tout, int unroll, float* out_out,
                           const float* fluid_tab, const int64_t* file_tab, int P, float* fluid_out, int B, int H, int W, int Ho, int Wo,
                           bf_stream_t stream);
+/* bf_clip_gather_unroll with a seeded mirror in x and a seeded window per sample (csrc/clip_store.hip), one launch.
+ * bf_clip_gather_job carries bf_clip_gather_unroll's arguments under their names there (unroll >= 1; reserved is unread); the outputs are
+ * in_out (B, Tin, Cin, Hc, Wc), out_out (unroll, B, Tout, Cout, Hc, Wc) and the plain fluid_out (B, P).  With plain[c][t][y][x] the value
+ * bf_clip_gather_unroll forms on its Ho x Wo grid BEFORE normalisation, sample b gets
+ *   out[c][t][y][x] = (s_c * plain[c][t][y0 + y][xs] - diff[c]) / div[c],   xs = x0 + x, or x0 + Wc - 1 - x when the sample is mirrored
+ *   (the window is chosen first, then mirrored), s_c = -1 iff the sample is mirrored and the segment's odd table holds a non-zero at c
+ *   (in_odd [Cin], out_odd [Cout], int32 in DEVICE memory: 1 where the channel's field changes sign under x -> -x), else +1.
+ * The decision is one Philox4x32-10 block per sample (Random123's constants, as bf_clip_noise): key = {low, high word of seed}, counter =
+ *   {0xFFFFFFFF, low 32 bits of idx[b] clamped to 0 .. nsamples - 1, draw, 0} -> (w0, w1, w2, w3).  bf_clip_noise's counter word 0 is a group
+ *   number < 2^29, so under one seed the two never share a block.
+ *   mirrored iff w0 < flip_thr      (flip_thr = min(round(p * 2^32), 2^32) as a 64-bit value: 0 never mirrors, 2^32 always does)
+ *   x0 = (w1 * (Wo - Wc + 1)) >> 32 in 64-bit arithmetic;  y0 = (w2 * (Ho - Hc + 1)) >> 32 when crop_y == 1, 0 when crop_y == 0 (the window
+ *   keeps output row 0, the heater row);  w3 is unused.  seed and draw are read as unsigned bit patterns.
+ *   eval_view == 1 draws nothing: never mirrored, x0 = (Wo - Wc) / 2, y0 = 0 (the deterministic view for validation).
+ * The input clip, every target clip and all frames of a sample share its decision: a pure function of (seed, sample, draw), whatever B and
+ * the sample's place in the batch.  Requires bf_clip_gather_unroll's conditions and 1 <= Hc <= Ho, 1 <= Wc <= Wo; a null record or a null
+ * required member is refused as "bf_clip_gather_augment: null pointer", every check is made before any HIP call.  Loads and stores are 16
+ * bytes wide when Ho x Wo = H x W and W, Wc and the sample's x0 are multiples of 4, scalar otherwise. */
+typedef struct bf_clip_gather_job {
+    const float* src; const int64_t *idx, *first_tab;
+    const int32_t* in_field; const float *in_diff, *in_div; float* in_out;
+    const int32_t* out_field; const float *out_diff, *out_div; float* out_out;
+    const float* fluid_tab; const int64_t* file_tab; float* fluid_out;
+    int64_t field_stride, nframes, nsamples;
+    int32_t Cin, Tin, Cout, Tout, unroll, P, B, H, W, Ho, Wo, reserved;
+} bf_clip_gather_job;
+typedef struct bf_clip_augment {
+    const int32_t *in_odd, *out_odd;
+    int64_t seed, flip_thr;
+    int32_t draw, Hc, Wc, crop_y, eval_view, reserved;
+} bf_clip_augment;
+int bf_clip_gather_augment(const bf_clip_gather_job* job, const bf_clip_augment* augment, bf_stream_t stream);
 /* Seeded Gaussian noise on a batch of clips (csrc/noise.hip): dst[b][t][c][y][x] = fmaf(sigma[c], z, src[b][t][c][y][x]) on contiguous fp32
  * (B, T, C, H, W); an element of a channel with sigma[c] == 0 is handed back bit for bit.  dst == src (in place) or two buffers that do not
  * overlap.  z is a pure function of (seed, sample id, draw, pass, element index e inside the sample's flattened (T, C, H, W) clip):
