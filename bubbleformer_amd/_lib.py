@@ -125,6 +125,14 @@ class ClipAugment(C.Structure):
     _fields_ = [("in_odd", vp), ("out_odd", vp), ("seed", i64), ("flip_thr", i64)] + [(n, i32) for n in ("draw", "Hc", "Wc", "crop_y", "eval_view", "reserved")]
 
 
+class ClipGatherQ16Job(C.Structure):
+    """bf_clip_gather_q16_job: the 16-bit store's codes and segment tables, then bf_clip_gather_job's members (read during the call only)."""
+    _fields_ = [("codes", vp), ("frame_seg", vp), ("seg_lo", fp), ("seg_step", fp), ("idx", vp), ("first_tab", vp), ("in_field", vp), ("in_diff", fp),
+                ("in_div", fp), ("in_out", fp), ("out_field", vp), ("out_diff", fp), ("out_div", fp), ("out_out", fp), ("fluid_tab", fp), ("file_tab", vp),
+                ("fluid_out", fp), ("field_stride", i64), ("nframes", i64), ("nsamples", i64)] + [
+        (n, i32) for n in ("nfiles", "Cin", "Tin", "Cout", "Tout", "unroll", "P", "B", "H", "W", "Ho", "Wo")]
+
+
 class RenderTile(C.Structure):
     """bf_render_tile: what one slot of an image shows (bf_render_tiles)."""
     _fields_ = [("a", fp), ("b", fp), ("mask", fp), ("frame_stride", i64), ("slot_stride", i64), ("mask_frame_stride", i64), ("mask_slot_stride", i64),
@@ -232,6 +240,9 @@ SIGNATURES = {
     "bf_clip_gather_unroll": (C.c_int, [fp, i64, i64, vp, i64, vp, vp, fp, fp, C.c_int, C.c_int, fp, vp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, vp, C.c_int,
                                         fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_clip_gather_augment": (C.c_int, [P(ClipGatherJob), P(ClipAugment), vp]),
+    "bf_clip_encode_q16": (C.c_int, [fp, vp, i64, f32, f32, vp]),
+    "bf_clip_decode_q16": (C.c_int, [vp, i64, vp, fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "bf_clip_gather_q16": (C.c_int, [P(ClipGatherQ16Job), P(ClipAugment), vp]),
     "bf_clip_noise": (C.c_int, [fp, fp, fp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bf_rollout_score_ws_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_rollout_score": (C.c_int, [P(RolloutStep), C.c_int, f32, fp, fp, fp, fp, fp, fp, vp, i64, vp]),

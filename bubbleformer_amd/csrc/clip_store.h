@@ -20,6 +20,12 @@ __device__ __forceinline__ float denormalise(float v, float q, float d) {
     return prod + d;
 }
 
+// What the batch gathers pass their kernels by value, for the fp32 store (clip_store.hip) and the 16-bit one (clip_store_q16.hip): one clip
+// segment of a sample -- its channels' field ids and constants, its output, its frame count and first frame behind the sample's first --
+// and the seeded mirror / window draw
+struct ClipSeg { const int* field; const float* diff; const float* dv; float* out; int T, C, t0; };
+struct ClipAugment { const int* odd_a; const int* odd_b; uint32_t k0, k1, draw; unsigned long long thr; int Hc, Wc, random_y, eval_view; };
+
 // | |grad phi| - 1 | at pixel (x, y) of an H x W frame read through at(row, column): central differences, replicate-padded borders
 template <class At>
 __device__ __forceinline__ float eikonal_l1_px(At at, int x, int y, int H, int W, float inv_2dx) {

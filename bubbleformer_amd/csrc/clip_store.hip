@@ -65,7 +65,6 @@ extern "C" int bf_clip_gather(const float* src, int64_t field_stride, const int3
 // A training batch in ONE launch: the input clips (frames first .. first + Tin - 1), the target clips (the Tout frames behind them) and the
 // per-sample fluid-parameter rows, all indexed by SAMPLE number on the device (first_tab / file_tab: absolute first frame and file of every
 // sample of the dataset) -- what took two launches and three index kernels of the host framework (first_tab[idx], file_tab[idx], fluid[...]).
-struct ClipSeg { const int* field; const float* diff; const float* dv; float* out; int T, C, t0; };
 __global__ void __launch_bounds__(NT) clip_gather_batch_kernel(const float* __restrict__ src, long field_stride, const long* __restrict__ idx, long nsamples,
                                                               const long* __restrict__ first_tab, ClipSeg a, ClipSeg b,
                                                               const float* __restrict__ fluid_tab, const long* __restrict__ file_tab, int P,
@@ -148,7 +147,6 @@ __global__ void __launch_bounds__(NT) clip_gather_unroll_kernel(const float* __r
 // A thread serves 4 output pixels of a row.  16-byte loads and stores when the map is the identity and W, Wc and x0 are multiples of 4
 // (a mirrored quad is then one aligned quad read back to front); scalar loads otherwise (an odd origin, a ragged window, a downsampled
 // store), still with one 16-byte store per quad when Wc is a multiple of 4.  A kernel of its own, as clip_gather_unroll_kernel is and for its reason.
-struct ClipAugment { const int* odd_a; const int* odd_b; uint32_t k0, k1, draw; unsigned long long thr; int Hc, Wc, random_y, eval_view; };
 __global__ void __launch_bounds__(NT) clip_gather_augment_kernel(const float* __restrict__ src, long field_stride, const long* __restrict__ idx, long nsamples,
                                                                 const long* __restrict__ first_tab, ClipSeg a, ClipSeg b,
                                                                 const float* __restrict__ fluid_tab, const long* __restrict__ file_tab, int P,

@@ -1,1 +1,1 @@
-from .dataset import BubbleForecast, DeviceClipStore  # noqa: F401
+from .dataset import BubbleForecast, DeviceClipStore, Q16ClipStore  # noqa: F401

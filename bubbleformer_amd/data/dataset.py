@@ -4,7 +4,8 @@
 (bubbleformer/data/dataset.py:17-184) but reads the trajectory files with the in-tree HDF5 reader (no h5py), and adds the
 MI355X-side path: ``device_store()`` puts every trajectory in HBM once (a BubbleML study is a few GB; one GPU has 288 GB) and
 ``DeviceClipStore.gather`` builds a whole batch of normalised (input, target) clips with ONE HIP kernel (`bf_clip_gather`,
-csrc/clip_store.hip) -- no host-side slicing, stacking or H2D copy per step.
+csrc/clip_store.hip) -- no host-side slicing, stacking or H2D copy per step.  ``device_store(dev, storage="q16")`` holds the same
+trajectories as 16-bit codes in half the bytes and decodes them inside that launch (``Q16ClipStore``, csrc/clip_store_q16.hip).
 """
 import json
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -148,8 +149,16 @@ class BubbleForecast(Dataset):
         return inp.float().permute(1, 0, 2, 3), out.float().permute(1, 0, 2, 3)
 
     # ---------------------------------------------------------------- device-resident path
-    def device_store(self, device) -> "DeviceClipStore":
-        return DeviceClipStore(self, device)
+    def device_store(self, device, storage: str = "fp32", staging_frames: Optional[int] = None) -> "DeviceClipStore":
+        """Every trajectory resident on ``device``.  ``storage="fp32"``: one fp32 tensor, filled through one host tensor of the dataset's size
+        (``DeviceClipStore``).  ``storage="q16"``: 16-bit codes with one affine scale per (field, file), half the bytes, encoded on the device
+        as the files are uploaded through two pinned staging buffers of ``staging_frames`` frames each (None: 64 MB's worth, at least 1) and
+        decoded inside the gather's launch (``Q16ClipStore``; a GPU only: a CPU device raises ValueError)."""
+        if storage == "fp32":
+            return DeviceClipStore(self, device)
+        if storage == "q16":
+            return Q16ClipStore(self, device, staging_frames)
+        raise ValueError(f"device_store: storage {storage!r} must be 'fp32' or 'q16'")
 
 
 class DeviceClipStore:
@@ -157,7 +166,23 @@ class DeviceClipStore:
     frame axis); ``gather(indices)`` returns the batch the reference's DataLoader would have collated from ``dataset[i]``:
     ``(B, T, C_in, H', W')``, ``(B, T, C_out, H', W')`` [, ``(B, 9)`` fluid parameters] -- built by one kernel launch."""
 
-    def __init__(self, ds: BubbleForecast, device):
+    storage = "fp32"
+
+    def __init__(self, ds: BubbleForecast, device, frames: Optional[torch.Tensor] = None):
+        """``frames``: the resident tensor, when the caller has it already (``Q16ClipStore.to_fp32``); None reads the dataset's files."""
+        self._setup(ds, device)
+        if frames is None:
+            total = int(self.frame0[-1])
+            host = torch.empty((len(self.fields), total, self.H, self.W), dtype=torch.float32)
+            for fi, f in enumerate(ds.data):
+                for ci, name in enumerate(self.fields):
+                    host[ci, self.frame0[fi]:self.frame0[fi + 1]] = torch.from_numpy(np.array(f[name][...], dtype=np.float32))
+            frames = host.to(self.device)
+        self.frames = frames
+        self._tables()
+
+    def _setup(self, ds: BubbleForecast, device):
+        """Everything but the frames: the geometry, the field order, the files' places on the frame axis, the fluid rows."""
         self.ds = ds
         self.device = torch.empty(0, device=device).device      # indexed ("cuda" -> "cuda:0"): gather() compares index tensors' devices with it
         shapes = {tuple(f[ds.fields[0]].shape[1:]) for f in ds.data}
@@ -166,18 +191,16 @@ class DeviceClipStore:
         (self.H, self.W), = shapes
         self.fields = sorted(ds.fields)
         self.frame0 = np.concatenate([[0], np.cumsum(ds.traj_lens)]).astype(np.int64)       # first frame of each file on the frame axis
-        total = int(self.frame0[-1])
-        host = torch.empty((len(self.fields), total, self.H, self.W), dtype=torch.float32)
-        for fi, f in enumerate(ds.data):
-            for ci, name in enumerate(self.fields):
-                host[ci, self.frame0[fi]:self.frame0[fi + 1]] = torch.from_numpy(np.array(f[name][...], dtype=np.float32))
-        self.frames = host.to(self.device)
         self._unroll_masks = {}       # per (dataset geometry, k): which samples are in ds.unrollable(k)
         self._odd_tabs = {}           # per (odd fields, input fields, output fields): the sign-eligibility tables of gather(augment=...)
         self.fluid = None
         if ds.return_fluid_params:
             self.fluid = torch.tensor([_fluid_vector(fp) for fp in ds.fluid_params], dtype=torch.float32, device=self.device)
-        self._tables()
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the stored frames hold on the device."""
+        return self.frames.numel() * self.frames.element_size()
 
     def normalize(self) -> Tuple[Dict, Dict]:
         """``BubbleForecast.normalize()`` from the trajectories in HBM: {sum, sum of squares, min, max} of every (field, file) segment by ONE
@@ -295,12 +318,11 @@ class DeviceClipStore:
         that gathers (bf_clip_gather_augment): the clips come out ``(B, T, C, Hc, Wc)`` / ``(k, B, T, C, Hc, Wc)``, the fluid rows
         unchanged; ``utils.augment.augment_plan`` states the same decisions on the host.  A crop larger than the output grid and a CPU
         store raise ValueError.  None or an inactive spec: exactly the calls made without the argument, and ``draw`` is unread."""
-        from .. import ops
         ds = self.ds
         if unroll is not None and (int(unroll) != unroll or unroll < 1):
             raise ValueError(f"gather: unroll {unroll!r} must be None or an integer >= 1")
         if augment is not None:
-            from ..utils.augment import AugmentSpec, flip_threshold
+            from ..utils.augment import AugmentSpec
             if not isinstance(augment, AugmentSpec):
                 raise ValueError(f"gather: augment {augment!r} must be None or a utils.augment.AugmentSpec")
             if not augment.active:
@@ -322,26 +344,146 @@ class DeviceClipStore:
             idx = host.pin_memory().to(self.device, non_blocking=True) if self.device.type == "cuda" else host.to(self.device)
         tw, f = ds.time_window, ds.downsample_factor
         ho, wo = (self.H // f, self.W // f) if f > 1 else (self.H, self.W)
+        fl_files = file_all if self.fluid is not None else None
+        inp, out, fl = self._launch(idx.contiguous(), first_all, fl_files, None if unroll is None else int(unroll), augment, window if augment is not None else None,
+                                    int(draw), ho, wo)
+        return (inp, out, fl) if self.fluid is not None else (inp, out)
+
+    def _launch(self, idx, first_all, fl_files, unroll, augment, window, draw, ho, wo):
+        """The gather's launch on this store's form -> (input clips, target clips, fluid rows or None)."""
+        from .. import ops
+        tw = self.ds.time_window
         if augment is not None:              # one launch: the mirrored / windowed input clip, target clips and the plain fluid rows
+            from ..utils.augment import flip_threshold
             in_odd, out_odd = self._odd_tables(augment.odd_fields)
-            inp, out, fl = ops.clip_gather_augment(self.frames, idx.contiguous(), first_all, tw, 1 if unroll is None else int(unroll), self.in_tab,
-                                                   self.out_tab, ho, wo, in_odd, out_odd, augment.seed, int(draw), flip_threshold(augment.flip_p),
-                                                   window[0], window[1], augment.crop_y == "random", augment.eval, self.fluid,
-                                                   file_all if self.fluid is not None else None)
-            if unroll is None:
-                out = out[0]
-            return (inp, out, fl) if self.fluid is not None else (inp, out)
+            inp, out, fl = ops.clip_gather_augment(self.frames, idx, first_all, tw, 1 if unroll is None else unroll, self.in_tab,
+                                                   self.out_tab, ho, wo, in_odd, out_odd, augment.seed, draw, flip_threshold(augment.flip_p),
+                                                   window[0], window[1], augment.crop_y == "random", augment.eval, self.fluid, fl_files)
+            return inp, (out[0] if unroll is None else out), fl
         if unroll is not None:               # one launch: the input clip, all `unroll` target clips and the fluid rows
-            inp, out, fl = ops.clip_gather_unroll(self.frames, idx.contiguous(), first_all, tw, int(unroll), self.in_tab, self.out_tab, ho, wo,
-                                                  self.fluid, file_all if self.fluid is not None else None)
-            return (inp, out, fl) if self.fluid is not None else (inp, out)
+            return ops.clip_gather_unroll(self.frames, idx, first_all, tw, unroll, self.in_tab, self.out_tab, ho, wo, self.fluid, fl_files)
         if self.device.type == "cuda":       # one launch: both clips and the fluid rows, indexed by sample number on the device
-            inp, out, fl = ops.clip_gather_batch(self.frames, idx.contiguous(), first_all, tw, self.in_tab, self.out_tab, ho, wo,
-                                                 self.fluid, file_all if self.fluid is not None else None)
-            return (inp, out, fl) if self.fluid is not None else (inp, out)
+            return ops.clip_gather_batch(self.frames, idx, first_all, tw, self.in_tab, self.out_tab, ho, wo, self.fluid, fl_files)
         first = first_all[idx]
         inp = ops.clip_gather(self.frames, first, 0, tw, self.in_tab, ho, wo)
         out = ops.clip_gather(self.frames, first, tw, tw, self.out_tab, ho, wo)
-        if self.fluid is not None:
-            return inp, out, self.fluid[file_all[idx]]
-        return inp, out
+        return inp, out, (self.fluid[fl_files[idx]] if self.fluid is not None else None)
+
+
+def q16_scale(lo, hi) -> Tuple[np.float32, np.float32]:
+    """(step, inv) of a 16-bit segment whose values span lo .. hi (csrc/clip_store_q16.hip states the format): the quotients are taken in
+    fp64 and rounded to fp32 once; a constant segment has both 0."""
+    span = float(hi) - float(lo)
+    if span == 0.0:
+        return np.float32(0.0), np.float32(0.0)
+    return np.float32(span / 65535.0), np.float32(65535.0 / span)
+
+
+class Q16ClipStore(DeviceClipStore):
+    """``DeviceClipStore`` in half the bytes: every value resident as a 16-bit code, one affine scale per (field, file) segment, decoded
+    inside the gather's one launch (bf_clip_gather_q16; csrc/clip_store_q16.hip states the format, DESIGN.md section 27 the bound:
+    ``|decoded - x| <= 0.53 step + 2^-24 max(|lo|, |hi|)``, step = (max - min) / 65535 of the segment).  A value closer to zero than half a
+    step may come back with the other sign -- a ``dfun`` that close to the interface.  ``gather``, ``normalize``, ``field_std`` and the
+    tables are DeviceClipStore's; ``gather`` returns bit for bit what ``to_fp32().gather`` returns.  There is no ``frames`` tensor: the
+    rollout evaluation, which reads stored frames in its own kernels, takes ``to_fp32()``.
+
+    The fill reads ONE field of ONE file on the host at a time, takes its minimum and maximum there, and sends it through two pinned
+    buffers of ``staging_frames`` frames to two device buffers of that size, the copy of a chunk running beside the encode of the one
+    before it: per chunk bf_field_stats on the staged fp32 values, then bf_clip_encode_q16 into the chunk's place.  Neither side ever
+    holds the dataset in fp32.  The chunks' {sum, sum of squares, min, max} are combined on the host in fp64, in chunk order:
+    ``normalize()`` and ``field_std()`` use these statistics of the ORIGINAL values, so the constants are the fp32 store's up to the order of
+    an fp64 sum."""
+
+    storage = "q16"
+    STAGING_BYTES = 64 << 20
+
+    def __init__(self, ds: BubbleForecast, device, staging_frames: Optional[int] = None):
+        from .. import _lib as L
+        from .. import ops
+        from ..ops import _p, _stream
+        if torch.empty(0, device=device).device.type != "cuda":
+            raise ValueError("device_store: storage 'q16' is encoded and decoded by device kernels (csrc/clip_store_q16.hip); a CPU store has none")
+        self._setup(ds, device)
+        px, nfile, nfield, total = self.H * self.W, len(ds.traj_lens), len(self.fields), int(self.frame0[-1])
+        sf = max(1, self.STAGING_BYTES // (px * 4)) if staging_frames is None else int(staging_frames)
+        if sf < 1 or (staging_frames is not None and sf != staging_frames):
+            raise ValueError(f"device_store: staging_frames {staging_frames!r} must be None or an integer >= 1")
+        sf = min(sf, max(int(n) for n in ds.traj_lens))
+        self.staging_frames = sf
+        self.codes = torch.empty((nfield, total, self.H, self.W), dtype=torch.int16, device=self.device)      # the codes' bit patterns
+        chunks = [[(a, min(a + sf, int(n))) for a in range(0, int(n), sf)] for n in ds.traj_lens]               # per file: its chunks' frame ranges
+        lens = torch.tensor([(b - a) * px for _ in self.fields for file_chunks in chunks for a, b in file_chunks], dtype=torch.int64, device=self.device)
+        zero = torch.zeros(1, dtype=torch.int64, device=self.device)
+        stats = torch.empty((lens.numel(), 4), dtype=torch.float64, device=self.device)
+        ws = torch.empty(L.lib().bf_field_stats_ws_doubles(1), dtype=torch.float64, device=self.device)
+        pinned = [torch.empty((sf, self.H, self.W), dtype=torch.float32).pin_memory() for _ in range(2)]
+        staged = [torch.empty((sf, self.H, self.W), dtype=torch.float32, device=self.device) for _ in range(2)]
+        copied = [torch.cuda.Event() for _ in range(2)]       # the chunk in staged[b] has arrived (and pinned[b] may be refilled)
+        encoded = [torch.cuda.Event() for _ in range(2)]      # staged[b] has been read (and may be overwritten)
+        lo_tab, step_tab = np.zeros((nfield, nfile), dtype=np.float32), np.zeros((nfield, nfile), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+            k = 0
+            for ci, name in enumerate(self.fields):
+                for fi, f in enumerate(ds.data):
+                    arr = np.array(f[name][...], dtype=np.float32)          # one field of one file: all the fp32 the host ever holds
+                    lo, hi = arr.min(), arr.max()
+                    step, inv = q16_scale(lo, hi)
+                    lo_tab[ci, fi], step_tab[ci, fi] = lo, step
+                    for a, b in chunks[fi]:
+                        s = k & 1
+                        if k >= 2:
+                            copied[s].synchronize()
+                        pinned[s][:b - a].copy_(torch.from_numpy(arr[a:b]))
+                        with torch.cuda.stream(side):
+                            if k >= 2:
+                                side.wait_event(encoded[s])
+                            staged[s][:b - a].copy_(pinned[s][:b - a], non_blocking=True)
+                            copied[s].record(side)
+                        main.wait_event(copied[s])
+                        L.check(L.lib().bf_field_stats(_p(staged[s]), _p(zero), _p(lens) + 8 * k, 1, _p(stats) + 32 * k, _p(ws), _stream()), "bf_field_stats")
+                        ops.clip_encode_q16(staged[s][:b - a], self.codes[ci, int(self.frame0[fi]) + a:int(self.frame0[fi]) + b], float(lo), float(inv))
+                        encoded[s].record(main)
+                        k += 1
+            st = stats.cpu().numpy()                                         # waits for the last encode
+            side.synchronize()
+        del staged, pinned
+        self._stats = np.zeros((nfield, nfile, 4), dtype=np.float64)
+        k = 0
+        for ci in range(nfield):
+            for fi in range(nfile):
+                acc = [0.0, 0.0, np.inf, -np.inf]
+                for _ in chunks[fi]:
+                    acc = [acc[0] + st[k, 0], acc[1] + st[k, 1], min(acc[2], st[k, 2]), max(acc[3], st[k, 3])]
+                    k += 1
+                self._stats[ci, fi] = acc
+        self._counts = np.asarray([[int(n) * px for n in ds.traj_lens] for _ in self.fields], dtype=np.float64)
+        self.frame_seg = torch.from_numpy(np.repeat(np.arange(nfile, dtype=np.int32), np.asarray(ds.traj_lens, dtype=np.int64))).to(self.device)
+        self.seg_lo, self.seg_step = torch.from_numpy(lo_tab).to(self.device), torch.from_numpy(step_tab).to(self.device)
+        self._tables()
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the store holds on the device: the codes, the frames' file numbers and the two segment tables."""
+        return sum(t.numel() * t.element_size() for t in (self.codes, self.frame_seg, self.seg_lo, self.seg_step))
+
+    def _segment_stats(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The statistics taken while the store was filled -- those of the original values, not of the decoded ones."""
+        return self._stats, self._counts
+
+    def to_fp32(self) -> DeviceClipStore:
+        """An ordinary ``DeviceClipStore`` over the decoded frames, filled by one decode launch: for small stores, rollout evaluation and tests."""
+        from .. import ops
+        return DeviceClipStore(self.ds, self.device, frames=ops.clip_decode_q16(self.codes, self.frame_seg, self.seg_lo, self.seg_step))
+
+    def _launch(self, idx, first_all, fl_files, unroll, augment, window, draw, ho, wo):
+        """One bf_clip_gather_q16 launch, whatever the call asks for."""
+        from .. import ops
+        aug = None
+        if augment is not None:
+            from ..utils.augment import flip_threshold
+            aug = (*self._odd_tables(augment.odd_fields), augment.seed, draw, flip_threshold(augment.flip_p), window[0], window[1], augment.crop_y == "random",
+                   augment.eval)
+        inp, out, fl = ops.clip_gather_q16(self.codes, self.frame_seg, self.seg_lo, self.seg_step, idx, first_all, self.ds.time_window,
+                                           1 if unroll is None else unroll, self.in_tab, self.out_tab, ho, wo, aug, self.fluid, fl_files)
+        return inp, (out[0] if unroll is None else out), fl

@@ -53,7 +53,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None, augment=None) -> Dict:
+        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None, augment=None, train_storage: str = "fp32") -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -92,6 +92,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     sees ``augment.eval_view()`` -- never mirrored, the window centred in x on the heater row -- so its clips have the training shape;
     without a crop validation is gathered plainly.  Panels show what validation saw.  Composes with ``unroll_steps``, ``input_noise``,
     accumulation and conditioning; None or an inactive spec: every call, history and parameter bit for bit as without it.
+    ``train_storage``: the form the TRAINING set is held in on the device, handed to ``train_set.device_store(dev, storage=...)``: "fp32", or
+    "q16" -- 16-bit codes decoded inside the gather's launch, half the resident bytes, every clip within the store's bound of the original
+    (data.Q16ClipStore); the training losses are bit for bit those of training on the decoded frames.  The validation store stays fp32:
+    validation losses are against exact targets.  ``hist["train_storage"]`` and the checkpoint's hyper-parameters record the value.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -104,7 +108,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         raise ValueError(f"unroll_steps = {k}: no sample of the training set has {k} target clips inside its own file")
     n_pool = len(train_set) if pool is None else len(pool)
     per_epoch = len(batches(epoch_indices(n_pool, 0, seed, True, rank, world), batch_size, limit_train_batches))
-    store = train_set.device_store(dev)
+    store = train_set.device_store(dev, storage=train_storage)
     vstore = val_set.device_store(dev) if val_set is not None else None
     steps_per_epoch = accumulation_plan(per_epoch, accumulate_grad_batches)[1]
     sched = CosineWarmupLR(lr, warmup_iters, max_epochs * steps_per_epoch, eta_min) if warmup_iters is not None else None
@@ -126,7 +130,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
                      unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std, weight_average=weight_average,
                      param_groups=param_groups)
     norm = (train_set.diff_terms, train_set.div_terms)
-    hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": []}
+    hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": [], "train_storage": store.storage}
     if step.grad_norm is not None:
         hist["grad_norm"] = []
     if step.group_grad_norm is not None:
@@ -191,7 +195,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             if log is not None:
                 log(entry)
         if checkpoint_path is not None and rank == 0:
-            save_checkpoint(checkpoint_path, model, hyper_parameters, norm, step, epoch=epoch)       # one atomic write
+            save_checkpoint(checkpoint_path, model, dict(hyper_parameters or {}, train_storage=store.storage), norm, step, epoch=epoch)       # one atomic write
     return hist
 
 

@@ -986,6 +986,76 @@ def clip_gather_augment(frames: torch.Tensor, idx: torch.Tensor, first_tab: torc
     return inp, out, fl
 
 
+def clip_encode_q16(src: torch.Tensor, dst: torch.Tensor, lo: float, inv: float) -> torch.Tensor:
+    """dst = the 16-bit codes of the contiguous fp32 ``src`` under one segment's (lo, inv) (bf_clip_encode_q16; csrc/clip_store_q16.hip
+    states the format): ``dst`` is a contiguous int16 tensor of src's element count holding the codes' bit patterns, typically a slice
+    of the store the chunk ``src`` belongs to.  One launch on the current stream."""
+    _require_gpu(src)
+    if src.dtype != torch.float32 or dst.dtype != torch.int16 or not src.is_contiguous() or not dst.is_contiguous() or src.numel() != dst.numel() or dst.device != src.device:
+        raise L.BubbleformerHipError("clip_encode_q16: src must be contiguous fp32 and dst contiguous int16 of the same size on the same device")
+    L.check(L.lib().bf_clip_encode_q16(_p(src), _p(dst), src.numel(), float(lo), float(inv), _stream()), "bf_clip_encode_q16")
+    return dst
+
+
+def _q16_tables(who: str, codes: torch.Tensor, frame_seg: torch.Tensor, seg_lo: torch.Tensor, seg_step: torch.Tensor) -> int:
+    """The checks the two readers of a 16-bit store share: codes [fields][frames][H][W] int16, frame_seg [frames] int32, seg_lo / seg_step
+    [fields][files] fp32 -> the file count."""
+    _require_gpu(codes)
+    if codes.dim() != 4 or codes.dtype != torch.int16 or not codes.is_contiguous():
+        raise L.BubbleformerHipError(f"{who}: codes must be a contiguous int16 tensor [fields][frames][H][W]")
+    nf, total = codes.shape[:2]
+    if seg_lo.dim() != 2 or seg_lo.shape[0] != nf:
+        raise L.BubbleformerHipError(f"{who}: seg_lo must be [fields][files]")
+    shape = tuple(seg_lo.shape)
+    _check_tensors(who, codes.device, {"frame_seg": (frame_seg, (total,), torch.int32), "seg_lo": (seg_lo, shape, torch.float32), "seg_step": (seg_step, shape, torch.float32)})
+    return shape[1]
+
+
+def clip_decode_q16(codes: torch.Tensor, frame_seg: torch.Tensor, seg_lo: torch.Tensor, seg_step: torch.Tensor) -> torch.Tensor:
+    """The fp32 frames [fields][frames][H][W] a 16-bit store decodes to, one launch (bf_clip_decode_q16)."""
+    nfiles = _q16_tables("clip_decode_q16", codes, frame_seg, seg_lo, seg_step)
+    nf, total, H, W = codes.shape
+    out = torch.empty((nf, total, H, W), dtype=torch.float32, device=codes.device)
+    L.check(L.lib().bf_clip_decode_q16(_p(codes), total * H * W, _p(frame_seg), _p(seg_lo), _p(seg_step), _p(out), total, nf, nfiles, H, W, _stream()),
+            "bf_clip_decode_q16")
+    return out
+
+
+def clip_gather_q16(codes: torch.Tensor, frame_seg: torch.Tensor, seg_lo: torch.Tensor, seg_step: torch.Tensor, idx: torch.Tensor, first_tab: torch.Tensor,
+                    T: int, unroll: int, in_table, out_table, Ho: int, Wo: int, augment: Optional[tuple] = None, fluid_tab: Optional[torch.Tensor] = None,
+                    file_tab: Optional[torch.Tensor] = None):
+    """clip_gather_unroll / clip_gather_augment on a 16-bit store, decoding inside the one launch (bf_clip_gather_q16): -> input clips
+    (B, T, Cin, Hc, Wc), target clips (unroll, B, T, Cout, Hc, Wc) and the fluid rows, bit for bit what those give on
+    ``clip_decode_q16(codes, ...)``.  ``augment``: None -- the whole Ho x Wo grid, nothing mirrored -- or clip_gather_augment's
+    ``(in_odd, out_odd, seed, draw, flip_thr, Hc, Wc, random_y, eval_view)`` under its conventions."""
+    nfiles = _q16_tables("clip_gather_q16", codes, frame_seg, seg_lo, seg_step)
+    (iid, idf, idv), (oid, odf, odv) = in_table, out_table
+    nf, total, H, W = codes.shape
+    B = idx.numel()
+    if int(unroll) != unroll or unroll < 1:
+        raise ValueError(f"clip_gather_q16: unroll {unroll!r} must be an integer >= 1")
+    Hc, Wc, aug = Ho, Wo, None
+    if augment is not None:
+        in_odd, out_odd, seed, draw, flip_thr, Hc, Wc, random_y, eval_view = augment
+        if not (1 <= int(Hc) <= Ho and 1 <= int(Wc) <= Wo):
+            raise ValueError(f"clip_gather_q16: the window {(Hc, Wc)} must lie inside the output grid {(Ho, Wo)}")
+        _check_tensors("clip_gather_q16", codes.device, {"in_odd": (in_odd, (iid.numel(),), torch.int32), "out_odd": (out_odd, (oid.numel(),), torch.int32)})
+        signed = lambda v, bits: (v & (2 ** bits - 1)) - (2 ** bits if v & 2 ** (bits - 1) else 0)      # noqa: E731  (the record's signed bit patterns)
+        aug = L.ClipAugment(in_odd=_p(in_odd), out_odd=_p(out_odd), seed=signed(int(seed), 64), flip_thr=int(flip_thr), draw=signed(int(draw), 32), Hc=int(Hc),
+                            Wc=int(Wc), crop_y=int(bool(random_y)), eval_view=int(bool(eval_view)))
+    inp = torch.empty((B, T, iid.numel(), Hc, Wc), dtype=torch.float32, device=codes.device)
+    out = torch.empty((int(unroll), B, T, oid.numel(), Hc, Wc), dtype=torch.float32, device=codes.device)
+    P = int(fluid_tab.shape[1]) if fluid_tab is not None else 0
+    fl = torch.empty((B, P), dtype=torch.float32, device=codes.device) if fluid_tab is not None else None
+    job = L.ClipGatherQ16Job(codes=_p(codes), frame_seg=_p(frame_seg), seg_lo=_p(seg_lo), seg_step=_p(seg_step), idx=_p(idx), first_tab=_p(first_tab),
+                             in_field=_p(iid), in_diff=_p(idf), in_div=_p(idv), in_out=_p(inp), out_field=_p(oid), out_diff=_p(odf), out_div=_p(odv),
+                             out_out=_p(out), fluid_tab=_p(fluid_tab) if fl is not None else None, file_tab=_p(file_tab) if fl is not None else None,
+                             fluid_out=_p(fl) if fl is not None else None, field_stride=total * H * W, nframes=total, nsamples=first_tab.numel(),
+                             nfiles=nfiles, Cin=iid.numel(), Tin=T, Cout=oid.numel(), Tout=T, unroll=int(unroll), P=P, B=B, H=H, W=W, Ho=Ho, Wo=Wo)
+    L.check(L.lib().bf_clip_gather_q16(C.byref(job), C.byref(aug) if aug is not None else None, _stream()), "bf_clip_gather_q16")
+    return inp, out, fl
+
+
 def clip_noise(src: torch.Tensor, sigma: torch.Tensor, sample_ids: Optional[torch.Tensor], draw: int, pass_index: int, seed: int,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = src + sigma[c] * z on contiguous fp32 clips (B, T, C, H, W), z the seeded normals of bf_clip_noise (csrc/noise.hip): a pure

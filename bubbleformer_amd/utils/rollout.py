@@ -326,6 +326,16 @@ def _to_device(values, dtype, device) -> torch.Tensor:
     return host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host.to(device)
 
 
+def _frames_store(data, device):
+    """``data`` as the store whose fp32 frames the rollout kernels read where they lie: a DeviceClipStore, or a dataset's.  A store in
+    another storage form is refused -- its ``to_fp32()`` is what to pass."""
+    from ..data.dataset import DeviceClipStore
+    store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
+    if store.storage != "fp32":
+        raise ValueError(f"rollout evaluation reads stored fp32 frames inside its kernels and this store's storage is {store.storage!r}: pass store.to_fp32()")
+    return store
+
+
 def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_graph: bool = True, sdf_field: Optional[str] = "dfun",
                       keep_predictions: bool = False, heatflux: "Optional[HeaterSpec]" = None,  # noqa: F821 (physics.HeaterSpec)
                       bubbles: "Optional[BubbleSpec]" = None,  # noqa: F821 (physics.BubbleSpec)
@@ -384,9 +394,8 @@ def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True
                        errors=None, ensemble=None) -> RolloutReport:
     """The one implementation behind ``evaluate_rollouts`` (redistance = None) and ``evaluate_rollouts_redistanced``."""
     from .. import ops
-    from ..data.dataset import DeviceClipStore
     device = next(model.parameters()).device
-    store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
+    store = _frames_store(data, device)
     ds = store.ds
     members = None
     if ensemble is not None:
@@ -551,12 +560,11 @@ def render_rollouts(report: RolloutReport, data, starts: Sequence[int], save_dir
     Keyword arguments go to ``plot_bubbleml``; the channels follow the report's field names unless given.  Returns {b: its result}."""
     import os
     from .. import ops
-    from ..data.dataset import DeviceClipStore
     from .plot_utils import plot_bubbleml
     if report.predictions is None:
         raise ValueError("this report kept no predictions: call evaluate_rollouts(..., keep_predictions=True)")
     device = report.predictions.device
-    store = data if isinstance(data, DeviceClipStore) else data.device_store(device)
+    store = _frames_store(data, device)
     B, frames, _, Ho, Wo = report.predictions.shape
     T = int(store.ds.time_window)
     plan = plan_rollouts(store.ds, starts, frames // T)

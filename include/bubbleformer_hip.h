@@ -393,6 +393,38 @@ typedef struct bf_clip_augment {
     int32_t draw, Hc, Wc, crop_y, eval_view, reserved;
 } bf_clip_augment;
 int bf_clip_gather_augment(const bf_clip_gather_job* job, const bf_clip_augment* augment, bf_stream_t stream);
+/* The 16-bit form of the store (csrc/clip_store_q16.hip states the format): codes [fields][frames][H][W] of 16 bits,
+ * one affine scale per SEGMENT = all frames of one field of one file, tables indexed field * nfiles + file.  Per segment lo / hi = the exact
+ * fp32 minimum / maximum, step = fp32(((double)hi - (double)lo) / 65535.0), inv = fp32(65535.0 / ((double)hi - (double)lo)), both 0 when
+ * hi == lo.  code = clamp(rintf((x - lo) * inv), 0, 65535) and x^ = fp32(fp32((float)code * step) + lo), every operation rounded on its
+ * own (no fma): np.float32 arithmetic gives the same bits.  |x^ - x| <= 0.53 step + 2^-24 max(|lo|, |hi|); a constant segment and lo decode
+ * exactly; a value closer to zero than step / 2 may change sign.
+ * bf_clip_encode_q16: dst[i] = code(src[i]) for the n values of one staged chunk of one segment (src 4-byte, dst 2-byte aligned; 16-byte
+ *   loads and 8-byte stores when src is 16-byte and dst 8-byte aligned, scalar otherwise and for the last n % 4 values).
+ * bf_clip_decode_q16: dst [nfields][nframes][H][W] fp32, contiguous, = the decoded store, one launch; frame_seg [nframes] int32 = the file
+ *   of every frame of the store's frame axis (held into 0 .. nfiles - 1), seg_lo / seg_step [nfields * nfiles] fp32, all on the DEVICE.
+ * bf_clip_gather_q16: ONE launch for what bf_clip_gather_batch, bf_clip_gather_unroll and bf_clip_gather_augment give on the decoded store,
+ *   bit for bit: x^ takes the stored value's place in their expressions (the mirror's sign goes on x^, then (.. - diff) / div).  The job is
+ *   bf_clip_gather_job's members (unroll >= 1) with `codes`, the three tables of bf_clip_decode_q16 and nfiles in front of them; augment may
+ *   be NULL: the whole Ho x Wo grid, no mirror, in_out (B, Tin, Cin, Ho, Wo), out_out (unroll, B, Tout, Cout, Ho, Wo).  The scale of a value
+ *   is that of the frame actually read (frame_seg of the clamped frame number), not of the sample's file.  Requires what
+ *   bf_clip_gather_augment requires of its records (the codes in src's place: 2-byte aligned, and 8-byte aligned with field_stride a
+ *   multiple of 4 when Ho x Wo = H x W and W and the window's width are multiples of 4: rows are then read four codes at a time wherever a
+ *   sample's x0 is a multiple of 4, scalar otherwise); a null job or required member is refused as "bf_clip_gather_q16: null pointer", and
+ *   every check is made before any HIP call.  No LDS, no atomics, no workspace; capturable; two calls give the same bits. */
+typedef struct bf_clip_gather_q16_job {
+    const uint16_t* codes; const int32_t* frame_seg; const float *seg_lo, *seg_step;
+    const int64_t *idx, *first_tab;
+    const int32_t* in_field; const float *in_diff, *in_div; float* in_out;
+    const int32_t* out_field; const float *out_diff, *out_div; float* out_out;
+    const float* fluid_tab; const int64_t* file_tab; float* fluid_out;
+    int64_t field_stride, nframes, nsamples;
+    int32_t nfiles, Cin, Tin, Cout, Tout, unroll, P, B, H, W, Ho, Wo;
+} bf_clip_gather_q16_job;
+int bf_clip_encode_q16(const float* src, uint16_t* dst, int64_t n, float lo, float inv, bf_stream_t stream);
+int bf_clip_decode_q16(const uint16_t* codes, int64_t field_stride, const int32_t* frame_seg, const float* seg_lo, const float* seg_step, float* dst,
+                       int64_t nframes, int nfields, int nfiles, int H, int W, bf_stream_t stream);
+int bf_clip_gather_q16(const bf_clip_gather_q16_job* job, const bf_clip_augment* augment, bf_stream_t stream);
 /* Seeded Gaussian noise on a batch of clips (csrc/noise.hip): dst[b][t][c][y][x] = fmaf(sigma[c], z, src[b][t][c][y][x]) on contiguous fp32
  * (B, T, C, H, W); an element of a channel with sigma[c] == 0 is handed back bit for bit.  dst == src (in place) or two buffers that do not
  * overlap.  z is a pure function of (seed, sample id, draw, pass, element index e inside the sample's flattened (T, C, H, W) clip):
