@@ -107,9 +107,9 @@ class EnsembleRows(C.Structure):
 
 
 class OptStep(C.Structure):
-    """bf_opt_step: one fused optimizer step -- buffers, clip coefficient, average, parameter groups, sizes, scalars (read during the call only)."""
+    """bf_opt_step: one fused optimizer step -- buffers, clip coefficient, average, parameter groups, guard flag, sizes, scalars (read during the call only)."""
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("coef_dev", fp), ("avg", fp), ("chunk_group", vp), ("group_lr_scale", fp),
-                ("group_weight_decay", fp), ("group_frozen", vp), ("n", i64), ("step", i32), ("n_groups", i32)] + [
+                ("group_weight_decay", fp), ("group_frozen", vp), ("live_dev", vp), ("n", i64), ("step", i32), ("n_groups", i32)] + [
         (n, f32) for n in ("lr", "beta1", "beta2", "eps", "wd", "gscale", "clip_value", "avg_weight")]
 
 
@@ -231,6 +231,9 @@ SIGNATURES = {
     "bf_group_sumsq_ws_doubles": (i64, [i64]),
     "bf_group_sumsq": (C.c_int, [fp, i64, vp, C.c_int, vp, vp, i64, vp]),
     "bf_group_clip_coef": (C.c_int, [vp, vp, C.c_int, f32, f32, fp, fp, vp]),
+    "bf_step_guard": (C.c_int, [fp, i32, vp, vp]),
+    "bf_nonfinite_scan_ws_len": (i64, [i64]),
+    "bf_nonfinite_scan": (C.c_int, [fp, i64, vp, vp, i64, vp]),
     "bf_eikonal_sum": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, vp, vp]),
     "bf_eikonal_l1_frames": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, vp]),
     "bf_heatflux_rows": (C.c_int, [fp, fp, i64, i64, C.c_int, f32, f32, f32, f32, fp, vp]),

@@ -8,6 +8,9 @@
 //                                               selects the learning-rate scale, the weight decay and a frozen flag (parameter groups)
 //   bf_weight_average / bf_swap_buffers      -> the average's update alone; two flat buffers exchanged
 //   bf_group_sumsq / bf_group_clip_coef      -> the norm above per group, and over the groups that are not frozen
+//   bf_step_guard                            -> whether that norm is finite, as a flag in device memory the optimizers' live_dev reads (a step on
+//                                               a non-finite gradient is skipped on the device), with the skip counters beside it
+//   bf_nonfinite_scan                        -> where a buffer's first inf / NaN is and how many it holds (the diagnostic, outside the step)
 //
 // The norm is a fixed-order reduction: no float atomics, and nothing in its order depends on the device.
 //   pass 1  the buffer's G = n / 4 16-byte groups are cut into slabs of gn_slab_groups(G) groups -- a function of n alone.  Workgroup s
@@ -185,6 +188,85 @@ __global__ void __launch_bounds__(BF_OPT_MAX_GROUPS) group_clip_coef_kernel(cons
         out[1] = c > 1.f ? 1.f : c;                      // a NaN norm stays a NaN coefficient (torch.clamp)
     }
 }
+
+// ---------------------------------------------------------------------------- the step guard and the non-finite scan
+// guard = {live, consecutive, skipped, last_skipped_step}; one lane, plain stores
+__global__ void step_guard_kernel(const float* __restrict__ norm, int step, int32_t* __restrict__ guard) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool live = (__float_as_uint(norm[0]) & 0x7f800000u) != 0x7f800000u;      // isfinite, whatever the floating-point flags of the build
+    guard[0] = live ? 1 : 0;
+    if (live) {
+        guard[1] = 0;
+    } else {
+        guard[1] = guard[1] + 1;
+        guard[2] = guard[2] + 1;
+        guard[3] = step;
+    }
+}
+
+constexpr long long NF_NONE = 0x7fffffffffffffffLL;      // no non-finite element seen
+// {minimum, sum} over the workgroup, valid in thread 0; integers, so any order gives the same result
+__device__ __forceinline__ void nf_block_reduce(long long& first, long long& count, long long (*red)[2]) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long f = __shfl_xor(first, o, 64), c = __shfl_xor(count, o, 64);
+        first = f < first ? f : first;
+        count += c;
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = first; red[threadIdx.x >> 6][1] = count; }
+    __syncthreads();
+    first = red[0][0]; count = red[0][1];
+#pragma unroll
+    for (int w = 1; w < GN_NT / 64; ++w) {
+        first = red[w][0] < first ? red[w][0] : first;
+        count += red[w][1];
+    }
+}
+__device__ __forceinline__ void nf_take(float x, long e, long long& first, long long& count) {
+    if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) {
+        first = e < first ? e : first;
+        ++count;
+    }
+}
+
+// slab s of grad_sumsq_kernel's cut: part[2 s] = the slab's smallest non-finite index (NF_NONE: none), part[2 s + 1] = how many it holds
+__global__ void __launch_bounds__(GN_NT) nonfinite_slab_kernel(const float* __restrict__ x, long n, long slab_groups, long long* __restrict__ part) {
+    __shared__ long long red[GN_NT / 64][2];
+    const long G = n / 4;
+    const long g0 = (long)blockIdx.x * slab_groups, g1 = min(G, g0 + slab_groups);
+    const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+    long long first = NF_NONE, count = 0;
+    for (long i = g0 + threadIdx.x; i < g1; i += GN_NT) {
+        const float4 q = x4[i];
+        nf_take(q.x, 4 * i, first, count); nf_take(q.y, 4 * i + 1, first, count);
+        nf_take(q.z, 4 * i + 2, first, count); nf_take(q.w, 4 * i + 3, first, count);
+    }
+    nf_block_reduce(first, count, red);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == gridDim.x - 1)
+            for (long k = G * 4; k < n; ++k) nf_take(x[k], k, first, count);
+        part[2 * blockIdx.x] = first;
+        part[2 * blockIdx.x + 1] = count;
+    }
+}
+
+__global__ void __launch_bounds__(GN_NT) nonfinite_finish_kernel(const long long* __restrict__ part, int nslabs, long long* __restrict__ out) {
+    __shared__ long long red[GN_NT / 64][2];
+    long long first = NF_NONE, count = 0;
+#pragma unroll
+    for (int k = 0; k < GN_MAX_SLABS / GN_NT; ++k) {
+        const int s = threadIdx.x * (GN_MAX_SLABS / GN_NT) + k;
+        if (s < nslabs) {
+            first = part[2 * s] < first ? part[2 * s] : first;
+            count += part[2 * s + 1];
+        }
+    }
+    nf_block_reduce(first, count, red);
+    if (threadIdx.x == 0) {
+        out[0] = first == NF_NONE ? -1 : first;
+        out[1] = count;
+    }
+}
 }  // namespace
 
 extern "C" int64_t bf_grad_norm_ws_doubles(int64_t n) { return n > 0 ? gn_slabs((long)(n / 4)) : 0; }
@@ -208,7 +290,7 @@ extern "C" int bf_grad_norm(const float* g, int64_t n, float gscale, float max_n
 
 // ---------------------------------------------------------------------------- the optimizers
 // The one checked path of bf_adamw / bf_adam / bf_lion: every check of the record, each under the calling entry's name and before any HIP
-// call, then the instantiation by one rule -- GRP when there is a chunk map, AVG when there is an average, and MODE = the clamp when
+// call, then the instantiation by one rule -- GRP when there is a chunk map, AVG when there is an average, GUARD when there is a guard flag, and MODE = the clamp when
 // clip_value is finite (+inf = no clamp: the other two have no clamp code at all), else the device coefficient when there is one, else the
 // host scale (whose bits a coefficient of 1 would give).
 #define BF_OPT_REQUIRE(who, cond, what)                                  \
@@ -237,8 +319,9 @@ static int opt_step(int rule, const char* who, const bf_opt_step* s, bf_stream_t
         BF_OPT_REQUIRE(who, s->n_groups >= 1 && s->n_groups <= BF_OPT_MAX_GROUPS, "n_groups must be 1 .. 64");
         BF_OPT_REQUIRE(who, (uintptr_t)s->group_lr_scale % 4 == 0 && (uintptr_t)s->group_weight_decay % 4 == 0, "the group tables must be 4-byte aligned");
     }
+    BF_OPT_REQUIRE(who, (uintptr_t)s->live_dev % 4 == 0, "the guard flag must be 4-byte aligned");
     const int mode = !isinf(s->clip_value) ? BF_OPT_DEV_CLAMP : (s->coef_dev ? BF_OPT_DEV : BF_OPT_HOST);
-    return opt_launch_table[mode][s->avg != nullptr][s->chunk_group != nullptr](rule, *s, (hipStream_t)stream);
+    return opt_launch_table[mode][s->avg != nullptr][s->chunk_group != nullptr][s->live_dev != nullptr](rule, *s, (hipStream_t)stream);
 }
 #undef BF_OPT_REQUIRE
 
@@ -292,6 +375,32 @@ extern "C" int bf_group_clip_coef(const double* sums, const uint8_t* frozen, int
     BF_REQUIRE(max_norm > 0.f, "bf_group_clip_coef: max_norm must be positive");
     hipLaunchKernelGGL(group_clip_coef_kernel, dim3(1), dim3(BF_OPT_MAX_GROUPS), 0, (hipStream_t)stream, sums, frozen, n_groups, gscale, max_norm, out,
                        group_norm);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bf_step_guard(const float* norm, int32_t step, int32_t* guard, bf_stream_t stream) {
+    BF_REQUIRE(norm && guard, "bf_step_guard: null pointer");
+    BF_REQUIRE((uintptr_t)norm % 4 == 0 && (uintptr_t)guard % 4 == 0, "bf_step_guard: the norm and the guard record must be 4-byte aligned");
+    hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, norm, (int)step, guard);
+    BF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t bf_nonfinite_scan_ws_len(int64_t n) { return n > 0 ? 2 * (int64_t)gn_slabs((long)(n / 4)) : 0; }
+
+extern "C" int bf_nonfinite_scan(const float* x, int64_t n, int64_t* out, int64_t* ws, int64_t ws_len, bf_stream_t stream) {
+    BF_REQUIRE(x && out, "bf_nonfinite_scan: null pointer");
+    BF_REQUIRE(n > 0, "bf_nonfinite_scan: n must be positive");
+    BF_REQUIRE(BF_OPT_ALIGNED(x) && (uintptr_t)out % 8 == 0, "bf_nonfinite_scan: the buffer must be 16-byte aligned and the output 8-byte aligned");
+    const long G = (long)(n / 4);
+    const int nslabs = gn_slabs(G);
+    BF_REQUIRE(ws && ws_len >= 2 * (int64_t)nslabs && (uintptr_t)ws % 8 == 0, "bf_nonfinite_scan: the workspace is smaller than bf_nonfinite_scan_ws_len(n)");
+    static_assert(sizeof(long long) == sizeof(int64_t), "the kernels' long long is the ABI's int64_t");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nonfinite_slab_kernel, dim3(nslabs), dim3(GN_NT), 0, st, x, (long)n, gn_slab_groups(G), reinterpret_cast<long long*>(ws));
+    BF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nonfinite_finish_kernel, dim3(1), dim3(GN_NT), 0, st, reinterpret_cast<const long long*>(ws), nslabs, reinterpret_cast<long long*>(out));
     BF_CHECK_LAUNCH();
     return 0;
 }

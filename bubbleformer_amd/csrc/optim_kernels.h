@@ -1,4 +1,4 @@
-// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates <MODE, AVG, GRP>, behind one entry point each in gradclip.hip
+// The fused flat-buffer optimizers (AdamW, Adam, Lion) as kernel templates <MODE, AVG, GRP, GUARD>, behind one entry point each in gradclip.hip
 // (bf_adamw / bf_adam / bf_lion, which take a bf_opt_step record and choose the instantiation by one rule: opt_step there).
 //   MODE  where the gradient scale comes from (read once per thread, before the loop), and one clamp on the scaled gradient:
 //           BF_OPT_HOST       a host float, gscale
@@ -12,7 +12,10 @@
 //         frozen flag replace the launch's lr and wd for that chunk (opt_group_table / opt_group_of).  A 16-byte access never straddles a
 //         chunk, the 16 lanes that share a chunk share the lookup, and a frozen chunk is skipped by those 16 lanes together: the live chunks
 //         keep their 256-byte runs.  GRP = false has no trace of it either.
-// One body per optimizer; all 3 x 3 x 2 x 2 instantiations exist (opt_launch_table).
+//   GUARD the launch first reads one int32 in device memory (bf_step_guard's `live`) and, where that is 0, returns before it reads or writes
+//         anything else: the step is skipped on the device, with no host round trip.  The flag is uniform, so every workgroup leaves
+//         together, ahead of the group table's barrier.  GUARD = false: an empty record, nothing is passed or read.
+// One body per optimizer; all 3 x 3 x 2 x 2 x 2 instantiations exist (opt_launch_table).
 #pragma once
 #include <algorithm>
 
@@ -96,12 +99,22 @@ __device__ __forceinline__ void opt_group_table(float2* tab, const opt_groups<tr
         if (i1 < n4) id_next = G.chunk[i1 / BF_OPT_CHUNK4];    \
     }
 
+// ---------------------------------------------------------------------------- the step guard
+template <bool GUARD> struct opt_guard {};
+template <> struct opt_guard<true> { const int32_t* live; };
+#define BF_OPT_GUARD()                                         \
+    if constexpr (GUARD) {                                     \
+        if (L.live[0] == 0) return;                            \
+    }
+
 // ---------------------------------------------------------------------------- AdamW (torch.optim.AdamW semantics)
-template <int MODE, bool AVG, bool GRP>
+template <int MODE, bool AVG, bool GRP, bool GUARD>
 __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
+                                                         float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G,
+                                                         const opt_guard<GUARD> L) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GUARD()
     BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -144,11 +157,13 @@ __global__ void __launch_bounds__(BF_OPT_NT) adamw_kernel(float* __restrict__ p,
 // ---------------------------------------------------------------------------- Adam (torch.optim.Adam semantics, single-tensor path)
 // Weight decay is an L2 term on the gradient (g += wd*p), so it passes through both moments; AdamW above decays the parameter instead.
 // Zero padding stays zero: p = g = m = v = 0 gives m / (sqrt(v) / sqrt_bc2 + eps) = 0.
-template <int MODE, bool AVG, bool GRP>
+template <int MODE, bool AVG, bool GRP, bool GUARD>
 __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
+                                                        float bc1, float sqrt_bc2, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G,
+                                                         const opt_guard<GUARD> L) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GUARD()
     BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -192,10 +207,12 @@ __global__ void __launch_bounds__(BF_OPT_NT) adam_kernel(float* __restrict__ p, 
 // ---------------------------------------------------------------------------- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization
 // Algorithms"; the update lion_pytorch.Lion applies at bubbleformer/modules.py:139-140):
 //   p *= 1 - lr*wd;  p -= lr * sign(b1*m + (1-b1)*g);  m = b2*m + (1-b2)*g
-template <int MODE, bool AVG, bool GRP>
+template <int MODE, bool AVG, bool GRP, bool GUARD>
 __global__ void __launch_bounds__(BF_OPT_NT) lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n, float lr,
-                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G) {
+                                                        float b1, float b2, float wd, float gscale, const float* __restrict__ coef, float clip, float* __restrict__ a, float w, const opt_groups<GRP> G,
+                                                         const opt_guard<GUARD> L) {
     constexpr int NT = BF_OPT_NT;
+    BF_OPT_GUARD()
     BF_OPT_GROUP_TABLE()
     const float gs = opt_scale<MODE>(gscale, coef);
     const long n4 = n / 4;
@@ -265,32 +282,36 @@ enum { BF_OPT_ADAMW = 0, BF_OPT_ADAM = 1, BF_OPT_LION = 2 };      // the update 
 
 // the launch of one checked step (gradclip.hip: opt_step).  Without groups the kernel gets the record's wd, with them 0 (every group brings
 // its own); without an average it gets a = nullptr, w = 0.
-template <int MODE, bool AVG, bool GRP>
+template <int MODE, bool AVG, bool GRP, bool GUARD>
 int opt_launch(int rule, const bf_opt_step& s, hipStream_t st) {
     opt_groups<GRP> G;
     if constexpr (GRP) G = {s.chunk_group, s.group_lr_scale, s.group_weight_decay, s.group_frozen, s.n_groups};
+    opt_guard<GUARD> L;
+    if constexpr (GUARD) L = {s.live_dev};
     const float wd = GRP ? 0.f : s.wd, w = AVG ? s.avg_weight : 0.f;
     float* a = AVG ? s.avg : nullptr;
     const dim3 grid(opt_grid_for(s.n)), block(BF_OPT_NT);
     if (rule == BF_OPT_LION) {
-        hipLaunchKernelGGL((lion_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, (long)s.n, s.lr, s.beta1, s.beta2, wd, s.gscale, s.coef_dev,
-                           s.clip_value, a, w, G);
+        hipLaunchKernelGGL((lion_kernel<MODE, AVG, GRP, GUARD>), grid, block, 0, st, s.p, s.g, s.m, (long)s.n, s.lr, s.beta1, s.beta2, wd, s.gscale, s.coef_dev,
+                           s.clip_value, a, w, G, L);
     } else {
         const float bc1 = 1.f - powf(s.beta1, (float)s.step);
         const float sbc2 = sqrtf(1.f - powf(s.beta2, (float)s.step));
         if (rule == BF_OPT_ADAMW)
-            hipLaunchKernelGGL((adamw_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
-                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G);
+            hipLaunchKernelGGL((adamw_kernel<MODE, AVG, GRP, GUARD>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
+                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G, L);
         else
-            hipLaunchKernelGGL((adam_kernel<MODE, AVG, GRP>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
-                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G);
+            hipLaunchKernelGGL((adam_kernel<MODE, AVG, GRP, GUARD>), grid, block, 0, st, s.p, s.g, s.m, s.v, (long)s.n, s.lr, s.beta1, s.beta2, s.eps, wd, bc1,
+                               sbc2, s.gscale, s.coef_dev, s.clip_value, a, w, G, L);
     }
     BF_CHECK_LAUNCH();
     return 0;
 }
-// [MODE][AVG][GRP]: every instantiation, named once
-#define BF_OPT_ROW(MODE) {{opt_launch<MODE, false, false>, opt_launch<MODE, false, true>}, {opt_launch<MODE, true, false>, opt_launch<MODE, true, true>}}
-constexpr int (*opt_launch_table[3][2][2])(int, const bf_opt_step&, hipStream_t) = {BF_OPT_ROW(BF_OPT_HOST), BF_OPT_ROW(BF_OPT_DEV),
-                                                                                    BF_OPT_ROW(BF_OPT_DEV_CLAMP)};
+// [MODE][AVG][GRP][GUARD]: every instantiation, named once
+#define BF_OPT_PAIR(MODE, AVG, GRP) {opt_launch<MODE, AVG, GRP, false>, opt_launch<MODE, AVG, GRP, true>}
+#define BF_OPT_ROW(MODE) {{BF_OPT_PAIR(MODE, false, false), BF_OPT_PAIR(MODE, false, true)}, {BF_OPT_PAIR(MODE, true, false), BF_OPT_PAIR(MODE, true, true)}}
+constexpr int (*opt_launch_table[3][2][2][2])(int, const bf_opt_step&, hipStream_t) = {BF_OPT_ROW(BF_OPT_HOST), BF_OPT_ROW(BF_OPT_DEV),
+                                                                                       BF_OPT_ROW(BF_OPT_DEV_CLAMP)};
 #undef BF_OPT_ROW
+#undef BF_OPT_PAIR
 }  // namespace

@@ -53,7 +53,8 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         resume_from: Optional[str] = None, hyper_parameters: Optional[dict] = None, log: Optional[Callable[[Dict], None]] = None,
         criterion: Optional[Callable] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
         accumulate_grad_batches: int = 1, panel_dir: Optional[str] = None, unroll_steps: int = 1, unroll_weights=None,
-        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None, augment=None, train_storage: str = "fp32") -> Dict:
+        unroll_backprop: bool = True, input_noise=None, weight_average=None, param_groups=None, augment=None, train_storage: str = "fp32",
+        step_guard=None) -> Dict:
     """Trains `model` (a bubbleformer_amd model on the GPU) on `train_set` (data.BubbleForecast, already normalised).  Defaults are the
     reference's: Lion lr 5e-5 wd 0.1 (config/optim_cfg/lion.yaml), cosine schedule with 1000 warm-up steps to 1e-6
     (config/scheduler_cfg/cosine_warmup.yaml).  ``optimizer="adamw"`` / ``"adam"`` are the reference's other choices
@@ -96,6 +97,14 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     "q16" -- 16-bit codes decoded inside the gather's launch, half the resident bytes, every clip within the store's bound of the original
     (data.Q16ClipStore); the training losses are bit for bit those of training on the decoded frames.  The validation store stays fp32:
     validation losses are against exact targets.  ``hist["train_storage"]`` and the checkpoint's hyper-parameters record the value.
+    ``step_guard``: a utils.guard.GuardSpec -- an optimizer step whose gradient is not finite is skipped on the device (TrainStep).
+    ``hist["skipped"]`` holds one 0 / 1 per optimizer step, kept as ``grad_norm`` is (a device scalar cloned per step, read at the end of the
+    epoch), ``hist["guard_norm"]`` the guard's own gradient norm of every optimizer step where there is no clipping by norm, and the `log`
+    dict of a batch that stepped carries ``live`` (1 = taken) as a device scalar.  ``epoch_train_loss`` is then the mean over the batches
+    whose loss is finite.  Where the epoch synchronises anyway fit reads the counters, and raises FloatingPointError carrying
+    ``step.diagnose()`` when the run ends the epoch in a streak of ``max_consecutive`` or more skipped steps -- before validation and before
+    the checkpoint is written, so no file is written during such a streak.  Checkpoints carry the count of skipped steps and a resumed
+    run continues it.  None: every call, history key and parameter bit for bit as without it.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -128,7 +137,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
                      gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm,
                      accumulate_grad_batches=accumulate_grad_batches, unroll_steps=unroll_steps, unroll_weights=unroll_weights,
                      unroll_backprop=unroll_backprop, input_noise=input_noise, field_std=field_std, weight_average=weight_average,
-                     param_groups=param_groups)
+                     param_groups=param_groups, step_guard=step_guard)
     norm = (train_set.diff_terms, train_set.div_terms)
     hist: Dict[str, list] = {"train_loss": [], "lr": [], "val_loss": [], "epoch_train_loss": [], "train_storage": store.storage}
     if step.grad_norm is not None:
@@ -137,6 +146,10 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         hist["group_grad_norm"] = []
     if k > 1:
         hist["unroll_loss"] = []
+    if step.guard is not None:
+        hist["skipped"] = []
+        if step.guard_norm is not None:
+            hist["guard_norm"] = []
     if step.avg is not None and vstore is not None:
         hist["val_loss_avg"] = []
     first_epoch = 0
@@ -146,7 +159,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(steps_per_epoch, 1)
     for epoch in range(first_epoch, max_epochs):
         model.train()
-        losses, norms, gnorms, per_pass = [], [], [], []
+        losses, norms, gnorms, per_pass, lives, wnorms = [], [], [], [], [], []
         order = epoch_indices(n_pool, epoch, seed, True, rank, world)
         todo = batches(order if pool is None else [pool[i] for i in order], batch_size, limit_train_batches)
         for bi, idx in enumerate(todo):
@@ -171,6 +184,11 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
                 if step.group_grad_norm is not None:
                     gnorms.append(step.group_grad_norm.clone())
                     entry["group_grad_norm"] = gnorms[-1]
+            if step.guard is not None and step.step_no != before:
+                lives.append(step.guard[0].clone())          # the next step overwrites the record
+                entry["live"] = lives[-1]
+                if step.guard_norm is not None:
+                    wnorms.append(step.guard_norm[0].clone())
             if log is not None:
                 log(entry)
         ep = torch.stack(losses).float()
@@ -181,7 +199,16 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             hist["group_grad_norm"].extend(torch.stack(gnorms).tolist())
         if per_pass:
             hist["unroll_loss"].extend(torch.stack(per_pass).tolist())
-        hist["epoch_train_loss"].append(float(ep.mean()))
+        if lives:
+            hist["skipped"].extend((1 - torch.stack(lives)).tolist())
+        if wnorms:
+            hist["guard_norm"].extend(torch.stack(wnorms).tolist())
+        hist["epoch_train_loss"].append(float(ep.mean() if step.guard is None else ep[torch.isfinite(ep)].mean()))
+        if step.guard is not None:
+            counts = step.guard_counts()
+            if step_guard.tripped(counts["consecutive"]):
+                raise FloatingPointError(f"epoch {epoch} ends in a streak of {counts['consecutive']} skipped optimizer steps ({counts['skipped']} "
+                                         f"skipped in all, the last at step {counts['last_skipped_step']}): {step.diagnose()}")
         if vstore is not None:
             sample = [] if panel_dir is not None and rank == 0 else None
             hist["val_loss"].append(validate(model, val_set, vstore, batch_size, limit_val_batches, rank, world, criterion, sample, val_view))

@@ -1680,7 +1680,15 @@ def group_clip_coef_(sums: torch.Tensor, groups: ParamGroupTables, out: torch.Te
     return out
 
 
-def _opt_step(who: str, p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups) -> "L.OptStep":
+def _live_ptr(live: Optional[torch.Tensor], p: torch.Tensor, who: str):
+    if live is None:
+        return None
+    if not isinstance(live, torch.Tensor) or live.dtype != torch.int32 or live.numel() != 1 or live.device != p.device:
+        raise L.BubbleformerHipError(f"{who}: live must be one torch.int32 element on {p.device} (e.g. step_guard_'s guard[:1])")
+    return live.data_ptr()
+
+
+def _opt_step(who: str, p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups, live=None) -> "L.OptStep":
     """The bf_opt_step record of one adamw_ / adam_ / lion_ call, built by field name (lion_: v None, step 0, eps 0)."""
     av = _avg_args(avg, avg_weight, p, who)
     rec = L.OptStep(p=_p(p), g=_p(g), m=_p(m), v=None if v is None else _p(v), coef_dev=_coef_ptr(coef, p, who), n=p.numel(), step=int(step),
@@ -1690,12 +1698,15 @@ def _opt_step(who: str, p, g, m, v, step, lr, betas, eps, weight_decay, grad_sca
         rec.avg, rec.avg_weight = av
     if groups is not None:
         rec.chunk_group, rec.group_lr_scale, rec.group_weight_decay, rec.group_frozen, rec.n_groups = _group_args(groups, p, who)
+    if live is not None:
+        rec.live_dev = _live_ptr(live, p, who)
     return rec
 
 
 def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0.9, 0.99), weight_decay: float = 0.0,
           grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None, clip_value: Optional[float] = None,
-          avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None, groups: Optional[ParamGroupTables] = None) -> None:
+          avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None, groups: Optional[ParamGroupTables] = None,
+          live: Optional[torch.Tensor] = None) -> None:
     """Fused Lion over flat fp32 buffers (lion_pytorch.Lion semantics, bubbleformer/modules.py:139-140).  coef: one fp32 on the device
     that multiplies grad_scale (grad_norm_'s out[1:]); clip_value: the scaled gradient is clamped to +-clip_value first
     (torch.nn.utils.clip_grad_value_).  Both None: the host-scale kernel.  avg / avg_weight (together or not at all): the same launch
@@ -1703,9 +1714,12 @@ def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0
     (1 copies p); p and m come out bit for bit as without them (weight_average_ is that update alone).  groups (param_group_tables):
     parameter groups -- an element whose chunk belongs to group k is stepped with lr * lr_scale[k] and weight_decay[k], a frozen group's
     chunks are neither read nor written (p, m, avg keep their bits); the ``weight_decay`` argument is then ignored, every group has its
-    own.  One launch (bf_lion) for every combination of coef / clip_value / avg / groups.  None: exactly the kernels launched without it."""
+    own.  live (one int32 on the device, step_guard_'s guard[:1]): the launch reads it first and, where it is 0, reads nothing else and
+    writes nothing -- the step is skipped on the device, with no host round trip; where it is not 0 the results are bit for bit those
+    without it.  One launch (bf_lion) for every combination of coef / clip_value / avg / groups / live.  None: exactly the kernels
+    launched without it."""
     _require_gpu(p)
-    rec = _opt_step("lion_", p, g, m, None, 0, lr, betas, 0.0, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    rec = _opt_step("lion_", p, g, m, None, 0, lr, betas, 0.0, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups, live)
     L.check(L.lib().bf_lion(C.byref(rec), _stream()), "bf_lion")
     _weights_changed()
 
@@ -1713,11 +1727,11 @@ def lion_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, betas=(0
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
            eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
            clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None,
-           groups: Optional[ParamGroupTables] = None) -> None:
+           groups: Optional[ParamGroupTables] = None, live: Optional[torch.Tensor] = None) -> None:
     """Fused AdamW over flat fp32 buffers (torch.optim.AdamW semantics, bubbleformer/modules.py:135-136).  coef / clip_value / avg /
-    avg_weight / groups: see lion_ (bf_adamw; m and v of a frozen chunk keep their bits too)."""
+    avg_weight / groups / live: see lion_ (bf_adamw; m and v of a frozen chunk, and of a skipped step, keep their bits too)."""
     _require_gpu(p)
-    rec = _opt_step("adamw_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    rec = _opt_step("adamw_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups, live)
     L.check(L.lib().bf_adamw(C.byref(rec), _stream()), "bf_adamw")
     _weights_changed()
 
@@ -1725,15 +1739,53 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
 def adam_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999),
           eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, coef: Optional[torch.Tensor] = None,
           clip_value: Optional[float] = None, avg: Optional[torch.Tensor] = None, avg_weight: Optional[float] = None,
-          groups: Optional[ParamGroupTables] = None) -> None:
+          groups: Optional[ParamGroupTables] = None, live: Optional[torch.Tensor] = None) -> None:
     """Fused Adam over flat fp32 buffers (torch.optim.Adam semantics, bubbleformer/modules.py:137-138, config/optim_cfg/adam.yaml):
     weight decay is an L2 term added to the gradient before the moments, not AdamW's decoupled decay.  coef / clip_value: see lion_
     (the clamp comes before the L2 term, as clip_grad_value_ before optimizer.step()).  avg / avg_weight / groups: see lion_
-    (bf_adam: a group's weight decay is its L2 term)."""
+    (bf_adam: a group's weight decay is its L2 term).  live: see lion_."""
     _require_gpu(p)
-    rec = _opt_step("adam_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups)
+    rec = _opt_step("adam_", p, g, m, v, step, lr, betas, eps, weight_decay, grad_scale, coef, clip_value, avg, avg_weight, groups, live)
     L.check(L.lib().bf_adam(C.byref(rec), _stream()), "bf_adam")
     _weights_changed()
+
+
+def step_guard_(norm: torch.Tensor, guard: torch.Tensor, step: int) -> torch.Tensor:
+    """The device decision whether an optimizer step is taken (bf_step_guard, one tiny launch): ``guard`` (four int32 on the device:
+    {live, consecutive, skipped, last_skipped_step}) is updated from ``norm`` (one fp32 on the device: grad_norm_'s or group_clip_coef_'s
+    out[:1]) -- live = isfinite(norm); a non-finite norm adds one to consecutive and skipped and records ``step``, a finite one clears
+    consecutive.  ``guard[:1]`` is the optimizers' ``live=``.  The norm's fp64 sum of squares is non-finite exactly when some element is."""
+    _require_gpu(norm)
+    if norm.dtype != torch.float32 or norm.numel() != 1:
+        raise L.BubbleformerHipError("step_guard_: norm must be one torch.float32 element (e.g. grad_norm_'s out[:1])")
+    if guard.dtype != torch.int32 or not guard.is_contiguous() or guard.numel() != 4 or guard.device != norm.device:
+        raise L.BubbleformerHipError(f"step_guard_: guard must be a contiguous torch.int32 tensor of 4 elements on {norm.device}")
+    L.check(L.lib().bf_step_guard(norm.data_ptr(), int(step), _p(guard), _stream()), "bf_step_guard")
+    return guard
+
+
+def nonfinite_scan_workspace(n: int, device) -> torch.Tensor:
+    """The int64 slab partials of nonfinite_scan for a buffer of n elements (two per slab, at most 1024 slabs)."""
+    return torch.empty(int(L.lib().bf_nonfinite_scan_ws_len(int(n))), dtype=torch.int64, device=device)
+
+
+def nonfinite_scan(buf: torch.Tensor, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = {index of the first inf / NaN in buf, or -1; how many buf holds} (two int64 on the device, allocated when None) over a flat
+    fp32 buffer (bf_nonfinite_scan: grad_norm_'s slabs, integers only, no atomics).  The diagnostic after a skipped step, never part of
+    one.  ws: nonfinite_scan_workspace(buf.numel(), device), allocated per call when None."""
+    _require_gpu(buf)
+    if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.dim() != 1:
+        raise L.BubbleformerHipError("nonfinite_scan: buf must be a contiguous 1-D torch.float32 tensor")
+    if out is None:
+        out = torch.empty(2, dtype=torch.int64, device=buf.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 2 or out.device != buf.device:
+        raise L.BubbleformerHipError(f"nonfinite_scan: out must be a contiguous torch.int64 tensor of 2 elements on {buf.device}")
+    if ws is None:
+        ws = nonfinite_scan_workspace(buf.numel(), buf.device)
+    elif ws.dtype != torch.int64 or not ws.is_contiguous() or ws.device != buf.device:
+        raise L.BubbleformerHipError(f"nonfinite_scan: ws must be a contiguous torch.int64 tensor on {buf.device}")
+    L.check(L.lib().bf_nonfinite_scan(_p(buf), buf.numel(), _p(out), _p(ws), ws.numel(), _stream()), "bf_nonfinite_scan")
+    return out
 
 
 def _flat_pair(a: torch.Tensor, b: torch.Tensor, who: str) -> None:

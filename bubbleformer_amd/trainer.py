@@ -12,7 +12,8 @@
                       ``accumulate_grad_batches=k`` the exchange and the optimizer run on every k-th call only; with
                       ``unroll_steps=k`` the model is run through k of its own predictions with a loss on each (``unroll_plan``);
                       with ``weight_average=`` the optimizer kernel also keeps an averaged copy of the weights (EMA / SWA);
-                      with ``param_groups=`` it freezes parameters and gives groups their own learning-rate scale and weight decay.
+                      with ``param_groups=`` it freezes parameters and gives groups their own learning-rate scale and weight decay;
+                      with ``step_guard=`` a step whose gradient is not finite is skipped, by a flag the optimizer launch reads on the device.
 Device agnostic where it can be (the reducer and the flat views are tested on CPU with gloo); the model itself
 only runs on the GPU.
 """
@@ -297,19 +298,40 @@ class TrainStep:
     frozen ones included, of the last optimizer step.  Clipping by value, the averaged weights, accumulation, unrolling and input noise work
     as without groups; every rank builds the same tables from the same specs.  ``requires_grad=False`` is not a way to freeze here: such a
     parameter has no home in the flat buffers.  None: nothing is built and the optimizer calls are the ones made without the argument.
-    utils.param_groups.group_norms(step) gives every group's parameter and gradient norm on demand."""
+    utils.param_groups.group_norms(step) gives every group's parameter and gradient norm on demand.
+    step_guard = utils.guard.GuardSpec: an optimizer step whose gradient holds an inf or a NaN is not taken -- parameters, moments and the
+    averaged copy keep their bits -- and training goes on, as under AMP's GradScaler.  The decision is made on the device and read by the
+    optimizer launch itself, so the step still never synchronises with the host.  After the bucket exchange (data parallel: every rank then
+    holds the same gradient, so every rank decides alike with no further collective) the 2-norm of the gradient is the witness: its fp64 sum
+    of squares is non-finite exactly when some element is (include/bubbleformer_hip.h: bf_step_guard; a finite gradient whose scaled norm
+    exceeds fp32's 3.4e38 is skipped too).  With clipping by norm it is the norm the step computes anyway; otherwise (no clipping, or
+    clipping by value) the step computes one for the guard alone, with max_norm = +inf, into ``guard_norm`` ({norm, coef} on the device,
+    None with clipping by norm) -- the optimizer is not handed that coefficient and keeps the scale mode it has without the guard.  With
+    param_groups the norm is the one over the groups that are not frozen: a NaN in a frozen parameter's gradient reaches nothing and does not
+    skip the step.  One bf_step_guard launch then updates ``guard``, four int32 on the device {live, consecutive, skipped,
+    last_skipped_step}, and the optimizer reads ``guard[0]``.  ``guard_counts()`` reads the counters (it synchronises); ``diagnose()`` finds
+    the first non-finite element of the parameters or the gradient and names its parameter.  The host-side counters cannot know the
+    device's decision without the synchronisation this exists to avoid, so they advance on a skipped step as on any other: ``step_no`` (hence
+    Adam's bias correction and the noise / augmentation draw), the scheduler (the learning-rate schedule counts the skipped step) and
+    ``n_averaged`` (an SWA mean stays a convex combination of the snapshots taken, but is no longer exactly uniform; the average starts as a
+    copy of the parameters, so a skipped "copy" step leaves it finite).  Not protected: state a forward pass writes outside the flat buffers
+    -- the one case is ClassicUnet's BatchNorm running statistics, which a non-finite activation reaches before any gradient exists.
+    None: no buffer, no launch, and the optimizer calls are the ones made without the argument."""
 
     def __init__(self, model: nn.Module, lr: float = 2.5e-4, weight_decay: float = 1e-2, betas=None, eps: float = 1e-8,
                  optimizer: str = "adamw", scheduler=None, criterion=None, gradient_clip_val: Optional[float] = None,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1, unroll_steps: int = 1, unroll_weights=None,
-                 unroll_backprop: bool = True, input_noise=None, field_std=None, weight_average=None, param_groups=None):
+                 unroll_backprop: bool = True, input_noise=None, field_std=None, weight_average=None, param_groups=None, step_guard=None):
         from . import ops
         from .utils.averaging import AverageSpec
+        from .utils.guard import GuardSpec
         from .utils.noise import NoiseSpec
         if weight_average is not None and not isinstance(weight_average, AverageSpec):
             raise ValueError(f"weight_average {weight_average!r} must be None or a utils.averaging.AverageSpec")
         if input_noise is not None and not isinstance(input_noise, NoiseSpec):
             raise ValueError(f"input_noise {input_noise!r} must be None or a utils.noise.NoiseSpec")
+        if step_guard is not None and not isinstance(step_guard, GuardSpec):
+            raise ValueError(f"step_guard {step_guard!r} must be None or a utils.guard.GuardSpec")
         if input_noise is not None and input_noise.active and input_noise.relative and field_std is None:
             raise ValueError("input_noise: NoiseSpec(relative=True) needs the input fields' standard deviations -- train through fit(), which "
                              "takes them from the training store, or pass field_std= (DeviceClipStore.field_std())")
@@ -356,6 +378,15 @@ class TrainStep:
             self.grad_norm = torch.zeros(2, dtype=torch.float32, device=self.flat.flat.device)
             self._coef = self.grad_norm[1:]
             self._norm_ws = None
+        self.step_guard = step_guard
+        self.guard = None         # step_guard: the device record {live, consecutive, skipped, last_skipped_step}
+        self.guard_norm = None    # step_guard without "norm" clipping: device {norm, coef} of the last optimizer step, for the guard alone
+        if step_guard is not None:
+            self.guard = torch.tensor([1, 0, 0, -1], dtype=torch.int32, device=self.flat.flat.device)
+            self._live = self.guard[:1]
+            if self.grad_norm is None:
+                self.guard_norm = torch.zeros(2, dtype=torch.float32, device=self.flat.flat.device)
+                self._norm_ws = None
         self._unroll_w = None
         if self.unroll_steps > 1:
             self._unroll_w = torch.tensor(self.unroll_weights, dtype=torch.float32, device=self.flat.flat.device)
@@ -384,6 +415,7 @@ class TrainStep:
                                                   flat.numel, flat.flat.device)
         if self.grad_norm is not None:
             self.group_grad_norm = torch.zeros(len(res), dtype=torch.float32, device=flat.flat.device)
+        if self.grad_norm is not None or self.guard is not None:
             self._group_sums = torch.zeros(len(res), dtype=torch.float64, device=flat.flat.device)
 
     @staticmethod
@@ -399,7 +431,7 @@ class TrainStep:
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
             return
         avg = getattr(self, "avg", None)      # the averaged weights and their update count travel too, once the step holds them
-        for t in (self.flat.flat, self.m, self.v, avg):
+        for t in (self.flat.flat, self.m, self.v, avg, getattr(self, "guard", None)):      # ... and the guard's counters
             if t is not None:
                 dist.broadcast(t, src=0)
         n = torch.tensor([self.step_no] + ([self.n_averaged] if avg is not None else []), dtype=torch.int64, device=self.flat.flat.device)
@@ -479,6 +511,12 @@ class TrainStep:
             clip = {"coef": self._coef}
         elif self.clip_val is not None:
             clip = {"clip_value": self.clip_val}
+        if self.guard is not None:
+            witness = self.grad_norm
+            if witness is None:                  # no norm clipping: a norm for the guard alone; its coefficient is not handed on
+                witness = self._guard_witness(gscale)
+            self.ops.step_guard_(witness[:1], self.guard, self.step_no)
+            clip["live"] = self._live
         if self.weight_average is not None:
             w = self.weight_average.weight(self.step_no, self.n_averaged)
             if w is not None:
@@ -495,6 +533,44 @@ class TrainStep:
             self.ops.lion_(self.flat.flat, self.flat.grad, self.m, lr, self.betas, self.wd, gscale, **clip)
         if self.scheduler is not None:
             self.scheduler.step()
+
+    # ---------------------------------------------------------------------------------------- the step guard
+    def _guard_witness(self, gscale: float) -> torch.Tensor:
+        """{norm, coef} of the exchanged gradient into ``guard_norm``, as clipping by norm with max_norm = +inf would form them (over the
+        groups that are not frozen, with param_groups)."""
+        inf = float("inf")
+        if self.groups is not None:
+            if self._norm_ws is None:
+                self._norm_ws = self.ops.group_sumsq_workspace(self.flat.numel, self.flat.grad.device)
+            self.ops.group_sumsq(self.flat.grad, self.groups, self._group_sums, self._norm_ws)
+            return self.ops.group_clip_coef_(self._group_sums, self.groups, self.guard_norm, inf, gscale)
+        if self._norm_ws is None:
+            self._norm_ws = self.ops.grad_norm_workspace(self.flat.numel, self.flat.grad.device)
+        return self.ops.grad_norm_(self.flat.grad, self.guard_norm, inf, gscale, self._norm_ws)
+
+    def guard_counts(self) -> dict:
+        """{"skipped", "consecutive", "last_skipped_step"} of the device record: optimizer steps skipped so far, the length of the streak
+        the run is in (0 after a step that was taken) and the ``step_no`` of the last skipped step (-1: none).  This copies the record to
+        the host and so SYNCHRONISES with the device: call it where the run waits anyway (fit does at the end of an epoch)."""
+        if self.guard is None:
+            raise RuntimeError("guard_counts(): this TrainStep has no guard (step_guard=None)")
+        live, consecutive, skipped, last = self.guard.tolist()
+        return {"skipped": skipped, "consecutive": consecutive, "last_skipped_step": last}
+
+    def diagnose(self) -> dict:
+        """Where the first non-finite value is: ops.nonfinite_scan over the parameters first, then over the gradient buffer (which holds
+        the last call's gradient until the next call clears it).  -> {"buffer": "parameters" | "gradient" | None, "parameter": the name
+        of the parameter the element belongs to, or "padding after <name>" (None when nothing was found), "index": its place in the flat
+        buffer (-1), "count": how many non-finite elements that buffer holds (0)}.  A diagnostic for after something has gone wrong: two
+        launches per buffer and a synchronisation, never part of a step; it needs no guard."""
+        from .utils.guard import locate
+        name_of = {id(p): n for n, p in self.model.named_parameters()}
+        for what, buf in (("parameters", self.flat.flat), ("gradient", self.flat.grad)):
+            first, count = self.ops.nonfinite_scan(buf).tolist()
+            if count:
+                where = locate(first, [name_of[id(p)] for p in self.flat.params], self.flat.offsets, [p.numel() for p in self.flat.params])
+                return {"buffer": what, "parameter": where, "index": first, "count": count}
+        return {"buffer": None, "parameter": None, "index": -1, "count": 0}
 
     # ---------------------------------------------------------------------------------------- the averaged weights
     def _refuse_while_swapped(self, what: str) -> None:

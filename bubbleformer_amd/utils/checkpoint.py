@@ -10,6 +10,7 @@ checkpoint written here resumes here, while its "state_dict" loads anywhere the 
 averaged copy of the weights (TrainStep(weight_average=...)) adds "weight_average": its spec, the update count and the flat average;
 a step with parameter groups (TrainStep(param_groups=...)) adds "param_groups": its partition, a list of {name, lr_scale, weight_decay,
 frozen, params: [names]} (utils.param_groups.ResolvedGroups.partition), which a grouped step checks on loading;
+a step with a guard (TrainStep(step_guard=...)) adds "step_guard": {"skipped": the optimizer steps skipped so far};
 `save_checkpoint(averaged=True)` instead writes the averaged weights AS the "state_dict", with no training state: the file to release.
 
 `load_checkpoint` also resumes from a file the reference's Lightning run wrote (e.g. the pre-emption `hpc_ckpt_*.ckpt` files of
@@ -65,6 +66,8 @@ def save_checkpoint(path: str, model: torch.nn.Module, hyper_parameters: Optiona
                                       "every": spec.every, "n_averaged": int(train_step.n_averaged), "avg": train_step.avg.detach().cpu()}
         if getattr(train_step, "resolved_groups", None) is not None:
             ckpt["param_groups"] = train_step.resolved_groups.partition()
+        if getattr(train_step, "guard", None) is not None:
+            ckpt["step_guard"] = {"skipped": int(train_step.guard[2])}
     if epoch is not None:
         ckpt["epoch"] = int(epoch)
     tmp = path + ".tmp"
@@ -203,7 +206,8 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
     its average from the loaded parameters with a count of 0; a step that does not average ignores the key.  A training step with parameter
     groups refuses (ValueError, before any weight is written) a file whose "param_groups" partition differs from its own -- the moments of a
     parameter that was frozen there are not the moments of one that trained; a file without the key loads as always, and a step without
-    groups ignores it.  The reference's multi-group torch.optim state stays refused (flat_state_from_torch_optim), and a grouped step refuses a
+    groups ignores it.  A training step with a guard takes "step_guard" -- its device record restarts live, out of any streak, with the file's
+    count of skipped steps (0 from a file without the key); a step without a guard ignores the key.  The reference's multi-group torch.optim state stays refused (flat_state_from_torch_optim), and a grouped step refuses a
     reference state whose weight_decay is not its own (its default group's row was built from that).  Unpickling a real Lightning file
     whose hyper_parameters hold OmegaConf objects needs the `omegaconf` package (not a dependency of this project)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
@@ -247,6 +251,9 @@ def load_checkpoint(path: str, model: torch.nn.Module, train_step=None, map_loca
         else:                                 # an older file, or the reference's: the average starts from the loaded weights
             train_step.avg.copy_(train_step.flat.flat)
             train_step.n_averaged = 0
+    if train_step is not None and getattr(train_step, "guard", None) is not None:      # a file without the key: nothing skipped so far
+        skipped = int((ckpt.get("step_guard") or {}).get("skipped", 0))
+        train_step.guard.copy_(torch.tensor([1, 0, skipped, -1], dtype=torch.int32))
     from .. import ops
     ops._weights_changed()                    # prepared inference weights (ops.trunk_eval) are re-made from the loaded parameters
     if train_step is not None and hasattr(train_step, "sync_from_rank0"):

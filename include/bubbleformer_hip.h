@@ -721,6 +721,11 @@ int bf_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float*
  *   groups: one group of scale 1 gives those bits.  group_lr_scale[k] == 0 with group_frozen[k] == 0 is torch's lr = 0: the moments move, the
  *   parameter does not.  A chunk of a frozen group is neither read nor written: p, m, v and avg keep their bits and nothing in its gradient (a NaN
  *   included) reaches anything.  The entry points cannot check the map's ids without reading it; the kernels treat an id >= n_groups as frozen.
+ * Step guard: live_dev = NULL means none, and the launch is the one made before the member existed.  Otherwise live_dev is
+ *   one int32 in DEVICE memory, 4-byte aligned ("<entry>: the guard flag must be 4-byte aligned"), e.g. bf_step_guard's guard[0].  The launch reads
+ *   it first.  live_dev[0] == 0: it reads nothing else and writes nothing -- p, m, v and avg keep their bits, in every scale mode, with and without
+ *   the average and the groups, whatever g holds.  live_dev[0] != 0: the results are bit for bit those of the same record with live_dev = NULL.
+ *   The record grew by this member without a new bf_abi_version: a caller zero-initialises the record and is compiled against this header.
  * A null record or a null required pointer is refused as "<entry>: null pointer", and every other check is made, before any HIP call. */
 #define BF_OPT_CHUNK 64
 #define BF_OPT_MAX_GROUPS 64
@@ -728,6 +733,7 @@ typedef struct bf_opt_step {
     float* p; const float* g; float *m, *v;
     const float* coef_dev; float* avg;
     const uint8_t* chunk_group; const float *group_lr_scale, *group_weight_decay; const uint8_t* group_frozen;
+    const int32_t* live_dev;
     int64_t n;
     int32_t step, n_groups;
     float lr, beta1, beta2, eps, wd, gscale, clip_value, avg_weight;
@@ -735,6 +741,22 @@ typedef struct bf_opt_step {
 int bf_adamw(const bf_opt_step* s, bf_stream_t stream);
 int bf_adam(const bf_opt_step* s, bf_stream_t stream);
 int bf_lion(const bf_opt_step* s, bf_stream_t stream);
+/* bf_step_guard: the device decision whether an optimizer step is taken (one tiny launch, no host round trip).  norm = one fp32 in DEVICE memory,
+ * out[0] of bf_grad_norm or bf_group_clip_coef; guard = four int32 in DEVICE memory, {live, consecutive, skipped, last_skipped_step}:
+ *   live = isfinite(norm[0]);   not live: consecutive += 1, skipped += 1, last_skipped_step = step;   live: consecutive = 0
+ * guard + 0 is what bf_opt_step's live_dev takes.  Why the norm is a sufficient witness: it is gscale * sqrt(sum g^2) with the squares and the
+ * sum in fp64 over fp32 values.  A finite fp32 square is below 1.2e77, so the sum of n of them cannot overflow fp64 (1.8e308) for any n a
+ * buffer can have, and an inf or a NaN element makes the sum inf or NaN, which nothing later removes: with a finite gscale the sum is non-finite
+ * exactly when some element is.  The one extra case is the rounding to fp32: a finite gradient whose scaled 2-norm exceeds 3.4e38 has an inf
+ * norm and is skipped too.  Elements of frozen groups are outside bf_group_clip_coef's norm and so outside the decision.
+ * Both pointers must be 4-byte aligned and not NULL; refused before any HIP call. */
+int bf_step_guard(const float* norm, int32_t step, int32_t* guard, bf_stream_t stream);
+/* bf_nonfinite_scan: the diagnostic after a skipped step -- out = {index of the first element of x[n] (fp32, 16-byte aligned, n > 0) that is an inf
+ * or a NaN, or -1; the number of such elements} (two int64 in DEVICE memory).  bf_grad_norm's slab rule: 16-byte loads, the n % 4 trailing
+ * elements joined to the last slab, one {minimum index, count} per slab in ws (at least bf_nonfinite_scan_ws_len(n) int64, 8-byte aligned) and
+ * one finishing workgroup; integers only, no atomics, so two calls agree. */
+int64_t bf_nonfinite_scan_ws_len(int64_t n);
+int bf_nonfinite_scan(const float* x, int64_t n, int64_t* out, int64_t* ws, int64_t ws_len, bf_stream_t stream);
 /* bf_weight_average is the optimizers' avg update alone (same bits; w as avg_weight); bf_swap_buffers exchanges two non-overlapping 16-byte
  * aligned buffers exactly, in one launch. */
 int bf_weight_average(float* avg, const float* p, int64_t n, float w, bf_stream_t stream);

@@ -16,7 +16,14 @@ ungrouped step, (b) the step with its record's groups set and every group live -
 layer_decay(0.75) on the model's parameter names and shapes, (c) the grouped step with the trunk (blocks.*) frozen.  The grouped launches also read one map
 byte per 64 elements; a frozen chunk moves no other byte, so (c) is reported beside the live share of the buffer.
 
-Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average | --groups]"""
+--guard times the step guard per optimizer (AdamW, Lion) under the same protocol: (a) "unguarded", the launch of a
+record without live_dev -- with --parent-lib (a libbubbleformer_hip.so built from the commit before the guard, whose record has no such
+member) beside "parent", the same launch from that library, alternating in the same rounds, and the parent's own run-to-run spread
+(ms_min .. ms_max over the rounds) is the yardstick for their difference; (b) "guarded_live", the record with live_dev set and the flag 1;
+(c) "skipped", the flag 0: the launch reads four bytes and leaves; (d) "norm_and_guard", bf_grad_norm + bf_step_guard, what a step without
+clipping by norm adds for the guard (one 4-byte read per element, three tiny launches).
+
+Usage: python tools/adam_bench.py [--rounds R] [--reps K] [--average | --groups | --guard [--parent-lib PATH]]"""
 import argparse
 import ctypes as C
 import json
@@ -177,19 +184,78 @@ def time_groups(cfg, n, rounds, reps):
     return out
 
 
+class ParentOptStep(C.Structure):
+    """bf_opt_step as it was before live_dev: what a library built from the parent commit reads."""
+    _fields_ = [f for f in L.OptStep._fields_ if f[0] != "live_dev"]
+
+
+def parent_call(lib, entry, p, g, m, v=None, **fields):
+    rec = ParentOptStep(**{**dict(p=_p(p), g=_p(g), m=_p(m), v=None if v is None else _p(v), n=p.numel(), gscale=1.0, clip_value=float("inf")), **fields})
+    fn, ref, st = getattr(lib, entry), C.byref(rec), C.c_void_p(_stream())
+    fn.restype = C.c_int
+    return lambda: fn(ref, st)
+
+
+def time_guard(n, rounds, reps, parent_lib=None):
+    """Per optimizer: "unguarded", "guarded_live", "skipped" (ms per launch), "norm_and_guard" (bf_grad_norm + bf_step_guard), and with a
+    parent library "parent" with the spread its rounds show; every difference is reported in ms beside that spread."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    p = torch.randn(n, device="cuda", generator=g) * 0.02
+    grad = torch.randn(n, device="cuda", generator=g) * 1e-3
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    h, st = L.lib(), _stream()
+    one, zero = torch.ones(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    pair, guard = torch.zeros(2, device="cuda"), torch.tensor([1, 0, 0, -1], dtype=torch.int32, device="cuda")
+    ws = torch.empty(int(h.bf_grad_norm_ws_doubles(n)), dtype=torch.float64, device="cuda")
+
+    def norm_and_guard():
+        h.bf_grad_norm(_p(grad), n, 1.0, float("inf"), _p(pair), _p(ws), ws.numel(), st)
+        return h.bf_step_guard(_p(pair), 1, _p(guard), st)
+    out = {}
+    for opt, entry, base, hyper in (("adamw", "bf_adamw", 28, dict(ADAM, wd=1e-2)), ("lion", "bf_lion", 20, LION)):
+        bufs = (p, grad, m, v) if opt == "adamw" else (p, grad, m)
+        calls = {}
+        if parent_lib is not None:
+            calls["parent"] = parent_call(parent_lib, entry, *bufs, **hyper)
+        calls.update(unguarded=opt_call(entry, *bufs, **hyper), guarded_live=opt_call(entry, *bufs, live_dev=_p(one), **hyper),
+                     skipped=opt_call(entry, *bufs, live_dev=_p(zero), **hyper), norm_and_guard=norm_and_guard)
+        ms = rounds_of(calls, rounds, reps)
+        res = {k: summary(ms[k], n, 4 if k == "norm_and_guard" else base) for k in calls}
+        for k in ("GB_s", "hbm_peak_share"):
+            res["skipped"].pop(k)                  # a skipped launch moves four bytes
+        yard = res.get("parent", res["unguarded"])
+        res["spread_ms"] = round(yard["ms_max"] - yard["ms_min"], 4)
+        res["spread_of"] = "parent" if "parent" in res else "unguarded"
+        if "parent" in res:
+            res["unguarded_minus_parent_ms"] = round(res["unguarded"]["ms"] - res["parent"]["ms"], 4)
+        res["guarded_live_minus_unguarded_ms"] = round(res["guarded_live"]["ms"] - res["unguarded"]["ms"], 4)
+        out[opt] = res
+    assert torch.isfinite(p).all() and guard.tolist() == [1, 0, 0, -1]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--average", action="store_true", help="time the averaged-weights step: plain, fused (avg set), plain + bf_weight_average")
     ap.add_argument("--groups", action="store_true", help="time the parameter-group launch: ungrouped, every group live, trunk frozen")
+    ap.add_argument("--guard", action="store_true", help="time the step guard: unguarded, guarded live, skipped, the norm pass + bf_step_guard")
+    ap.add_argument("--parent-lib", default=None, help="--guard: a libbubbleformer_hip.so built from the commit before the guard, timed beside this tree's")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/adam_bench.py times GPU kernels: no GPU found"
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "bytes_per_element": BYTES_PER_ELEMENT}
+    parent = None
+    if args.guard and args.parent_lib:
+        L.lib()                                      # this tree's library first: it binds the HIP runtime both use
+        parent = C.CDLL(os.path.abspath(args.parent_lib))
+        res["parent_lib"] = os.path.basename(args.parent_lib)
     for name, cfg in MODELS.items():
         params, n = flat_sizes(cfg)
         if args.groups:
             timed = time_groups(cfg, n, args.rounds, args.reps)
+        elif args.guard:
+            timed = time_guard(n, args.rounds, args.reps, parent)
         else:
             timed = (time_average if args.average else time_kernels)(n, args.rounds, args.reps)
         res[name] = dict(parameters=params, flat_elements=n, **timed)
