@@ -278,6 +278,11 @@ SIGNATURES = {
     "bf_lp_rows_fwd": (C.c_int, [fp, fp, i64, i64, C.c_double, fp, vp, vp, i64, vp]),
     "bf_lp_rows_bwd": (C.c_int, [fp, fp, fp, vp, i64, i64, C.c_double, fp, vp]),
     "bf_eikonal_bwd": (C.c_int, [fp, i64, C.c_int, C.c_int, f32, fp, fp, vp]),
+    "bf_wlp_ws_doubles": (i64, [i64, C.c_int, C.c_int, C.c_int]),
+    "bf_wlp_fwd": (C.c_int, [fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, P(C.c_double), C.c_double,
+                             C.c_double, fp, fp, vp, vp, i64, vp]),
+    "bf_wlp_bwd": (C.c_int, [fp, fp, fp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, P(C.c_double),
+                             C.c_double, C.c_double, fp, vp]),
     "bf_temporal_saved_bytes": (i64, [P(Dims)]),
     "bf_spatial_saved_bytes": (i64, [P(Dims)]),
     "bf_embed_saved_bytes": (i64, [P(Dims)]),

@@ -105,6 +105,9 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
     ``step.diagnose()`` when the run ends the epoch in a streak of ``max_consecutive`` or more skipped steps -- before validation and before
     the checkpoint is written, so no file is written during such a streak.  Checkpoints carry the count of skipped steps and a resumed
     run continues it.  None: every call, history key and parameter bit for bit as without it.
+    A criterion with a ``field_terms()`` method (utils.losses.InterfaceLpLoss): ``hist["field_loss"]`` keeps the C per-field terms of every
+    training batch (of its last pass where the step is unrolled), kept as ``grad_norm`` is -- device clones, read at the end of the epoch -- and
+    the `log` dict of a batch carries them as a device tensor.
     Returns the history."""
     dev = next(model.parameters()).device
     conditioned = getattr(train_set, "return_fluid_params", False)
@@ -152,6 +155,9 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             hist["guard_norm"] = []
     if step.avg is not None and vstore is not None:
         hist["val_loss_avg"] = []
+    field_terms = getattr(criterion, "field_terms", None)
+    if field_terms is not None:
+        hist["field_loss"] = []
     first_epoch = 0
     if resume_from is not None:
         ck = load_checkpoint(resume_from, model, step)
@@ -159,7 +165,7 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
         first_epoch = int(ck["epoch"]) + 1 if "epoch" in ck else int(ck.get("global_step", 0)) // max(steps_per_epoch, 1)
     for epoch in range(first_epoch, max_epochs):
         model.train()
-        losses, norms, gnorms, per_pass, lives, wnorms = [], [], [], [], [], []
+        losses, norms, gnorms, per_pass, lives, wnorms, fterms = [], [], [], [], [], [], []
         order = epoch_indices(n_pool, epoch, seed, True, rank, world)
         todo = batches(order if pool is None else [pool[i] for i in order], batch_size, limit_train_batches)
         for bi, idx in enumerate(todo):
@@ -178,6 +184,9 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
                 per_pass.append(step.unroll_losses)
             hist["lr"].append(cur_lr)
             entry = {"epoch": epoch, "batch_idx": bi, "global_step": step.step_no, "train_loss": loss, "learning_rate": cur_lr}
+            if field_terms is not None:
+                fterms.append(field_terms())                 # a clone of what the batch's (last) forward left on the device
+                entry["field_loss"] = fterms[-1]
             if step.grad_norm is not None and step.step_no != before:
                 norms.append(step.grad_norm[0].clone())      # the next step overwrites the pair
                 entry["grad_norm"] = norms[-1]
@@ -197,6 +206,8 @@ def fit(model: torch.nn.Module, train_set, val_set=None, *, batch_size: int, max
             hist["grad_norm"].extend(torch.stack(norms).tolist())
         if gnorms:
             hist["group_grad_norm"].extend(torch.stack(gnorms).tolist())
+        if fterms:
+            hist["field_loss"].extend(torch.stack(fterms).tolist())
         if per_pass:
             hist["unroll_loss"].extend(torch.stack(per_pass).tolist())
         if lives:

@@ -2,7 +2,9 @@
 
 ``LpLoss`` has the reference's constructor, attributes and reduction behaviour; its relative Lp norm per row and the gradient of it run
 in csrc/losses.hip (bf_lp_rows_fwd / bf_lp_rows_bwd), the reductions over the leading dims are ordinary torch ops on the small tensor of
-per-row ratios.  ``eikonal_loss`` is `physics.eikonal_loss` with a backward (bf_eikonal_bwd).  Inputs are fp32 tensors on the GPU; there
+per-row ratios.  ``eikonal_loss`` is `physics.eikonal_loss` with a backward (bf_eikonal_bwd).  ``InterfaceLpLoss`` (no reference
+program) is the training configuration of LpLoss with a pixel weight around the target's liquid-vapour interface, a weight per field and an
+optional Eikonal penalty, forward and backward in their own kernels (bf_wlp_fwd / bf_wlp_bwd).  Inputs are fp32 tensors on the GPU; there
 is no CPU path.
 """
 import math
@@ -163,3 +165,138 @@ def eikonal_loss(phi: torch.Tensor) -> torch.Tensor:
     if phi.dim() < 2 or phi.numel() == 0:
         raise L.BubbleformerHipError(f"eikonal_loss expects (..., H, W); got {tuple(phi.shape)}")
     return _EikonalFn.apply(phi)
+
+
+_WLP_WS_DOUBLES = {}      # (frames, C, H, W) -> bf_wlp_ws_doubles
+
+
+class _InterfaceLpFn(torch.autograd.Function):
+    """(pred, y) -> the scalar of InterfaceLpLoss; the criterion keeps the terms the forward left on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, y, crit):
+        B, T, Cn, H, W = pred.shape
+        frames = B * T
+        pred, y = pred.contiguous(), y.contiguous()
+        lib = L.lib()
+        nws = _WLP_WS_DOUBLES.get((frames, Cn, H, W))
+        if nws is None:
+            nws = _WLP_WS_DOUBLES[(frames, Cn, H, W)] = lib.bf_wlp_ws_doubles(frames, Cn, H, W)
+        if nws < 0:
+            raise L.BubbleformerHipError(f"InterfaceLpLoss: {frames} frames of {Cn} x {H} x {W} are out of range")
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        terms = torch.empty(1 + Cn, dtype=torch.float32, device=pred.device)
+        buf = torch.empty(2 * frames * Cn + nws, dtype=torch.float64, device=pred.device)      # the saved sums, then the call's workspace
+        sums = buf[:2 * frames * Cn]
+        ctx.args = (frames, Cn, H, W) + crit._abi_args(Cn)
+        L.check(lib.bf_wlp_fwd(pred.data_ptr(), y.data_ptr(), *ctx.args, loss.data_ptr(), terms.data_ptr(), sums.data_ptr(),
+                               sums.data_ptr() + 16 * frames * Cn, nws, _stream()), "bf_wlp_fwd")
+        ctx.save_for_backward(pred, y, sums)
+        crit._terms = terms
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, y, sums = ctx.saved_tensors
+        g = g.contiguous().float().reshape(1)
+        dpred = _like_offset(pred)
+        L.check(L.lib().bf_wlp_bwd(pred.data_ptr(), y.data_ptr(), g.data_ptr(), sums.data_ptr(), *ctx.args, dpred.data_ptr(), _stream()), "bf_wlp_bwd")
+        return dpred, None, None
+
+
+class InterfaceLpLoss(nn.Module):
+    """The relative L2 of LpLoss's training configuration with every pixel weighted by its distance to the liquid-vapour interface of the
+    TARGET frame, a weight per field, and an optional Eikonal penalty on the predicted signed distance -- one native criterion for
+    ``TrainStep(criterion=...)`` / ``fit(criterion=...)`` (csrc/losses.hip: bf_wlp_fwd / bf_wlp_bwd; no reference program).
+
+    pred, y: (B, T, C, H, W) fp32 on the GPU in the dataset's normalised units, stored = (x - diff) / div; y never requires a gradient.  With
+    phi_t = y[:, :, sdf_channel] * div + diff (the simulated signed distance, in the reference's units, grid spacing dx):
+        w        = 1 + gain * max(0, 1 - |phi_t| / band)              a hat of half-width `band` (phi's units) and height `gain` >= 0
+        rho      = sqrt(sum_hw w (pred - y)^2 / sum_hw w y^2)         per (b, t, c); one weight map for the C fields of a frame
+        L_data   = sum_c field_weights[c] * mean_{b,t} rho[b, t, c]
+        L_eik    = eikonal * mean_{b,t,h,w} (|grad (pred[:, :, sdf_channel] * div + diff)| - 1)^2      (torch.gradient, spacing dx)
+    and forward returns L_data + L_eik, a scalar fp32 tensor differentiable w.r.t. pred.  gain = 0, unit field weights and eikonal = 0 give
+    ``LpLoss(d=2, p=2, reduce_dims=[0, 1, 2], reductions=["mean", "mean", "sum"])``.  A flat cell of the predicted distance contributes 0 to the
+    penalty's gradient (see ``eikonal_loss``).
+
+    ``band`` and ``gain`` have no defaults: no value has been validated by a training run.  ``field_terms()`` / ``eikonal_term()`` return the C
+    values ``field_weights[c] * mean rho`` and the penalty of the last forward as device tensors (clones; no host synchronisation)."""
+
+    def __init__(self, sdf_channel: int, band: float, gain: float, *, diff: float = 0.0, div: float = 1.0, field_weights=None,
+                 eikonal: float = 0.0, dx: float = EIKONAL_DX):
+        super().__init__()
+        if not (isinstance(sdf_channel, int) and sdf_channel >= 0):
+            raise ValueError(f"InterfaceLpLoss: sdf_channel = {sdf_channel!r} must be an int >= 0")
+        band, gain, diff, div, eikonal, dx = (float(v) for v in (band, gain, diff, div, eikonal, dx))
+        if not (math.isfinite(gain) and gain >= 0.0):
+            raise ValueError(f"InterfaceLpLoss: gain = {gain!r} must be finite and >= 0")
+        if gain > 0.0 and not (math.isfinite(band) and band > 0.0):
+            raise ValueError(f"InterfaceLpLoss: band = {band!r} must be positive and finite (the units of the signed distance)")
+        if not (math.isfinite(div) and div != 0.0 and math.isfinite(diff)):
+            raise ValueError(f"InterfaceLpLoss: diff = {diff!r}, div = {div!r} must be finite and div not 0")
+        if not (math.isfinite(eikonal) and eikonal >= 0.0 and math.isfinite(dx) and dx > 0.0):
+            raise ValueError(f"InterfaceLpLoss: eikonal = {eikonal!r} must be finite and >= 0, dx = {dx!r} positive")
+        if field_weights is not None:
+            field_weights = tuple(float(a) for a in field_weights)
+            if not all(math.isfinite(a) and a >= 0.0 for a in field_weights):
+                raise ValueError(f"InterfaceLpLoss: field weights {field_weights} must be finite and >= 0")
+        self.sdf_channel, self.band, self.gain, self.diff, self.div = sdf_channel, band, gain, diff, div
+        self.field_weights, self.eikonal, self.dx = field_weights, eikonal, dx
+        self._terms = None
+
+    @classmethod
+    def for_dataset(cls, ds, band: float, gain: float, sdf_field: str = "dfun", field_weights=None, eikonal: float = 0.0):
+        """The criterion of a normalised dataset (data.BubbleForecast): the channel of ``sdf_field`` among ``ds.output_fields``, its constants
+        from ``ds.diff_terms`` / ``ds.div_terms``, dx = ds.downsample_factor / 32; ``field_weights`` a sequence in the order of the output
+        fields or a dict by field name (fields it does not name weigh 1)."""
+        fields = list(ds.output_fields)
+        if sdf_field not in fields:
+            raise ValueError(f"InterfaceLpLoss: the dataset's output fields {fields} have no {sdf_field!r}")
+        s = fields.index(sdf_field)
+        if isinstance(field_weights, dict):
+            unknown = [k for k in field_weights if k not in fields]
+            if unknown:
+                raise ValueError(f"InterfaceLpLoss: field weights name {unknown}, not among the output fields {fields}")
+            field_weights = [float(field_weights.get(n, 1.0)) for n in fields]
+        try:
+            diff, div = float(ds.diff_terms[sdf_field]), float(ds.div_terms[sdf_field])
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"InterfaceLpLoss: the dataset has no normalisation constants for {sdf_field!r} (call normalize() first)") from None
+        return cls(s, band, gain, diff=diff, div=div, field_weights=field_weights, eikonal=eikonal,
+                   dx=EIKONAL_DX * float(getattr(ds, "downsample_factor", 1)))
+
+    def _abi_args(self, Cn: int):
+        a = self.field_weights
+        if a is not None and len(a) != Cn:
+            raise L.BubbleformerHipError(f"InterfaceLpLoss: {len(a)} field weights for {Cn} fields")
+        import ctypes
+        arr = (ctypes.c_double * Cn)(*a) if a is not None else None      # read by the library during the call only
+        return (self.sdf_channel, self.diff, self.div, self.band, self.gain, arr, self.eikonal, self.dx)
+
+    def forward(self, pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        _require_gpu_f32(pred, "InterfaceLpLoss")
+        _require_gpu_f32(y, "InterfaceLpLoss")
+        if y.requires_grad and torch.is_grad_enabled():
+            raise L.BubbleformerHipError("InterfaceLpLoss: a gradient w.r.t. the target is not implemented (the target must not require grad)")
+        if pred.shape != y.shape:
+            raise L.BubbleformerHipError(f"InterfaceLpLoss: prediction {tuple(pred.shape)} and target {tuple(y.shape)} differ in shape")
+        if pred.dim() != 5:
+            raise L.BubbleformerHipError(f"InterfaceLpLoss expects (B, T, C, H, W); got {tuple(pred.shape)}")
+        if pred.numel() == 0:
+            raise L.BubbleformerHipError("InterfaceLpLoss: empty input")
+        if pred.shape[2] <= self.sdf_channel:
+            raise L.BubbleformerHipError(f"InterfaceLpLoss: sdf_channel = {self.sdf_channel} lies outside the {pred.shape[2]} fields of {tuple(pred.shape)}")
+        return _InterfaceLpFn.apply(pred, y, self)
+
+    def _last(self) -> torch.Tensor:
+        if self._terms is None:
+            raise L.BubbleformerHipError("InterfaceLpLoss: no forward has run yet")
+        return self._terms
+
+    def field_terms(self) -> torch.Tensor:
+        """(C,) fp32 on the device: field_weights[c] * mean_{b,t} rho[b, t, c] of the last forward."""
+        return self._last()[1:].clone()
+
+    def eikonal_term(self) -> torch.Tensor:
+        """The Eikonal penalty of the last forward (0 where eikonal = 0): a 0-dim fp32 tensor on the device."""
+        return self._last()[0].clone()

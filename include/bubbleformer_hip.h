@@ -34,6 +34,7 @@
  *   bf_clip_noise ............ seeded Gaussian input noise of a training step (no reference program; Philox4x32-10 + Box-Muller)
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
+ *   bf_wlp_* ................. the interface-weighted criterion: a hat weight around the target's zero level set, field weights, Eikonal penalty (no reference program)
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
@@ -685,6 +686,32 @@ int bf_lp_rows_bwd(const float* pred, const float* y, const float* g, const doub
  * in DEVICE memory.  Gather form (no atomics), fp64 arithmetic, one rounding.  A cell with |grad phi| = 0 contributes 0 (autograd of the reference's
  * expression gives 0 * inf = NaN there).  A 1-wide axis has a zero derivative. */
 int bf_eikonal_bwd(const float* phi, int64_t frames, int H, int W, float dx, const float* g, float* dphi, bf_stream_t stream);
+/* The interface-weighted criterion (no reference program; csrc/losses.hip).  pred, y [frames][C][H][W] fp32 in the dataset's normalised units
+ * (frames = B * T in 1 .. 2^20, C in 1 .. 16, H and W in 1 .. 32768), 4-byte aligned; 16-byte loads where H * W is a multiple of 4 and pred, y
+ * (and dpred) sit at the same offset from a 16-byte boundary, scalars otherwise.  s in [0, C) is the channel of the signed distance, stored as
+ * (phi - diff_s) / div_s (div_s != 0).  With phi_t = y[f][s] * div_s + diff_s:
+ *   w[f][i]   = 1 + gain * max(0, 1 - |phi_t[i]| / band)     fp64, from the target alone, one weight for the C fields of a pixel
+ *               (gain >= 0 and finite; band > 0 in phi's units where gain > 0, not read where gain = 0)
+ *   S_e[f][c] = sum_i w (pred - y)^2,  S_y[f][c] = sum_i w y^2     fp64, added in a fixed order (no atomics: the same bits on every call)
+ *   terms[1 + c] = field_weights[c] * mean over f of sqrt(S_e / S_y)     quotient, root and mean in fp64, rounded once
+ *   terms[0]  = eikonal * mean over f, i of (|grad (pred[f][s] * div_s + diff_s)| - 1)^2, gradients as torch.gradient(spacing=dx, edge_order=1) in
+ *               fp64 on the channel where it lies inside pred (eikonal >= 0; 0 launches nothing for it and leaves terms[0] = 0; dx > 0 otherwise)
+ *   loss[0]   = sum_c terms[1 + c] + terms[0], added in fp64, rounded once.
+ * field_weights: C fp64 in HOST memory, finite and >= 0, read during the call; NULL = all 1.  loss (1 fp32), terms (1 + C fp32) and sums
+ * (2 * frames * C fp64: {S_e, S_y} per row, what bf_wlp_bwd reads) are DEVICE memory, sums and ws 8-byte aligned; ws: bf_wlp_ws_doubles(frames, C, H, W)
+ * doubles (-1: sizes out of range).  A row with S_y = 0 gives an inf or NaN ratio (and term, and loss), as the reference's quotient of norms
+ * does; a row with S_e = 0 gives the ratio 0.
+ * bf_wlp_bwd: dpred[f][c][i] = g[0] * field_weights[c] / frames * w * (pred - y) / sqrt(S_e S_y), the row coefficient in fp64 and every element rounded
+ * once; a row with S_e = 0 gets zeros.  With eikonal > 0 a second launch adds g[0] * d terms[0] / d pred to channel s (bf_eikonal_bwd's gather
+ * form with the chain factor div_s; a cell with |grad| = 0 contributes 0).  Every element of dpred is written, whatever the options; dpred may
+ * not overlap pred or y.  g = one fp32 in DEVICE memory.  The other arguments are those of the forward call that left `sums`.
+ * Every check runs before any HIP call. */
+int64_t bf_wlp_ws_doubles(int64_t frames, int C, int H, int W);
+int bf_wlp_fwd(const float* pred, const float* y, int64_t frames, int C, int H, int W, int s, double diff_s, double div_s, double band, double gain,
+               const double* field_weights, double eikonal, double dx, float* loss, float* terms, double* sums, double* ws, int64_t ws_doubles,
+               bf_stream_t stream);
+int bf_wlp_bwd(const float* pred, const float* y, const float* g, const double* sums, int64_t frames, int C, int H, int W, int s, double diff_s,
+               double div_s, double band, double gain, const double* field_weights, double eikonal, double dx, float* dpred, bf_stream_t stream);
 /* Gradient clipping without a host round trip (csrc/gradclip.hip).
  * bf_grad_norm: out = {norm, coef} (two fp32 in DEVICE memory) of the flat gradient buffer g[n] (fp32, 16-byte aligned, n > 0):
  *   norm = gscale * sqrt(sum g^2)   squares and sums in fp64, rounded once to fp32; gscale = the factor the optimizer applies to g

@@ -16,7 +16,13 @@ Both tensors together (151 MB) fit the 256 MiB Infinity Cache and the timed call
 working set that can stay in that cache, not of HBM; in a training step the prediction has just been written and the gradient is read next,
 which is the same situation.  `hbm_peak_share` divides by the 8 TB/s HBM figure all the same, as the other tools here do.
 
-Usage: python tools/losses_bench.py [--rounds R] [--reps K] [--step-reps K] [--no-step]"""
+`--interface` adds the interface-weighted criterion (utils.losses.InterfaceLpLoss, gain 4, band 0.5 in the units of its SDF channel, field
+weights 1 / 0.5 / 2 / 0.25) at the same shape, without and with its Eikonal penalty (2e-3): forward + backward call by call and as a graph
+replay, in one group with the native LpLoss of the training configuration (the data term moves LpLoss's bytes, so `*_over_lp_graph` is the
+price of the weight) and with the same weighted expression in stock torch ops; and one more whole training step,
+TrainStep(criterion=InterfaceLpLoss with the penalty), beside the other three.
+
+Usage: python tools/losses_bench.py [--rounds R] [--reps K] [--step-reps K] [--no-step] [--interface]"""
 import argparse
 import json
 import os
@@ -50,6 +56,22 @@ def eager_lp(d, p, reduce_dims, reductions):
 def eager_eikonal(phi):
     gy, gx = torch.gradient(phi, spacing=1 / 32, dim=(-2, -1), edge_order=1)
     return ((torch.sqrt(gy ** 2 + gx ** 2) - 1.0) ** 2).mean()
+
+
+INTERFACE = dict(sdf_channel=0, band=0.5, gain=4.0, diff=0.37, div=1.98, field_weights=(1.0, 0.5, 2.0, 0.25))
+INTERFACE_EIKONAL = 2e-3
+
+
+def eager_interface(sdf_channel, band, gain, diff, div, field_weights, eikonal, device):
+    """InterfaceLpLoss's expression in stock torch ops: the hat weight from the target, the weighted quotient per row, the field weights, the penalty."""
+    a = torch.tensor(field_weights, dtype=torch.float32, device=device)
+
+    def f(pred, y):
+        w = (1 + gain * (1 - (y[:, :, sdf_channel] * div + diff).abs() / band).clamp(min=0)).unsqueeze(2)
+        rho = ((w * (pred - y) ** 2).sum((-2, -1)) / (w * y ** 2).sum((-2, -1))).sqrt()
+        out = (rho.mean((0, 1)) * a).sum()
+        return out + eikonal * eager_eikonal(pred[:, :, sdf_channel] * div + diff) if eikonal > 0 else out
+    return f
 
 
 def timed(calls, rounds, reps):
@@ -133,16 +155,40 @@ def lp_group(kw, pred, y, rounds, reps, parts=False):
     return out
 
 
-def step_group(rounds, reps):
+def interface_group(pred, y, rounds, reps):
+    from bubbleformer_amd.utils import InterfaceLpLoss, LpLoss
+    kw = dict(INTERFACE)
+    s, band, gain = kw.pop("sdf_channel"), kw.pop("band"), kw.pop("gain")
+    variants = {"lp": LpLoss(**TRAINING), "interface": InterfaceLpLoss(s, band, gain, **kw),
+                "interface_eikonal": InterfaceLpLoss(s, band, gain, eikonal=INTERFACE_EIKONAL, **kw),
+                "eager_interface": eager_interface(eikonal=0.0, device=pred.device, **INTERFACE),
+                "eager_interface_eikonal": eager_interface(eikonal=INTERFACE_EIKONAL, device=pred.device, **INTERFACE)}
+    calls = {k + "_fwd_bwd": fwd_bwd(c, pred, y) for k, c in variants.items()}
+    calls.update({k + "_fwd_bwd_graph": graphed(c, pred, y) for k, c in variants.items()})
+    ms = timed(calls, rounds, reps)
+    out = {k: summary(t, 5 * pred.numel() * 4) for k, t in ms.items()}
+    med = {k: statistics.median(t) for k, t in ms.items()}
+    for tag in ("", "_graph"):
+        for k in ("interface", "interface_eikonal"):
+            out[f"{k}_over_lp{tag}"] = round(med[f"{k}_fwd_bwd{tag}"] / med[f"lp_fwd_bwd{tag}"], 3)
+            out[f"eager_over_native_{k}{tag}"] = round(med[f"eager_{k}_fwd_bwd{tag}"] / med[f"{k}_fwd_bwd{tag}"], 3)
+    return out
+
+
+def step_group(rounds, reps, interface=False):
     from bubbleformer_amd.models import get_model
     from bubbleformer_amd.trainer import TrainStep
-    from bubbleformer_amd.utils import LpLoss
+    from bubbleformer_amd.utils import InterfaceLpLoss, LpLoss
     g = torch.Generator(device="cuda").manual_seed(42)
     x = torch.randn(SHAPE, device="cuda", generator=g)
     y = torch.randn(SHAPE, device="cuda", generator=g)
     c = torch.randn((SHAPE[0], 9), device="cuda", generator=g)
     steps = {}
-    for name, crit in (("fused", None), ("native_criterion", LpLoss(**TRAINING)), ("eager_criterion", eager_lp(**TRAINING))):
+    legs = [("fused", None), ("native_criterion", LpLoss(**TRAINING)), ("eager_criterion", eager_lp(**TRAINING))]
+    if interface:
+        kw = dict(INTERFACE)
+        legs.append(("interface_criterion", InterfaceLpLoss(kw.pop("sdf_channel"), kw.pop("band"), kw.pop("gain"), eikonal=INTERFACE_EIKONAL, **kw)))
+    for name, crit in legs:
         torch.manual_seed(0)
         model = get_model("filmavit", time_window=SHAPE[1], drop_path=0.2, compute_dtype=torch.bfloat16, **SMALL).cuda().train()
         step = TrainStep(model, lr=2.5e-4, weight_decay=1e-2, criterion=crit)
@@ -150,6 +196,8 @@ def step_group(rounds, reps):
     ms = timed(steps, rounds, reps)
     out = {k: {"ms": round(statistics.median(t), 3), "ms_min": round(min(t), 3), "ms_max": round(max(t), 3)} for k, t in ms.items()}
     out["unfused_price_ms"] = round(statistics.median(ms["native_criterion"]) - statistics.median(ms["fused"]), 3)
+    if interface:
+        out["interface_price_ms"] = round(statistics.median(ms["interface_criterion"]) - statistics.median(ms["native_criterion"]), 3)
     return out
 
 
@@ -159,6 +207,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--step-reps", type=int, default=20, help="training steps per round (a step is tens of milliseconds)")
     ap.add_argument("--no-step", action="store_true", help="skip the whole-training-step comparison")
+    ap.add_argument("--interface", action="store_true", help="add the interface-weighted criterion's group and its training-step leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/losses_bench.py times GPU kernels: no GPU found"
     from bubbleformer_amd.utils import eikonal_loss
@@ -175,10 +224,12 @@ def main():
                args.rounds, args.reps)
     res["eikonal_one_channel"] = {k: summary(t, 3 * phi.numel() * 4) for k, t in ms.items()}
     res["eikonal_one_channel"]["eager_over_native"] = round(statistics.median(ms["eager_fwd_bwd"]) / statistics.median(ms["native_fwd_bwd"]), 3)
+    if args.interface:
+        res["interface"] = interface_group(pred, y, args.rounds, args.reps)
     if not args.no_step:
         del pred, y, phi
         torch.cuda.empty_cache()
-        res["train_step_filmavit_small_bf16_b8"] = step_group(args.rounds, args.step_reps)
+        res["train_step_filmavit_small_bf16_b8"] = step_group(args.rounds, args.step_reps, args.interface)
     print(json.dumps(res))
 
 
