@@ -855,6 +855,7 @@ extern "C" int bf_gemm_fwd_frames(int dtype, int M, int N, int K, const void* A,
     if (off || dtype != BF_DTYPE_BF16 || S != FM || !pair_shape_ok(M, N, K, lda, ldb) || K < 2 * PK) return 1;
     BF_REQUIRE(A && Bt && out, "bf_gemm_fwd_frames: null pointer");
     BF_REQUIRE(!colscale == !colshift, "bf_gemm_fwd_frames: column scale and shift come together");
+    if (fscale && !colscale) return 1;      // epi_lin applies the frame factor in its scaled form only: without the column tables it would be dropped
     if (((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)add | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)colscale | (uintptr_t)colshift) & 15) return 1;
     PairArgs a;
     memset(&a, 0, sizeof(a));

@@ -137,7 +137,8 @@ int bf_gemm_inbwd_frames_chain(int dtype, int M, int N, int K, const void* A, in
  * stage's opening norm of the last tensor written, n2->out = IN(.) * w + b (no g, no resid).  Each leaves mean / rstd / sc / sh [frames][N]
  * as bf_in_stats does.  Bt is the weight TRANSPOSED ([in][out], N contiguous).  Replaces bf_gemm + bf_in_stats (+ bf_affine_apply) -- one
  * read of the activation and one launch per norm less -- with identical bits.  Returns 0 when done, 1 when the shape is not covered
- * (bf16, S = 144, M % 288 = N % 128 = K % 64 = 0, K >= 128, 16-byte aligned operands), < 0 on error. */
+ * (bf16, S = 144, M % 288 = N % 128 = K % 64 = 0, K >= 128, 16-byte aligned operands, fscale only together with colscale / colshift),
+ * < 0 on error. */
 typedef struct bf_frame_norm {
     const float *w, *b;             /* affine [N] */
     const float* g; int32_t gdiv;   /* optional post scale [frames / gdiv][N] */

@@ -35,6 +35,10 @@ Statistics (`in_stats`; in_stats_kernel, in_stats_slice_kernel + in_stats_merge_
       e_M2 = sum_i [e_qi + n_i (2 |m_i - m| e_d + e_d^2)] + gamma_{N+4} sum_i [M2_i + e_qi + n_i (|m_i - m| + e_d)^2].
     `merge` takes slice partials as exact inputs (bf_in_stats_merge_slices, whose partials another kernel wrote): e_i = e_qi = 0.
 
+  carried input (`ex`, one-workgroup form; tests/frame_bounds.py: a norm behind a product that is never stored).  Rows within ex of x
+    have their mean within mean(ex) of m and -- centring being an orthogonal projection -- sqrt(M2) within ||ex||_2, so M2 moves by at
+    most 2 sqrt(M2) ||ex|| + ||ex||^2; the roundings above are then charged on the rows as carried (|x| + ex, M2 plus that).
+
 Apply (`affine_apply`).  t = fmaf(z, sc, sh): u |t|; + resid: u (|t| + |resid|); store.
 
 Backward (`in_bwd`; in_bwd_kernel, in_bwd_slice_kernel + in_slice_sum_kernel, in_reduce_block).  mean and rstd are the GIVEN fp32
@@ -47,6 +51,8 @@ a correct kernel computes; tests/test_norm_bounds.py proves it equals autograd a
     dyn = fl(dy d): e_dyn = |dy| e_d + u |dyn|.  Without GELU dyn = dy, exact.
   s1 = sum dyn, s2 = sum fl(dyn xh): e_s1 = sum e_dyn + gamma_n sum (|dyn| + e_dyn); e_s2 likewise on the products with their carried
     operand errors, n + 1 for the product's rounding.  n = S rows, plus the slice count on the sliced path.
+  A gradient that is itself within e_dy of dy (`e_dy`; a fused producer's fp32 accumulator) starts e_dyn at e_dy (behind a GELU: plus
+    e_dy (|d| + e_d)); everything below carries it.
   dx.  The one-workgroup kernel forms dyn - (s1 + xh s2) / S (4 roundings), the sliced kernel dyn - s1/S - xh (s2/S) (5).  Each
     rounding is charged u on the magnitude sum Mg = |dyn| + |s1| / S + |xh s2| / S plus the carried error E, not on the cancelled
     result: E_I = E + 5u (Mg + E), E = e_dyn + e_s1 / S + (e_xh |s2| + |xh| e_s2 + e_xh e_s2) / S.  Then P = rs w g and P I: k = 2
@@ -117,14 +123,22 @@ def colsum_split(nrows, C):
 
 
 # ---------------------------------------------------------------------------------------------------- statistics
-def _moments(x):
-    """x (..., n, C) -> exact mean, M2, the mean's error bound and the second moment's, for one workgroup's two passes."""
+def _moments(x, ex=None):
+    """x (..., n, C) -> exact mean, M2, the mean's error bound and the second moment's, for one workgroup's two passes.  ex: elementwise
+    bound on a deviation the kernel's rows carry from x (None: they are x)."""
     n = x.shape[-2]
     m = x.mean(-2)
     M2 = ((x - m.unsqueeze(-2)) ** 2).sum(-2)
-    e_m = (1 + U32) * gamma(n) * x.abs().sum(-2) / n + U32 * m.abs()
-    e_q = n * e_m ** 2 + gamma(n + 3) * (M2 + n * e_m ** 2)
-    return m, M2, e_m, e_q
+    if ex is None:
+        e_m = (1 + U32) * gamma(n) * x.abs().sum(-2) / n + U32 * m.abs()
+        e_q = n * e_m ** 2 + gamma(n + 3) * (M2 + n * e_m ** 2)
+        return m, M2, e_m, e_q
+    dm = ex.sum(-2) / n                                   # the rows' own mean moves by at most this
+    d2 = (ex ** 2).sum(-2).sqrt()
+    dM2 = 2 * M2.sqrt() * d2 + d2 ** 2                    # centring is an orthogonal projection: |sqrt M2' - sqrt M2| <= ||ex||
+    e_r = (1 + U32) * gamma(n) * (x.abs() + ex).sum(-2) / n + U32 * (m.abs() + dm)      # the roundings, on the rows as carried
+    e_q = n * e_r ** 2 + gamma(n + 3) * (M2 + dM2 + n * e_r ** 2)
+    return m, M2, e_r + dm, e_q + dM2
 
 
 def _merge(mi, ei, qi, eqi, ni, S):
@@ -165,13 +179,15 @@ def _finish_stats(m, M2, e_mu, e_M2, S, w, b, g, gb):
     return dict(mean=(m, e_mu), rstd=(r, e_r), sc=(a, e_a), sh=(s, e_s))
 
 
-def in_stats(x, w, b, g=None, gb=None, slices=None):
+def in_stats(x, w, b, g=None, gb=None, slices=None, ex=None):
     """x (F, S, C) exact stored values; w / b (C,) fp32; g / gb (F, C) fp32, already expanded per frame (g[f // gdiv]); slices: rows per
-    slice on the sliced path, None for one workgroup per frame -> {"mean" | "rstd" | "sc" | "sh": (ref, bnd)}, each (F, C)."""
+    slice on the sliced path, None for one workgroup per frame; ex (F, S, C), one-workgroup form only: the rows the kernel sums are within
+    ex of x (a producer's error carried in; absent: they are x) -> {"mean" | "rstd" | "sc" | "sh": (ref, bnd)}, each (F, C)."""
     x = x.double()
     S = x.shape[1]
+    assert ex is None or slices is None
     if slices is None:
-        m, M2, e_mu, e_M2 = _moments(x)
+        m, M2, e_mu, e_M2 = _moments(x, None if ex is None else ex.double())
     else:
         parts = [_moments(x[:, s0:s0 + slices]) for s0 in range(0, S, slices)]
         ni = torch.tensor([min(slices, S - s0) for s0 in range(0, S, slices)])
@@ -208,9 +224,10 @@ def affine_apply(z, sc, sh=None, resid=None, bf16=False):
 
 
 # ---------------------------------------------------------------------------------------------------- backward
-def in_bwd(dy, x, mean, rstd, w, b, g=None, add=None, gelu=False, bf16=False, nslices=0):
+def in_bwd(dy, x, mean, rstd, w, b, g=None, add=None, gelu=False, bf16=False, nslices=0, e_dy=None):
     """dy / x / add (F, S, C) exact; mean / rstd (F, C) the given fp32 statistics; w / b (C,); g (F, C) already expanded per frame.
-    nslices: backward slices on the sliced path, 0 otherwise.
+    nslices: backward slices on the sliced path, 0 otherwise.  e_dy (F, S, C): the gradient the kernel holds is within e_dy of dy (a fused
+    producer's accumulator; absent: it is dy).
     -> {"dx": (ref, bnd) (F, S, C), "s1" | "s2": (ref, bnd) (F, C) the per-frame sums the parameter gradients are made of}."""
     dy, x = dy.double(), x.double()
     S = x.shape[1]
@@ -225,8 +242,10 @@ def in_bwd(dy, x, mean, rstd, w, b, g=None, add=None, gelu=False, bf16=False, ns
         e_d = e_d + L_DGELU * e_z
         dyn = dy * d
         e_dyn = dy.abs() * e_d + U32 * dyn.abs()
+        if e_dy is not None:
+            e_dyn = e_dyn + e_dy.double() * (d.abs() + e_d) * (1 + U32)
     else:
-        dyn, e_dyn = dy, torch.zeros_like(dy)
+        dyn, e_dyn = dy, (torch.zeros_like(dy) if e_dy is None else e_dy.double())
     n = S + nslices
     s1 = dyn.sum(1)
     e_s1 = e_dyn.sum(1) + gamma(n) * (dyn.abs() + e_dyn).sum(1)
