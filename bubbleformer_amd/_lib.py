@@ -283,6 +283,9 @@ SIGNATURES = {
                              C.c_double, fp, fp, vp, vp, i64, vp]),
     "bf_wlp_bwd": (C.c_int, [fp, fp, fp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, P(C.c_double),
                              C.c_double, C.c_double, fp, vp]),
+    "bf_slp_ws_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
+    "bf_slp_fwd": (C.c_int, [fp, fp, i64, C.c_int, C.c_int, C.c_int, vp, P(C.c_double), C.c_int, P(C.c_double), fp, fp, vp, vp, vp, i64, vp]),
+    "bf_slp_bwd": (C.c_int, [vp, fp, vp, i64, C.c_int, C.c_int, C.c_int, P(C.c_double), fp, vp]),
     "bf_temporal_saved_bytes": (i64, [P(Dims)]),
     "bf_spatial_saved_bytes": (i64, [P(Dims)]),
     "bf_embed_saved_bytes": (i64, [P(Dims)]),

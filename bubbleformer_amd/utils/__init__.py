@@ -1,5 +1,5 @@
 from .lr_schedulers import CosineWarmupLR  # noqa: F401
-from .losses import InterfaceLpLoss, LpLoss, eikonal_loss  # noqa: F401
+from .losses import InterfaceLpLoss, LpLoss, SpectralLpLoss, eikonal_loss  # noqa: F401
 from .noise import NoiseSpec, add_gaussian_noise  # noqa: F401
 from .augment import AugmentSpec, augment_plan  # noqa: F401
 from .physics import BubbleCensus, BubbleSpec, BubbleTracks, HeaterSpec, bubble_census, bubble_tracks, heatflux_series, kde_kl_divergence  # noqa: F401

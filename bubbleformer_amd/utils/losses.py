@@ -5,7 +5,8 @@ in csrc/losses.hip (bf_lp_rows_fwd / bf_lp_rows_bwd), the reductions over the le
 per-row ratios.  ``eikonal_loss`` is `physics.eikonal_loss` with a backward (bf_eikonal_bwd).  ``InterfaceLpLoss`` (no reference
 program) is the training configuration of LpLoss with a pixel weight around the target's liquid-vapour interface, a weight per field and an
 optional Eikonal penalty, forward and backward in their own kernels (bf_wlp_fwd / bf_wlp_bwd).  Inputs are fp32 tensors on the GPU; there
-is no CPU path.
+is no CPU path.  ``SpectralLpLoss`` (no reference program) is the same relative L2 taken in Fourier space with a weight per radial shell and
+field, on fp32 transforms of its own (csrc/spectral_loss.hip: bf_slp_fwd / bf_slp_bwd).
 """
 import math
 from typing import List, Union
@@ -300,3 +301,179 @@ class InterfaceLpLoss(nn.Module):
     def eikonal_term(self) -> torch.Tensor:
         """The Eikonal penalty of the last forward (0 where eikonal = 0): a 0-dim fp32 tensor on the device."""
         return self._last()[0].clone()
+
+
+_SLP_WS_BYTES = {}      # (frames, C, H, W) -> bf_slp_ws_bytes
+
+
+class _SpectralLpFn(torch.autograd.Function):
+    """(pred, y) -> the scalar of SpectralLpLoss; the criterion keeps the terms the forward left on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, y, crit):
+        import ctypes
+        B, T, Cn, H, W = pred.shape
+        frames = B * T
+        pred, y = pred.contiguous(), y.contiguous()
+        lib = L.lib()
+        nws = _SLP_WS_BYTES.get((frames, Cn, H, W))
+        if nws is None:
+            nws = _SLP_WS_BYTES[(frames, Cn, H, W)] = lib.bf_slp_ws_bytes(frames, Cn, H, W)
+        if nws < 0:
+            raise L.BubbleformerHipError(f"SpectralLpLoss: {frames} frames of {Cn} x {H} x {W} are out of range (a side may be at most 1024)")
+        table, host = crit._tables(Cn, pred.device)
+        a = crit.field_weights
+        weights = (ctypes.c_double * Cn)(*a) if a is not None else None      # read by the library during the call only
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        terms = torch.empty(2 * Cn, dtype=torch.float32, device=pred.device)
+        sums = torch.empty(2 * frames * Cn, dtype=torch.float64, device=pred.device)
+        spec = torch.empty((frames * Cn, H, W // 2 + 1, 2), dtype=torch.float32, device=pred.device)      # the one saved intermediate
+        ws = torch.empty(nws, dtype=torch.uint8, device=pred.device)
+        L.check(lib.bf_slp_fwd(pred.data_ptr(), y.data_ptr(), frames, Cn, H, W, table.data_ptr(), host, table.shape[1], weights, loss.data_ptr(),
+                               terms.data_ptr(), sums.data_ptr(), spec.data_ptr(), ws.data_ptr(), nws, _stream()), "bf_slp_fwd")
+        ctx.save_for_backward(spec, sums)
+        ctx.args = (frames, Cn, H, W, weights)
+        ctx.like = (pred.shape, (pred.data_ptr() % 16) // 4, pred.device)      # the gradient's shape and offset: pred itself is not kept
+        crit._terms = terms
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        spec, sums = ctx.saved_tensors
+        g = g.contiguous().float().reshape(1)
+        shape, off, device = ctx.like
+        dpred = torch.empty(math.prod(shape) + off, dtype=torch.float32, device=device)[off:].view(shape)
+        L.check(L.lib().bf_slp_bwd(spec.data_ptr(), g.data_ptr(), sums.data_ptr(), *ctx.args, dpred.data_ptr(), _stream()), "bf_slp_bwd")
+        return dpred, None, None
+
+
+class SpectralLpLoss(nn.Module):
+    """The relative L2 of LpLoss's training configuration taken in Fourier space, with one weight per radial shell and per field -- a native
+    criterion for ``TrainStep(criterion=...)`` / ``fit(criterion=...)`` (csrc/spectral_loss.hip: bf_slp_fwd / bf_slp_bwd; no reference program;
+    DESIGN.md section 30).
+
+    pred, y: (B, T, C, H, W) fp32 on the GPU in normalised units; y never requires a gradient.  With E, Y the unnormalised 2-D DFTs of
+    pred - y and y, and q(k) the shell of mode k as ``physics.field_errors`` counts it (``physics.shell_count(H, W)`` = K shells; the rows of
+    ``spectrum_*`` index the same shells as this table):
+        S_e  = sum_k w[c][q(k)] |E_k|^2 / (H W),   S_y the same sum over Y,   rho = sqrt(S_e / S_y)      per (b, t, c)
+        L    = sum_c field_weights[c] * mean_{b,t} rho
+    ``shell_weights`` is a (C, K) table of weights >= 0 (a (K,) table is broadcast over the fields; a field whose table is all zero is refused).
+    w = 1 and unit field weights give ``LpLoss(d=2, p=2, reduce_dims=[0, 1, 2], reductions=["mean", "mean", "sum"])`` up to the transform's
+    rounding.  The criterion is bound to the grid whose shell count its table has (``grid=(H, W)``, or the first grid it meets); another grid
+    is refused.
+
+    The transforms are fp32, every sum fp64 in a fixed order: two calls give the same bits.  The fp32 noise floor of a transform is about
+    eta^2 of a field's TOTAL power, eta = (8 log2(H W) + ...) 2^-24 (7e-6 at 192 x 192): weights whose range approaches 1 / eta^2 make S_y of a
+    smooth target noise-dominated.  The forward saves one intermediate for the backward, frames * H * (W/2 + 1) * 8 bytes with frames =
+    B * T * C (76 MB at (8, 16, 4, 192, 192)), per pass of an unrolled step.
+
+    ``gain``, ``power`` and ``floor`` of the constructors below have no defaults: no value has been validated by a training run.
+    ``field_terms()`` returns the C values ``field_weights[c] * mean rho`` of the last forward, ``plain_terms()`` the same at w = 1 (the plain
+    relative L2, for monitoring), as device tensors (clones; no host synchronisation)."""
+
+    def __init__(self, shell_weights, *, field_weights=None, grid=None):
+        super().__init__()
+        w = torch.as_tensor(shell_weights).detach().to("cpu", torch.float64).contiguous()
+        if w.dim() == 1:
+            w = w[None]
+        if w.dim() != 2 or w.shape[1] == 0 or w.shape[0] == 0:
+            raise ValueError(f"SpectralLpLoss: shell weights must be a (K,) or (C, K) table; got {tuple(w.shape)}")
+        if not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise ValueError("SpectralLpLoss: shell weights must be finite and >= 0")
+        if not bool((w > 0).any(dim=1).all()):
+            raise ValueError("SpectralLpLoss: a field's shell weights are all zero")
+        if field_weights is not None:
+            field_weights = tuple(float(a) for a in field_weights)
+            if not all(math.isfinite(a) and a >= 0.0 for a in field_weights):
+                raise ValueError(f"SpectralLpLoss: field weights {field_weights} must be finite and >= 0")
+            if w.shape[0] not in (1, len(field_weights)):
+                raise ValueError(f"SpectralLpLoss: {len(field_weights)} field weights for a table of {w.shape[0]} fields")
+        if grid is not None:
+            from .physics import shell_count
+            grid = (int(grid[0]), int(grid[1]))
+            if shell_count(*grid) != w.shape[1]:
+                raise ValueError(f"SpectralLpLoss: a {grid[0]} x {grid[1]} grid has {shell_count(*grid)} shells; the table has {w.shape[1]}")
+        self.shell_weights, self.field_weights, self.grid = w, field_weights, grid
+        self._device_tables = {}      # (device, C) -> ((C, K) fp64 on the device, the same table as a ctypes array); made once, never moved
+        self._terms = None
+
+    @classmethod
+    def power_law(cls, H: int, W: int, gain: float, power: float, C=None, *, field_weights=None):
+        """w[q] = 1 + gain * (q / (K - 1))^power on the shells of an H x W grid, the same for every field (C: the number of rows, None = one
+        row that is broadcast).  gain >= 0 and power > 0; neither has a default."""
+        from .physics import shell_count
+        gain, power = float(gain), float(power)
+        if not (math.isfinite(gain) and gain >= 0.0 and math.isfinite(power) and power > 0.0):
+            raise ValueError(f"SpectralLpLoss: gain = {gain!r} must be finite and >= 0, power = {power!r} finite and > 0")
+        K = shell_count(H, W)
+        q = torch.arange(K, dtype=torch.float64) / max(K - 1, 1)
+        w = 1.0 + gain * q ** power
+        return cls(w if C is None else w[None].repeat(int(C), 1), field_weights=field_weights, grid=(H, W))
+
+    @classmethod
+    def from_spectrum(cls, spectrum_target, floor: float, *, field_weights=None, grid=None):
+        """Whitening weights from a measured target spectrum P_y (C, K) or (K,) -- the mean over frames of
+        ``physics.field_errors(...).spectrum_target``: w[c][q] proportional to 1 / max(P_y[c][q], floor * max_q P_y[c]), scaled so that
+        sum_q w P_y = sum_q P_y (a target with that spectrum keeps its S_y).  0 < floor <= 1; it has no default."""
+        floor = float(floor)
+        if not (math.isfinite(floor) and 0.0 < floor <= 1.0):
+            raise ValueError(f"SpectralLpLoss: floor = {floor!r} must lie in (0, 1]")
+        P = torch.as_tensor(spectrum_target).detach().to("cpu", torch.float64)
+        if P.dim() == 1:
+            P = P[None]
+        if P.dim() != 2 or not bool((torch.isfinite(P) & (P >= 0)).all()) or not bool((P.amax(dim=1) > 0).all()):
+            raise ValueError("SpectralLpLoss: the target spectrum must be a finite (K,) or (C, K) table >= 0 with power in every field")
+        w = 1.0 / torch.maximum(P, floor * P.amax(dim=1, keepdim=True))
+        w = w * (P.sum(dim=1, keepdim=True) / (w * P).sum(dim=1, keepdim=True))
+        return cls(w, field_weights=field_weights, grid=grid)
+
+    def _tables(self, Cn: int, device):
+        key = (str(device), Cn)
+        got = self._device_tables.get(key)
+        if got is None:
+            import ctypes
+            w = self.shell_weights
+            if w.shape[0] not in (1, Cn):
+                raise L.BubbleformerHipError(f"SpectralLpLoss: a table of {w.shape[0]} fields for {Cn} fields")
+            if self.field_weights is not None and len(self.field_weights) != Cn:
+                raise L.BubbleformerHipError(f"SpectralLpLoss: {len(self.field_weights)} field weights for {Cn} fields")
+            full = w.expand(Cn, w.shape[1]).contiguous()
+            got = self._device_tables[key] = (full.to(device), (ctypes.c_double * full.numel())(*full.flatten().tolist()))
+        return got
+
+    def forward(self, pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        _require_gpu_f32(pred, "SpectralLpLoss")
+        _require_gpu_f32(y, "SpectralLpLoss")
+        if y.requires_grad and torch.is_grad_enabled():
+            raise L.BubbleformerHipError("SpectralLpLoss: a gradient w.r.t. the target is not implemented (the target must not require grad)")
+        if pred.shape != y.shape:
+            raise L.BubbleformerHipError(f"SpectralLpLoss: prediction {tuple(pred.shape)} and target {tuple(y.shape)} differ in shape")
+        if pred.dim() != 5:
+            raise L.BubbleformerHipError(f"SpectralLpLoss expects (B, T, C, H, W); got {tuple(pred.shape)}")
+        if pred.numel() == 0:
+            raise L.BubbleformerHipError("SpectralLpLoss: empty input")
+        from .physics import shell_count
+        H, W = pred.shape[-2:]
+        K = self.shell_weights.shape[1]
+        if (self.grid is not None and (H, W) != self.grid) or shell_count(H, W) != K:
+            bound = f"the {self.grid[0]} x {self.grid[1]} grid" if self.grid is not None else "a grid"
+            raise L.BubbleformerHipError(f"SpectralLpLoss: the table is bound to {bound} of {K} shells; got {H} x {W} ({shell_count(H, W)} shells)")
+        self._tables(pred.shape[2], pred.device)      # refuses a wrong number of fields before the grid is bound
+        if self.grid is None:
+            self.grid = (H, W)
+        return _SpectralLpFn.apply(pred, y, self)
+
+    def _last(self) -> torch.Tensor:
+        if self._terms is None:
+            raise L.BubbleformerHipError("SpectralLpLoss: no forward has run yet")
+        return self._terms
+
+    def field_terms(self) -> torch.Tensor:
+        """(C,) fp32 on the device: field_weights[c] * mean_{b,t} rho[b, t, c] of the last forward."""
+        t = self._last()
+        return t[:t.numel() // 2].clone()
+
+    def plain_terms(self) -> torch.Tensor:
+        """(C,) fp32 on the device: the same terms at w = 1, the plain relative L2 per field of the last forward."""
+        t = self._last()
+        return t[t.numel() // 2:].clone()

@@ -35,6 +35,7 @@
  *   bf_eikonal_sum / bf_heatflux_rows .. eikonal_loss utils/losses.py:5-15, heatflux utils/heatflux.py:3-38
  *   bf_lp_rows_* / bf_eikonal_bwd .. LpLoss.forward for any d / p (and its autograd) utils/losses.py:67-94; autograd of eikonal_loss utils/losses.py:5-15
  *   bf_wlp_* ................. the interface-weighted criterion: a hat weight around the target's zero level set, field weights, Eikonal penalty (no reference program)
+ *   bf_slp_* ................. the shell-weighted spectral criterion: one weight per radial shell and field on |FFT|^2, field weights (no reference program)
  *   bf_rollout_score ......... the evaluation loop's scores of one step: scripts/inference.py:230-266, utils/plot_utils.py:30-33
  *   bf_rollout_heatflux ...... heatflux utils/heatflux.py:3-38 per step of that loop; bf_kde_kl: examples/data_visualization.ipynb cell 4
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
@@ -713,6 +714,30 @@ int bf_wlp_fwd(const float* pred, const float* y, int64_t frames, int C, int H, 
                bf_stream_t stream);
 int bf_wlp_bwd(const float* pred, const float* y, const float* g, const double* sums, int64_t frames, int C, int H, int W, int s, double diff_s,
                double div_s, double band, double gain, const double* field_weights, double eikonal, double dx, float* dpred, bf_stream_t stream);
+/* The shell-weighted spectral criterion (no reference program; csrc/spectral_loss.hip).  pred, y [frames][C][H][W] fp32 in
+ * normalised units (frames = B * T in 1 .. 2^20, C in 1 .. 16, H and W in 1 .. 1024), 4-byte aligned, read as scalars.  With X(ky, kx) the
+ * unnormalised 2-D DFT, q(ky, kx) the shell of bf_field_errors (signed frequencies folded at H/2, W/2; S = min(H, W); the largest q with
+ * q^2 H^2 W^2 <= S^2 (fy^2 W^2 + fx^2 H^2) in int64) and K = isqrt(S^2 / 2) + 1 shells:
+ *   S_e[f][c] = sum_k w[c][q(k)] |E_k|^2 / (H W),  E = DFT(pred - y);  S_y the same sum over DFT(y)      fp32 transforms, fp64 sums in a fixed order
+ *   terms[c]     = field_weights[c] * mean over f of sqrt(S_e / S_y)       quotient, root and mean in fp64, rounded once
+ *   terms[C + c] = the same at w = 1 (the plain relative L2, for monitoring)
+ *   loss[0]      = sum_c terms[c], added in fp64, rounded once.
+ * shell_weights: the (C, K) table of doubles in DEVICE memory, 8-byte aligned, read by the kernels; shell_weights_host: the same table in HOST
+ * memory, read during the call for the checks only (every weight finite and >= 0, no field's row all zero); K must be the shell count of (H, W).
+ * Nothing in the library compares the two tables (that would take a copy from the device, and no HIP call precedes the checks): that they hold the
+ * same values is the CALLER's duty.  utils.losses.SpectralLpLoss builds both from one host tensor, once per device, and never writes either again.
+ * field_weights: C fp64 in HOST memory, finite and >= 0, read during the call; NULL = all 1.  loss (1 fp32), terms (2 C fp32), sums (2 * frames * C
+ * fp64: {S_e, S_y} per row) and spec (frames * C * H * (W/2 + 1) * 8 bytes, 8-byte aligned: the filtered half-spectrum of the error, inverse-
+ * transformed along y -- with sums, all bf_slp_bwd reads) are DEVICE memory; ws: bf_slp_ws_bytes(frames, C, H, W) bytes, 16-byte aligned
+ * (-1: sizes out of range).  A row with S_y = 0 gives an inf or NaN ratio, as the quotient of norms does; a row with S_e = 0 gives the ratio 0.
+ * bf_slp_bwd: dpred[f][c] = g[0] * field_weights[c] / frames * Re ifft2(w E) / sqrt(S_e S_y), the row coefficient in fp64, every element
+ * written and rounded once; a row with S_e = 0 gets zeros.  g = one fp32 in DEVICE memory; dpred may not overlap spec.  The other arguments
+ * are those of the forward call that left `sums` and `spec`.  Every check runs before any HIP call. */
+int64_t bf_slp_ws_bytes(int64_t frames, int C, int H, int W);
+int bf_slp_fwd(const float* pred, const float* y, int64_t frames, int C, int H, int W, const double* shell_weights, const double* shell_weights_host,
+               int K, const double* field_weights, float* loss, float* terms, double* sums, void* spec, void* ws, int64_t ws_bytes, bf_stream_t stream);
+int bf_slp_bwd(const void* spec, const float* g, const double* sums, int64_t frames, int C, int H, int W, const double* field_weights, float* dpred,
+               bf_stream_t stream);
 /* Gradient clipping without a host round trip (csrc/gradclip.hip).
  * bf_grad_norm: out = {norm, coef} (two fp32 in DEVICE memory) of the flat gradient buffer g[n] (fp32, 16-byte aligned, n > 0):
  *   norm = gscale * sqrt(sum g^2)   squares and sums in fp64, rounded once to fp32; gscale = the factor the optimizer applies to g

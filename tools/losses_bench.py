@@ -22,7 +22,14 @@ replay, in one group with the native LpLoss of the training configuration (the d
 price of the weight) and with the same weighted expression in stock torch ops; and one more whole training step,
 TrainStep(criterion=InterfaceLpLoss with the penalty), beside the other three.
 
-Usage: python tools/losses_bench.py [--rounds R] [--reps K] [--step-reps K] [--no-step] [--interface]"""
+`--spectral` adds the shell-weighted spectral criterion (utils.losses.SpectralLpLoss, w = 1 + 100 (q / (K - 1))^2, field weights 1 / 0.5 / 2 /
+0.25) at the same shape under the same protocol: forward + backward call by call and as a graph replay, in one group with the native LpLoss
+of the training configuration and with the same expression in stock torch ops in fp32 (torch.fft.rfft2, an index by shell, and the irfft2
+of its autograd backward: the rocFFT route); and one more whole training step, TrainStep(criterion=SpectralLpLoss), beside the others.
+Bytes of the native call: the forward reads both tensors and writes and re-reads both half-spectra (and the error's once more, filtered), the
+backward reads the saved half-spectrum and writes the gradient: 2 + 5 x 1.01 + 1.01 + 1 = 9.1 tensors of 75.5 MB.
+
+Usage: python tools/losses_bench.py [--rounds R] [--reps K] [--step-reps K] [--no-step] [--interface] [--spectral]"""
 import argparse
 import json
 import os
@@ -72,6 +79,60 @@ def eager_interface(sdf_channel, band, gain, diff, div, field_weights, eikonal, 
         out = (rho.mean((0, 1)) * a).sum()
         return out + eikonal * eager_eikonal(pred[:, :, sdf_channel] * div + diff) if eikonal > 0 else out
     return f
+
+
+SPECTRAL = dict(gain=100.0, power=2.0, field_weights=(1.0, 0.5, 2.0, 0.25))
+
+
+def shell_table_half(H, W):
+    """(H, W // 2 + 1) int64: the shell of mode (ky, kx <= W / 2), DESIGN.md section 18's rule in Python integers."""
+    import math
+    S = min(H, W)
+    rows = []
+    for ky in range(H):
+        fy = ky if ky <= H // 2 else ky - H
+        rows.append([math.isqrt(S * S * (fy * fy * W * W + fx * fx * H * H) // (H * H * W * W)) for fx in range(W // 2 + 1)])
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def eager_spectral(shell_weights, field_weights, H, W, device):
+    """SpectralLpLoss's expression in stock torch ops, fp32: rfft2, the weight of every mode by an index into the table, the Hermitian half
+    counted twice where it is mirrored; autograd's backward runs the irfft2."""
+    wm = shell_weights.to(device, torch.float32)[:, shell_table_half(H, W).to(device)]
+    kx = torch.arange(W // 2 + 1, device=device)
+    wm = wm * torch.where((kx == 0) | (2 * kx == W), 1.0, 2.0).to(torch.float32)
+    a = torch.tensor(field_weights, dtype=torch.float32, device=device)
+
+    def f(pred, y):
+        E, Y = torch.fft.rfft2(pred - y), torch.fft.rfft2(y)
+        se, sy = (wm * (E.real ** 2 + E.imag ** 2)).sum((-2, -1)), (wm * (Y.real ** 2 + Y.imag ** 2)).sum((-2, -1))
+        return ((se / sy).sqrt().mean((0, 1)) * a).sum()
+    return f
+
+
+def spectral_criterion():
+    from bubbleformer_amd.utils import SpectralLpLoss
+    return SpectralLpLoss.power_law(SHAPE[-2], SHAPE[-1], SPECTRAL["gain"], SPECTRAL["power"], C=SHAPE[2], field_weights=SPECTRAL["field_weights"])
+
+
+def spectral_group(pred, y, rounds, reps):
+    from bubbleformer_amd.utils import LpLoss
+    crit = spectral_criterion()
+    variants = {"lp": LpLoss(**TRAINING), "spectral": crit,
+                "eager_spectral": eager_spectral(crit.shell_weights, SPECTRAL["field_weights"], SHAPE[-2], SHAPE[-1], pred.device)}
+    calls = {k + "_fwd_bwd": fwd_bwd(c, pred, y) for k, c in variants.items()}
+    calls.update({k + "_fwd_bwd_graph": graphed(c, pred, y) for k, c in variants.items()})
+    ms = timed(calls, rounds, reps)
+    tensor = pred.numel() * 4
+    half = (SHAPE[-1] // 2 + 1) * 2 / SHAPE[-1]
+    nbytes = {k: (3 + 6 * half) * tensor if "spectral" in k else 5 * tensor for k in calls}
+    out = {k: summary(t, nbytes[k]) for k, t in ms.items()}
+    out["saved_intermediate_MB"] = round(half * tensor / 1e6, 1)
+    med = {k: statistics.median(t) for k, t in ms.items()}
+    for tag in ("", "_graph"):
+        out[f"spectral_over_lp{tag}"] = round(med[f"spectral_fwd_bwd{tag}"] / med[f"lp_fwd_bwd{tag}"], 3)
+        out[f"eager_over_native_spectral{tag}"] = round(med[f"eager_spectral_fwd_bwd{tag}"] / med[f"spectral_fwd_bwd{tag}"], 3)
+    return out
 
 
 def timed(calls, rounds, reps):
@@ -175,7 +236,7 @@ def interface_group(pred, y, rounds, reps):
     return out
 
 
-def step_group(rounds, reps, interface=False):
+def step_group(rounds, reps, interface=False, spectral=False):
     from bubbleformer_amd.models import get_model
     from bubbleformer_amd.trainer import TrainStep
     from bubbleformer_amd.utils import InterfaceLpLoss, LpLoss
@@ -188,6 +249,8 @@ def step_group(rounds, reps, interface=False):
     if interface:
         kw = dict(INTERFACE)
         legs.append(("interface_criterion", InterfaceLpLoss(kw.pop("sdf_channel"), kw.pop("band"), kw.pop("gain"), eikonal=INTERFACE_EIKONAL, **kw)))
+    if spectral:
+        legs.append(("spectral_criterion", spectral_criterion()))
     for name, crit in legs:
         torch.manual_seed(0)
         model = get_model("filmavit", time_window=SHAPE[1], drop_path=0.2, compute_dtype=torch.bfloat16, **SMALL).cuda().train()
@@ -198,6 +261,8 @@ def step_group(rounds, reps, interface=False):
     out["unfused_price_ms"] = round(statistics.median(ms["native_criterion"]) - statistics.median(ms["fused"]), 3)
     if interface:
         out["interface_price_ms"] = round(statistics.median(ms["interface_criterion"]) - statistics.median(ms["native_criterion"]), 3)
+    if spectral:
+        out["spectral_price_ms"] = round(statistics.median(ms["spectral_criterion"]) - statistics.median(ms["native_criterion"]), 3)
     return out
 
 
@@ -208,6 +273,7 @@ def main():
     ap.add_argument("--step-reps", type=int, default=20, help="training steps per round (a step is tens of milliseconds)")
     ap.add_argument("--no-step", action="store_true", help="skip the whole-training-step comparison")
     ap.add_argument("--interface", action="store_true", help="add the interface-weighted criterion's group and its training-step leg")
+    ap.add_argument("--spectral", action="store_true", help="add the shell-weighted spectral criterion's group and its training-step leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "tools/losses_bench.py times GPU kernels: no GPU found"
     from bubbleformer_amd.utils import eikonal_loss
@@ -226,10 +292,12 @@ def main():
     res["eikonal_one_channel"]["eager_over_native"] = round(statistics.median(ms["eager_fwd_bwd"]) / statistics.median(ms["native_fwd_bwd"]), 3)
     if args.interface:
         res["interface"] = interface_group(pred, y, args.rounds, args.reps)
+    if args.spectral:
+        res["spectral"] = spectral_group(pred, y, args.rounds, args.reps)
     if not args.no_step:
         del pred, y, phi
         torch.cuda.empty_cache()
-        res["train_step_filmavit_small_bf16_b8"] = step_group(args.rounds, args.step_reps, args.interface)
+        res["train_step_filmavit_small_bf16_b8"] = step_group(args.rounds, args.step_reps, args.interface, args.spectral)
     print(json.dumps(res))
 
 
