@@ -96,6 +96,11 @@ class LinkRows(C.Structure):
     _fields_ = [(n, vp) for n in ("successor", "n_successors", "predecessor", "n_predecessors", "departure_area", "events")]
 
 
+class MatchRows(C.Structure):
+    """bf_match_rows: bf_bubble_match's six outputs, all required."""
+    _fields_ = [(n, vp) for n in ("match_pred", "match_target", "overlap", "displacement", "counts", "mask")]
+
+
 class ErrorRows(C.Structure):
     _fields_ = [(n, vp) for n in ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error",
                                   "spectrum_pred", "spectrum_target")]
@@ -265,6 +270,9 @@ SIGNATURES = {
     "bf_bubble_links": (C.c_int, [vp, P(CensusRows), i64, C.c_int, C.c_int, C.c_int, C.c_int, P(LinkRows), vp, i64, vp]),
     "bf_bubble_track_ids": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp]),
     "bf_rollout_bubble_links": (C.c_int, [P(RolloutStep), C.c_int, vp, P(CensusRows), P(CensusRows), P(LinkRows), P(LinkRows), vp, i64, vp]),
+    "bf_bubble_match_ws_bytes": (i64, [i64, C.c_int]),
+    "bf_bubble_match": (C.c_int, [vp, vp, P(CensusRows), P(CensusRows), i64, C.c_int, C.c_int, C.c_int, C.c_float, P(MatchRows), vp, i64, vp]),
+    "bf_rollout_bubble_match": (C.c_int, [P(RolloutStep), C.c_int, C.c_float, vp, P(CensusRows), P(CensusRows), P(MatchRows), vp, i64, vp]),
     "bf_field_errors_ws_bytes": (i64, [i64, C.c_int, C.c_int]),
     "bf_field_errors": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),
     "bf_rollout_errors": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(ErrorRows), vp, i64, vp]),

@@ -1412,6 +1412,90 @@ def rollout_bubble_links(pred: torch.Tensor, frames: torch.Tensor, first: torch.
                                             _p(ws), ws.numel(), stream), "bf_rollout_bubble_links")
 
 
+def bubble_match_workspace(pairs: int, max_bubbles: int, device) -> torch.Tensor:
+    """The workspace ``bubble_match`` (and, with pairs = B * T, ``rollout_bubble_match``) needs: allocate once, outside a graph capture.  It holds
+    every pair's centroid sums and best-partner rows, and the overlap tables that do not fit ``bubble_links_lds_entries()``; more records than the
+    library supports are refused here, before any launch."""
+    nbytes = L.lib().bf_bubble_match_ws_bytes(int(pairs), int(max_bubbles))
+    if nbytes <= 0:
+        raise L.BubbleformerHipError(f"bubble_match_workspace: {pairs} pairs with {max_bubbles} records are not supported (at least one pair, "
+                                     "1 to 2^15 records per frame)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _match_rows(lead: tuple, mb: int) -> dict:
+    """name -> (shape, dtype) of the six outputs of a match call whose pair axes are ``lead``."""
+    i32 = torch.int32
+    return {"match_pred": (lead + (mb,), i32), "match_target": (lead + (mb,), i32), "overlap": (lead + (mb,), i32),
+            "displacement": (lead + (mb,), torch.float32), "counts": (lead + (6,), i32), "mask": (lead + (2,), i32)}
+
+
+def _match_record(who: str, device, lead: tuple, mb: int, given: dict):
+    """The six match tensors (``_match_rows(lead, mb)``), checked -> bf_match_rows."""
+    shapes = _match_rows(lead, mb)
+    if given.keys() != shapes.keys():
+        raise L.BubbleformerHipError(f"{who}: rows must hold exactly {sorted(shapes)}")
+    _check_tensors(who, device, {k: (given[k], shape, dtype) for k, (shape, dtype) in shapes.items()})
+    return L.MatchRows(**{k: _p(given[k]) for k in shapes})
+
+
+def _check_min_iou(who: str, min_iou) -> float:
+    if not 0.0 <= float(min_iou) <= 1.0:                    # a NaN fails both comparisons
+        raise L.BubbleformerHipError(f"{who}: min_iou must be in [0, 1], got {min_iou!r}")
+    return float(min_iou)
+
+
+def bubble_match(labels_pred: torch.Tensor, labels_tgt: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor, attached_pred: torch.Tensor,
+                 attached_tgt: torch.Tensor, area_pred: torch.Tensor, area_tgt: torch.Tensor, min_iou: float, ws: torch.Tensor, rows: dict) -> None:
+    """Predicted bubbles matched to simulated ones, frame by frame (bf_bubble_match; include/bubbleformer_hip.h has the contract): labels (F, H, W),
+    count / attached (F,) and area (F, max_bubbles) int32 of both sides as ``bubble_census`` left them -> rows: a dict of match_pred, match_target,
+    overlap (F, max_bubbles) int32, displacement (F, max_bubbles) fp32, counts (F, 6) and mask (F, 2) int32.  ws:
+    ``bubble_match_workspace(F, max_bubbles)``.  Allocates nothing: capturable in a HIP graph."""
+    _require_gpu(labels_pred)
+    i32 = torch.int32
+    if labels_pred.dim() != 3 or labels_pred.dtype != i32 or not labels_pred.is_contiguous():
+        raise L.BubbleformerHipError("bubble_match: labels_pred must be a contiguous int32 (frames, H, W) tensor")
+    if area_pred.dim() != 2:
+        raise L.BubbleformerHipError("bubble_match: area_pred must be a (frames, max_bubbles) tensor")
+    F, H, W = (int(v) for v in labels_pred.shape)
+    mb, dev = int(area_pred.shape[-1]), labels_pred.device
+    _check_tensors("bubble_match", dev, {"labels_tgt": (labels_tgt, (F, H, W), i32), "ws": (ws, (ws.numel(),), torch.uint8)})
+    census_pred = _census_rows("bubble_match", dev, "_pred", (F,), mb, count_pred, None, attached_pred, area_pred, need_cells=False)
+    census_tgt = _census_rows("bubble_match", dev, "_tgt", (F,), mb, count_tgt, None, attached_tgt, area_tgt, need_cells=False)
+    record = _match_record("bubble_match", dev, (F,), mb, rows)
+    if F < 1 or H < 1 or W < 1 or mb < 1:
+        raise L.BubbleformerHipError(f"bubble_match: needs at least one frame of at least one cell and one record, got {tuple(labels_pred.shape)}")
+    min_iou = _check_min_iou("bubble_match", min_iou)
+    need = L.lib().bf_bubble_match_ws_bytes(F, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("bubble_match: the workspace is smaller than bubble_match_workspace(frames, max_bubbles)")
+    L.check(L.lib().bf_bubble_match(_p(labels_pred), _p(labels_tgt), C.byref(census_pred), C.byref(census_tgt), F, H, W, mb, min_iou, C.byref(record),
+                                    _p(ws), ws.numel(), _stream()), "bf_bubble_match")
+
+
+def rollout_bubble_match(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, steps: int, max_bubbles: int,
+                         min_iou: float, ws: torch.Tensor, labels: torch.Tensor, count_pred: torch.Tensor, count_tgt: torch.Tensor,
+                         attached_pred: torch.Tensor, attached_tgt: torch.Tensor, area_pred: torch.Tensor, area_tgt: torch.Tensor, rows: dict) -> None:
+    """The matches of one rollout step (bf_rollout_bubble_match; include/bubbleformer_hip.h has the contract), on the ring and the census rows the
+    step's ``rollout_bubbles_labelled`` wrote: the predicted frame (b, t) against the simulated one, s = the int32 ``step`` tensor ON THE DEVICE,
+    which this call only reads -- issue it after ``rollout_bubbles_labelled`` and BEFORE the step's ``rollout_score``.  rows: a dict of
+    match_pred, match_target, overlap (B, steps*T, max_bubbles) int32, displacement (B, steps*T, max_bubbles) fp32, counts (B, steps*T, 6) and
+    mask (B, steps*T, 2) int32; the call writes row s * T + t.  ws: ``bubble_match_workspace(B * T, max_bubbles)``.  Allocates nothing."""
+    rec, stream = _rollout_step_args("rollout_bubble_match", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    mb, dev = int(max_bubbles), pred.device
+    _check_tensors("rollout_bubble_match", dev, {"labels": (labels, (2, 2, B, T, Ho, Wo), torch.int32), "ws": (ws, (ws.numel(),), torch.uint8)})
+    census_pred = _census_rows("rollout_bubble_match", dev, "_pred", (B, steps * T), mb, count_pred, None, attached_pred, area_pred, need_cells=False)
+    census_tgt = _census_rows("rollout_bubble_match", dev, "_tgt", (B, steps * T), mb, count_tgt, None, attached_tgt, area_tgt, need_cells=False)
+    record = _match_record("rollout_bubble_match", dev, (B, steps * T), mb, rows)
+    min_iou = _check_min_iou("rollout_bubble_match", min_iou)
+    need = L.lib().bf_bubble_match_ws_bytes(B * T, mb)
+    if need <= 0 or ws.numel() < need:
+        raise L.BubbleformerHipError("rollout_bubble_match: the workspace is smaller than bubble_match_workspace(B * T, max_bubbles)")
+    L.check(L.lib().bf_rollout_bubble_match(C.byref(rec), mb, min_iou, _p(labels), C.byref(census_pred), C.byref(census_tgt), C.byref(record), _p(ws),
+                                            ws.numel(), stream), "bf_rollout_bubble_match")
+
+
 _ERROR_ROWS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
                "spectrum_target")
 

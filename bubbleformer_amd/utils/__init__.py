@@ -2,7 +2,7 @@ from .lr_schedulers import CosineWarmupLR  # noqa: F401
 from .losses import InterfaceLpLoss, LpLoss, SpectralLpLoss, eikonal_loss  # noqa: F401
 from .noise import NoiseSpec, add_gaussian_noise  # noqa: F401
 from .augment import AugmentSpec, augment_plan  # noqa: F401
-from .physics import BubbleCensus, BubbleSpec, BubbleTracks, HeaterSpec, bubble_census, bubble_tracks, heatflux_series, kde_kl_divergence  # noqa: F401
+from .physics import BubbleCensus, BubbleMatch, BubbleSpec, BubbleTracks, HeaterSpec, bubble_census, bubble_match, bubble_tracks, heatflux_series, kde_kl_divergence  # noqa: F401
 from .physics import RedistanceSpec, redistance  # noqa: F401
 from .physics import ErrorSpec, FieldErrors, field_errors, shell_count  # noqa: F401
 from .physics import EnsembleScores, EnsembleSpec, ensemble_scores  # noqa: F401

@@ -130,25 +130,47 @@ def kde_kl_divergence(sim: torch.Tensor, model: torch.Tensor, points: int = 1000
     return (kl[0],) + tuple(t[0] for t in extra) if single else (kl,) + extra
 
 
-@dataclasses.dataclass(frozen=True)
+@dataclasses.dataclass(frozen=True, eq=False)
 class BubbleSpec:
     """The bubble census of a rollout (``evaluate_rollouts(..., bubbles=BubbleSpec())``): which output field is the signed distance, how cells
     connect (4: edges, 8: edges and corners), how many per-bubble records a frame keeps, and the cell size for the equivalent diameters.  With
-    ``track`` the bubbles are also followed from frame to frame (``bubble_tracks``): the report gains the link, event and departure rows."""
+    ``track`` the bubbles are also followed from frame to frame (``bubble_tracks``): the report gains the link, event and departure rows.  With
+    ``match`` the predicted bubbles of every frame are matched to the simulated ones (``bubble_match``; ``min_iou`` is its IoU bound): the report
+    gains the match rows and the detection scores."""
     sdf_field: str = "dfun"
     connectivity: int = 4
     max_bubbles: int = 256
     dx: float = 1.0 / 32
     track: bool = False
+    # constructor arguments behind `track`, by position or by name, and attributes of the instance; dataclasses.fields() ends at `track` as before
+    match: dataclasses.InitVar[bool] = False
+    min_iou: dataclasses.InitVar[float] = 0.0
 
-    def __post_init__(self):
+    def __post_init__(self, match, min_iou):
         _check_census_arguments(self.connectivity, self.max_bubbles)
         if not isinstance(self.track, bool):
             raise ValueError(f"track must be True or False, got {self.track!r}")
-        if self.track and int(self.max_bubbles) > MAX_TRACKED_BUBBLES:
-            raise ValueError(f"tracking keeps at most {MAX_TRACKED_BUBBLES} records per frame, got max_bubbles = {self.max_bubbles}")
+        if not isinstance(match, bool):
+            raise ValueError(f"match must be True or False, got {match!r}")
+        _check_min_iou(min_iou)
+        if (self.track or match) and int(self.max_bubbles) > MAX_TRACKED_BUBBLES:
+            raise ValueError(f"tracking and matching keep at most {MAX_TRACKED_BUBBLES} records per frame, got max_bubbles = {self.max_bubbles}")
         if not self.dx > 0:
             raise ValueError(f"dx must be positive, got {self.dx}")
+        object.__setattr__(self, "match", match)
+        object.__setattr__(self, "min_iou", float(min_iou))
+
+    def _key(self):
+        return dataclasses.astuple(self) + (self.match, self.min_iou)
+
+    def __eq__(self, other):
+        return self._key() == other._key() if isinstance(other, BubbleSpec) else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "BubbleSpec(" + ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self)) + f", match={self.match!r}, min_iou={self.min_iou!r})"
 
     def channel(self, fields: Sequence[str]) -> int:
         """The signed-distance channel among the output fields."""
@@ -159,6 +181,11 @@ class BubbleSpec:
 
 
 MAX_TRACKED_BUBBLES = 1 << 15          # bf_bubble_links' limit: an overlap table of max_bubbles^2 int32 indices
+
+
+def _check_min_iou(min_iou) -> None:
+    if isinstance(min_iou, bool) or not isinstance(min_iou, (int, float)) or not 0.0 <= float(min_iou) <= 1.0:        # a NaN fails both comparisons
+        raise ValueError(f"min_iou must be a number in [0, 1], got {min_iou!r}")
 
 
 def _check_census_arguments(connectivity, max_bubbles) -> None:
@@ -357,6 +384,108 @@ def bubble_tracks(phi: torch.Tensor, *, connectivity: int = 4, max_bubbles: int 
     ops.bubble_track_ids(census.count.reshape(N, T), rows["successor"], rows["predecessor"], track_id, n_tracks)
     return BubbleTracks(census, **{k: v.reshape(lead + v.shape[1:]) for k, v in rows.items()}, track_id=track_id.reshape(lead + (T, mb)),
                         n_tracks=n_tracks.reshape(lead))
+
+
+def _quotient(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """num / den in fp64, rounded once to fp32; NaN where den is 0."""
+    den = den.to(torch.float64)
+    return (num.to(torch.float64) / torch.where(den == 0, torch.full_like(den, float("nan")), den)).to(torch.float32)
+
+
+def detection_scores(counts: torch.Tensor, attached: bool = False):
+    """counts (..., 6) int32 as ``bubble_match`` leaves them -> (precision, recall, csi), each (...) fp32: hits / (hits + false alarms), hits /
+    (hits + misses), hits / (hits + misses + false alarms), of all bubbles or with ``attached`` of those on the heater.  Every quotient in fp64,
+    rounded once; NaN where the denominator is 0 and in an invalid pair (-1).  On the device; never synchronises."""
+    hits, misses, alarms = (counts[..., (3 if attached else 0) + q].to(torch.float64) for q in range(3))
+    bad = torch.full_like(hits, float("nan"))
+    hits = torch.where(hits < 0, bad, hits)
+    return _quotient(hits, hits + alarms), _quotient(hits, hits + misses), _quotient(hits, hits + misses + alarms)
+
+
+def mask_iou(mask: torch.Tensor) -> torch.Tensor:
+    """mask (..., 2) int32 (cells vapour on both sides, on either) -> (...) fp32 IoU of the whole vapour mask: the quotient in fp64, rounded once;
+    NaN where neither side has vapour and in an invalid pair (-1)."""
+    both = mask[..., 0].to(torch.float64)
+    return _quotient(torch.where(both < 0, torch.full_like(both, float("nan")), both), mask[..., 1])
+
+
+def matched_iou(overlap: torch.Tensor, match_pred: torch.Tensor, area_pred: torch.Tensor, area_target: torch.Tensor) -> torch.Tensor:
+    """(..., max_bubbles) fp32 per predicted slot: overlap / (area_pred[i] + area_target[match] - overlap) of a matched pair, the quotient in
+    fp64, rounded once; NaN in unmatched and unused slots and in an invalid pair."""
+    matched = match_pred > 0
+    partner = torch.gather(area_target, -1, (match_pred.to(torch.int64) - 1).clamp(min=0))
+    union = torch.where(matched, area_pred + partner - overlap, torch.zeros_like(overlap))
+    return _quotient(overlap, union)
+
+
+def centroid_error(displacement: torch.Tensor, match_pred: torch.Tensor, dx: float = 1.0) -> torch.Tensor:
+    """(...) fp32: the mean centroid displacement of a frame's matched pairs times ``dx`` (the sum and the quotient in fp64, rounded once); NaN
+    where a frame has no matched pair."""
+    matched = match_pred > 0
+    total = torch.where(matched, displacement.to(torch.float64), torch.zeros((), dtype=torch.float64, device=displacement.device)).sum(-1)
+    return _quotient(total * float(dx), matched.sum(-1))
+
+
+@dataclasses.dataclass
+class BubbleMatch:
+    """What ``bubble_match`` returns; every tensor is on the device and keeps the fields' leading dims.  Slot k of match_pred, overlap and
+    displacement is predicted bubble k + 1, slot k of match_target simulated bubble k + 1; 0 means unmatched or unused."""
+    match_pred: torch.Tensor                        # (..., max_bubbles) int32  the matched simulated bubble
+    match_target: torch.Tensor                      # (..., max_bubbles) int32  the matched predicted bubble
+    overlap: torch.Tensor                           # (..., max_bubbles) int32  cells the matched pair shares
+    displacement: torch.Tensor                      # (..., max_bubbles) fp32   distance between the pair's centroids, in cells
+    counts: torch.Tensor                            # (..., 6) int32            hits, misses, false alarms; the same three on the heater
+    mask: torch.Tensor                              # (..., 2) int32            cells vapour on both sides, on either
+    count_pred: torch.Tensor                        # (...) int32               the two censuses' rows
+    count_target: torch.Tensor
+    attached_pred: torch.Tensor
+    attached_target: torch.Tensor
+    area_pred: torch.Tensor                         # (..., max_bubbles) int32
+    area_target: torch.Tensor
+
+    def iou(self) -> torch.Tensor:
+        """(..., max_bubbles) fp32: the IoU of every matched pair at the predicted bubble's slot, NaN elsewhere."""
+        return matched_iou(self.overlap, self.match_pred, self.area_pred, self.area_target)
+
+    def precision(self, attached: bool = False) -> torch.Tensor:
+        return detection_scores(self.counts, attached)[0]
+
+    def recall(self, attached: bool = False) -> torch.Tensor:
+        return detection_scores(self.counts, attached)[1]
+
+    def csi(self, attached: bool = False) -> torch.Tensor:
+        """The critical success index hits / (hits + misses + false alarms); as precision and recall NaN where the denominator is 0."""
+        return detection_scores(self.counts, attached)[2]
+
+    def mask_iou(self) -> torch.Tensor:
+        return mask_iou(self.mask)
+
+    def centroid_error(self, dx: float = 1.0 / 32) -> torch.Tensor:
+        """(...) fp32: the mean centroid displacement of every frame's matched pairs, in units of ``dx`` per cell."""
+        return centroid_error(self.displacement, self.match_pred, dx)
+
+
+def bubble_match(phi_pred: torch.Tensor, phi_target: torch.Tensor, *, connectivity: int = 4, max_bubbles: int = 256, min_iou: float = 0.0) -> BubbleMatch:
+    """The bubbles of phi_pred matched to those of phi_target, two (..., H, W) signed-distance fields of one shape in physical units on the
+    device, frame by frame: a predicted and a simulated bubble are matched when each is the other's largest overlap and
+    their IoU is at least ``min_iou``.  Two labelled censuses (``bubble_census``), then one launch, a workgroup per frame pair
+    (``ops.bubble_match``); never synchronises; the same bits on every call, and for a pair alone or in a batch."""
+    _check_census_arguments(connectivity, max_bubbles)
+    _check_min_iou(min_iou)
+    if phi_pred.dim() < 2 or phi_pred.shape != phi_target.shape:
+        raise ValueError(f"bubble_match expects two (..., H, W) fields of one shape, got {tuple(phi_pred.shape)} and {tuple(phi_target.shape)}")
+    if int(max_bubbles) > MAX_TRACKED_BUBBLES:
+        raise ValueError(f"matching keeps at most {MAX_TRACKED_BUBBLES} records per frame, got max_bubbles = {max_bubbles}")
+    from .. import ops
+    sides = [bubble_census(phi, connectivity=connectivity, max_bubbles=max_bubbles, return_labels=True) for phi in (phi_pred, phi_target)]
+    lead, (H, W), mb = tuple(phi_pred.shape[:-2]), phi_pred.shape[-2:], int(max_bubbles)
+    F = sides[0].count.numel()
+    rows = {k: torch.empty((F,) + shape[1:], dtype=dtype, device=phi_pred.device) for k, (shape, dtype) in ops._match_rows((F,), mb).items()}
+    ops.bubble_match(*(c.labels.reshape(F, H, W) for c in sides), *(c.count.reshape(F) for c in sides), *(c.attached.reshape(F) for c in sides),
+                     *(c.area.reshape(F, mb) for c in sides), float(min_iou), ops.bubble_match_workspace(F, mb, phi_pred.device), rows)
+    p, s = sides
+    return BubbleMatch(**{k: v.reshape(lead + v.shape[1:]) for k, v in rows.items()}, count_pred=p.count, count_target=s.count,
+                       attached_pred=p.attached, attached_target=s.attached, area_pred=p.area, area_target=s.area)
 
 
 @dataclasses.dataclass(frozen=True)

@@ -147,6 +147,14 @@ class RolloutReport:
     bubble_predecessor_target: Optional[torch.Tensor] = None
     bubble_departure_area_pred: Optional[torch.Tensor] = None   # (B, steps*T-1, max_bubbles) int32 cells of a bubble that leaves the heater, else 0
     bubble_departure_area_target: Optional[torch.Tensor] = None
+    # with BubbleSpec(match=True): row s * T + t is the predicted frame t of step s against the simulated one (physics.bubble_match), else None.
+    # Attributes that evaluate_rollouts sets, as the error rows below and for the same reason
+    bubble_match_pred = None                            # (B, steps*T, max_bubbles) int32   the simulated bubble matched to predicted bubble k + 1, or 0
+    bubble_match_target = None                          # (B, steps*T, max_bubbles) int32   the predicted bubble matched to simulated bubble k + 1, or 0
+    bubble_match_overlap = None                         # (B, steps*T, max_bubbles) int32   cells the matched pair shares, at the predicted bubble's slot
+    bubble_match_displacement = None                    # (B, steps*T, max_bubbles) fp32    distance between the pair's centroids, in cells
+    bubble_match_counts = None                          # (B, steps*T, 6) int32   hits, misses, false alarms; the same three for bubbles on the heater
+    bubble_mask_cells = None                            # (B, steps*T, 2) int32   cells vapour on both sides, on either
     # with errors=ErrorSpec(): e = prediction - target in fp64 (physics.field_errors), else None.  Attributes that evaluate_rollouts sets, not
     # constructor arguments: the dataclass fields end at the tracking rows, so positional callers and dataclasses.fields() stay as they are
     rmse = None                                         # (B, steps*T, C)     fp32 sqrt(mean e^2)
@@ -209,7 +217,7 @@ class RolloutReport:
         if self.bubble_events_pred is not None:
             for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
-        for key in _ERROR_KEYS + _ENSEMBLE_KEYS + _REDISTANCE_KEYS:
+        for key in _MATCH_KEYS + _ERROR_KEYS + _ENSEMBLE_KEYS + _REDISTANCE_KEYS:
             if getattr(self, key) is not None:
                 out[key] = getattr(self, key)
         torch.save(out, path)
@@ -310,9 +318,42 @@ class RolloutReport:
             return torch.full((), float("nan"), dtype=torch.float64, device=sim.device)
         return kde_kl_divergence(sim, model, points)
 
+    def _matches(self):
+        if self.bubble_match_counts is None:
+            raise ValueError("this report has no bubble matching: call evaluate_rollouts(..., bubbles=BubbleSpec(match=True))")
+
+    def bubble_detection(self, attached: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(precision, recall, critical success index) against lead time, each (B, steps*T) fp32: hits / (hits + false alarms), hits / (hits +
+        misses), hits / (hits + misses + false alarms) of every frame's bubbles, or with ``attached`` of those on the heater; NaN where the
+        denominator is 0 (``physics.detection_scores``).  On the device; never synchronises."""
+        from .physics import detection_scores
+        self._matches()
+        return detection_scores(self.bubble_match_counts, attached)
+
+    def mask_iou(self) -> torch.Tensor:
+        """(B, steps*T) fp32: the IoU of the predicted and the simulated vapour mask of every frame, NaN where neither has vapour."""
+        from .physics import mask_iou
+        self._matches()
+        return mask_iou(self.bubble_mask_cells)
+
+    def matched_iou(self) -> torch.Tensor:
+        """(B, steps*T, max_bubbles) fp32: the IoU of every matched pair at the predicted bubble's slot, NaN elsewhere."""
+        from .physics import matched_iou
+        self._matches()
+        return matched_iou(self.bubble_match_overlap, self.bubble_match_pred, self.bubble_area_pred, self.bubble_area_target)
+
+    def centroid_error(self, dx: Optional[float] = None) -> torch.Tensor:
+        """(B, steps*T) fp32: the mean centroid displacement of every frame's matched pairs times ``dx`` (default: the census' cell size), NaN
+        where a frame has no matched pair."""
+        from .physics import centroid_error
+        self._matches()
+        return centroid_error(self.bubble_match_displacement, self.bubble_match_pred, self.bubble_dx if dx is None else dx)
+
 
 _TRACK_KEYS = ("bubble_events_pred", "bubble_events_target", "bubble_successor_pred", "bubble_successor_target", "bubble_predecessor_pred",
                "bubble_predecessor_target", "bubble_departure_area_pred", "bubble_departure_area_target")
+_MATCH_KEYS = ("bubble_match_pred", "bubble_match_target", "bubble_match_overlap", "bubble_match_displacement", "bubble_match_counts",
+               "bubble_mask_cells")
 _ERROR_KEYS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interface_cells", "spectral_error", "spectrum_error", "spectrum_pred",
                "spectrum_target")
 _ENSEMBLE_KEYS = ("ensemble_members", "ensemble_mean_rmse", "ensemble_spread", "ensemble_crps", "ensemble_rank_hist", "ensemble_mean")
@@ -354,7 +395,9 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     likewise leaves the bubble census of every predicted and simulated frame (``ops.rollout_bubbles``, one more launch before the scoring
     call): the ``bubble_*`` and ``vapour_fraction_*`` rows of the report; with ``BubbleSpec(track=True)`` that launch also leaves its label
     images and one more (``ops.rollout_bubble_links``) follows the bubbles into this step's frames: the ``bubble_events_*``, ``bubble_successor_*``,
-    ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows.  With ``errors`` (a ``physics.ErrorSpec``) one more call before the scoring
+    ``bubble_predecessor_*`` and ``bubble_departure_area_*`` rows; with ``BubbleSpec(match=True)`` one more (``ops.rollout_bubble_match``) matches
+    the predicted bubbles of every frame of the step to the simulated ones: the ``bubble_match_*`` and ``bubble_mask_cells`` rows, which
+    ``report.bubble_detection()``, ``mask_iou()``, ``matched_iou()`` and ``centroid_error()`` read.  With ``errors`` (a ``physics.ErrorSpec``) one more call before the scoring
     call (``ops.rollout_errors``) leaves ``physics.field_errors``' rows of every predicted frame and field against the stored target: ``rmse``,
     ``max_error``, ``boundary_rmse``, the interface rows when the signed-distance field is among the outputs, and with ``spectra`` the shell
     spectra and the band-limited errors; ``None`` leaves the launches and the report as they are without it.  Never synchronises.
@@ -458,16 +501,24 @@ def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True
         bub = {"count": rows(), "cells": rows(), "attached": rows(), "area": rows(mb)}
         bub_args = (bubbles.channel(fields), steps, int(bubbles.connectivity), mb, ops.bubble_census_workspace(2 * B * T, Ho, Wo, mb, device),
                     *bub["count"], *bub["cells"], *bub["attached"], *bub["area"])
-        if not bubbles.track:
+        if not (bubbles.track or bubbles.match):
             before_score.append(lambda pred, step: ops.rollout_bubbles(pred, store.frames, first, step, store.out_tab, *bub_args))
-        else:                                       # the labelled census in its place, then the links of the pairs that end in this step
+        else:                                       # the labelled census in its place; its ring serves the links and the matches alike
             ring = torch.empty((2, 2, B, T, Ho, Wo), dtype=torch.int32, device=device)
+            before_score.append(lambda pred, step: ops.rollout_bubbles_labelled(pred, store.frames, first, step, store.out_tab, *bub_args, ring))
+        if bubbles.track:                           # the links of the pairs that end in this step
             link_rows = [{k: torch.empty((B,) + shape, dtype=torch.int32, device=device) for k, shape in ops._link_rows((steps * T - 1,), mb).items()}
                          for _ in range(2)]
             link_ws = ops.bubble_links_workspace(2 * B * T, mb, device)
-            before_score.append(lambda pred, step: ops.rollout_bubbles_labelled(pred, store.frames, first, step, store.out_tab, *bub_args, ring))
             before_score.append(lambda pred, step: ops.rollout_bubble_links(pred, store.frames, first, step, store.out_tab, steps, mb, link_ws, ring,
                                                                             *bub["count"], *bub["attached"], *bub["area"], *link_rows))
+        match_rows = None
+        if bubbles.match:                           # every predicted frame of this step against the simulated one
+            match_rows = {k: torch.empty(shape, dtype=dtype, device=device) for k, (shape, dtype) in ops._match_rows((B, steps * T), mb).items()}
+            match_ws = ops.bubble_match_workspace(B * T, mb, device)
+            before_score.append(lambda pred, step: ops.rollout_bubble_match(pred, store.frames, first, step, store.out_tab, steps, mb,
+                                                                            float(bubbles.min_iou), match_ws, ring, *bub["count"], *bub["attached"],
+                                                                            *bub["area"], match_rows))
     err_rows = None
     if errors is not None:
         err_sdf = fields.index(errors.sdf_field) if errors.sdf_field in fields else -1
@@ -538,6 +589,10 @@ def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True
             for key in ("events", "successor", "predecessor", "departure_area"):
                 setattr(report, f"bubble_{key}_pred", link_rows[0][key])
                 setattr(report, f"bubble_{key}_target", link_rows[1][key])
+        if match_rows is not None:
+            for key in ("match_pred", "match_target", "overlap", "displacement", "counts"):
+                setattr(report, "bubble_match_" + key.replace("match_", ""), match_rows[key])
+            report.bubble_mask_cells = match_rows["mask"]
     if err_rows is not None:
         for key, rows in err_rows.items():
             setattr(report, key, rows)

@@ -41,6 +41,7 @@
  *   bf_bubble_census ......... connected components of the vapour mask per frame (no reference program); bf_rollout_bubbles: per step of that loop
  *   bf_redistance ............ first-order redistancing of a signed-distance field (no reference program); bf_rollout_redistance: per step, in place
  *   bf_bubble_links .......... bubbles followed from frame to frame, bf_bubble_track_ids (no reference program); bf_rollout_bubble_links: per step
+ *   bf_bubble_match .......... predicted bubbles matched to simulated ones (no reference program); bf_rollout_bubble_match: per step
  *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
  *   bf_ensemble_scores ....... ensemble-mean RMSE, spread, CRPS and rank histogram across members (no reference program); bf_rollout_ensemble: per step
  *   bf_render_ranges / bf_render_tiles .. plot_bubbleml and the wandb_*_plotter strips: utils/plot_utils.py:12-228 (no matplotlib, no cv2)
@@ -476,6 +477,8 @@ typedef struct bf_rollout_step {
 typedef struct bf_census_rows { int32_t *count, *cells, *attached, *area; } bf_census_rows;
 /* One side's link rows: bf_bubble_links' five [pairs][max_bubbles] outputs and events [pairs][5] */
 typedef struct bf_link_rows { int32_t *successor, *n_successors, *predecessor, *n_predecessors, *departure_area, *events; } bf_link_rows;
+/* bf_bubble_match's outputs, row = frame pair: three int32 rows and displacement [rows][max_bubbles], counts [rows][6], mask [rows][2]; all required */
+typedef struct bf_match_rows { int32_t *match_pred, *match_target, *overlap; float* displacement; int32_t *counts, *mask; } bf_match_rows;
 /* bf_field_errors' outputs; each may be NULL and is then not computed */
 typedef struct bf_error_rows {
     float *rmse, *max_error, *boundary_rmse, *interface_rmse;
@@ -624,6 +627,43 @@ int bf_bubble_track_ids(const int32_t* count, const int32_t* successor, const in
 int bf_rollout_bubble_links(const bf_rollout_step* s, int max_bubbles, const int32_t* labels, const bf_census_rows* census_pred,
                             const bf_census_rows* census_tgt, const bf_link_rows* links_pred, const bf_link_rows* links_tgt, void* ws,
                             int64_t ws_bytes, bf_stream_t stream);
+/* Predicted bubbles scored against simulated ones, object by object (csrc/bubble_tracks.hip; the reference has no program for it).
+ * A pair is a prediction frame P and the simulation frame S of the same time: labels_pred, labels_tgt [frames][H][W] and each census' count / attached
+ * [frames] and area [frames][max_bubbles] are what bf_bubble_census left for the two sides (cells is unread and may be NULL).  With kp = min(count_p,
+ * max_bubbles), ks likewise (labels above them have no record and count as liquid for the table), overlap[i][j] = the number of cells with Lp == i and
+ * Ls == j, best_s[i] = the j of the largest overlap[i][j] > 0 (ties to the smallest j, 0 if none) and best_p[j] the same per simulated bubble over
+ * the predicted ones, predicted bubble i and simulated bubble j are MATCHED iff best_s[i] == j, best_p[j] == i and
+ *   (double)overlap[i][j] >= (double)min_iou * (double)(area_p[i] + area_s[j] - overlap[i][j])
+ * (the union is below 2^24, so the fp64 product is exact and the comparison has one answer everywhere; min_iou = 0 is mutual best overlap alone).
+ * Per pair, row = pair:
+ *   match_pred [rows][max_bubbles] int32     slot i - 1: the matched j, or 0;
+ *   match_target [rows][max_bubbles] int32   slot j - 1: the matched i, or 0;
+ *   overlap [rows][max_bubbles] int32        slot i - 1: overlap[i][match], or 0 (the pair's IoU is overlap / (area_p[i] + area_s[j] - overlap));
+ *   displacement [rows][max_bubbles] fp32    slot i - 1: the Euclidean distance in cells between the centroids of a matched pair; a centroid is the
+ *                                            quotient of exact integer sums of y and x per label (taken by this kernel) by the census area; quotients,
+ *                                            differences, squares, their sum and the root in fp64 without fused contraction, one rounding to fp32;
+ *                                            0 in unmatched and unused slots;
+ *   counts [rows][6] int32                   hits (matched pairs), misses (ks - hits), false alarms (kp - hits); then the same three for bubbles on the
+ *                                            heater: a heater hit is a matched pair with i <= attached_p and j <= attached_s, heater misses are
+ *                                            min(attached_s, ks) - heater hits, heater false alarms min(attached_p, kp) - heater hits;
+ *   mask [rows][2] int32                     the cells that are vapour on both sides, and on either side; any label > 0 counts, also above max_bubbles.
+ * Slots behind kp / ks hold 0.  A pair with a frame whose count is -1 holds -1 in every integer output and NaN in displacement.  Every member of
+ * rows is required.  One workgroup owns a pair; its kp x ks table is in LDS when kp * ks <= bf_bubble_links_lds_entries(), in its slice of the
+ * workspace otherwise (bf_bubble_links' workgroup-uniform branch); the y / x sums are 64-bit integers in the slice.  Integer atomics only: the same bits
+ * on every call, and for a pair alone or in a batch.  Any H, W >= 1 with H * W <= 2^24 and max_bubbles <= 2^15 (refused beyond, before any launch);
+ * min_iou outside [0, 1] or NaN is refused.  Allocation-free, capturable, never makes the host wait.  ws: bf_bubble_match_ws_bytes(frames,
+ * max_bubbles) bytes, 16-byte aligned, contents irrelevant before and after (0 from the query: sizes out of range). */
+int64_t bf_bubble_match_ws_bytes(int64_t pairs, int max_bubbles);
+int bf_bubble_match(const int32_t* labels_pred, const int32_t* labels_tgt, const bf_census_rows* census_pred, const bf_census_rows* census_tgt,
+                    int64_t frames, int H, int W, int max_bubbles, float min_iou, const bf_match_rows* rows, void* ws, int64_t ws_bytes,
+                    bf_stream_t stream);
+/* bf_bubble_match for ONE rollout step, on the ring `labels` the step's bf_rollout_bubbles filled and the census rows it wrote: issue the call after
+ * it.  s: see bf_rollout_step (checked, the fields unread).  With the step number s = *s->step, the pair (side 0, side 1) of frame (b, t) from half
+ * s & 1 goes to row s * T + t of rows shaped [B][steps*T][...]; no other row is touched, and with s outside [0, steps) nothing is written.
+ * census_*: count / attached [B][steps*T] and area [B][steps*T][max_bubbles]; cells is unread and may be NULL.
+ * ws: bf_bubble_match_ws_bytes(B * T, max_bubbles) bytes, 16-byte aligned. */
+int bf_rollout_bubble_match(const bf_rollout_step* s, int max_bubbles, float min_iou, const int32_t* labels, const bf_census_rows* census_pred,
+                            const bf_census_rows* census_tgt, const bf_match_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream);
 /* Where a prediction is wrong and at which scales (csrc/spectra.hip; the reference has no program for it).  pred, target
  * [frames][H][W] fp32, e = pred - target in fp64; sdf (optional) [frames][H][W] fp32 in physical units.  Any member of rows may be NULL and is then not computed:
  *   rmse, max_error, boundary_rmse [frames] fp32   sqrt(mean e^2); max |e| (NaN if any e is NaN); the root mean square over the outer ring of cells;
