@@ -180,6 +180,25 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Workgroup reductions in a fixed order, fp64: every thread gets the reduction of v over the WAVES waves of the workgroup, formed by wave_sum's
+// 32 -> 1 butterfly inside a wave, then the waves in order starting from red[0] (red: WAVES doubles of LDS).  The kernels that promise the
+// same bits on every call, and the same bits as each other, take their sums through this one text.
+enum { RED_SUM = 0, RED_MIN = 1, RED_MAX = 2 };
+template <int OP> __device__ __forceinline__ double red_op(double a, double b) {
+    if constexpr (OP == RED_SUM) return a + b;
+    else if constexpr (OP == RED_MIN) return fmin(a, b);
+    else return fmax(a, b);
+}
+template <int OP, int WAVES> __device__ __forceinline__ double block_reduce(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = red_op<OP>(v, __shfl_xor(v, o, 64));
+    __syncthreads();                                                        // red may still be read from the previous reduction
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+    for (int w = 1; w < WAVES; ++w) t = red_op<OP>(t, red[w]);
+    return t;
+}
 
 static inline int bf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t bf_esize(int dtype) { return dtype == BF_DTYPE_BF16 ? 2 : 4; }

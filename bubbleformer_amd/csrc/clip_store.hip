@@ -289,7 +289,7 @@ extern "C" int bf_clip_gather_augment(const bf_clip_gather_job* j, const bf_clip
 constexpr int FS_ROWS = 64;      // workgroups per segment
 __global__ void __launch_bounds__(NT) field_stats_kernel(const float* __restrict__ src, const long* __restrict__ seg_begin, const long* __restrict__ seg_len,
                                                         double* __restrict__ part) {
-    __shared__ double red[NT / 64][4];
+    __shared__ double red[NT / 64][4];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const int seg = blockIdx.y;
     const float* p = src + seg_begin[seg];
     const long n = seg_len[seg];

@@ -40,7 +40,7 @@ __device__ __forceinline__ long ens_out_row(const EnsArgs& a, int s, int f) {
 template <int MC>
 __global__ void __launch_bounds__(NT) ensemble_kernel(EnsArgs a) {
     constexpr int UJ = MC <= 8 ? 4 : 1;
-    __shared__ double red[NT / 64][4];
+    __shared__ double red[NT / 64][4];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     __shared__ int hist[ENS_MAX_MEMBERS + 1];
     const RolloutStep& v = a.v;
     int s = 0;

@@ -40,7 +40,7 @@ __device__ __forceinline__ double gn_wave_sum(double v) {
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);      // every lane ends with the same tree over the 64 values
     return v;
 }
-// sum over the workgroup in a fixed order; the result is valid in thread 0
+// sum over the workgroup in a fixed order; the result is valid in thread 0.  Not bf_common.h's block_reduce: gn_wave_sum's order gives other bits
 __device__ __forceinline__ double gn_block_sum(double v, double* red) {
     v = gn_wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -205,7 +205,7 @@ __global__ void step_guard_kernel(const float* __restrict__ norm, int step, int3
 }
 
 constexpr long long NF_NONE = 0x7fffffffffffffffLL;      // no non-finite element seen
-// {minimum, sum} over the workgroup, valid in thread 0; integers, so any order gives the same result
+// {minimum, sum} over the workgroup, valid in thread 0; integers, so any order gives the same result.  Two values at once: not bf_common.h's block_reduce
 __device__ __forceinline__ void nf_block_reduce(long long& first, long long& count, long long (*red)[2]) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

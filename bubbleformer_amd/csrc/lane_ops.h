@@ -1,7 +1,8 @@
 // Lane, LDS-transpose, LDS-DMA and wait-count primitives of the gfx950 kernels: each defined once, device code only, no host state.
 // What belongs here: a short __forceinline__ wrapper round one instruction sequence that more than one kernel file needs (DPP and
 // v_permlane*_swap reductions, ds_read_tr16_b64 reads, global_load_lds issue, counted s_waitcnt, fences).  What does not: anything that
-// knows a tile shape or an operand layout (gemm_common.h), and reductions whose summation order another kernel must reproduce.
+// knows a tile shape or an operand layout (gemm_common.h), and reductions whose summation order another kernel must reproduce: the ordered
+// fp64 workgroup reduction is bf_common.h's block_reduce (beside wave_sum), the LDS transform and the radial shell are fft_lines.h's.
 #pragma once
 #include "bf_common.h"
 

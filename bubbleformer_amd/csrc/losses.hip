@@ -124,7 +124,7 @@ __device__ __forceinline__ long lp_span_len(long n, int chunks) { return ((n + c
 template <int MODE>
 __global__ void __launch_bounds__(NT) lp_long_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ y, long n, int chunks, LpPow pw,
                                                         double* __restrict__ part) {
-    __shared__ double red[NT / 64][2];
+    __shared__ double red[NT / 64][2];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const long row = blockIdx.x / chunks;
     const int c = (int)(blockIdx.x % chunks);
     const float* p = pred + row * n;
@@ -265,16 +265,12 @@ __device__ __forceinline__ double eik_weight(int j, int i, int n) {
     return i == j + 1 ? 0.5 : i == j - 1 ? -0.5 : 0.0;
 }
 // One workgroup per EIK_TH x EIK_TW tile of one frame: q_y, q_x of the tile and a one-cell rim go to LDS once (1.16 roots per cell instead of 5), then
-// every cell of the tile gathers from LDS.
+// every cell of the tile gathers from LDS.  The tile at (y0, x0) of the frame f: its adjoint is stored to the frame d, or added to it (ADD).
+// The one text of eikonal_loss's backward and of the interface criterion's penalty: the same stencil, the same order of terms.
 constexpr int EIK_TH = 16, EIK_TW = 64;
-__global__ void __launch_bounds__(NT) eikonal_bwd_kernel(const float* __restrict__ phi, long frames, int H, int W, int tiles_y, int tiles_x, double inv_dx,
-                                                        const float* __restrict__ g, float* __restrict__ dphi) {
+template <bool ADD>
+__device__ __forceinline__ void eik_bwd_tile(const float* __restrict__ f, float* __restrict__ d, int H, int W, int y0, int x0, double inv_dx, double scale) {
     __shared__ double qy[EIK_TH + 2][EIK_TW + 2], qx[EIK_TH + 2][EIK_TW + 2];
-    const long tile = blockIdx.x;
-    const int x0 = (int)(tile % tiles_x) * EIK_TW, y0 = (int)((tile / tiles_x) % tiles_y) * EIK_TH;
-    const long frame = tile / ((long)tiles_x * tiles_y);
-    const float* f = phi + frame * ((long)H * W);
-    const double scale = 2.0 * (double)g[0] / (double)(frames * H * W);
     for (int i = threadIdx.x; i < (EIK_TH + 2) * (EIK_TW + 2); i += NT) {
         const int ly = i / (EIK_TW + 2), lx = i % (EIK_TW + 2), y = y0 - 1 + ly, x = x0 - 1 + lx;
         EikCell c = {0.0, 0.0};
@@ -298,8 +294,18 @@ __global__ void __launch_bounds__(NT) eikonal_bwd_kernel(const float* __restrict
                 if (k != 0.0) acc += k * qx[ly + 1][j - x0 + 1];
             }
         }
-        dphi[frame * ((long)H * W) + (long)y * W + x] = (float)(acc * inv_dx);
+        float* o = d + (long)y * W + x;
+        if constexpr (ADD) *o += (float)(acc * inv_dx);
+        else *o = (float)(acc * inv_dx);
     }
+}
+__global__ void __launch_bounds__(NT) eikonal_bwd_kernel(const float* __restrict__ phi, long frames, int H, int W, int tiles_y, int tiles_x, double inv_dx,
+                                                        const float* __restrict__ g, float* __restrict__ dphi) {
+    const long tile = blockIdx.x;
+    const int x0 = (int)(tile % tiles_x) * EIK_TW, y0 = (int)((tile / tiles_x) % tiles_y) * EIK_TH;
+    const long frame = tile / ((long)tiles_x * tiles_y);
+    const double scale = 2.0 * (double)g[0] / (double)(frames * H * W);
+    eik_bwd_tile<false>(phi + frame * ((long)H * W), dphi + frame * ((long)H * W), H, W, y0, x0, inv_dx, scale);
 }
 
 // ---- The interface-weighted criterion.  pred, y are [frames][C][hw] fp32 (frames = B * T, hw = H * W), s the channel of the signed distance:
@@ -320,16 +326,6 @@ struct WlpFields { double a[WLP_MAX_C]; };
 
 __device__ __forceinline__ double wlp_weight(float ys, const WlpHat& hat) {
     return 1.0 + hat.gain * fmax(0.0, 1.0 - fabs((double)ys * hat.div + hat.diff) * hat.inv_band);
-}
-// every thread gets the sum of v over the workgroup: butterfly inside a wave, then the waves in order
-__device__ __forceinline__ double wlp_block_sum(double v, double* red) {
-    v = wave_sum(v);
-    __syncthreads();                                  // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < NT / 64; ++w) t += red[w];
-    return t;
 }
 template <int CT> __device__ __forceinline__ void wlp_px_sums(const float* __restrict__ pf, const float* __restrict__ yf, long hw, int C, int s, long i,
                                                               const WlpHat& hat, double (&se)[CT], double (&sy)[CT]) {
@@ -410,7 +406,7 @@ __device__ __forceinline__ WlpGroup wlp_group(long frames, int chunks, int width
 template <int CT>
 __global__ void __launch_bounds__(NT) wlp_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ y, long frames, long hw, int C, int s, int chunks,
                                                     int width, WlpHat hat, double* __restrict__ part) {
-    __shared__ double red[NT / 64][2 * CT];
+    __shared__ double red[NT / 64][2 * CT];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const WlpGroup g = wlp_group(frames, chunks, width);
     double se[CT], sy[CT];
 #pragma unroll
@@ -459,7 +455,7 @@ __global__ void __launch_bounds__(NT) wlp_eik_fwd_kernel(const float* __restrict
         const double m = sqrt(d.qy * d.qy + d.qx * d.qx) - 1.0;
         acc += m * m;
     }
-    acc = wlp_block_sum(acc, red);
+    acc = block_reduce<RED_SUM, NT / 64>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 // One workgroup: sums[row] = the spans of row (frame, c) in span order; rho = sqrt(S_e / S_y); terms[1 + c] = a_c * mean over the frames of rho, added in a
@@ -479,13 +475,13 @@ __global__ void __launch_bounds__(NT) wlp_finish_kernel(const double* __restrict
     for (int c = 0; c < C; ++c) {
         double acc = 0.0;
         for (long f = threadIdx.x; f < frames; f += NT) acc += rho[f * C + c];
-        const double term = fa.a[c] * (wlp_block_sum(acc, red) / (double)frames);
+        const double term = fa.a[c] * (block_reduce<RED_SUM, NT / 64>(acc, red) / (double)frames);
         if (threadIdx.x == 0) terms[1 + c] = (float)term;
         total += term;
     }
     double acc = 0.0;
     for (int i = threadIdx.x; i < eik_n; i += NT) acc += eik_part[i];
-    const double eik = eik_n > 0 ? eik_scale * wlp_block_sum(acc, red) : 0.0;
+    const double eik = eik_n > 0 ? eik_scale * block_reduce<RED_SUM, NT / 64>(acc, red) : 0.0;
     if (threadIdx.x == 0) { terms[0] = (float)eik; loss[0] = (float)(total + eik); }
 }
 // dpred = g * a_c / frames * w * (pred - y) / sqrt(S_e S_y): the row coefficient in fp64, every element rounded once; a row with S_e = 0 gets zeros
@@ -514,42 +510,15 @@ __global__ void __launch_bounds__(NT) wlp_bwd_kernel(const float* __restrict__ p
     if (g.span == 0 && g.lane < h) wlp_px_grad<CT>(pf, yf, df, hw, C, s, g.lane, hat, coef);
     wlp_span_grad<CT>(pf + h, yf + h, df + h, hw, C, s, lo, hi, g.lane, width, vec, hat, coef);
 }
-// eikonal_bwd_kernel's tile (kept apart so that kernel keeps its instruction stream) on a channel that lies inside pred: frames fstride apart, the channel at `off`, spacing 1 / inv_dx (= dx / div); the adjoint
-// is ADDED to dpred's channel (the data term's launch has written it).  scale = 2 g lambda / (frames H W) is formed from g[0] here.
+// eik_bwd_tile on a channel that lies inside pred: frames fstride apart, the channel at `off`, spacing 1 / inv_dx (= dx / div); the adjoint is ADDED to
+// dpred's channel (the data term's launch has written it).  scale = 2 g lambda / (frames H W) is formed from g[0] here.
 __global__ void __launch_bounds__(NT) wlp_eik_bwd_kernel(const float* __restrict__ pred, long frames, long fstride, long off, int H, int W, int tiles_y, int tiles_x,
                                                         double inv_dx, double lambda, const float* __restrict__ g, float* __restrict__ dpred) {
-    __shared__ double qy[EIK_TH + 2][EIK_TW + 2], qx[EIK_TH + 2][EIK_TW + 2];
     const long tile = blockIdx.x;
     const int x0 = (int)(tile % tiles_x) * EIK_TW, y0 = (int)((tile / tiles_x) % tiles_y) * EIK_TH;
     const long frame = tile / ((long)tiles_x * tiles_y);
-    const float* f = pred + frame * fstride + off;
-    float* d = dpred + frame * fstride + off;
     const double scale = 2.0 * (double)g[0] * lambda / (double)(frames * H * W);
-    for (int i = threadIdx.x; i < (EIK_TH + 2) * (EIK_TW + 2); i += NT) {
-        const int ly = i / (EIK_TW + 2), lx = i % (EIK_TW + 2), y = y0 - 1 + ly, x = x0 - 1 + lx;
-        EikCell c = {0.0, 0.0};
-        if (y >= 0 && y < H && x >= 0 && x < W) c = eik_cell(f, y, x, H, W, inv_dx, scale);
-        qy[ly][lx] = c.qy; qx[ly][lx] = c.qx;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < EIK_TH * EIK_TW; i += NT) {
-        const int ly = i / EIK_TW, lx = i % EIK_TW, y = y0 + ly, x = x0 + lx;
-        if (y >= H || x >= W) continue;
-        double acc = 0.0;
-        if (H > 1) {
-            for (int j = max(y - 1, 0); j <= min(y + 1, H - 1); ++j) {
-                const double k = eik_weight(j, y, H);
-                if (k != 0.0) acc += k * qy[j - y0 + 1][lx + 1];
-            }
-        }
-        if (W > 1) {
-            for (int j = max(x - 1, 0); j <= min(x + 1, W - 1); ++j) {
-                const double k = eik_weight(j, x, W);
-                if (k != 0.0) acc += k * qx[ly + 1][j - x0 + 1];
-            }
-        }
-        d[(long)y * W + x] += (float)(acc * inv_dx);
-    }
+    eik_bwd_tile<true>(pred + frame * fstride + off, dpred + frame * fstride + off, H, W, y0, x0, inv_dx, scale);
 }
 
 // spans per frame: enough workgroups to fill the chip, every lane of a span with whole 16-byte groups

@@ -24,25 +24,6 @@ constexpr int KDE_STATS = 4;           // {mean, unbiased variance, min, max} pe
 
 int grid_for(long total) { return (int)std::max<long>(1, std::min<long>((total + NT - 1) / NT, 256L * 16)); }
 
-// ---------------------------------------------------------------------------- workgroup reductions in a fixed order
-enum { RED_SUM = 0, RED_MIN = 1, RED_MAX = 2 };
-template <int OP> __device__ __forceinline__ double red_op(double a, double b) {
-    if constexpr (OP == RED_SUM) return a + b;
-    else if constexpr (OP == RED_MIN) return fmin(a, b);
-    else return fmax(a, b);
-}
-// every thread gets the reduction of v over the workgroup, formed in a fixed order (butterfly inside a wave, then the waves in order)
-template <int OP> __device__ __forceinline__ double block_reduce(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = red_op<OP>(v, __shfl_xor(v, o, 64));
-    __syncthreads();                                                        // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < NT / 64; ++w) t = red_op<OP>(t, red[w]);
-    return t;
-}
-
 // ---------------------------------------------------------------------------- physics metrics of a clip
 // Eikonal residual of a signed-distance field (utils/losses.py:5-15): torch.gradient(edge_order=1, spacing=dx) along H and W
 // (central differences inside, one-sided at the borders), out += sum over pixels of (|grad phi| - 1)^2   (caller divides by the count)
@@ -65,7 +46,7 @@ __global__ void __launch_bounds__(NT) eikonal_kernel(const float* __restrict__ p
         const float r = sqrtf(gy * gy + gx * gx) - 1.f;
         acc += (double)(r * r);
     }
-    const double t = block_reduce<RED_SUM>(acc, red);
+    const double t = block_reduce<RED_SUM, NT / 64>(acc, red);
     if (threadIdx.x == 0) atomicAdd(out, t);
 }
 // The rollout notebook's Eikonal score (scripts/inference_autoregressive.ipynb, `get_eikonal_loss`): per frame, the mean of
@@ -77,7 +58,7 @@ __global__ void __launch_bounds__(NT) eikonal_l1_kernel(const float* __restrict_
     double acc = 0.0;
     for (int i = threadIdx.x; i < H * W; i += NT)
         acc += (double)eikonal_l1_px([&](int yy, int xx) { return f[yy * W + xx]; }, i % W, i / W, H, W, inv_2dx);
-    const double t = block_reduce<RED_SUM>(acc, red);
+    const double t = block_reduce<RED_SUM, NT / 64>(acc, red);
     if (threadIdx.x == 0) out[blockIdx.x] = (float)(t / ((double)H * W));
 }
 // Heater heat flux per frame (utils/heatflux.py:17-38): heater_row_flux of the bottom row y = 0, coef = 0.054 / (dx * lc).  A wave per frame.
@@ -97,12 +78,12 @@ __global__ void __launch_bounds__(NT) kde_stats_kernel(const double* __restrict_
     const double* v = (set ? q : p) + (long)r * len;
     double sum = 0.0, lo = INFINITY, hi = -INFINITY;
     for (long j = threadIdx.x; j < len; j += NT) { const double x = v[j]; sum += x; lo = fmin(lo, x); hi = fmax(hi, x); }
-    const double mean = block_reduce<RED_SUM>(sum, red) / (double)len;
-    lo = block_reduce<RED_MIN>(lo, red);
-    hi = block_reduce<RED_MAX>(hi, red);
+    const double mean = block_reduce<RED_SUM, NT / 64>(sum, red) / (double)len;
+    lo = block_reduce<RED_MIN, NT / 64>(lo, red);
+    hi = block_reduce<RED_MAX, NT / 64>(hi, red);
     double sq = 0.0;
     for (long j = threadIdx.x; j < len; j += NT) { const double e = v[j] - mean; sq += e * e; }
-    const double var = block_reduce<RED_SUM>(sq, red) / (double)(len - 1);
+    const double var = block_reduce<RED_SUM, NT / 64>(sq, red) / (double)(len - 1);
     if (threadIdx.x == 0) {
         double* st = stats + ((long)r * 2 + set) * KDE_STATS;
         st[0] = mean; st[1] = var; st[2] = lo; st[3] = hi;
@@ -175,8 +156,8 @@ __global__ void __launch_bounds__(NT) kde_finish_kernel(long n, long m, int poin
         if (i < simpson_n) s1 += ((i == 0 || i == simpson_n - 1) ? 1.0 : (i & 1) ? 4.0 : 2.0) * f;
         if (simpson_n != points && i >= points - 3) s2 += (i == points - 1 ? 5.0 : i == points - 2 ? 8.0 : -1.0) * f;
     }
-    s1 = block_reduce<RED_SUM>(s1, red);
-    s2 = block_reduce<RED_SUM>(s2, red);
+    s1 = block_reduce<RED_SUM, NT / 64>(s1, red);
+    s2 = block_reduce<RED_SUM, NT / 64>(s2, red);
     if (threadIdx.x == 0) kl[r] = step * (s1 / 3.0) + step * (s2 / 12.0);
 }
 }  // namespace

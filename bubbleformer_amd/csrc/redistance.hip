@@ -67,7 +67,7 @@ __device__ void redistance_frame(const D dist, const PhiSrc src, Write write, bo
                                  int* rounds_out, float* change_out) {
     __shared__ int s_flag[2];
     __shared__ int s_count[2];
-    __shared__ double s_sum[NW];
+    __shared__ double s_sum[NW];      // added from 0.0 by one thread in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const int n = H * W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int plane1 = (n + 1) >> 1;                                        // where the cells of colour 1 begin
     const float inv_W = 1.f / (float)W, inf = __uint_as_float(INF_BITS);

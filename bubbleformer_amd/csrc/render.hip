@@ -21,7 +21,7 @@ constexpr double RN_INF = __builtin_huge_val();
 // ---------------------------------------------------------------------------------------------------------------- ranges
 __global__ void __launch_bounds__(RN_NT) render_ranges_kernel(const float* __restrict__ src, long frames, int C, long HW, int c_sdf, int c_temp,
                                                              int c_velx, int c_vely, double* __restrict__ part) {
-    __shared__ double red[RN_NT / 64][4];
+    __shared__ double red[RN_NT / 64][4];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const int qn = blockIdx.y;                                                      // 0 signed distance, 1 temperature, 2 speed
     const int ca = qn == 0 ? c_sdf : qn == 1 ? c_temp : c_velx, cb = qn == 2 ? c_vely : 0;
     const long n = frames * HW;

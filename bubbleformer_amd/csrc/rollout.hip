@@ -22,7 +22,7 @@ constexpr int RS_QUADS = 1024, RS_MAX_ROWS = 64;      // 4-pixel groups per work
 int score_rows(int Ho, int Wo) { return (int)std::max<long>(1, std::min<long>(RS_MAX_ROWS, ((long)Ho * ((Wo + 3) / 4) + RS_QUADS - 1) / RS_QUADS)); }
 
 __global__ void __launch_bounds__(NT) rollout_score_kernel(ScoreArgs a) {
-    __shared__ double red[NT / 64][4];
+    __shared__ double red[NT / 64][4];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const RolloutStep& v = a.v;
     const int s = v.current();
     if (s < 0) return;                                                     // a step behind the last row: nothing is written (pass 2 leaves the counter alone)

@@ -11,10 +11,10 @@
 //   rows       L rows of one real field (e = p - y, p or y: never two fields in one transform) -> Hermitian half-spectrum [y][kx <= W/2];
 //   columns    L columns kx of that half-spectrum -> the full transform in LDS -> |X|^2 per shell, per column in a set order;
 //   finish     one workgroup per frame adds chunks and column groups in order, divides, takes roots and bands, rounds.
-// The transform is a Stockham autosort in LDS over the mixed-radix factorisation of the side (4s, then 2, 3, 5, then every other prime
-// factor by one generic radix-p stage of p terms per output, so a prime side is a plain DFT: correct, merely slow).
-// A mode's shell is decided in int64 (the floating-point root only proposes a candidate that the integer inequalities correct).
+// The transform and a mode's shell are fft_lines.h's (the spectral criterion's too): a Stockham autosort in LDS over the mixed-radix
+// factorisation of the side, here in complex fp64 on dense lines (line stride = side); the shell is decided in int64.
 #include "clip_store.h"
+#include "fft_lines.h"
 #include <algorithm>
 
 namespace {
@@ -26,28 +26,8 @@ constexpr int PW_PIX = 4096, PW_MAX_CHUNKS = 64;   // pixels per pointwise workg
 constexpr int PW_VALS = 6;                         // {sum e^2, ring sum e^2, interface sum e^2, max |e|, NaN seen, interface cells}
 
 typedef double2 cplx;
-__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cplx cadd(cplx a, cplx b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cplx csub(cplx a, cplx b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ cplx mul_mi(cplx a) { return make_double2(a.y, -a.x); }        // a * (-i)
-
-struct Plan { int n, nf; short r[12]; };           // n = product of r[0 .. nf)
-Plan make_plan(int n) {
-    Plan p{n, 0, {}};
-    int m = n;
-    auto take = [&](int r) { while (m % r == 0) { p.r[p.nf++] = (short)r; m /= r; } };
-    take(4); take(2); take(3); take(5);
-    for (int r = 7; m > 1; r += 2) take(r);
-    return p;
-}
+static_assert(NT == FFT_NT, "the transform's stage loops stride by the workgroup size");
 int lines_for(int n) { return std::max(1, std::min(MAX_LINES, LINE_ELEMS / n)); }
-int shell_count(int H, int W) {
-    const long S = std::min(H, W), v = S * S / 2;
-    long q = (long)sqrt((double)v);
-    while ((q + 1) * (q + 1) <= v) ++q;
-    while (q * q > v) --q;
-    return (int)q + 1;
-}
 int pw_chunks(int H, int W) { return (int)std::max<long>(1, std::min<long>(PW_MAX_CHUNKS, ((long)H * W + PW_PIX - 1) / PW_PIX)); }
 
 struct WsLayout {                                  // byte offsets into the workspace, each 16-byte aligned
@@ -114,9 +94,7 @@ __global__ void __launch_bounds__(NT) twiddle_kernel(cplx* tw_w, int W, cplx* tw
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= W + H) return;
     const int n = i < W ? W : H, j = i < W ? i : i - W;
-    double sn, cs;
-    sincospi(2.0 * (double)j / (double)n, &sn, &cs);
-    (i < W ? tw_w : tw_h)[j] = make_double2(cs, -sn);
+    (i < W ? tw_w : tw_h)[j] = twiddle<cplx>(j, n);
 }
 
 __global__ void __launch_bounds__(NT) interface_mask_kernel(ErrArgs a, long mframes) {
@@ -137,7 +115,7 @@ __global__ void __launch_bounds__(NT) interface_mask_kernel(ErrArgs a, long mfra
 }
 
 __global__ void __launch_bounds__(NT) pointwise_kernel(ErrArgs a) {
-    __shared__ double red[NT / 64][PW_VALS];
+    __shared__ double red[NT / 64][PW_VALS];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     int s;
     if (!live(a, s)) return;
     const int chunks = a.lay.chunks, H = a.H, W = a.W;
@@ -171,79 +149,7 @@ __global__ void __launch_bounds__(NT) pointwise_kernel(ErrArgs a) {
     }
 }
 
-// ---------------------------------------------------------------------------- the transform
-template <int R> __device__ __forceinline__ void butterfly(cplx* v);
-template <> __device__ __forceinline__ void butterfly<2>(cplx* v) { const cplx a = v[0]; v[0] = cadd(a, v[1]); v[1] = csub(a, v[1]); }
-template <> __device__ __forceinline__ void butterfly<3>(cplx* v) {
-    const double s3 = 0.86602540378443864676;
-    const cplx t = cadd(v[1], v[2]), m = make_double2(v[0].x - 0.5 * t.x, v[0].y - 0.5 * t.y), d = csub(v[1], v[2]);
-    const cplx r = mul_mi(make_double2(s3 * d.x, s3 * d.y));
-    v[0] = cadd(v[0], t); v[1] = cadd(m, r); v[2] = csub(m, r);
-}
-template <> __device__ __forceinline__ void butterfly<4>(cplx* v) {
-    const cplx a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = mul_mi(csub(v[1], v[3]));
-    v[0] = cadd(a0, a2); v[1] = cadd(a1, a3); v[2] = csub(a0, a2); v[3] = csub(a1, a3);
-}
-template <> __device__ __forceinline__ void butterfly<5>(cplx* v) {
-    const double c1 = 0.30901699437494742410, c2 = -0.80901699437494742410, s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;
-    const cplx a1 = cadd(v[1], v[4]), a2 = cadd(v[2], v[3]), b1 = csub(v[1], v[4]), b2 = csub(v[2], v[3]);
-    const cplx r1 = make_double2(v[0].x + c1 * a1.x + c2 * a2.x, v[0].y + c1 * a1.y + c2 * a2.y);
-    const cplx r2 = make_double2(v[0].x + c2 * a1.x + c1 * a2.x, v[0].y + c2 * a1.y + c1 * a2.y);
-    const cplx i1 = mul_mi(make_double2(s1 * b1.x + s2 * b2.x, s1 * b1.y + s2 * b2.y));
-    const cplx i2 = mul_mi(make_double2(s2 * b1.x - s1 * b2.x, s2 * b1.y - s1 * b2.y));
-    v[0] = cadd(v[0], cadd(a1, a2)); v[1] = cadd(r1, i1); v[4] = csub(r1, i1); v[2] = cadd(r2, i2); v[3] = csub(r2, i2);
-}
-
-// one Stockham stage of radix R over `lines` lines of N: butterfly j of a line reads x[j + t * N/R], turned by w^(t k) with k = j % Ns and
-// w = exp(-2 pi i / (Ns R)), and writes y[(j - k) R + k + t Ns]
-template <int R> __device__ __forceinline__ void stage(const cplx* x, cplx* y, const cplx* tw, int N, int Ns, int lines) {
-    const int T = N / R, stride = T / Ns;
-    for (int i = threadIdx.x; i < lines * T; i += NT) {
-        const int l = i / T, j = i - l * T, k = j % Ns;
-        const cplx* src = x + l * N + j;
-        cplx v[R];
-        v[0] = src[0];
-#pragma unroll
-        for (int t = 1; t < R; ++t) v[t] = cmul(src[t * T], tw[t * k * stride]);
-        butterfly<R>(v);
-        cplx* dst = y + l * N + (j - k) * R + k;
-#pragma unroll
-        for (int t = 0; t < R; ++t) dst[t * Ns] = v[t];
-    }
-}
-// any other prime factor p: a thread per OUTPUT adds its p terms in order; both turns are one table entry, stepped modulo N
-__device__ __forceinline__ void stage_generic(const cplx* x, cplx* y, const cplx* tw, int N, int Ns, int p, int lines) {
-    const int T = N / p, stride = T / Ns;
-    for (int i = threadIdx.x; i < lines * N; i += NT) {
-        const int l = i / N, o = i - l * N, k = o % Ns, u = (o / Ns) % p, j = (o / (Ns * p)) * Ns + k;
-        const int step = (k * stride + u * T) % N;
-        const cplx* src = x + l * N + j;
-        cplx acc = src[0];
-        for (int t = 1, idx = step; t < p; ++t) {
-            acc = cadd(acc, cmul(src[t * T], tw[idx]));
-            idx += step; if (idx >= N) idx -= N;
-        }
-        y[l * N + o] = acc;
-    }
-}
-// `lines` transforms of length plan.n from x; returns the buffer (x or y) that holds them.  Every thread of the workgroup calls this.
-__device__ __forceinline__ cplx* fft_lines(cplx* x, cplx* y, const cplx* tw, const Plan& plan, int lines) {
-    const int N = plan.n;
-    int Ns = 1;
-    for (int f = 0; f < plan.nf; ++f) {
-        const int r = plan.r[f];
-        if (r == 4) stage<4>(x, y, tw, N, Ns, lines);
-        else if (r == 2) stage<2>(x, y, tw, N, Ns, lines);
-        else if (r == 3) stage<3>(x, y, tw, N, Ns, lines);
-        else if (r == 5) stage<5>(x, y, tw, N, Ns, lines);
-        else stage_generic(x, y, tw, N, Ns, r, lines);
-        __syncthreads();
-        cplx* t = x; x = y; y = t;
-        Ns *= r;
-    }
-    return x;
-}
-
+// ---------------------------------------------------------------------------- the transform (fft_lines.h), dense lines
 struct FftLds { cplx tw[MAX_SIDE]; cplx a[LINE_ELEMS]; cplx b[LINE_ELEMS]; };
 
 // rows: workgroup = (frame, field slot, group of rows_w rows).  inter [frame][slot][y][kx] complex fp64, kx in [0, W/2]
@@ -270,15 +176,6 @@ __global__ void __launch_bounds__(NT) spectra_rows_kernel(ErrArgs a) {
         const int l = i / Wh, kx = i - l * Wh;
         inter[(long)l * Wh + kx] = out[l * W + kx];
     }
-}
-
-// the shell of mode (fy, fx): the largest q with q^2 H^2 W^2 <= S^2 (fy^2 W^2 + fx^2 H^2), in int64
-__device__ __forceinline__ int shell_of(long fy, long fx, long H, long W) {
-    const long S = min(H, W), D = H * H * W * W, V = S * S * (fy * fy * W * W + fx * fx * H * H);
-    long q = (long)sqrt((double)V / (double)D);
-    while ((q + 1) * (q + 1) * D <= V) ++q;
-    while (q > 0 && q * q * D > V) --q;
-    return (int)q;
 }
 
 // columns: workgroup = (frame, field slot, group of rows_h columns kx).  For a column the shell does not fall as |fy| grows, so the modes of

@@ -1,11 +1,11 @@
 // The shell-weighted spectral criterion (utils.losses.SpectralLpLoss; no reference program): the training configuration's
 // relative L2 taken in Fourier space with one weight per radial shell and per field.  pred, y are [rows][H][W] fp32, rows = B * T * C, field
-// c = row % C; X(ky, kx) = sum x[r][s] exp(-2 pi i (ky r / H + kx s / W)), the shell q(ky, kx) section 18's (csrc/spectra.hip), bit for bit:
+// c = row % C; X(ky, kx) = sum x[r][s] exp(-2 pi i (ky r / H + kx s / W)), the shell q(ky, kx) section 18's, by the same text (csrc/fft_lines.h):
 //   S_e[row] = sum_k w[c][q(k)] |E_k|^2 / (H W),  S_y the same over Y,  rho = sqrt(S_e / S_y),  loss = sum_c a_c mean_{b,t} rho
 //   dpred    = g a_c / (B T) * Re ifft2(w E) / sqrt(S_e S_y)
-// The transforms are fp32 (float2) Stockham autosorts in LDS over the mixed-radix factorisation of the side (4s, then 2, 3, 5, then every other
-// prime factor by one generic radix-p stage), spectra.hip's plan; twiddles are formed in fp64 by sincospi and rounded once; every sum is fp64
-// in an order that depends on (H, W) alone (no float atomics): two calls give the same bits, a frame the same bits alone and in a batch.
+// The transforms are fft_lines.h's Stockham autosorts in LDS, here in fp32 (float2) on lines an odd stride apart; twiddles are formed in fp64
+// by sincospi and rounded once; every sum is fp64 in an order that depends on (H, W) alone (no float atomics): two calls give the same bits,
+// a frame the same bits alone and in a batch.
 //
 // Launches of the forward, all on the caller's stream:
 //   tables    exp(-2 pi i j / N) for N = W and N = H, and the shell of every mode (ky, kx <= W/2) as int16 (built in every call, nothing kept);
@@ -17,7 +17,7 @@
 //   finish    one workgroup: column groups in order, ratios, means over the frames, field terms, loss; leaves {S_e, S_y}.
 // The backward is one launch: a group of rows of the saved half-spectrum, the Hermitian line rebuilt in LDS, transformed along x, the real part
 // times the row coefficient written to every element of dpred.
-#include "bf_common.h"
+#include "fft_lines.h"
 #include <algorithm>
 #include <string>
 
@@ -30,29 +30,9 @@ constexpr int SLP_MAX_C = 16;
 constexpr int PART = 4;                            // {sum w |E|^2, sum w |Y|^2, sum |E|^2, sum |Y|^2} per (row, column group)
 
 typedef float2 cplx;
-__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cplx cadd(cplx a, cplx b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cplx csub(cplx a, cplx b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ cplx mul_mi(cplx a) { return make_float2(a.y, -a.x); }          // a * (-i)
-
-struct Plan { int n, nf; short r[12]; };           // n = product of r[0 .. nf)
-Plan make_plan(int n) {
-    Plan p{n, 0, {}};
-    int m = n;
-    auto take = [&](int r) { while (m % r == 0) { p.r[p.nf++] = (short)r; m /= r; } };
-    take(4); take(2); take(3); take(5);
-    for (int r = 7; m > 1; r += 2) take(r);
-    return p;
-}
+static_assert(NT == FFT_NT, "the transform's stage loops stride by the workgroup size");
 int line_stride(int n) { return n | 1; }           // odd: the lines of a transposed load fall into different LDS banks
 int lines_for(int n, int fields) { return std::max(1, std::min(MAX_LINES / fields, LINE_ELEMS / (fields * line_stride(n)))); }
-int shell_count(int H, int W) {
-    const long S = std::min(H, W), v = S * S / 2;
-    long q = (long)sqrt((double)v);
-    while ((q + 1) * (q + 1) <= v) ++q;
-    while (q * q > v) --q;
-    return (int)q + 1;
-}
 
 struct SlpFields { double a[SLP_MAX_C]; };
 struct SlpLayout {                                 // byte offsets into the workspace, each 16-byte aligned
@@ -86,101 +66,14 @@ struct SlpColsArgs {                               // what the column kernel rea
     Plan ph;
 };
 
-// ---------------------------------------------------------------------------- the transform
-template <int R> __device__ __forceinline__ void butterfly(cplx* v);
-template <> __device__ __forceinline__ void butterfly<2>(cplx* v) { const cplx a = v[0]; v[0] = cadd(a, v[1]); v[1] = csub(a, v[1]); }
-template <> __device__ __forceinline__ void butterfly<3>(cplx* v) {
-    const float s3 = 0.86602540378443864676f;
-    const cplx t = cadd(v[1], v[2]), m = make_float2(v[0].x - 0.5f * t.x, v[0].y - 0.5f * t.y), d = csub(v[1], v[2]);
-    const cplx r = mul_mi(make_float2(s3 * d.x, s3 * d.y));
-    v[0] = cadd(v[0], t); v[1] = cadd(m, r); v[2] = csub(m, r);
-}
-template <> __device__ __forceinline__ void butterfly<4>(cplx* v) {
-    const cplx a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = mul_mi(csub(v[1], v[3]));
-    v[0] = cadd(a0, a2); v[1] = cadd(a1, a3); v[2] = csub(a0, a2); v[3] = csub(a1, a3);
-}
-template <> __device__ __forceinline__ void butterfly<5>(cplx* v) {
-    const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f, s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-    const cplx a1 = cadd(v[1], v[4]), a2 = cadd(v[2], v[3]), b1 = csub(v[1], v[4]), b2 = csub(v[2], v[3]);
-    const cplx r1 = make_float2(v[0].x + c1 * a1.x + c2 * a2.x, v[0].y + c1 * a1.y + c2 * a2.y);
-    const cplx r2 = make_float2(v[0].x + c2 * a1.x + c1 * a2.x, v[0].y + c2 * a1.y + c1 * a2.y);
-    const cplx i1 = mul_mi(make_float2(s1 * b1.x + s2 * b2.x, s1 * b1.y + s2 * b2.y));
-    const cplx i2 = mul_mi(make_float2(s2 * b1.x - s1 * b2.x, s2 * b1.y - s1 * b2.y));
-    v[0] = cadd(v[0], cadd(a1, a2)); v[1] = cadd(r1, i1); v[4] = csub(r1, i1); v[2] = cadd(r2, i2); v[3] = csub(r2, i2);
-}
-
-// one Stockham stage of radix R over `lines` lines of N, `ls` elements apart: butterfly j of a line reads x[j + t * N/R], turned by w^(t k) with
-// k = j % Ns and w = exp(-2 pi i / (Ns R)), and writes y[(j - k) R + k + t Ns]
-template <int R> __device__ __forceinline__ void stage(const cplx* x, cplx* y, const cplx* tw, int N, int Ns, int lines, int ls) {
-    const int T = N / R, stride = T / Ns;
-    for (int i = threadIdx.x; i < lines * T; i += NT) {
-        const int l = i / T, j = i - l * T, k = j % Ns;
-        const cplx* src = x + l * ls + j;
-        cplx v[R];
-        v[0] = src[0];
-#pragma unroll
-        for (int t = 1; t < R; ++t) v[t] = cmul(src[t * T], tw[t * k * stride]);
-        butterfly<R>(v);
-        cplx* dst = y + l * ls + (j - k) * R + k;
-#pragma unroll
-        for (int t = 0; t < R; ++t) dst[t * Ns] = v[t];
-    }
-}
-// any other prime factor p: a thread per OUTPUT adds its p terms in order; both turns are one table entry, stepped modulo N
-__device__ __forceinline__ void stage_generic(const cplx* x, cplx* y, const cplx* tw, int N, int Ns, int p, int lines, int ls) {
-    const int T = N / p, stride = T / Ns;
-    for (int i = threadIdx.x; i < lines * N; i += NT) {
-        const int l = i / N, o = i - l * N, k = o % Ns, u = (o / Ns) % p, j = (o / (Ns * p)) * Ns + k;
-        const int step = (k * stride + u * T) % N;
-        const cplx* src = x + l * ls + j;
-        cplx acc = src[0];
-        for (int t = 1, idx = step; t < p; ++t) {
-            acc = cadd(acc, cmul(src[t * T], tw[idx]));
-            idx += step; if (idx >= N) idx -= N;
-        }
-        y[l * ls + o] = acc;
-    }
-}
-// `lines` transforms of length plan.n from x; returns the buffer (x or y) that holds them.  Every thread of the workgroup calls this; the
-// caller has synchronised after filling x, and the result is synchronised.
-__device__ __forceinline__ cplx* fft_lines(cplx* x, cplx* y, const cplx* tw, const Plan& plan, int lines, int ls) {
-    const int N = plan.n;
-    int Ns = 1;
-    for (int f = 0; f < plan.nf; ++f) {
-        const int r = plan.r[f];
-        if (r == 4) stage<4>(x, y, tw, N, Ns, lines, ls);
-        else if (r == 2) stage<2>(x, y, tw, N, Ns, lines, ls);
-        else if (r == 3) stage<3>(x, y, tw, N, Ns, lines, ls);
-        else if (r == 5) stage<5>(x, y, tw, N, Ns, lines, ls);
-        else stage_generic(x, y, tw, N, Ns, r, lines, ls);
-        __syncthreads();
-        cplx* t = x; x = y; y = t;
-        Ns *= r;
-    }
-    return x;
-}
-
+// ---------------------------------------------------------------------------- the transform (fft_lines.h), lines an odd stride apart
 struct FftLds { cplx tw[MAX_SIDE]; cplx a[LINE_ELEMS]; cplx b[LINE_ELEMS]; };
-
-__device__ __forceinline__ cplx twiddle(int j, int n) {                    // exp(-2 pi i j / n): fp64, rounded once
-    double sn, cs;
-    sincospi(2.0 * (double)j / (double)n, &sn, &cs);
-    return make_float2((float)cs, (float)-sn);
-}
-// the shell of mode (fy, fx): the largest q with q^2 H^2 W^2 <= S^2 (fy^2 W^2 + fx^2 H^2), in int64 (spectra.hip's rule)
-__device__ __forceinline__ int shell_of(long fy, long fx, long H, long W) {
-    const long S = min(H, W), D = H * H * W * W, V = S * S * (fy * fy * W * W + fx * fx * H * H);
-    long q = (long)sqrt((double)V / (double)D);
-    while ((q + 1) * (q + 1) * D <= V) ++q;
-    while (q > 0 && q * q * D > V) --q;
-    return (int)q;
-}
 
 __global__ void __launch_bounds__(NT) slp_tables_kernel(cplx* tw_w, cplx* tw_h, short* shell, int H, int W) {
     const int Wh = W / 2 + 1;
     const long i = (long)blockIdx.x * NT + threadIdx.x;
-    if (i < W) tw_w[i] = twiddle((int)i, W);
-    else if (i < W + H) tw_h[i - W] = twiddle((int)(i - W), H);
+    if (i < W) tw_w[i] = twiddle<cplx>((int)i, W);
+    else if (i < W + H) tw_h[i - W] = twiddle<cplx>((int)(i - W), H);
     else if (i < W + H + (long)H * Wh) {
         const long m = i - W - H;
         const int ky = (int)(m / Wh), kx = (int)(m - (long)ky * Wh);
@@ -219,7 +112,7 @@ __global__ void __launch_bounds__(NT) slp_rows_kernel(SlpArgs a) {
 // modes in a set order, the lanes by butterfly, the waves in order.
 __global__ void __launch_bounds__(NT) slp_cols_kernel(SlpColsArgs a) {
     __shared__ FftLds L;
-    __shared__ double red[NT / 64][PART];
+    __shared__ double red[NT / 64][PART];      // several values at once in this kernel's own order, which its restatement's bits pin: not bf_common.h's block_reduce
     const int H = a.H, W = a.W, Wh = W / 2 + 1, per = a.per, groups = a.groups, ls = H | 1;
     const int g = blockIdx.x % groups;
     const long r = blockIdx.x / groups;
@@ -271,16 +164,6 @@ __global__ void __launch_bounds__(NT) slp_cols_kernel(SlpColsArgs a) {
     }
 }
 
-// every thread gets the sum of v over the workgroup: butterfly inside a wave, then the waves in order
-__device__ __forceinline__ double slp_block_sum(double v, double* red) {
-    v = wave_sum(v);
-    __syncthreads();                                  // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < NT / 64; ++w) t += red[w];
-    return t;
-}
 // One workgroup: sums[row] = {S_e, S_y}, the column groups in order, over H W; rho = sqrt(S_e / S_y) and the same at w = 1; terms[c] = a_c * mean
 // over the frames of rho, terms[C + c] the same at w = 1, added in a fixed order; loss = sum_c terms[c].  All fp64, each output rounded once.
 __global__ void __launch_bounds__(NT) slp_finish_kernel(SlpArgs a, SlpFields fa, double* __restrict__ sums, float* __restrict__ loss, float* __restrict__ terms) {
@@ -302,7 +185,7 @@ __global__ void __launch_bounds__(NT) slp_finish_kernel(SlpArgs a, SlpFields fa,
     for (int c = 0; c < C; ++c) {
         double aw = 0.0, a1 = 0.0;
         for (long f = threadIdx.x; f < frames; f += NT) { aw += rho[2 * (f * C + c)]; a1 += rho[2 * (f * C + c) + 1]; }
-        const double tw = fa.a[c] * (slp_block_sum(aw, red) / (double)frames), t1 = fa.a[c] * (slp_block_sum(a1, red) / (double)frames);
+        const double tw = fa.a[c] * (block_reduce<RED_SUM, NT / 64>(aw, red) / (double)frames), t1 = fa.a[c] * (block_reduce<RED_SUM, NT / 64>(a1, red) / (double)frames);
         if (threadIdx.x == 0) { terms[c] = (float)tw; terms[C + c] = (float)t1; }
         total += tw;
     }
@@ -318,7 +201,7 @@ __global__ void __launch_bounds__(NT) slp_bwd_kernel(const cplx* __restrict__ sp
     const int g = blockIdx.x % groups;
     const long r = blockIdx.x / groups;
     const int y0 = g * per, n = min(per, H - y0);
-    for (int i = threadIdx.x; i < W; i += NT) L.tw[i] = twiddle(i, W);
+    for (int i = threadIdx.x; i < W; i += NT) L.tw[i] = twiddle<cplx>(i, W);
     const double se = sums[2 * r], sy = sums[2 * r + 1];
     const double coef = se != 0.0 ? (double)gout[0] * fa.a[r % C] / (double)(rows / C) / sqrt(se * sy) / ((double)H * (double)W) : 0.0;
     const cplx* src = spec + (r * H + y0) * Wh;

@@ -209,6 +209,26 @@ def test_two_calls_give_the_same_bits():
     assert torch.equal(v1, v2) and torch.equal(t1, t2) and torch.equal(e1, e2) and torch.equal(g1, g2)
 
 
+def test_the_penalty_alone_has_the_bits_of_eikonal_loss_backward():
+    """The penalty's backward and eikonal_loss's backward run one tile body (losses.hip's eik_bwd_tile).  With zero field weights the data term
+    writes zeros and the tile adds onto them; with diff = 0, div = 1, eikonal = 1 and the default dx both kernels get inv_dx = 32 exactly and
+    scale = 2 g / (B T H W), g = 1: the same bits.  33 x 70 is three tile rows and two tile columns, both with ragged ends."""
+    from bubbleformer_amd.utils import InterfaceLpLoss, eikonal_loss
+    shape, s = (2, 2, 3, 33, 70), 1
+    pred, y = (t.to(DEV) for t in IR.make_inputs(shape, s, 1.0, 0.0, 1.0))
+    crit = InterfaceLpLoss(s, band=1.0, gain=0.0, diff=0.0, div=1.0, field_weights=(0, 0, 0), eikonal=1.0)
+    a = pred.detach().requires_grad_(True)
+    loss = crit(a, y)
+    loss.backward()
+    phi = pred[:, :, s].detach().clone().requires_grad_(True)
+    eikonal_loss(phi).backward()
+    torch.cuda.synchronize()
+    assert float(phi.grad.abs().max()) > 0.0
+    assert torch.equal(a.grad[:, :, s], phi.grad)
+    assert float(a.grad[:, :, 0].abs().max()) == 0.0 and float(a.grad[:, :, 2].abs().max()) == 0.0
+    assert torch.equal(crit.eikonal_term(), loss.detach())
+
+
 def test_forward_and_backward_capture_into_a_graph():
     shape, s = (2, 4, 4, 96, 96), 0
     crit = _criterion(shape, s, 2, LAM)
