@@ -111,6 +111,12 @@ class EnsembleRows(C.Structure):
     _fields_ = [(n, vp) for n in ("mean_rmse", "spread", "crps", "rank_hist", "mean")]
 
 
+class FlowRows(C.Structure):
+    """bf_flow_rows: four per-frame rows, then three per-pair rows; any may be NULL and is then not computed."""
+    _fields_ = [(n, vp) for n in ("divergence_rms", "kinetic_energy", "enstrophy", "bulk_cells", "transport_rms", "interface_speed_rms",
+                                  "transport_cells")]
+
+
 class OptStep(C.Structure):
     """bf_opt_step: one fused optimizer step -- buffers, clip coefficient, average, parameter groups, guard flag, sizes, scalars (read during the call only)."""
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("coef_dev", fp), ("avg", fp), ("chunk_group", vp), ("group_lr_scale", fp),
@@ -279,6 +285,8 @@ SIGNATURES = {
     "bf_ensemble_scores_ws_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_ensemble_scores": (C.c_int, [fp, i64, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(EnsembleRows), vp, i64, vp]),
     "bf_rollout_ensemble": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, P(EnsembleRows), vp, i64, vp]),
+    "bf_flow_consistency": (C.c_int, [fp, fp, fp, i64, C.c_int, C.c_int, C.c_int, f32, f32, f32, C.c_int, P(FlowRows), vp]),
+    "bf_rollout_flow": (C.c_int, [P(RolloutStep), C.c_int, C.c_int, C.c_int, f32, f32, f32, C.c_int, fp, P(FlowRows), P(FlowRows), vp]),
     "bf_render_ranges_ws_doubles": (i64, []),
     "bf_render_ranges": (C.c_int, [fp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "bf_render_tiles": (C.c_int, [P(RenderTile), C.c_int, P(RenderGeom), i64, vp, vp, vp, vp]),

@@ -1633,6 +1633,56 @@ def rollout_ensemble(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tens
     L.check(L.lib().bf_rollout_ensemble(C.byref(rec), M, int(bool(fair)), C.byref(out), _p(ws), ws.numel(), stream), "bf_rollout_ensemble")
 
 
+_FLOW_FRAME_ROWS = ("divergence_rms", "kinetic_energy", "enstrophy", "bulk_cells")
+_FLOW_PAIR_ROWS = ("transport_rms", "interface_speed_rms", "transport_cells")
+_FLOW_ROWS = _FLOW_FRAME_ROWS + _FLOW_PAIR_ROWS
+
+
+def _flow_rows(who: str, device, frame_lead: tuple, pair_lead: tuple, rows: dict):
+    """The seven optional outputs of the flow calls, checked -> bf_flow_rows: the frame rows of shape frame_lead, the pair rows of pair_lead."""
+    unknown = set(rows) - set(_FLOW_ROWS)
+    if unknown:
+        raise L.BubbleformerHipError(f"{who}: unknown outputs {sorted(unknown)}")
+    dtype = lambda k: torch.int32 if k.endswith("_cells") else torch.float32
+    want = {k: (rows.get(k), frame_lead if k in _FLOW_FRAME_ROWS else pair_lead, dtype(k)) for k in _FLOW_ROWS}
+    _check_tensors(who, device, want, _FLOW_ROWS)
+    return L.FlowRows(**{k: _p(rows.get(k)) for k in _FLOW_ROWS})
+
+
+def flow_consistency(sdf: torch.Tensor, velx: torch.Tensor, vely: torch.Tensor, dx: float, dt: float, band: float, interface_radius: int = 1,
+                     **rows: Optional[torch.Tensor]) -> None:
+    """Do a signed-distance field and a velocity agree with each other (bf_flow_consistency; include/bubbleformer_hip.h has the contract)?  sdf, velx,
+    vely (S, T, H, W) fp32 in physical units, H and W from 3 to 1024.  rows: any of divergence_rms, kinetic_energy, enstrophy (S, T) fp32, bulk_cells
+    (S, T) int32, transport_rms, interface_speed_rms (S, T - 1) fp32 and transport_cells (S, T - 1) int32, row t - 1 the pair that ends in frame t;
+    what is left out is not computed.  No workspace; allocates nothing: capturable in a HIP graph."""
+    _require_gpu(sdf)
+    if sdf.dim() != 4 or sdf.dtype != torch.float32 or not sdf.is_contiguous():
+        raise L.BubbleformerHipError("flow_consistency: sdf must be a contiguous fp32 (sequences, T, H, W) tensor")
+    S, T, H, W = (int(v) for v in sdf.shape)
+    _check_tensors("flow_consistency", sdf.device, {"velx": (velx, (S, T, H, W), torch.float32), "vely": (vely, (S, T, H, W), torch.float32)})
+    rec = _flow_rows("flow_consistency", sdf.device, (S, T), (S, T - 1), rows)
+    L.check(L.lib().bf_flow_consistency(_p(sdf), _p(velx), _p(vely), S, T, H, W, float(dx), float(dt), float(band), int(interface_radius), C.byref(rec),
+                                        _stream()), "bf_flow_consistency")
+
+
+def rollout_flow(pred: torch.Tensor, frames: torch.Tensor, first: torch.Tensor, step: torch.Tensor, table, channels, steps: int, dx: float, dt: float,
+                 band: float, interface_radius: int, carry: torch.Tensor, rows_pred: dict, rows_target: dict) -> None:
+    """The flow-consistency rows of one rollout step (bf_rollout_flow; include/bubbleformer_hip.h has the contract), of the de-normalised prediction
+    (rows_pred) and of the stored frames ``first[b] + (s + 1) * T + t`` (rows_target): ``flow_consistency``'s frame rows at row s * T + t of
+    (B, steps*T), its pair rows at row s * T + t - 1 of (B, steps*T - 1), s = the int32 ``step`` tensor ON THE DEVICE, which this call only reads --
+    issue it BEFORE the step's ``rollout_score`` and after ``rollout_redistance``.  channels = (sdf, velx, vely) among the prediction's channels;
+    carry (2, B, 3, Ho, Wo) fp32 hands the step's last predicted frame to the next step's call and belongs to these calls alone.  Allocates nothing."""
+    rec, stream = _rollout_step_args("rollout_flow", pred, frames, first, step, table, steps)
+    B, T, Cn, Ho, Wo = pred.shape
+    _check_tensors("rollout_flow", pred.device, {"carry": (carry, (2, B, 3, Ho, Wo), torch.float32)})
+    sides = [_flow_rows("rollout_flow", pred.device, (B, steps * T), (B, steps * T - 1), rows) for rows in (rows_pred, rows_target)]
+    sdf_c, velx_c, vely_c = (int(c) for c in channels)
+    if not all(0 <= c < Cn for c in (sdf_c, velx_c, vely_c)):
+        raise L.BubbleformerHipError(f"rollout_flow: channels {(sdf_c, velx_c, vely_c)} are not among the prediction's {Cn}")
+    L.check(L.lib().bf_rollout_flow(C.byref(rec), sdf_c, velx_c, vely_c, float(dx), float(dt), float(band), int(interface_radius), _p(carry),
+                                    C.byref(sides[0]), C.byref(sides[1]), stream), "bf_rollout_flow")
+
+
 def grad_norm_workspace(n: int, device) -> torch.Tensor:
     """The fp64 slab partials of grad_norm_ for a buffer of n elements (at most 1024 doubles)."""
     return torch.empty(int(L.lib().bf_grad_norm_ws_doubles(int(n))), dtype=torch.float64, device=device)

@@ -6,5 +6,6 @@ from .physics import BubbleCensus, BubbleMatch, BubbleSpec, BubbleTracks, Heater
 from .physics import RedistanceSpec, redistance  # noqa: F401
 from .physics import ErrorSpec, FieldErrors, field_errors, shell_count  # noqa: F401
 from .physics import EnsembleScores, EnsembleSpec, ensemble_scores  # noqa: F401
+from .physics import FlowConsistency, FlowSpec, flow_consistency  # noqa: F401
 from .plot_utils import RenderLayout, RenderSpec, plot_bubbleml, render_panels, render_strip, sdf_strip, temp_strip, vel_strip  # noqa: F401
 from .png import read_png, write_apng, write_png  # noqa: F401

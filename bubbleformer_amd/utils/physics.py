@@ -569,7 +569,87 @@ def field_errors(pred: torch.Tensor, target: torch.Tensor, sdf: Optional[torch.T
     return FieldErrors(**{k: (rows[k].reshape(lead + tuple(rows[k].shape[1:])) if k in rows else None) for k in ops._ERROR_ROWS})
 
 
-MAX_ENSEMBLE_MEMBERS = 32              # bf_ensemble_scores' limit: the members of a pixel are held in registers
+@dataclasses.dataclass(frozen=True)
+class FlowSpec:
+    """The flow-consistency rows of a rollout (``evaluate_rollouts_flow(..., FlowSpec(dt))``) or of ``flow_consistency``: ``dt``, the time between
+    two stored frames in the units of ``dx`` over velocity -- it has NO default: neither the reference nor the dataset carries it, and a wrong one
+    would silently scale the transport residual -- the cell size, the half-width of the band around the interface in which the transport residual
+    is taken (None: 3 dx), how far from a cell the window that decides "bulk liquid" reaches, and which output fields are the signed distance and
+    the two velocity components."""
+    dt: float
+    dx: float = 1.0 / 32
+    band: Optional[float] = None
+    interface_radius: int = 1
+    sdf_field: str = "dfun"
+    velx_field: str = "velx"
+    vely_field: str = "vely"
+
+    def __post_init__(self):
+        for name in ("dt", "dx"):
+            value = getattr(self, name)
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not value > 0:
+                raise ValueError(f"{name} must be positive, got {value!r}")
+        if self.band is not None and not self.band > 0:
+            raise ValueError(f"band must be None or positive, got {self.band!r}")
+        if int(self.interface_radius) != self.interface_radius or int(self.interface_radius) < 1:
+            raise ValueError(f"interface_radius must be an integer of at least 1, got {self.interface_radius!r}")
+
+    def band_width(self) -> float:
+        """The band's half-width: ``band``, or 3 dx."""
+        return 3.0 * float(self.dx) if self.band is None else float(self.band)
+
+    def channels(self, fields: Sequence[str]) -> tuple:
+        """The (signed-distance, x-velocity, y-velocity) channels among the output fields."""
+        fields = list(fields)
+        for name in (self.sdf_field, self.velx_field, self.vely_field):
+            if name not in fields:
+                raise ValueError(f"the flow-consistency rows need the field {name!r} among the output fields {fields}")
+        return tuple(fields.index(name) for name in (self.sdf_field, self.velx_field, self.vely_field))
+
+
+@dataclasses.dataclass
+class FlowConsistency:
+    """What ``flow_consistency`` returns; every tensor is on the device.  The frame rows keep the leading dims (..., T) of the fields, the pair rows
+    are (..., T - 1): row t - 1 is the pair of frames that ends in frame t."""
+    divergence_rms: torch.Tensor                    # (..., T)      fp32  RMS of div (u, v) over the bulk-liquid cells; NaN where there is none
+    bulk_cells: torch.Tensor                        # (..., T)      int32 their number
+    kinetic_energy: torch.Tensor                    # (..., T)      fp32  mean of (u^2 + v^2) / 2 over all cells
+    enstrophy: torch.Tensor                         # (..., T)      fp32  mean of vorticity^2 / 2 over the interior cells
+    transport_rms: torch.Tensor                     # (..., T - 1)  fp32  RMS of phi_t + u . grad phi over the band cells; NaN where there is none
+    interface_speed_rms: torch.Tensor               # (..., T - 1)  fp32  RMS of phi_t alone over them
+    transport_cells: torch.Tensor                   # (..., T - 1)  int32 their number
+
+    def transport_ratio(self) -> torch.Tensor:
+        """transport_rms / interface_speed_rms: 0 where the velocity explains all of the interface's motion, about 1 or above where it explains
+        none.  Never synchronises."""
+        return self.transport_rms / self.interface_speed_rms
+
+
+def flow_consistency(sdf: torch.Tensor, velx: torch.Tensor, vely: torch.Tensor, *, spec: FlowSpec) -> FlowConsistency:
+    """Do the signed-distance field and the velocity of (..., T, H, W) frames in physical units agree with each other (``ops.flow_consistency``;
+    DESIGN.md section 32)?  Per frame: the RMS divergence of (velx, vely) over the bulk liquid (interior cells with no vapour cell, sdf > 0, in
+    their (2 r + 1)^2 window), the mean kinetic energy and the mean enstrophy.  Per pair of consecutive frames: the RMS of the level-set transport
+    residual phi_t + u . grad phi (time-centred, central differences) over the interior cells within ``band`` of the interface, and of phi_t alone.
+    x runs along W, y along H.  fp64 arithmetic, one rounding, one launch with a workgroup per frame, the same bits on every call and for a
+    sequence alone or in a batch; never synchronises."""
+    if sdf.dim() < 3 or sdf.shape != velx.shape or sdf.shape != vely.shape:
+        raise ValueError(f"flow_consistency expects sdf, velx and vely of one shape (..., T, H, W), got {tuple(sdf.shape)}, {tuple(velx.shape)} "
+                         f"and {tuple(vely.shape)}")
+    if sdf.numel() < 1:
+        raise ValueError(f"flow_consistency needs at least one frame, got {tuple(sdf.shape)}")
+    from .. import ops
+    _require_gpu(sdf)
+    lead, (T, H, W) = tuple(sdf.shape[:-3]), (int(v) for v in sdf.shape[-3:])
+    flat = lambda t: t.reshape(-1, T, H, W).contiguous().float()
+    phi, u, v = flat(sdf), flat(velx), flat(vely)
+    S = phi.shape[0]
+    rows = {k: torch.empty((S, T if k in ops._FLOW_FRAME_ROWS else T - 1), dtype=torch.int32 if k.endswith("_cells") else torch.float32,
+                           device=phi.device) for k in ops._FLOW_ROWS}
+    ops.flow_consistency(phi, u, v, float(spec.dx), float(spec.dt), spec.band_width(), int(spec.interface_radius), **rows)
+    return FlowConsistency(**{k: r.reshape(lead + (r.shape[1],)) for k, r in rows.items()})
+
+
+MAX_ENSEMBLE_MEMBERS = 32             # bf_ensemble_scores' limit: the members of a pixel are held in registers
 
 
 @dataclasses.dataclass(frozen=True)

@@ -177,6 +177,48 @@ class RolloutReport:
     # from evaluate_rollouts_redistanced: the status and the change of the correction of every predicted frame (physics.redistance), else None
     redistance_rounds = None                            # (B, steps*T)        int32 passes run; 0 one sign or a skipped step, -1 non-finite, -2 ran out
     redistance_change = None                            # (B, steps*T)        fp32 root mean square change of the physical field
+    # from evaluate_rollouts_flow: do the signed distance and the velocity of one side agree with each other (physics.flow_consistency), else None.
+    # The *_target rows are the SIMULATION's own residuals, the baseline to read the prediction's against: they are not zero, since the frames are
+    # stored at a coarse interval and boiling moves the interface relative to the fluid.  Attributes as the error rows are, for the same reason
+    flow_divergence_pred = None                         # (B, steps*T)        fp32 RMS divergence of the velocity over the bulk-liquid cells
+    flow_divergence_target = None
+    flow_bulk_cells_pred = None                         # (B, steps*T)        int32 their number
+    flow_bulk_cells_target = None
+    flow_kinetic_energy_pred = None                     # (B, steps*T)        fp32 mean (u^2 + v^2) / 2
+    flow_kinetic_energy_target = None
+    flow_enstrophy_pred = None                          # (B, steps*T)        fp32 mean vorticity^2 / 2 over the interior cells
+    flow_enstrophy_target = None
+    flow_transport_pred = None                          # (B, steps*T-1)      fp32 RMS of phi_t + u . grad phi near the interface; row s * T + t - 1 is the pair that ends in frame t of step s
+    flow_transport_target = None
+    flow_interface_speed_pred = None                    # (B, steps*T-1)      fp32 RMS of phi_t alone over the same cells
+    flow_interface_speed_target = None
+    flow_transport_cells_pred = None                    # (B, steps*T-1)      int32 their number
+    flow_transport_cells_target = None
+    flow_dx = None                                      # the FlowSpec's cell size and time between frames
+    flow_dt = None
+
+    def _flow(self):
+        if self.flow_divergence_pred is None:
+            raise ValueError("this report has no flow-consistency rows: call evaluate_rollouts_flow(..., FlowSpec(dt))")
+
+    def transport_ratio(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(prediction, simulation): (B, steps*T-1) fp32 flow_transport / flow_interface_speed of a side, 0 where its velocity explains all of its
+        interface's motion, about 1 or above where it explains none.  Read the prediction's against the simulation's, not against zero.  On the
+        device; never synchronises."""
+        self._flow()
+        return self.flow_transport_pred / self.flow_interface_speed_pred, self.flow_transport_target / self.flow_interface_speed_target
+
+    def energy_drift(self) -> torch.Tensor:
+        """(B, steps*T) fp32: flow_kinetic_energy_pred / flow_kinetic_energy_target, 1 for a prediction that keeps the flow's energy.  On the
+        device; never synchronises."""
+        self._flow()
+        return self.flow_kinetic_energy_pred / self.flow_kinetic_energy_target
+
+    def divergence_excess(self) -> torch.Tensor:
+        """(B, steps*T) fp32: flow_divergence_pred / flow_divergence_target, how much more compressible the predicted bulk liquid is than the
+        simulated one on the same stencil.  On the device; never synchronises."""
+        self._flow()
+        return self.flow_divergence_pred / self.flow_divergence_target
 
     def _ensemble(self):
         if self.ensemble_members is None:
@@ -217,7 +259,7 @@ class RolloutReport:
         if self.bubble_events_pred is not None:
             for key in _TRACK_KEYS:
                 out[key] = getattr(self, key)
-        for key in _MATCH_KEYS + _ERROR_KEYS + _ENSEMBLE_KEYS + _REDISTANCE_KEYS:
+        for key in _MATCH_KEYS + _ERROR_KEYS + _ENSEMBLE_KEYS + _REDISTANCE_KEYS + _FLOW_KEYS:
             if getattr(self, key) is not None:
                 out[key] = getattr(self, key)
         torch.save(out, path)
@@ -358,6 +400,10 @@ _ERROR_KEYS = ("rmse", "max_error", "boundary_rmse", "interface_rmse", "interfac
                "spectrum_target")
 _ENSEMBLE_KEYS = ("ensemble_members", "ensemble_mean_rmse", "ensemble_spread", "ensemble_crps", "ensemble_rank_hist", "ensemble_mean")
 _REDISTANCE_KEYS = ("redistance_rounds", "redistance_change")
+# report attribute -> member of bf_flow_rows, per side
+_FLOW_ROW_NAMES = {"flow_divergence": "divergence_rms", "flow_bulk_cells": "bulk_cells", "flow_kinetic_energy": "kinetic_energy", "flow_enstrophy": "enstrophy",
+                   "flow_transport": "transport_rms", "flow_interface_speed": "interface_speed_rms", "flow_transport_cells": "transport_cells"}
+_FLOW_KEYS = tuple(f"{name}_{side}" for name in _FLOW_ROW_NAMES for side in ("pred", "target")) + ("flow_dx", "flow_dt")
 _BUBBLE_KEYS = ("bubble_count_pred", "bubble_count_target", "bubble_attached_pred", "bubble_attached_target", "vapour_fraction_pred",
                 "vapour_fraction_target", "bubble_area_pred", "bubble_area_target")
 
@@ -413,7 +459,8 @@ def evaluate_rollouts(model, data, starts: Sequence[int], steps: int, *, use_gra
     ``report.spread_skill()`` and ``report.rank_histogram()`` read them.  ``EnsembleSpec(relative=True)`` takes ``store.field_std()`` first,
     which is ONE host synchronisation before the loop; nothing else of the call waits for the device.
 
-    ``evaluate_rollouts_redistanced`` is this call with the predicted signed-distance field redistanced in place at the head of every step."""
+    ``evaluate_rollouts_redistanced`` is this call with the predicted signed-distance field redistanced in place at the head of every step,
+    ``evaluate_rollouts_flow`` this call with the flow-consistency rows of both sides."""
     return _evaluate_rollouts(model, data, starts, steps, None, use_graph=use_graph, sdf_field=sdf_field, keep_predictions=keep_predictions,
                               heatflux=heatflux, bubbles=bubbles, errors=errors, ensemble=ensemble)
 
@@ -433,9 +480,29 @@ def evaluate_rollouts_redistanced(model, data, starts: Sequence[int], steps: int
     return _evaluate_rollouts(model, data, starts, steps, redistance, **options)
 
 
+def evaluate_rollouts_flow(model, data, starts: Sequence[int], steps: int, flow: "Optional[FlowSpec]", **options) -> RolloutReport:  # noqa: F821 (physics.FlowSpec)
+    """``evaluate_rollouts(model, data, starts, steps, **options)`` plus the question whether the fields of ONE prediction agree with each other.
+
+    With ``flow`` (a ``physics.FlowSpec``; its ``dt`` is the time between two stored frames) one more call before the scoring call
+    (``ops.rollout_flow``, captured with it) leaves ``physics.flow_consistency``'s rows of every frame and of every pair of consecutive frames,
+    for the de-normalised prediction and for the simulation: ``flow_divergence_*``, ``flow_bulk_cells_*``, ``flow_kinetic_energy_*`` and
+    ``flow_enstrophy_*`` (B, steps*T), ``flow_transport_*``, ``flow_interface_speed_*`` and ``flow_transport_cells_*`` (B, steps*T-1), where row
+    s * T + t - 1 is the pair that ends in frame t of step s -- pairs across a step boundary included; the pair from the last input frame to the
+    first predicted one is not scored.  The ``*_target`` rows are the simulation's own residuals and are NOT zero: the frames are stored at a
+    coarse interval, and boiling moves the interface relative to the fluid.  They are the baseline: ``report.transport_ratio()``,
+    ``energy_drift()`` and ``divergence_excess()`` set the prediction against them.  ``options`` are ``evaluate_rollouts``' keywords plus
+    ``redistance=`` (a ``physics.RedistanceSpec``, as ``evaluate_rollouts_redistanced`` takes it): the flow call is issued after the correction, so
+    the rows are those of the corrected signed distance.  With ``ensemble=`` the rows are per member.  ``flow=None`` is the call without it: the
+    same launches, the same bits.  Never synchronises.
+
+    A function of its own rather than one more keyword of ``evaluate_rollouts``: that function's parameter list is held as it is."""
+    redistance = options.pop("redistance", None)
+    return _evaluate_rollouts(model, data, starts, steps, redistance, flow=flow, **options)
+
+
 def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True, sdf_field="dfun", keep_predictions=False, heatflux=None, bubbles=None,
-                       errors=None, ensemble=None) -> RolloutReport:
-    """The one implementation behind ``evaluate_rollouts`` (redistance = None) and ``evaluate_rollouts_redistanced``."""
+                       errors=None, ensemble=None, flow=None) -> RolloutReport:
+    """The one implementation behind ``evaluate_rollouts`` (redistance = None), ``evaluate_rollouts_redistanced`` and ``evaluate_rollouts_flow``."""
     from .. import ops
     device = next(model.parameters()).device
     store = _frames_store(data, device)
@@ -486,6 +553,14 @@ def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True
                     ops.redistance_workspace(B * T, Ho, Wo, device))
         red_rows = (torch.empty((B, steps * T), dtype=torch.int32, device=device), new(B, steps * T))
         before_score.append(lambda pred, step: ops.rollout_redistance(pred, store.frames, first, step, store.out_tab, *red_args, *red_rows))
+    flow_rows = None
+    if flow is not None:                            # right behind the correction: the rows are those of the corrected signed distance
+        flow_channels = flow.channels(fields)
+        flow_rows = [{k: torch.empty((B, steps * T if k in ops._FLOW_FRAME_ROWS else steps * T - 1), dtype=torch.int32 if k.endswith("_cells") else torch.float32,
+                                     device=device) for k in ops._FLOW_ROWS} for _ in range(2)]
+        carry = new(2, B, 3, Ho, Wo)                # the step's last predicted frame in physical units, for the next step's first pair
+        before_score.append(lambda pred, step: ops.rollout_flow(pred, store.frames, first, step, store.out_tab, flow_channels, steps, float(flow.dx),
+                                                                float(flow.dt), flow.band_width(), int(flow.interface_radius), carry, *flow_rows))
     hf_p = hf_t = None
     if heatflux is not None:
         hf_channels = heatflux.channels(fields)
@@ -598,6 +673,11 @@ def _evaluate_rollouts(model, data, starts, steps, redistance, *, use_graph=True
             setattr(report, key, rows)
     if red_rows is not None:
         report.redistance_rounds, report.redistance_change = red_rows
+    if flow_rows is not None:
+        for name, member in _FLOW_ROW_NAMES.items():
+            setattr(report, name + "_pred", flow_rows[0][member])
+            setattr(report, name + "_target", flow_rows[1][member])
+        report.flow_dx, report.flow_dt = float(flow.dx), float(flow.dt)
     if ens_rows is not None:
         report.ensemble_members = members
         for key, rows in ens_rows.items():

@@ -44,6 +44,7 @@
  *   bf_bubble_match .......... predicted bubbles matched to simulated ones (no reference program); bf_rollout_bubble_match: per step
  *   bf_field_errors .......... pointwise, interface and shell-spectrum error rows per frame (no reference program); bf_rollout_errors: per step
  *   bf_ensemble_scores ....... ensemble-mean RMSE, spread, CRPS and rank histogram across members (no reference program); bf_rollout_ensemble: per step
+ *   bf_flow_consistency ...... divergence, kinetic energy, enstrophy and the level-set transport residual of (sdf, velocity) (no reference program); bf_rollout_flow: per step
  *   bf_render_ranges / bf_render_tiles .. plot_bubbleml and the wandb_*_plotter strips: utils/plot_utils.py:12-228 (no matplotlib, no cv2)
  *   bf_lion .................. lion_pytorch.Lion (the reference's default optimizer) at bubbleformer/modules.py:139-140
  *   bf_grad_norm, bf_opt_step's coef_dev / clip_value .. Trainer(gradient_clip_val, gradient_clip_algorithm): scripts/train.py:158-172 (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)
@@ -711,6 +712,46 @@ int bf_ensemble_scores(const float* members_ptr, int64_t member_stride, const fl
  * [Ho][Wo]) are written and no other; with the step number s = *s->step outside [0, steps) nothing is written.  The counter is read, not advanced: issue the
  * call before the step's bf_rollout_score.  ws: bf_ensemble_scores_ws_bytes(Bt * T * C, members, Ho, Wo) bytes. */
 int bf_rollout_ensemble(const bf_rollout_step* s, int members, int fair, const bf_ensemble_rows* rows, void* ws, int64_t ws_bytes, bf_stream_t stream);
+/* bf_flow_consistency's outputs */
+typedef struct bf_flow_rows {
+    float *divergence_rms, *kinetic_energy, *enstrophy; int32_t* bulk_cells;              /* [rows]  per frame */
+    float *transport_rms, *interface_speed_rms;         int32_t* transport_cells;         /* [pairs] per pair  */
+} bf_flow_rows;   /* any member may be NULL and is then not computed */
+/* Do a signed-distance field and a velocity field agree with each other (csrc/flow.hip; the reference has no program for it)?
+ * sdf, velx, vely [sequences][T][H][W] fp32 in physical units; x runs along W and y along H, row 0 is the heater row, the spacing is dx on both axes.
+ * Vapour is sdf > 0, anything else is liquid, an exact zero and a NaN too (bf_field_errors' convention).  Interior cells are 1 <= i <= H - 2,
+ * 1 <= j <= W - 2.  Every input is widened to fp64 before any arithmetic.  Per frame, row = sequence * T + t:
+ *   div(i, j) = ((u[i][j+1] - u[i][j-1]) + (v[i+1][j] - v[i-1][j])) / (2 dx),  w(i, j) = ((v[i][j+1] - v[i][j-1]) - (u[i+1][j] - u[i-1][j])) / (2 dx);
+ *   bulk_cells [rows] int32      the interior cells whose (2 r + 1)^2 window (r = interface_radius >= 1, clipped to the frame) holds no vapour cell;
+ *   divergence_rms [rows]        sqrt(sum over the bulk cells of div^2 / bulk_cells); NaN where there is none;
+ *   kinetic_energy [rows]        sum over ALL cells of (u^2 + v^2) / 2, divided by H W;
+ *   enstrophy [rows]             sum over the interior cells of w^2 / 2, divided by (H - 2) (W - 2).
+ * Per pair of consecutive frames of one sequence (0 the earlier, 1 the later), row = sequence * (T - 1) + t - 1 for the pair that ends in frame t
+ * (bf_bubble_links' convention), with pm = (phi0 + phi1) / 2, um = (u0 + u1) / 2, vm = (v0 + v1) / 2 and s = (phi1 - phi0) / dt:
+ *   transport_cells [pairs] int32   n = the band cells: the interior cells with |pm| < band;
+ *   transport_rms [pairs]           sqrt(sum over the band cells of (s + um dpm/dx + vm dpm/dy)^2 / n), central differences of pm at spacing dx;
+ *   interface_speed_rms [pairs]     sqrt(sum over the band cells of s^2 / n); both NaN where n = 0.
+ * T = 1 has no pairs and the three pair members are unread.  fp64 arithmetic, every sum in a fixed order (no float atomics), each value rounded once to
+ * fp32: the same bits on every call, and for a sequence alone or in a batch; a NaN or an inf that enters a sum makes that row non-finite and no other.
+ * One workgroup per frame does the frame's rows and the pair that ends in it.  H, W in [3, 1024], dx, dt, band > 0 (refused otherwise, before any
+ * HIP call).  No workspace; allocation-free, capturable, never makes the host wait. */
+int bf_flow_consistency(const float* sdf, const float* velx, const float* vely, int64_t sequences, int T, int H, int W, float dx, float dt,
+                        float band, int interface_radius, const bf_flow_rows* rows, bf_stream_t stream);
+/* bf_flow_consistency of ONE rollout step, of the prediction and of the simulation in one call.  s: see bf_rollout_step.  With the step number
+ * s = *s->step (read on the device, never written):
+ *   pred:   channels sdf_channel / velx_channel / vely_channel of s->pred as pred * div + diff (fp32 multiply, then add, unfused: the physical fields
+ *           bf_rollout_score's Eikonal rows and bf_rollout_heatflux see);
+ *   target: the stored raw frames first[b] + (s + 1) * T + t (clamped into the store) of field[channel], through bf_clip_gather's nearest-neighbour map
+ *           when Ho x Wo < H x W.
+ * The frame rows of (b, t) go to row s * T + t of a side's [B][steps*T], the pair that ends in frame t to row s * T + t - 1 of its [B][steps*T - 1];
+ * no other row is touched.  The pair from the last INPUT frame to the first predicted frame is not scored (bf_rollout_bubble_links does the same).
+ * The earlier frame of a pair across a step boundary is, for the target, the stored frame first[b] + (s + 1) * T - 1, and for the prediction the
+ * carry: carry [2][B][3][Ho][Wo] fp32, which the caller allocates and nothing else reads or writes; half s & 1 receives the physical (phi, u, v) of the
+ * step's last predicted frame, half (s - 1) & 1 is read at s >= 1 (two halves: reader and writer are different workgroups of one launch).  With s
+ * outside [0, steps) nothing is written, the carry included.  Refused before any HIP call: a null record or carry, a channel outside [0, C), Ho or
+ * Wo outside [3, 1024].  Issue the call before the step's bf_rollout_score, and after bf_rollout_redistance if that is used. */
+int bf_rollout_flow(const bf_rollout_step* s, int sdf_channel, int velx_channel, int vely_channel, float dx, float dt, float band,
+                    int interface_radius, float* carry, const bf_flow_rows* pred, const bf_flow_rows* target, bf_stream_t stream);
 /* The stand-alone criterion (utils/losses.py:67-94 for any d and any finite p >= 1; csrc/losses.hip).  pred, y [rows][n] fp32 (rows = product of the
  * leading dims, n = product of the last d), 4-byte aligned; 16-byte loads where pred and y (and dpred) sit at the same offset from a 16-byte boundary.
  * bf_lp_rows_fwd: sums[r] = {S_e = sum |pred - y|^p, S_y = sum |y|^p} in fp64, added in a fixed order (no atomics: the same bits on every call),
